@@ -13,13 +13,19 @@ library's streams; sampling every dispatch costs a little, so the timed loop its
 `cpu_baseline` times the oracle (a port: the reference has no k-mer filter) on the same reads on this box's
 host cores and checks every GPU pass bit against it.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run does only what the headline needs: it builds the bait set and the resident reads, warms up, times the K steps
+and prints the line (`value`, `ms_per_step`, the tally of the last step, the whole pass over the HBM peak).  Everything else
+-- `roofline`'s per-kernel figures (the sampled loop, the serial loop, the rocprofv3 --pmc child runs), `cpu_baseline` and
+every leg of `extra` described below -- is measured with `--full` only; the options after `--k` tune those legs.
+`--dump-outputs DIR` writes what the timed steps computed (see dump_outputs) so that two builds can be compared.
 
 Ranks are independent (each filters its own shard, no collective); the launcher's RANK / WORLD_SIZE are all this
 script needs, so torch is never imported: the barrier and the max over ranks go through a directory in /dev/shm.
 
-Beside the headline, at N = 1 (`extra`): files in / files out -- a bounded PE / SE run, configs[4] at its stated size
+Beside the headline, with --full, at N = 1 (`extra`): files in / files out -- a bounded PE / SE run, configs[4] at its stated size
 (33 333 334 single-end reads, one gzip member, device ingest: inflate, line index, pack, filter on the GPU; priced against the
 box's host-to-device copy rate, its roof) and an eighth of it compressed by the compressors people use (gzip, pigz, bgzip where the
 box has them) --, configs[2]'s other k (21 and 41) on the same resident reads (`extra.k_sweep`), and the Group-A row of
@@ -53,6 +59,10 @@ def parse():
     ap.add_argument("--prewarm-ms", type=float, default=100.0, help="keep the device busy with untimed passes for this long before the warm-up steps (clock ramp)")
     ap.add_argument("--reads", type=int, default=0, help="reads per GPU (default: the 5 Gbp set; at 8 GPUs a 1/8 shard of the 50 Gbp set)")
     ap.add_argument("--k", type=int, default=K)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what they computed as DIR/<name>.npy (rank 0's shard; see dump_outputs)")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything beside the headline too: per-kernel roofline, CPU baseline, the legs of `extra` (the options below)")
     ap.add_argument("--cpu-sample", type=int, default=READS_5GBP,
                     help="reads timed on the CPU oracle, all host threads (default: the whole set, a few seconds; 0 = skip)")
     ap.add_argument("--no-exhaustive", action="store_true", help="skip the extra exhaustive-mode measurement")
@@ -796,6 +806,34 @@ def realistic_leg(mf, a, dev, uniform_ms):
         ks.close()
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(d, mf, ks, reads, st):
+    """--dump-outputs DIR: what the timed steps computed in the last of them, as float64 .npy files (exact for every value written).
+    mf_filter_resident hands its caller the tally of its last pass; the pass bits stay on the device, so one more pass of the same
+    kind after the timed steps (mf_filter: the same kernels, then the bitmap copied down) fetches them, checked against the tally.
+      pass_count.npy   [reads, reads that passed]
+      pass_bits.npy    the pass bitmap as u32 words (bit i of word w: read 32 w + i); when the words would pass DUMP_LIMIT_BYTES,
+                       a fixed sample of them (seed 0), their word indices in pass_bits_index.npy"""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    bits, _, one = mf.filter_reads(ks, reads, THRESHOLD, mf.MODE_SCREENED)
+    n_set = int(np.unpackbits(bits.view(np.uint8)).sum())
+    if not n_set == one.n_pass == st.n_pass:
+        sys.exit(f"bench.py: the pass bits hold {n_set} reads, the pass that fetched them {one.n_pass}, the timed steps {st.n_pass}")
+    np.save(os.path.join(d, "pass_count.npy"), np.array([st.n_reads, st.n_pass], dtype=np.float64))
+    index = os.path.join(d, "pass_bits_index.npy")
+    if os.path.exists(index):
+        os.unlink(index)
+    room = DUMP_LIMIT_BYTES - 4096                       # (pass_count.npy and the .npy headers)
+    if bits.size * 8 <= room:
+        np.save(os.path.join(d, "pass_bits.npy"), bits.astype(np.float64))
+    else:
+        idx = np.sort(np.random.default_rng(0).choice(bits.size, room // 16, replace=False))
+        np.save(os.path.join(d, "pass_bits.npy"), bits[idx].astype(np.float64))
+        np.save(index, idx.astype(np.float64))
+
 
 def main():
     a = parse()
@@ -811,16 +849,17 @@ def main():
         a.reads = READS_50GBP_8 if world == 8 else READS_5GBP
     rdv = ShmRendezvous(rank, world) if world > 1 else None
     solo = rank == 0 and world == 1
+    full = a.full
 
     # ---- everything that needs child processes happens before this process touches the GPU
     import tempfile
-    tmpdir = tempfile.TemporaryDirectory(prefix="mf_bench_", dir="/tmp") if rank == 0 else None
+    tmpdir = tempfile.TemporaryDirectory(prefix="mf_bench_", dir="/tmp") if rank == 0 and full else None
     if rank == 0 and not solo:
         a.e2e_full_reads, a.no_group_a = 0, True     # with several ranks only the small paired set is made (file level over all devices)
-    files = prepare_inputs(a, tmpdir.name, solo) if rank == 0 else {}
+    files = prepare_inputs(a, tmpdir.name, solo) if tmpdir is not None else {}
     # N > 1: a .gz shard of its own for every rank (file level on its own GPU, beside the resident rate), made by child processes now
     rank_tmp, rank_gz = None, None
-    if world > 1 and a.rank_file_reads > 0 and not being_profiled():
+    if full and world > 1 and a.rank_file_reads > 0 and not being_profiled():
         try:
             rank_tmp = tempfile.TemporaryDirectory(prefix="mf_bench_r%d_" % rank, dir="/tmp")
             subprocess.check_call([sys.executable, os.path.join(ROOT, "tools", "make_fastq.py"), os.path.join(rank_tmp.name, "k"), "--pairs", str(a.rank_file_reads),
@@ -833,13 +872,13 @@ def main():
         os.environ.setdefault("MF_DEVPOOL_GB", "4")       # (ranks of one node: what a process keeps between calls stays small)
     live, valu = (None, None), (None, None)
     default_set = a.reads == READS_5GBP
-    if solo and not a.no_live_traffic and default_set:
+    if full and solo and not a.no_live_traffic and default_set:
         live = live_traffic(a.k)
         if a.k < 28 and live[0] is not None:                  # the stride-8 screen is bound by vector issue, not by HBM: count its instructions too
             valu = live_counters(("SQ_INSTS_VALU",), a.k)
     # configs[2]: the stride-8 legs of the k sweep get their own live instruction count (one more short child run each)
     sweep_valu = {}
-    if solo and not a.no_live_traffic and default_set and a.k_sweep and a.k_sweep != "none" and live[0] is not None:
+    if full and solo and not a.no_live_traffic and default_set and a.k_sweep and a.k_sweep != "none" and live[0] is not None:
         for kk in [int(x) for x in a.k_sweep.replace('"', "").split(",") if x.strip().isdigit()]:
             if kk < 28 and kk != a.k:
                 sweep_valu[kk] = live_counters(("SQ_INSTS_VALU",), kk)
@@ -857,7 +896,7 @@ def main():
                  "(MF_BENCH_SHARE_GPU=1 lets ranks share a device -- tests only, the figures mean nothing then)")
     dev = local_rank % max(1, n_dev)
     ks = mf.KmerSet.from_text(bait, a.k, dev)
-    want_cpu = solo and a.cpu_sample > 0
+    want_cpu = full and solo and a.cpu_sample > 0
     t0 = time.time()
     # every rank owns its own shard of whole pairs (weak scaling: fixed reads per GPU), no collective
     reads = mf.Reads.synth(a.reads, READ_LEN, seed=20261003 + rank, bait_text=bait,
@@ -888,20 +927,24 @@ def main():
     if rdv is not None:
         elapsed = rdv.allmax(mine)
         per_rank = rdv.gather(mine)
-
-    # kernel durations: the same K steps again, every dispatch sampled
-    os.environ["MF_EVENT_STRIDE"] = "1"
-    sp = mf.filter_resident(ks, reads, THRESHOLD, mf.MODE_SCREENED, a.steps)
-    os.environ["MF_EVENT_STRIDE"] = "8"
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, mf, ks, reads, st)
 
     total_reads = a.reads * world
     value = total_reads * a.steps / elapsed
     alg_bytes = st.algorithmic_bytes                     # per launch: ceil(2*bases/8) + ceil(reads/8)
-    screen_s = sp.ms_screen / 1e3
-    achieved = alg_bytes / screen_s / 1e9 if screen_s > 0 else 0.0
 
-    extra = {"ms_screen_kernel": round(sp.ms_screen, 4), "ms_mark_kernel": round(sp.ms_mark, 4), "ms_finish_kernel_phase0": round(sp.ms_exact, 4),
-             "ms_per_step_sampled_loop": round(sp.ms_total, 4), "kernel_samples": a.steps,
+    extra = {}
+    if full:
+        # kernel durations: the same K steps again, every dispatch sampled
+        os.environ["MF_EVENT_STRIDE"] = "1"
+        sp = mf.filter_resident(ks, reads, THRESHOLD, mf.MODE_SCREENED, a.steps)
+        os.environ["MF_EVENT_STRIDE"] = "8"
+        screen_s = sp.ms_screen / 1e3
+        achieved = alg_bytes / screen_s / 1e9 if screen_s > 0 else 0.0
+        extra.update({"ms_screen_kernel": round(sp.ms_screen, 4), "ms_mark_kernel": round(sp.ms_mark, 4), "ms_finish_kernel_phase0": round(sp.ms_exact, 4),
+                      "ms_per_step_sampled_loop": round(sp.ms_total, 4), "kernel_samples": a.steps})
+    extra.update({
              "ms_pass_events": round(st.ms_total, 4), "work_items": int(st.n_candidates), "passed": int(st.n_pass),
              "reads_per_gpu": a.reads, "synth_seconds": round(t_gen, 2), "prewarm_ms": a.prewarm_ms, "device": mf.device_name(dev),
              # configs[3]: "per-GPU + aggregate reads/s" -- every rank's own rate over its own K steps (the aggregate uses the slowest)
@@ -909,9 +952,9 @@ def main():
              "per_rank_ms_per_step": [round(t / a.steps * 1e3, 4) for t in per_rank],
              "pipelined": "consecutive steps overlap: finish kernels of step i run under the screen kernel of step i+1 (second stream) and "
                           "consecutive screen kernels go to two streams in turn, so the duration of a screen launch (ms_screen_kernel, "
-                          "roofline.achieved) includes time it shares the device with its neighbours; a step completes every ms_per_step"}
+                          "roofline.achieved) includes time it shares the device with its neighbours; a step completes every ms_per_step"})
     alone_frac = None
-    if solo:
+    if full and solo:
         one = mf.filter_resident(ks, reads, THRESHOLD, mf.MODE_SCREENED, 1)    # a single step: nothing to overlap with
         extra["ms_single_pass_latency"] = round(one.ms_total, 4)
         # the same kernel with the device to itself (option pass=serial: one stream, no overlap between steps), every dispatch sampled
@@ -925,12 +968,12 @@ def main():
                                             "ms_per_step_serial": round(alone.ms_total, 4)}
     whole_pass_frac = alg_bytes / (elapsed / a.steps) / 1e9 / HBM_PEAK_GBPS
     extra["whole_pass_frac_of_hbm_peak"] = round(whole_pass_frac, 4)
-    if rank == 0 and not a.no_exhaustive:
+    if full and rank == 0 and not a.no_exhaustive:
         ex = mf.filter_resident(ks, reads, THRESHOLD, mf.MODE_EXHAUSTIVE, 1)
         extra["exhaustive_reads_per_s"] = a.reads / (ex.ms_total / 1e3)
         extra["exhaustive_passed"] = int(ex.n_pass)
 
-    if solo and a.k_sweep and a.k_sweep != "none":
+    if full and solo and a.k_sweep and a.k_sweep != "none":
         # configs[2]: the other k on the same resident reads (a few steps each: set built on the device, warm-up, timed loop, sampled loop)
         sweep = {}
         for kk in [int(x) for x in a.k_sweep.replace('"', "").split(",") if x.strip().isdigit()]:
@@ -983,7 +1026,7 @@ def main():
             import traceback
             traceback.print_exc()
             extra[name] = {"error": str(e)[:200]}
-    if solo and default_set and not a.no_axes:
+    if full and solo and default_set and not a.no_axes:
         n_words_stream = (a.reads * READ_LEN + 15) // 16
         leg("bait_sweep", lambda: bait_sweep_leg(mf, reads, bait, a, dev, alg_bytes, n_words_stream))
         leg("threshold_sweep", lambda: threshold_leg(mf, ks, reads, bait, a, dev, alg_bytes))
@@ -1015,7 +1058,7 @@ def main():
         nw = n // 32
         extra["sample_bits_match_oracle"] = bool(np.array_equal(gbits[:nw], obits[:nw]))
         extra["sample_reads_checked"] = nw * 32
-    if solo:
+    if full and solo:
         reads.close()                                    # (the file-level runs want the device memory)
         if default_set and not a.no_axes:
             leg("realistic", lambda: realistic_leg(mf, a, dev, extra.get("threshold_sweep", {}).get("1", {}).get("ms_per_step") or elapsed / a.steps * 1e3))
@@ -1038,7 +1081,7 @@ def main():
                     extra["group_a"] = group_a(files)
                 except Exception as e:
                     extra["group_a"] = {"error": str(e)[:200]}
-    if world > 1:
+    if full and world > 1:
         # The file path over all the node's devices in ONE process (mf_filter_fastq_files(..., n_devices = N): batches of whole
         # pairs dealt to one worker per device, no collective) next to the resident rate above -- it is the host that feeds it,
         # and the north star's ">= 6x at 8 GPUs" is a different question for each of the two.  Rank 0 runs it, the others wait.
@@ -1083,14 +1126,14 @@ def main():
     if tmpdir is not None:
         tmpdir.cleanup()
 
-    traffic, traffic_src = committed_traffic()
-    if not default_set or a.k != K:
-        traffic, traffic_src = None, None              # the committed profile was taken on the default workload
-    if live[0] is not None:
-        traffic, traffic_src = live
-    elif live[1] and traffic_src:
-        traffic_src += f" (live collection unavailable: {live[1]})"
-    if rank == 0:
+    if rank == 0 and full:
+        traffic, traffic_src = committed_traffic()
+        if not default_set or a.k != K:
+            traffic, traffic_src = None, None              # the committed profile was taken on the default workload
+        if live[0] is not None:
+            traffic, traffic_src = live
+        elif live[1] and traffic_src:
+            traffic_src += f" (live collection unavailable: {live[1]})"
         hbm = {"achieved": achieved, "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBPS}
         roofline = {"bound": "hbm", **hbm, "traffic": traffic, "traffic_source": traffic_src,
                     "kernel": "screen_kernel", "algorithmic_bytes_per_launch": int(alg_bytes),
@@ -1111,6 +1154,12 @@ def main():
             else:
                 roofline.update({"achieved": None, "peak": VALU_PEAK_GINST, "unit": "G wave-instructions/s", "frac": None,
                                  "valu_source": f"no live SQ_INSTS_VALU reading ({valu[1] or live[1] or 'not collected'}); see profiles/ for the committed one"})
+    elif rank == 0:
+        # a plain run prices the whole pass only: the kernel's own duration, its traffic and the kernel alone take runs of their own (--full)
+        roofline = {"bound": "hbm" if a.k >= 28 else "valu", "kernel": "screen_kernel", "algorithmic_bytes_per_launch": int(alg_bytes),
+                    "whole_pass_frac": whole_pass_frac, "whole_pass_peak": HBM_PEAK_GBPS, "unit": "GB/s",
+                    "note": "whole_pass_frac: algorithmic bytes per ms_per_step over the HBM peak; per-kernel figures with --full"}
+    if rank == 0:
         out = {
             "metric": "filtered reads/sec on 5 Gbp PE150 k=31; achieved HBM GB/s vs peak",
             "value": value, "unit": "reads/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,

@@ -180,6 +180,37 @@ def test_resident_axis_legs_build_their_dictionaries(bench):
     assert z["window_bits_match_oracle"] and z["roofline"]["bound"] == "hbm"
 
 
+def test_dump_outputs_writes_the_pass_bits_within_the_limit(bench, tmp_path, monkeypatch):
+    """--dump-outputs: the tally and the pass bitmap of the timed steps as float64 (exact for u32 words); beyond the size limit a
+    fixed sample of the words with their indices; bits that disagree with the timed steps' tally end the run"""
+    import numpy as np
+    bits = np.random.default_rng(3).integers(0, 2**32, size=1000, dtype=np.uint32)
+    n_pass = int(np.unpackbits(bits.view(np.uint8)).sum())
+
+    class Lib:
+        MODE_SCREENED = 0
+
+        def filter_reads(self, ks, reads, thr, mode, want_hits=False):
+            return bits.copy(), None, types.SimpleNamespace(n_pass=n_pass)
+    st = types.SimpleNamespace(n_reads=32000, n_pass=n_pass)
+    d = tmp_path / "whole"
+    bench.dump_outputs(str(d), Lib(), None, None, st)
+    w, c = np.load(d / "pass_bits.npy"), np.load(d / "pass_count.npy")
+    assert w.dtype == c.dtype == np.float64 and np.array_equal(w, bits) and c.tolist() == [32000, n_pass]
+    assert not (d / "pass_bits_index.npy").exists()
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 4096 + 16 * 100)
+    idx = []
+    for run in ("part1", "part2"):
+        bench.dump_outputs(str(tmp_path / run), Lib(), None, None, st)
+        w, i = np.load(tmp_path / run / "pass_bits.npy"), np.load(tmp_path / run / "pass_bits_index.npy")
+        assert len(w) == len(i) == 100 and np.all(np.diff(i) > 0) and np.array_equal(w, bits[i.astype(np.int64)])
+        assert sum(f.stat().st_size for f in (tmp_path / run).iterdir()) <= bench.DUMP_LIMIT_BYTES
+        idx.append(i)
+    assert np.array_equal(*idx)                          # the same sample every time
+    with pytest.raises(SystemExit):
+        bench.dump_outputs(str(tmp_path / "bad"), Lib(), None, None, types.SimpleNamespace(n_reads=32000, n_pass=n_pass + 1))
+
+
 def test_a_leg_that_raised_is_found(bench):
     src = open(os.path.join(ROOT, "bench.py")).read()
     assert "find_errors(extra" in src and "sys.exit(\"bench.py: legs that raised" in src

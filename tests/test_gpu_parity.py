@@ -116,18 +116,20 @@ def test_synth_uniform_matches_oracle(mf, ol, bait_text):
 def test_fastq_files_match_oracle(mf, ol, bait_text, tmp_path, gz, batch, ingest, monkeypatch):
     """File level, through the chunked host pipeline (MF_INGEST=host: regular files take the device ingest path by default since round 5,
     tests/test_gpu_devingest.py) and through whatever the library picks; small batch sizes force many batches, carried partial
-    records and out-of-step mate files."""
+    records and out-of-step mate files.  On the default (device ingest) path the same cases cut the input into small slabs and
+    compressed chunks instead -- at `batch` 1 a plain slab holds about one record."""
     if ingest == "host":
         monkeypatch.setenv("MF_INGEST", "host")
-    elif batch is not None:
-        pytest.skip("the batch knobs are the host pipeline's")
     if batch is not None:
-        if gz and batch == 1:
-            pytest.skip("one-read batches are exercised on the plain files")
         monkeypatch.setenv("MF_BATCH_READS", str(batch))
         # plain files are mapped and parsed in parallel segments: tiny segments put a border inside
         # almost every record (headers, sequences, CRLF pairs, the partial tail)
         monkeypatch.setenv("MF_PARSE_SEG", "997" if batch == 700 else "64")
+        if ingest == "default":
+            # the device ingest path's own seams (the values of tests/test_gpu_devingest.py)
+            monkeypatch.setenv("MF_GZDEV_CHUNK_BYTES", "4096")
+            monkeypatch.setenv("MF_GZDEV_SLAB_CHUNKS", "3")
+            monkeypatch.setenv("MF_INGEST_SLAB_BYTES", "70001" if batch == 700 else "333")
     ext = ".fq.gz" if gz else ".fq"
     n1 = 3000 if batch != 1 else 150
     s1 = make_reads(bait_text, n1, seed=1)
@@ -381,17 +383,22 @@ def test_many_logical_devices_match_oracle(ol, bait_text, tmp_path, n_dev):
 
 
 @pytest.mark.parametrize("world", [2, 8])
-def test_bench_ranks_under_torchrun(tmp_path, world):
+def test_bench_ranks_under_torchrun(mf, tmp_path, world):
     """bench.py exactly as the driver launches it for N > 1 (torch.distributed.run, one process per rank), with the ranks
-    sharing the one visible GPU: the launcher's environment, the /dev/shm rendezvous, per-rank shards and rank 0's JSON line
-    (eight ranks: the shape of the 8-GPU run, with a small shard instead of configs[3]'s 41.67 M reads per rank)."""
+    sharing the visible GPUs: the launcher's environment, the /dev/shm rendezvous, per-rank shards and rank 0's JSON line
+    (eight ranks: the shape of the 8-GPU run, with a small shard instead of configs[3]'s 41.67 M reads per rank).  Two ranks may
+    share one GPU; eight processes holding one shared GPU open at once are more than a shared machine admits, so eight ranks
+    want eight GPUs."""
     import json
     import subprocess
     import sys
+    n_dev = mf.device_count()
+    if world > 2 and n_dev < world:
+        pytest.skip(f"needs {world} GPUs, found {n_dev}")
     port = 29000 + (os.getpid() + world) % 2000
     reads = 2000000 if world == 2 else 600000
     p = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world), "--master-addr", "127.0.0.1",
-                        "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--steps", "3", "--warmup", "1",
+                        "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--steps", "3", "--warmup", "1", "--full",
                         "--prewarm-ms", "5", "--reads", str(reads), "--no-exhaustive", "--cpu-sample", "0", "--e2e-pairs", "0", "--rank-file-reads", "60000"],
                        capture_output=True, timeout=600, cwd=str(tmp_path), env=dict(os.environ, MF_BENCH_SHARE_GPU="1"))
     assert p.returncode == 0, p.stderr.decode()[-3000:]
@@ -423,6 +430,32 @@ def test_bench_refuses_more_ranks_than_gpus(tmp_path):
                         "--reads", "100000", "--no-exhaustive", "--cpu-sample", "0", "--e2e-pairs", "0"],
                        capture_output=True, timeout=300, cwd=str(tmp_path), env=env)
     assert p.returncode != 0 and b"one rank per GPU" in p.stderr
+
+
+def test_bench_plain_run_dumps_what_it_timed(mf, ol, bait_text, tmp_path):
+    """bench.py without --full: the headline line alone; --dump-outputs writes the tally and the pass bits of the timed steps,
+    which are the oracle's bits for the same seeded reads."""
+    import json
+    import subprocess
+    import sys
+    n, steps = 300_000, 4
+    d = tmp_path / "out"
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", "1", "--prewarm-ms", "5",
+                        "--reads", str(n), "--dump-outputs", str(d)], capture_output=True, timeout=300, cwd=str(tmp_path))
+    assert p.returncode == 0, p.stderr.decode()[-3000:]
+    lines = [l for l in p.stdout.decode().splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    x = json.loads(lines[0])
+    assert x["steps"] == steps and x["cpu_baseline"] is None and x["roofline"]["whole_pass_frac"] > 0
+    assert not {"ms_screen_kernel", "k_sweep", "e2e_files", "exhaustive_reads_per_s"} & set(x["extra"])
+    assert abs(x["value"] - n * steps / (x["ms_per_step"] * steps / 1e3)) < 1e-6 * x["value"]
+    bits, count = np.load(d / "pass_bits.npy"), np.load(d / "pass_count.npy")
+    assert bits.dtype == count.dtype == np.float64 and count.tolist() == [n, x["extra"]["passed"]]
+    reads = mf.Reads.synth(n, 150, seed=20261003, bait_text=bait_text, mito_ppm=5000, sub_ppm=10000, n_read_ppm=10000, n_base_ppm=1000, keep_host=True)
+    R = ol.OracleReads.from_arrays(reads.host_words, np.arange(n + 1, dtype=np.uint64) * 150, reads.host_npos)
+    reads.close()
+    obits, _ = ol.filter_reads(ol.OracleTable(bait_text, 31), R, 1, threads=4)
+    assert np.array_equal(bits, obits.astype(np.float64))
 
 
 @pytest.mark.parametrize("k", [21, 31, 41])
