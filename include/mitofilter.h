@@ -227,6 +227,30 @@ int mf_filter_fastq_files_on(mf_kmerset *ks, const char *fq1, const char *fq2,
                              const int *devices, int n_devices,
                              uint64_t *kept, uint64_t *total);
 
+/* ---- record assignment: which bait record the baited reads come from.  No reference counterpart.
+ * A record is what the bait parser calls one ('>' at a line start opens it; sequence before any header is an anonymous leading
+ * record), numbered 0 .. R-1 in file order; its name is the header text after '>' up to the first space, tab or CR ("" for the
+ * anonymous one).  Empty records, records shorter than k and duplicate names are all kept and numbered.  A canonical k-mer of the
+ * set is UNIQUE to record j when j is the only record with a valid window holding it, else SHARED.  A read that passes
+ * (hits >= threshold) is assigned the record with the strictly largest number of its windows whose k-mer is unique to that record;
+ * MF_ASSIGN_AMBIGUOUS when that number is 0 for every record or the largest is tied; a read that does not pass: MF_ASSIGN_NONE.
+ * The per-slot record-owner table is built on the device by the first call that needs it.  Protein sets: MF_E_ARG. */
+#define MF_ASSIGN_AMBIGUOUS 0xFFFFFFFEu
+#define MF_ASSIGN_NONE      0xFFFFFFFFu
+int mf_kmerset_record_count(const mf_kmerset *ks, uint64_t *n_records);
+/* copies the NUL-terminated name; returns MF_E_ARG if buflen is too small and sets *needed (may be NULL) */
+int mf_kmerset_record_name(const mf_kmerset *ks, uint64_t i, char *buf, size_t buflen, size_t *needed);
+/* one pass like mf_filter, then assignment; out_bits (ceil(n_reads/32) u32) / assign_out (n_reads u32) / record_reads (R + 2 u64:
+ * reads assigned to each record, then ambiguous, then unassigned reads; they sum to n_reads) / stats (of the filter pass) each optional */
+int mf_assign(const mf_kmerset *ks, const mf_reads *reads, uint32_t threshold, int mode,
+              uint32_t *out_bits, uint32_t *assign_out, uint64_t *record_reads, mf_filter_stats_t *stats);
+/* mf_filter_fastq_files_on plus the per-record counts of the kept reads (R + 2 u64, mates counted one by one: a kept mate that
+ * did not pass its own threshold is unassigned; they sum to kept * (2 if paired else 1)); the same ingest path and output files
+ * byte-identical to it */
+int mf_filter_fastq_files_by_record(mf_kmerset *ks, const char *fq1, const char *fq2, const char *out1, const char *out2,
+                                    uint32_t threshold, int pair_mode, const int *devices, int n_devices,
+                                    uint64_t *record_reads, uint64_t *kept, uint64_t *total);
+
 /* Options that select which kernels a filter pass runs (process-wide; every variant gives the same bits and is parity-tested):
  *   pass=default|split|serial   adapt=0|1   finish_streams=0|1|2   screen_streams=1|2   split_pipe=0|1   exact_co=0|1
  * and, read when a k-mer set is BUILT (ABI 5; every form gives the same bits -- tests force them on small baits):

@@ -13,8 +13,11 @@
 // counterpart):
 //     fastfilter bait --bait BAIT.fa -k 31 [-t 1] --fq1 R1.fq [--fq2 R2.fq]
 //                     --out1 O1.fq [--out2 O2.fq] [--pair either|both] [--devices N]
+//                     [--report FILE]
 // which loads libmitofilter_hip.so (HIP kernels, gfx950) and prints the kept
-// read/pair count.  It has no CPU fallback: without the library or a GPU it
+// read/pair count.  --report writes how many kept reads (mates one by one)
+// each bait record attracted as a TSV (record, name, reads; then the
+// ambiguous and the unassigned reads); the FASTQ outputs are the same.  It has no CPU fallback: without the library or a GPU it
 // exits non-zero, which shell_call turns into a RuntimeError (helper.py:82-86).
 #include "../../include/mitofilter.h"
 #include "mf_coldtrace.h"
@@ -426,7 +429,7 @@ static std::string exe_dir()
 
 static int bait_main(int argc, char **argv)
 {
-    std::string bait, fq1, fq2, out1, out2, pair = "either", libpath;
+    std::string bait, fq1, fq2, out1, out2, pair = "either", libpath, report;
     int k = 0, devices = 1, gcode = 5; unsigned thr = 1; bool protein = false;
     std::vector<int> device_list;              // --device-list 2,3: these devices instead of 0 .. N - 1
     std::vector<std::pair<std::string, std::string>> options;      // --option pass=serial: how a filter pass is run (mf_set_option)
@@ -443,6 +446,7 @@ static int bait_main(int argc, char **argv)
         else if (o == "--out2") out2 = need("--out2");
         else if (o == "--pair") pair = need("--pair");
         else if (o == "--lib") libpath = need("--lib");
+        else if (o == "--report") report = need("--report");
         else if (o == "-k" || o == "--kmer") k = atoi(need("-k").c_str());
         else if (o == "-t" || o == "--threshold") thr = (unsigned)strtoul(need("-t").c_str(), nullptr, 10);
         else if (o == "--devices") devices = atoi(need("--devices").c_str());
@@ -462,10 +466,11 @@ static int bait_main(int argc, char **argv)
     }
     if (bait.empty() || fq1.empty() || out1.empty() || (fq2.empty() != out2.empty()) || (pair != "either" && pair != "both")) {
         fputs("usage: fastfilter bait --bait BAIT.fa [-k 31] [-t 1] --fq1 R1.fq [--fq2 R2.fq] --out1 O1.fq [--out2 O2.fq]"
-              " [--pair either|both] [--devices N | --device-list D0,D1,..] [--option name=value ..]\n"
+              " [--pair either|both] [--devices N | --device-list D0,D1,..] [--option name=value ..] [--report FILE]\n"
               "       fastfilter bait --protein --bait PROTEINS.fa [--code 5] [-k 9] ...   (six-frame peptide k-mers)\n", stderr);
         return 1;
     }
+    if (protein && !report.empty()) { fprintf(stderr, "error: --report needs a nucleotide bait (it cannot be combined with --protein)\n"); return 1; }
     if (k == 0) k = protein ? 9 : 31;
     if (libpath.empty()) { const char *e = getenv("MITOFILTER_LIB"); if (e && *e) libpath = e; }          // (as the Python wrapper and filter_v2 do)
     if (libpath.empty()) libpath = exe_dir() + "/../libmitofilter_hip.so";
@@ -488,7 +493,32 @@ static int bait_main(int argc, char **argv)
     mf::cold_mark("bait set built");
     uint64_t kept = 0, total = 0;
     setenv("MF_DEVPOOL_GB", "4096", 0);          // (a process that ends with the call gives no device memory back in between: the runtime frees it all at once)
-    int rc = device_list.empty()
+    std::vector<uint64_t> record_reads;
+    std::vector<std::string> record_names;
+    int rc;
+    if (!report.empty()) {
+#define SYM(name) auto p_##name = (decltype(&name))dlsym(h, #name); if (!p_##name) { fprintf(stderr, "error: %s lacks symbol %s\n", libpath.c_str(), #name); p_mf_kmerset_free(ks); return 2; }
+        SYM(mf_device_count) SYM(mf_kmerset_record_count) SYM(mf_kmerset_record_name) SYM(mf_filter_fastq_files_by_record)
+#undef SYM
+        uint64_t n_rec = 0;
+        rc = p_mf_kmerset_record_count(ks, &n_rec);
+        for (uint64_t i = 0; rc == MF_OK && i < n_rec; i++) {
+            size_t need = 0;
+            (void)p_mf_kmerset_record_name(ks, i, nullptr, 0, &need);
+            std::vector<char> buf(need ? need : 1);
+            rc = p_mf_kmerset_record_name(ks, i, buf.data(), buf.size(), nullptr);
+            record_names.emplace_back(buf.data());
+        }
+        if (rc == MF_OK && device_list.empty()) {          // (what mf_filter_fastq_files does with a device count: 0 .. N - 1, at most the devices there are)
+            const int have = p_mf_device_count();
+            for (int i = 0; i < std::min(std::max(devices, 1), std::max(have, 1)); i++) device_list.push_back(i);
+        }
+        record_reads.assign((size_t)n_rec + 2, 0);
+        if (rc == MF_OK)
+            rc = p_mf_filter_fastq_files_by_record(ks, fq1.c_str(), fq2.empty() ? nullptr : fq2.c_str(), out1.c_str(),
+                                                   out2.empty() ? nullptr : out2.c_str(), thr, pair == "both" ? MF_PAIR_BOTH : MF_PAIR_EITHER,
+                                                   device_list.data(), (int)device_list.size(), record_reads.data(), &kept, &total);
+    } else rc = device_list.empty()
         ? p_mf_filter_fastq_files(ks, fq1.c_str(), fq2.empty() ? nullptr : fq2.c_str(), out1.c_str(),
                                   out2.empty() ? nullptr : out2.c_str(), thr, pair == "both" ? MF_PAIR_BOTH : MF_PAIR_EITHER,
                                   devices, &kept, &total)
@@ -497,6 +527,19 @@ static int bait_main(int argc, char **argv)
                                      device_list.data(), (int)device_list.size(), &kept, &total);
     if (rc != MF_OK) { fprintf(stderr, "error: %s\n", p_mf_last_error()); p_mf_kmerset_free(ks); return 3; }
     mf::cold_mark("files filtered");
+    if (!report.empty()) {
+        FILE *f = fopen(report.c_str(), "w");
+        bool ok = f != nullptr;
+        if (ok) {
+            const size_t n_rec = record_names.size();
+            fputs("record\tname\treads\n", f);
+            for (size_t i = 0; i < n_rec; i++) fprintf(f, "%zu\t%s\t%llu\n", i, record_names[i].c_str(), (unsigned long long)record_reads[i]);
+            fprintf(f, "-\t*ambiguous*\t%llu\n-\t*unassigned*\t%llu\n", (unsigned long long)record_reads[n_rec], (unsigned long long)record_reads[n_rec + 1]);
+            ok = !ferror(f);
+            ok = fclose(f) == 0 && ok;
+        }
+        if (!ok) { fprintf(stderr, "error: cannot write the report %s\n", report.c_str()); p_mf_kmerset_free(ks); return 3; }
+    }
     printf("%llu\n", (unsigned long long)kept);      // same stdout contract as the contig filter
     // (the outputs are written and closed; what is left is the GPU runtime's teardown -- queues, code objects, a tenth of a second -- which a
     // process that is about to be gone has no use for; a profiler writes its files in a finaliser, so not under one)

@@ -6,6 +6,7 @@
 #include "mf_common.h"
 #include "mf_host.h"
 #include "mf_kernels.h"
+#include "mf_assign.h"
 #include "mf_pipeline.h"
 #include "mf_synth.h"
 #include "mf_coldtrace.h"
@@ -130,6 +131,7 @@ struct DevTables {
     uint32_t *front2 = nullptr, *front3 = nullptr, *pre = nullptr;      // bait-sized fronts of the large-bait screen (front_mode 1 .. 4); mode 4's one-bit LDS table
     KmerSetView view{};
     uint64_t n_keys = 0, n_smers = 0;
+    uint32_t *owner = nullptr;          // record owner of every slot of `keys` (mf_assign.h), built by the first call that asks for it
 };
 struct mf_kmerset {
     int k = 0, kw = 1;
@@ -568,7 +570,7 @@ int mf_kmerset_free(mf_kmerset *ks)
 {
     if (!ks) return MF_OK;
     for (auto &kv : ks->dev) {
-        if (hipSetDevice(phys(kv.first)) == hipSuccess) { hipFree(kv.second.keys); hipFree(kv.second.bloom); hipFree(kv.second.stab); hipFree(kv.second.kbloom); hipFree(kv.second.kbloom_co); hipFree(kv.second.plut); hipFree(kv.second.front2); hipFree(kv.second.front3); hipFree(kv.second.pre); }
+        if (hipSetDevice(phys(kv.first)) == hipSuccess) { hipFree(kv.second.keys); hipFree(kv.second.bloom); hipFree(kv.second.stab); hipFree(kv.second.kbloom); hipFree(kv.second.kbloom_co); hipFree(kv.second.plut); hipFree(kv.second.front2); hipFree(kv.second.front3); hipFree(kv.second.pre); hipFree(kv.second.owner); }
     }
     delete ks;
     return MF_OK;
@@ -590,6 +592,7 @@ void reads_release(mf_reads *r)
             if (r->ev_finish[i]) hipEventDestroy(r->ev_finish[i]);
         }
         hipFree(r->d_hits); hipFree(r->d_npos_blk); hipFree(r->d_off_blk);
+        hipFree(r->d_alist); hipFree(r->d_assign); hipFree(r->d_apairs); hipFree(r->d_acnt);
     }
     delete r;
 }
@@ -1055,14 +1058,125 @@ int mf_filter_packed(const mf_kmerset *ks, int device, const uint32_t *words, co
     return rc;
 }
 
+// -------------------------------------------------------- record assignment
+// The record-owner table of a set on `device` (its tables are built): made by the first call that asks for it, under the set's lock.
+// Sets that never assign reads never hold one.
+static int owner_table(mf_kmerset *ks, int device, DevTables *T)
+{
+    std::lock_guard<std::mutex> lk(ks->mu);
+    if (T->owner) return MF_OK;
+    DevCtx *ctx; int rc = get_ctx(device, &ctx); if (rc) return rc;
+    hipStream_t st = ctx->stream;
+    const BaitHost &B = ks->bait;
+    const uint32_t n_rec = (uint32_t)B.rec_len.size();
+    std::vector<uint64_t> starts((size_t)n_rec + 1, 0);
+    for (uint32_t j = 0; j < n_rec; j++) starts[j + 1] = starts[j] + B.rec_len[j];
+    DevScratch tmp;
+    uint32_t *d_words = nullptr, *d_hi = nullptr, *owner = nullptr; uint8_t *d_run = nullptr; uint64_t *d_start = nullptr;
+    HIPCHK(tmp.alloc(d_words, B.words.size() * 4));
+    HIPCHK(tmp.alloc(d_run, B.runlen.size()));
+    HIPCHK(tmp.alloc(d_start, starts.size() * 8));
+    HIPCHK(tmp.alloc(d_hi, ks->slots * 4));
+    HIPCHK(tmp.alloc(owner, ks->slots * 4));          // (released with the scratch unless the build completes)
+    HIPCHK(hipMemcpyAsync(d_words, B.words.data(), B.words.size() * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_run, B.runlen.data(), B.runlen.size(), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_start, starts.data(), starts.size() * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(launch_build_owner(BaitView{d_words, B.total, d_run}, d_start, n_rec, T->view, owner, d_hi, st));
+    HIPCHK(hipStreamSynchronize(st));
+    tmp.bufs.pop_back();
+    T->owner = owner;
+    return MF_OK;
+}
+
+// Assignment of the reads that passed the filter pass just run on this read set (its bitmap in r->d_bits[r->cur]).  assign_out: n_reads words;
+// record_reads: n_rec + 2 counts; pairs: (read << 32) | record of every passing read, in no particular order.  Each optional.
+static int assign_after_filter(mf_kmerset *ks, mf_reads *r, uint32_t *assign_out, uint64_t *record_reads, std::vector<uint64_t> *pairs)
+{
+    DevTables *T; int rc = build_on_device(ks, r->device, &T); if (rc) return rc;
+    rc = owner_table(ks, r->device, T); if (rc) return rc;
+    DevCtx *ctx; rc = get_ctx(r->device, &ctx, r->lane); if (rc) return rc;
+    hipStream_t st = ctx->stream;
+    const uint64_t n = r->v.n_reads;
+    const uint32_t n_rec = (uint32_t)ks->bait.rec_len.size();
+    const size_t n_cnt = (size_t)n_rec + 2;                          // records, ambiguous, the length of the list
+    HIPCHK(dev_reserve(r->d_acnt, r->cap_acnt, n_cnt * 8, false));
+    HIPCHK(hipMemsetAsync(r->d_acnt, 0, n_cnt * 8, st));
+    if (n) {
+        HIPCHK(dev_reserve(r->d_alist, r->cap_alist, n * 4, true));
+        if (assign_out) { HIPCHK(dev_reserve(r->d_assign, r->cap_assign, n * 4, true)); HIPCHK(hipMemsetAsync(r->d_assign, 0xFF, n * 4, st)); }
+        if (pairs) HIPCHK(dev_reserve(r->d_apairs, r->cap_apairs, n * 8, true));
+        HIPCHK(launch_pass_list(r->d_bits[r->cur], n, r->d_alist, r->d_acnt + n_rec + 1, st));
+        HIPCHK(launch_assign(r->v, T->view, T->owner, r->d_alist, r->d_acnt + n_rec + 1, n_rec, assign_out ? r->d_assign : nullptr,
+                             pairs ? r->d_apairs : nullptr, r->d_acnt, ctx->n_cu, st));
+    }
+    std::vector<unsigned long long> cnt(n_cnt, 0);
+    HIPCHK(hipMemcpyAsync(cnt.data(), r->d_acnt, n_cnt * 8, hipMemcpyDeviceToHost, st));
+    if (assign_out && n) HIPCHK(hipMemcpyAsync(assign_out, r->d_assign, n * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    const uint64_t listed = cnt[n_rec + 1];
+    if (pairs) {
+        pairs->resize(listed);
+        if (listed) { HIPCHK(hipMemcpyAsync(pairs->data(), r->d_apairs, listed * 8, hipMemcpyDeviceToHost, st)); HIPCHK(hipStreamSynchronize(st)); }
+    }
+    if (record_reads) {
+        for (uint32_t j = 0; j <= n_rec; j++) record_reads[j] = cnt[j];
+        record_reads[n_rec + 1] = n - listed;
+    }
+    return MF_OK;
+}
+
+static int need_nucleotide(const mf_kmerset *ks)
+{
+    if (!ks) return fail(MF_E_ARG, "NULL handle");
+    if (ks->kind != MF_KIND_NUCLEOTIDE) return fail(MF_E_ARG, "record assignment needs a nucleotide bait set");
+    return MF_OK;
+}
+
+extern "C" {
+
+int mf_kmerset_record_count(const mf_kmerset *ks, uint64_t *n_records)
+{
+    int rc = need_nucleotide(ks); if (rc) return rc;
+    if (!n_records) return fail(MF_E_ARG, "n_records is NULL");
+    *n_records = ks->bait.rec_len.size();
+    return MF_OK;
+}
+
+int mf_kmerset_record_name(const mf_kmerset *ks, uint64_t i, char *buf, size_t buflen, size_t *needed)
+{
+    int rc = need_nucleotide(ks); if (rc) return rc;
+    if (i >= ks->bait.names.size()) return fail(MF_E_ARG, "record %llu out of range (the set has %llu)", (unsigned long long)i, (unsigned long long)ks->bait.names.size());
+    const std::string &nm = ks->bait.names[i];
+    if (needed) *needed = nm.size() + 1;
+    if (!buf || buflen < nm.size() + 1) return fail(MF_E_ARG, "buffer too small: the name needs %llu bytes", (unsigned long long)(nm.size() + 1));
+    memcpy(buf, nm.c_str(), nm.size() + 1);
+    return MF_OK;
+}
+
+int mf_assign(const mf_kmerset *ks_, const mf_reads *reads_, uint32_t threshold, int mode, uint32_t *out_bits, uint32_t *assign_out,
+              uint64_t *record_reads, mf_filter_stats_t *stats)
+{
+    mf_kmerset *ks = const_cast<mf_kmerset *>(ks_);
+    mf_reads *r = const_cast<mf_reads *>(reads_);
+    int rc = need_nucleotide(ks); if (rc) return rc;
+    if (!r) return fail(MF_E_ARG, "NULL handle");
+    rc = filter_common(ks, r, threshold, mode, out_bits, nullptr, 1, stats);
+    if (rc) return rc;
+    return assign_after_filter(ks, r, assign_out, record_reads, nullptr);
+}
+
+} // extern "C"
+
 // ------------------------------------------------------------- file level
 // what the calling thread's last file-level call did (mf_last_ingest_stats)
 static thread_local mf_ingest_stats_t t_ingest_stats;
 static thread_local bool t_ingest_stats_valid = false;
 
 // the file-level call on a list of (logical) devices
+// tally (optional): the kept reads are counted per bait record as well (mf_filter_fastq_files_by_record), on whichever path takes the input
 static int filter_fastq_files_on(mf_kmerset *ks, const char *fq1, const char *fq2, const char *out1, const char *out2,
-                                 uint32_t threshold, int pair_mode, const int *devices, int n_devices, uint64_t *kept, uint64_t *total)
+                                 uint32_t threshold, int pair_mode, const int *devices, int n_devices, uint64_t *kept, uint64_t *total,
+                                 RecordTally *tally = nullptr)
 {
     if (!ks || !fq1 || !out1) return fail(MF_E_ARG, "NULL argument");
     if ((fq2 == nullptr) != (out2 == nullptr)) return fail(MF_E_ARG, "fq2 and out2 must be given together");
@@ -1096,7 +1210,12 @@ static int filter_fastq_files_on(mf_kmerset *ks, const char *fq1, const char *fq
         }
         if (!(ing && strcmp(ing, "host") == 0) && (force || any_gz || big_plain)) {
             std::string derr; IngestStats is;
-            const int drc = run_device_ingest(ks, fq1, fq2, out1, out2, threshold, pair_mode == MF_PAIR_BOTH, devices, n_devices, kept, total, derr, &is);
+            if (tally) tally->reads_pairs = [ks](mf_reads *R, std::vector<uint64_t> &pairs, std::string &err) -> int {
+                const int rc = assign_after_filter(ks, R, nullptr, nullptr, &pairs);
+                if (rc != MF_OK) err = t_err;
+                return rc;
+            };
+            const int drc = run_device_ingest(ks, fq1, fq2, out1, out2, threshold, pair_mode == MF_PAIR_BOTH, devices, n_devices, kept, total, derr, &is, tally);
             if (drc == MF_OK) {
                 mf_ingest_stats_t &o = t_ingest_stats;
                 memset(&o, 0, sizeof o);
@@ -1109,6 +1228,7 @@ static int filter_fastq_files_on(mf_kmerset *ks, const char *fq1, const char *fq
                 return MF_OK;
             }
             if (drc != MF_DEVINGEST_DECLINED) return fail(drc, "%s", derr.c_str());
+            if (tally) tally->reset(tally->n_rec);          // (nothing was kept on the path that declined)
             if (getenv("MF_PIPE_TIMING")) fprintf(stderr, "[mf device ingest] declined%s%s: the host pipeline takes the input\n", derr.empty() ? "" : ": ", derr.c_str());
         }
     }
@@ -1135,8 +1255,10 @@ static int filter_fastq_files_on(mf_kmerset *ks, const char *fq1, const char *fq
     const int lanes = (int)env_u32("MF_WORKERS_PER_DEVICE", 2) < 1 ? 1 : (int)env_u32("MF_WORKERS_PER_DEVICE", 2);
     const int n_workers = n_devices * lanes;
     std::vector<mf_reads *> arena((size_t)n_workers, nullptr);
-    BatchFilterFn fn = [ks, threshold, n_devices, dev_base, &arena](int worker, const PackedHost &P, uint64_t n, std::vector<uint32_t> &bits, std::string &err) -> int {
+    std::vector<uint64_t> batch_n((size_t)n_workers, 0);          // reads of the batch each worker filtered last
+    BatchFilterFn fn = [ks, threshold, n_devices, dev_base, &arena, &batch_n](int worker, const PackedHost &P, uint64_t n, std::vector<uint32_t> &bits, std::string &err) -> int {
         bits.assign((n + 31) / 32 + 1, 0);
+        batch_n[(size_t)worker] = n;
         if (n == 0) return MF_OK;
         const int device = dev_base + worker % n_devices, lane = worker / n_devices;
         DevCtx *ctx; int rc = get_ctx(device, &ctx, lane);
@@ -1151,9 +1273,16 @@ static int filter_fastq_files_on(mf_kmerset *ks, const char *fq1, const char *fq
         if (rc != MF_OK) err = t_err;
         return rc;
     };
+    if (tally) tally->worker_pairs = [ks, &arena, &batch_n](int worker, std::vector<uint64_t> &pairs, std::string &err) -> int {
+        pairs.clear();
+        if (batch_n[(size_t)worker] == 0) return MF_OK;
+        const int rc = assign_after_filter(ks, arena[(size_t)worker], nullptr, nullptr, &pairs);
+        if (rc != MF_OK) err = t_err;
+        return rc;
+    };
     PipelineStats ps; std::string perr;
     const auto t_pipe0 = std::chrono::steady_clock::now();
-    const int rc = run_fastq_pipeline(fq1, fq2, out1, out2, pair_mode == MF_PAIR_BOTH, n_workers, pack_threads, batch_reads, fn, ps, perr);
+    const int rc = run_fastq_pipeline(fq1, fq2, out1, out2, pair_mode == MF_PAIR_BOTH, n_workers, pack_threads, batch_reads, fn, ps, perr, tally);
     {
         mf_ingest_stats_t &o = t_ingest_stats;
         memset(&o, 0, sizeof o);
@@ -1189,6 +1318,20 @@ int mf_filter_fastq_files_on(mf_kmerset *ks, const char *fq1, const char *fq2, c
                              uint32_t threshold, int pair_mode, const int *devices, int n_devices, uint64_t *kept, uint64_t *total)
 {
     return filter_fastq_files_on(ks, fq1, fq2, out1, out2, threshold, pair_mode, devices, n_devices, kept, total);
+}
+
+int mf_filter_fastq_files_by_record(mf_kmerset *ks, const char *fq1, const char *fq2, const char *out1, const char *out2,
+                                    uint32_t threshold, int pair_mode, const int *devices, int n_devices,
+                                    uint64_t *record_reads, uint64_t *kept, uint64_t *total)
+{
+    int rc = need_nucleotide(ks); if (rc) return rc;
+    if (!record_reads) return fail(MF_E_ARG, "record_reads is NULL");
+    RecordTally tally;
+    tally.reset((uint32_t)ks->bait.rec_len.size());
+    rc = filter_fastq_files_on(ks, fq1, fq2, out1, out2, threshold, pair_mode, devices, n_devices, kept, total, &tally);
+    if (rc) return rc;
+    std::copy(tally.counts.begin(), tally.counts.end(), record_reads);
+    return MF_OK;
 }
 
 int mf_set_option(const char *name, const char *value)

@@ -75,6 +75,9 @@ struct mf_reads {
     int flip = 0;               // parity of the pipelined passes enqueued so far (which of two streams a pass's screen / finish kernels take)
     unsigned long long *tally_override = nullptr;       // set per pass by filter_common when every pass's tally is wanted
     size_t bitmap_bytes = 0;
+    // record assignment (mf_assign and the file-level call by record): the passing reads as a list, their records, the counters
+    uint32_t *d_alist = nullptr, *d_assign = nullptr; uint64_t *d_apairs = nullptr; unsigned long long *d_acnt = nullptr;
+    size_t cap_alist = 0, cap_assign = 0, cap_apairs = 0, cap_acnt = 0;
     // capacities (bytes), so that a handle can be refilled batch after batch without touching the allocator
     size_t cap_words = 0, cap_offsets = 0, cap_npos = 0, cap_bitmap = 0, cap_recs = 0, cap_rec_counts = 0, cap_hits = 0, cap_npos_blk = 0, cap_off_blk = 0;
 };

@@ -1,0 +1,210 @@
+// Record assignment of baited reads (gfx950, 64-wide waves).
+//
+//   build_owner_kernel   one thread per bait window: the window's slot in the key table, its record by a binary search over the record
+//                        starts, atomicMin / atomicMax of the record into two slot-indexed arrays; owner_finish_kernel keeps the record
+//                        where both agree and marks the key shared otherwise -- the same table whatever order the windows come in.
+//   pass_list_kernel     the passing reads of a pass bitmap as a list (one atomic append per non-zero bitmap word).
+//   assign_kernel        one wave per listed read, grid-stride.  Lanes take the read's windows 64 at a time: canonical key, slot,
+//                        owner.  The per-read tally u_j lives in a (record, count) map held one entry per lane in registers; a
+//                        ballot / readfirstlane leader loop folds the 64 lanes' owners into it, one distinct record per turn.  A read
+//                        that carries unique k-mers of more than 64 records is settled exactly by repeated sweeps: a full map keeps
+//                        the 64 smallest records it has seen (a record larger than all of them is skipped, the largest is evicted for
+//                        a smaller newcomer), so after a sweep the map holds exact counts of the smallest records, and the next sweep
+//                        starts behind them.
+#include "mf_assign.h"
+#include "mf_keys_dev.h"
+#include <algorithm>
+
+namespace mf {
+
+template <int KW>
+__global__ void __launch_bounds__(256)
+build_owner_kernel(BaitView B, const uint64_t *__restrict__ rec_start, uint32_t n_rec, KmerSetView S, uint32_t *__restrict__ lo,
+                   uint32_t *__restrict__ hi)
+{
+    const uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= B.total || B.runlen[p] < (uint32_t)S.k) return;          // (runlen: valid bases from p inside its record, capped at 255 >= k)
+    const uint64_t slot = table_find(S, canonical_at<KW>(B.words, p, S.k));
+    if (slot == ~0ULL) return;                                          // (cannot happen: every valid window's key is in the set)
+    uint32_t a = 0, b = n_rec;                                          // last record that starts at or before p (empty records start where the next does)
+    while (b - a > 1) { const uint32_t m = (a + b) >> 1; if (rec_start[m] <= p) a = m; else b = m; }
+    atomicMin(&lo[slot], a);
+    atomicMax(&hi[slot], a);
+}
+
+__global__ void owner_finish_kernel(uint32_t *__restrict__ lo, const uint32_t *__restrict__ hi, uint64_t slots)
+{
+    const uint64_t s = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (s < slots) { const uint32_t a = lo[s]; lo[s] = a == hi[s] ? a : OWNER_SHARED; }
+}
+
+// a thread takes PL_WPT consecutive bitmap words; the workgroup reserves its place in the list with ONE atomic (same-address atomics
+// serialise across the chip: one per non-zero word cost 0.18 ms on 33 M reads)
+constexpr int PL_BLOCK = 256, PL_WPT = 8;
+__global__ void __launch_bounds__(PL_BLOCK)
+pass_list_kernel(const uint32_t *__restrict__ bits, uint64_t n_reads, uint32_t *__restrict__ list, unsigned long long *__restrict__ n_list)
+{
+    __shared__ uint32_t s_wave[PL_BLOCK / 64];
+    __shared__ unsigned long long s_base;
+    const uint64_t n_w = (n_reads + 31) / 32;
+    const uint64_t w0 = ((uint64_t)blockIdx.x * PL_BLOCK + threadIdx.x) * PL_WPT;
+    uint32_t v[PL_WPT], cnt = 0;
+#pragma unroll
+    for (int j = 0; j < PL_WPT; j++) {
+        const uint64_t w = w0 + j;
+        v[j] = w < n_w ? bits[w] : 0u;
+        const uint64_t rem = w < n_w ? n_reads - w * 32 : 32;
+        if (rem < 32) v[j] &= (1u << rem) - 1;
+        cnt += __popc(v[j]);
+    }
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    uint32_t incl = cnt;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) { const uint32_t t = __shfl_up(incl, o); if (lane >= o) incl += t; }
+    if (lane == 63) s_wave[wid] = incl;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint32_t tot = 0;
+        for (int i = 0; i < PL_BLOCK / 64; i++) tot += s_wave[i];
+        s_base = tot ? atomicAdd(n_list, (unsigned long long)tot) : 0ull;
+    }
+    __syncthreads();
+    uint64_t at = s_base + incl - cnt;
+    for (int i = 0; i < wid; i++) at += s_wave[i];
+#pragma unroll
+    for (int j = 0; j < PL_WPT; j++)
+        for (uint32_t x = v[j]; x; x &= x - 1) list[at++] = (uint32_t)((w0 + j) * 32 + (uint32_t)(__ffs(x) - 1));
+}
+
+__device__ __forceinline__ uint32_t wave_max_u32(uint32_t v)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { const uint32_t t = __shfl_xor(v, o); v = t > v ? t : v; }
+    return v;
+}
+
+constexpr int ASSIGN_BLOCK = 512;
+constexpr uint32_t HIST_MAX = 8192;            // records + 1 up to this: the per-record counts gather in LDS first
+
+template <int KW>
+__global__ void __launch_bounds__(ASSIGN_BLOCK)
+assign_kernel(ReadsView R, KmerSetView S, const uint32_t *__restrict__ owner, const uint32_t *__restrict__ list,
+              const unsigned long long *__restrict__ n_list_p, uint32_t n_rec, uint32_t *__restrict__ assign, uint64_t *__restrict__ pairs,
+              unsigned long long *__restrict__ counts)
+{
+    // The counts: most reads of a set go to a few records, and same-address atomics serialise across the chip (one per read cost ~2 ms
+    // on 166 k passing reads): a wave adds runs of equal results, a workgroup gathers them in LDS and adds its non-zero entries at the end.
+    __shared__ uint32_t s_hist[HIST_MAX];
+    const bool lds_hist = n_rec + 1 <= HIST_MAX;
+    if (lds_hist) for (uint32_t j = threadIdx.x; j <= n_rec; j += blockDim.x) s_hist[j] = 0;
+    __syncthreads();
+    uint32_t run_rec = 0, run_cnt = 0;             // (lane 0) the current run of equal results
+    auto add = [&](uint32_t idx, uint32_t c) { if (lds_hist) atomicAdd(&s_hist[idx], c); else atomicAdd(&counts[idx], (unsigned long long)c); };
+    const int lane = threadIdx.x & 63;
+    const uint64_t n_list = *n_list_p;
+    const uint64_t n_waves = (uint64_t)gridDim.x * (ASSIGN_BLOCK / 64);
+    const int k = S.k;
+    for (uint64_t i = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6; i < n_list; i += n_waves) {
+        const uint32_t r = list[i];
+        uint64_t b0, len;
+        if (R.uniform_len) { b0 = (uint64_t)r * R.uniform_len; len = R.uniform_len; }
+        else { b0 = R.offsets[r]; len = R.offsets[r + 1] - b0; }
+        const uint64_t np = len >= (uint64_t)k ? len - k + 1 : 0;
+        const bool hasn = (R.has_n[r >> 5] >> (r & 31)) & 1u;
+        uint32_t best_cnt = 0, best_rec = ASSIGN_AMBIGUOUS; bool tie = false;
+        uint32_t lo_bound = 0;                       // the records this sweep counts: lo_bound and above
+        for (;;) {
+            uint32_t my_rec = OWNER_SHARED, my_cnt = 0;  // map entry `lane` (OWNER_SHARED: empty)
+            uint32_t n_ent = 0; bool overflow = false;
+            for (uint64_t p0 = 0; p0 < np; p0 += 64) {
+                const uint64_t p = p0 + (uint64_t)lane;
+                uint32_t id = OWNER_SHARED;
+                if (p < np) {
+                    const uint64_t g = b0 + p;
+                    bool valid = true;
+                    if (hasn) { const uint64_t ni = npos_lower_bound(R, g); valid = !(ni < R.n_npos && R.npos[ni] < g + (uint64_t)k); }
+                    if (valid) {
+                        const uint64_t slot = table_find(S, canonical_at<KW>(R.words, g, k));
+                        if (slot != ~0ULL) { const uint32_t o = owner[slot]; if (o != OWNER_SHARED && o >= lo_bound) id = o; }
+                    }
+                }
+                uint64_t pend = __ballot(id != OWNER_SHARED);
+                while (pend) {                                                         // one distinct record a turn (wave-uniform)
+                    const uint32_t L = __builtin_amdgcn_readfirstlane(__shfl(id, (int)(__ffsll((long long)pend) - 1)));
+                    const uint64_t same = __ballot(id == L);
+                    const uint32_t c = (uint32_t)__popcll(same);
+                    pend &= ~same;
+                    const uint64_t hit = __ballot(my_rec == L);
+                    if (hit) { if ((uint64_t)lane == (uint64_t)(__ffsll((long long)hit) - 1)) my_cnt += c; }
+                    else if (n_ent < 64) { if ((uint32_t)lane == n_ent) { my_rec = L; my_cnt = c; } n_ent++; }
+                    else {                                                              // full: keep the 64 smallest records
+                        overflow = true;
+                        const uint32_t mx = wave_max_u32(my_rec);
+                        if (L < mx) { if (my_rec == mx) { my_rec = L; my_cnt = c; } }
+                    }
+                }
+            }
+            // this sweep's winner, folded into the read's
+            const uint32_t cmax = wave_max_u32(my_cnt);
+            if (cmax) {
+                const uint64_t at = __ballot(my_cnt == cmax);
+                const uint32_t rec = __shfl(my_rec, (int)(__ffsll((long long)at) - 1));
+                if (cmax > best_cnt) { best_cnt = cmax; best_rec = rec; tie = __popcll(at) > 1; }
+                else if (cmax == best_cnt) tie = true;
+            }
+            if (!overflow) break;
+            lo_bound = wave_max_u32(my_rec) + 1;         // (a full map: every entry holds a record)
+        }
+        const uint32_t res = (best_cnt == 0 || tie) ? ASSIGN_AMBIGUOUS : best_rec;
+        if (lane == 0) {
+            if (assign) assign[r] = res;
+            if (pairs) pairs[i] = ((uint64_t)r << 32) | res;
+            const uint32_t idx = res == ASSIGN_AMBIGUOUS ? n_rec : res;
+            if (run_cnt && idx == run_rec) run_cnt++;
+            else { if (run_cnt) add(run_rec, run_cnt); run_rec = idx; run_cnt = 1; }
+        }
+    }
+    if (lane == 0 && run_cnt) add(run_rec, run_cnt);
+    __syncthreads();
+    if (lds_hist) for (uint32_t j = threadIdx.x; j <= n_rec; j += blockDim.x) if (s_hist[j]) atomicAdd(&counts[j], (unsigned long long)s_hist[j]);
+}
+
+static inline unsigned grid_of(uint64_t n, unsigned block) { return (unsigned)((n + block - 1) / block); }
+
+hipError_t launch_build_owner(const BaitView &B, const uint64_t *rec_start, uint32_t n_rec, const KmerSetView &S, uint32_t *owner,
+                              uint32_t *hi_scratch, hipStream_t st)
+{
+    const uint64_t slots = S.slot_mask + 1;
+    hipError_t e = hipMemsetAsync(owner, 0xFF, slots * 4, st);
+    if (e == hipSuccess) e = hipMemsetAsync(hi_scratch, 0, slots * 4, st);
+    if (e != hipSuccess) return e;
+    if (B.total && n_rec) {
+        if (S.kw == 1) hipLaunchKernelGGL(build_owner_kernel<1>, dim3(grid_of(B.total, 256)), dim3(256), 0, st, B, rec_start, n_rec, S, owner, hi_scratch);
+        else hipLaunchKernelGGL(build_owner_kernel<2>, dim3(grid_of(B.total, 256)), dim3(256), 0, st, B, rec_start, n_rec, S, owner, hi_scratch);
+    }
+    hipLaunchKernelGGL(owner_finish_kernel, dim3(grid_of(slots, 256)), dim3(256), 0, st, owner, hi_scratch, slots);
+    return hipGetLastError();
+}
+
+hipError_t launch_pass_list(const uint32_t *bits, uint64_t n_reads, uint32_t *list, unsigned long long *n_list, hipStream_t st)
+{
+    const uint64_t n_w = (n_reads + 31) / 32;
+    if (!n_w) return hipSuccess;
+    hipLaunchKernelGGL(pass_list_kernel, dim3(grid_of(n_w, PL_BLOCK * PL_WPT)), dim3(PL_BLOCK), 0, st, bits, n_reads, list, n_list);
+    return hipGetLastError();
+}
+
+hipError_t launch_assign(const ReadsView &R, const KmerSetView &S, const uint32_t *owner, const uint32_t *list, const unsigned long long *n_list,
+                         uint32_t n_rec, uint32_t *assign, uint64_t *pairs, unsigned long long *counts, int n_cu, hipStream_t st)
+{
+    if (!R.n_reads) return hipSuccess;
+    // the list's length is on the device: four workgroups (32 waves) a CU at most -- a few thousand flushes of the counts --, never
+    // more waves than reads
+    const uint64_t waves = std::min<uint64_t>((uint64_t)(n_cu > 0 ? n_cu : 1) * 32, R.n_reads);
+    const unsigned grid = grid_of(waves, ASSIGN_BLOCK / 64);
+    if (S.kw == 1) hipLaunchKernelGGL(assign_kernel<1>, dim3(grid), dim3(ASSIGN_BLOCK), 0, st, R, S, owner, list, n_list, n_rec, assign, pairs, counts);
+    else hipLaunchKernelGGL(assign_kernel<2>, dim3(grid), dim3(ASSIGN_BLOCK), 0, st, R, S, owner, list, n_list, n_rec, assign, pairs, counts);
+    return hipGetLastError();
+}
+
+} // namespace mf

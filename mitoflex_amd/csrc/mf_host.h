@@ -26,6 +26,7 @@ struct BaitHost {
     std::vector<uint8_t>  runlen;   // valid run length from each base (cap 255), 0 at invalid bases
     uint64_t total = 0;             // bases over all records (invalid ones included)
     std::vector<uint64_t> rec_len;  // per record
+    std::vector<std::string> names; // per record: header text after '>' up to the first space, tab or CR ("" for sequence before any header)
     uint64_t n_windows(int k) const;
     uint64_t n_swindows(int s) const;
 };

@@ -5,10 +5,38 @@
 #pragma once
 #include "mf_host.h"
 #include <functional>
+#include <mutex>
 #include <string>
 #include <vector>
 
+struct mf_reads;
+
 namespace mf {
+
+// Per-record counts of the kept reads of a file-level call (mf_filter_fastq_files_by_record).  The library hands the assignment in
+// through the two callbacks; the ingest paths call the one that is theirs right behind a batch's filter pass, on the read set that
+// still holds it, and tally once the pair rule has decided which reads are kept.  Pairs are (read in the batch << 32) | record, the
+// record being 0xFFFFFFFE for a passing read that no record wins; only passing reads have one.
+struct RecordTally {
+    uint32_t n_rec = 0;
+    std::vector<uint64_t> counts;               // n_rec + 2: kept reads (mates one by one) assigned to each record, ambiguous, unassigned
+    std::function<int(int worker, std::vector<uint64_t> &pairs, std::string &err)> worker_pairs;       // host pipeline: the batch `worker` has just filtered
+    std::function<int(mf_reads *reads, std::vector<uint64_t> &pairs, std::string &err)> reads_pairs;   // device ingest path: a piece's read set
+    std::mutex mu;
+    void reset(uint32_t n) { n_rec = n; counts.assign((size_t)n + 2, 0); }
+    // one mate's batch of n reads, n_kept of them kept (keep(i): read i is)
+    template <class KeepFn> void add(const std::vector<uint64_t> &pairs, uint64_t n, uint64_t n_kept, KeepFn keep)
+    {
+        std::lock_guard<std::mutex> lk(mu);
+        uint64_t assigned = 0;
+        for (const uint64_t pr : pairs) {
+            const uint64_t i = pr >> 32; const uint32_t rec = (uint32_t)pr;
+            if (i >= n || !keep(i)) continue;
+            counts[rec < n_rec ? rec : n_rec]++; assigned++;
+        }
+        counts[(size_t)n_rec + 1] += n_kept - assigned;      // kept without passing themselves (a mate kept through its partner)
+    }
+};
 
 // filter one packed mate batch on `device`; fills bits (ceil(n/32) u32).  Returns 0 or an MF_E_* code.
 using BatchFilterFn = std::function<int(int device, const PackedHost &, uint64_t n, std::vector<uint32_t> &bits, std::string &err)>;
@@ -17,7 +45,7 @@ struct PipelineStats { uint64_t kept = 0, total = 0, batches = 0; };
 
 int run_fastq_pipeline(const char *fq1, const char *fq2, const char *out1, const char *out2, bool pair_both,
                        int n_devices, int pack_threads, uint64_t batch_reads, const BatchFilterFn &filter,
-                       PipelineStats &stats, std::string &err);
+                       PipelineStats &stats, std::string &err, RecordTally *tally = nullptr);
 
 // ---------------------------------------------------------------- FASTQ quality filter (filter_v2)
 struct QualParams {

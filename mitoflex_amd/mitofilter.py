@@ -21,6 +21,9 @@ MODE_SCREENED = 0
 MODE_EXHAUSTIVE = 1
 PAIR_EITHER = 0
 PAIR_BOTH = 1
+# record assignment of a read that passes but that no record wins / of a read that does not pass (mf_assign)
+ASSIGN_AMBIGUOUS = 0xFFFFFFFE
+ASSIGN_NONE = 0xFFFFFFFF
 
 # every symbol include/mitofilter.h declares (checked by tests/test_abi.py)
 EXPORTS = (
@@ -30,6 +33,7 @@ EXPORTS = (
     "mf_kmerset_free", "mf_reads_from_packed", "mf_reads_from_fastq", "mf_reads_synth", "mf_reads_synth_ex", "mf_free_host",
     "mf_reads_info", "mf_reads_free", "mf_filter", "mf_filter_resident", "mf_filter_resident_passes", "mf_filter_packed",
     "mf_filter_fastq_files", "mf_filter_fastq_files_on", "mf_last_ingest_stats", "mf_h2d_bandwidth", "mf_set_option", "mf_qualfilter_files", "mf_release_cached",
+    "mf_kmerset_record_count", "mf_kmerset_record_name", "mf_assign", "mf_filter_fastq_files_by_record",
 )
 
 
@@ -123,6 +127,11 @@ def load(path: Optional[str] = None):
     L.mf_qualfilter_files.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_uint64, C.c_uint64, C.c_uint64,
                                       C.c_uint32, C.c_float, C.c_int, C.c_uint64, C.c_int, C.c_int, u64p, u64p,
                                       C.POINTER(C.c_int)]
+    L.mf_kmerset_record_count.argtypes = [vp, u64p]
+    L.mf_kmerset_record_name.argtypes = [vp, C.c_uint64, C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]
+    L.mf_assign.argtypes = [vp, vp, C.c_uint32, C.c_int, vp, vp, vp, C.POINTER(FilterStats)]
+    L.mf_filter_fastq_files_by_record.argtypes = [vp, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_uint32, C.c_int,
+                                                  C.POINTER(C.c_int), C.c_int, vp, u64p, u64p]
     if L.mf_abi_version() != 5:
         raise MitoFilterError("libmitofilter_hip ABI version mismatch")
     _lib = L
@@ -196,6 +205,21 @@ class KmerSet:
         i = KmerSetInfo()
         _chk(load().mf_kmerset_info(self._h, C.byref(i)))
         return i
+
+    @property
+    def record_names(self) -> list:
+        """Names of the bait's records in FASTA order (header text up to the first space, tab or CR; "" for sequence before any header)."""
+        L = load()
+        n = C.c_uint64()
+        _chk(L.mf_kmerset_record_count(self._h, C.byref(n)))
+        names = []
+        for i in range(n.value):
+            need = C.c_size_t()
+            L.mf_kmerset_record_name(self._h, i, None, 0, C.byref(need))
+            buf = C.create_string_buffer(max(need.value, 1))
+            _chk(L.mf_kmerset_record_name(self._h, i, buf, len(buf), None))
+            names.append(buf.value.decode(errors="replace"))
+        return names
 
     def export_table(self, device: int = 0) -> np.ndarray:
         i = self.info
@@ -285,6 +309,24 @@ def filter_reads(ks: KmerSet, reads: Reads, threshold: int = 1, mode: int = MODE
     return bits, (hits[:n] if want_hits else None), st
 
 
+def _n_records(ks: KmerSet) -> int:
+    n = C.c_uint64()
+    _chk(load().mf_kmerset_record_count(ks._h, C.byref(n)))
+    return n.value
+
+
+def assign_reads(ks: KmerSet, reads: Reads, threshold: int = 1, mode: int = MODE_SCREENED):
+    """One filter pass, then the bait record of every passing read.  -> (bits u32[ceil(n/32)], assign u32[n], counts u64[R + 2]):
+    assign holds a record index, ASSIGN_AMBIGUOUS or ASSIGN_NONE; counts are the reads of each record, then ambiguous, then unassigned."""
+    n = reads.info.n_reads
+    R = _n_records(ks)
+    bits = np.zeros(max((n + 31) // 32, 1), dtype=np.uint32)
+    assign = np.full(max(n, 1), ASSIGN_NONE, dtype=np.uint32)
+    counts = np.zeros(R + 2, dtype=np.uint64)
+    _chk(load().mf_assign(ks._h, reads._h, threshold, mode, bits.ctypes.data, assign.ctypes.data, counts.ctypes.data, None))
+    return bits[:(n + 31) // 32], assign[:n], counts
+
+
 def filter_resident(ks: KmerSet, reads: Reads, threshold: int = 1, mode: int = MODE_SCREENED, steps: int = 1) -> FilterStats:
     st = FilterStats()
     _chk(load().mf_filter_resident(ks._h, reads._h, threshold, mode, steps, C.byref(st)))
@@ -323,6 +365,22 @@ def filter_fastq_files(ks: KmerSet, fq1: str, fq2: Optional[str], out1: str, out
         _chk(load().mf_filter_fastq_files(ks._h, _enc(fq1), _enc(fq2), _enc(out1), _enc(out2), threshold, pair_mode,
                                           n_devices, C.byref(kept), C.byref(total)))
     return kept.value, total.value
+
+
+def filter_fastq_files_by_record(ks: KmerSet, fq1: str, fq2: Optional[str], out1: str, out2: Optional[str],
+                                 threshold: int = 1, pair_mode: int = PAIR_EITHER, devices: Optional[Sequence[int]] = None,
+                                 n_devices: int = 1):
+    """filter_fastq_files plus the bait record of every kept read.  -> (kept, total, counts u64[R + 2]): kept reads (mates one by
+    one) of each record, then ambiguous, then unassigned (a mate kept only through its partner).  devices: an explicit list of
+    device indices (instead of 0 .. n_devices - 1)."""
+    if devices is None:
+        devices = list(range(n_devices))
+    arr = (C.c_int * len(devices))(*[int(d) for d in devices])
+    counts = np.zeros(_n_records(ks) + 2, dtype=np.uint64)
+    kept, total = C.c_uint64(), C.c_uint64()
+    _chk(load().mf_filter_fastq_files_by_record(ks._h, _enc(fq1), _enc(fq2), _enc(out1), _enc(out2), threshold, pair_mode,
+                                                arr, len(devices), counts.ctypes.data, C.byref(kept), C.byref(total)))
+    return kept.value, total.value, counts
 
 
 def set_option(name: str, value) -> None:
