@@ -251,6 +251,37 @@ int mf_filter_fastq_files_by_record(mf_kmerset *ks, const char *fq1, const char 
                                     uint32_t threshold, int pair_mode, const int *devices, int n_devices,
                                     uint64_t *record_reads, uint64_t *kept, uint64_t *total);
 
+/* ---- group assignment: which GROUP of bait records the baited reads come from, for nucleotide and protein sets.  No reference
+ * counterpart.  The calls above keep their behaviour (protein sets included: MF_E_ARG).
+ * Records: protein sets follow the same record rules as nucleotide sets ('>' at a line start opens a record; its name is the header
+ * text up to the first space, tab or CR).
+ * Grouping: every record belongs to one group; groups are numbered 0 .. G-1 in order of first appearance.  By default, and after
+ * mf_kmerset_group_records(ks, NULL, 0), the grouping is the IDENTITY: each record is its own group, named after it (G = R; duplicate
+ * names are not merged).  mf_kmerset_group_records(ks, sep, f) (f >= 1) names a record's group by the f-th sep-separated token of its
+ * name, counting from 1; a name with fewer than f fields is its own group name.  (MT_database headers, gi_NC_<acc>_<GENE>_<Genus>_
+ * <species>_<len>_aa: sep "_", f = 4 groups by gene.)
+ * Windows of a read: nucleotide sets, its valid k-windows (as mf_assign); protein sets, the (frame, window) pairs that count as hits
+ * (six frames, kp codons, all sense codons, no invalid base): 2 * max(0, L - 3kp + 1) of them for a read of length L.
+ * A key is UNIQUE to group g when every record with a valid window holding it belongs to g.  A read that passes (hits >= threshold)
+ * is assigned the group with the strictly largest number of its windows whose key is unique to that group; MF_ASSIGN_AMBIGUOUS when
+ * there is none or the largest is tied; a read that does not pass: MF_ASSIGN_NONE.  Under the identity grouping a nucleotide set's
+ * grouped calls return exactly what mf_assign / mf_filter_fastq_files_by_record return.
+ * The per-slot group-owner table is built on each device by the first grouped call there; it is separate from the record-owner
+ * table, so mf_assign is unaffected by the grouping. */
+/* sep NULL or field 0: identity.  Frees the set's group-owner tables on every device: it must not run while another call uses the set. */
+int mf_kmerset_group_records(mf_kmerset *ks, const char *sep, int field);
+int mf_kmerset_group_count(const mf_kmerset *ks, uint64_t *n_groups);
+/* copies the NUL-terminated name; returns MF_E_ARG if buflen is too small and sets *needed (may be NULL) */
+int mf_kmerset_group_name(const mf_kmerset *ks, uint64_t i, char *buf, size_t buflen, size_t *needed);
+/* mf_assign by group: group_reads has G + 2 entries (each group, then ambiguous, then unassigned reads) */
+int mf_assign_groups(const mf_kmerset *ks, const mf_reads *reads, uint32_t threshold, int mode,
+                     uint32_t *out_bits, uint32_t *assign_out, uint64_t *group_reads, mf_filter_stats_t *stats);
+/* mf_filter_fastq_files_by_record by group (G + 2 u64); the same ingest path and output files byte-identical to
+ * mf_filter_fastq_files_on */
+int mf_filter_fastq_files_by_group(mf_kmerset *ks, const char *fq1, const char *fq2, const char *out1, const char *out2,
+                                   uint32_t threshold, int pair_mode, const int *devices, int n_devices,
+                                   uint64_t *group_reads, uint64_t *kept, uint64_t *total);
+
 /* Options that select which kernels a filter pass runs (process-wide; every variant gives the same bits and is parity-tested):
  *   pass=default|split|serial   adapt=0|1   finish_streams=0|1|2   screen_streams=1|2   split_pipe=0|1   exact_co=0|1
  * and, read when a k-mer set is BUILT (ABI 5; every form gives the same bits -- tests force them on small baits):

@@ -13,11 +13,13 @@
 // counterpart):
 //     fastfilter bait --bait BAIT.fa -k 31 [-t 1] --fq1 R1.fq [--fq2 R2.fq]
 //                     --out1 O1.fq [--out2 O2.fq] [--pair either|both] [--devices N]
-//                     [--report FILE]
+//                     [--report FILE | --group-report FILE [--group-field N] [--group-sep C]]
 // which loads libmitofilter_hip.so (HIP kernels, gfx950) and prints the kept
 // read/pair count.  --report writes how many kept reads (mates one by one)
 // each bait record attracted as a TSV (record, name, reads; then the
-// ambiguous and the unassigned reads); the FASTQ outputs are the same.  It has no CPU fallback: without the library or a GPU it
+// ambiguous and the unassigned reads); the FASTQ outputs are the same.  --group-report does the same per group of records
+// (group, name, reads), for protein baits too: the records themselves, or with --group-field N the N-th --group-sep separated
+// field of the record name (default separator '_'; MT_database headers by gene: --group-field 4).  It has no CPU fallback: without the library or a GPU it
 // exits non-zero, which shell_call turns into a RuntimeError (helper.py:82-86).
 #include "../../include/mitofilter.h"
 #include "mf_coldtrace.h"
@@ -429,7 +431,8 @@ static std::string exe_dir()
 
 static int bait_main(int argc, char **argv)
 {
-    std::string bait, fq1, fq2, out1, out2, pair = "either", libpath, report;
+    std::string bait, fq1, fq2, out1, out2, pair = "either", libpath, report, group_report, group_sep;
+    int group_field = -1; bool have_sep = false;
     int k = 0, devices = 1, gcode = 5; unsigned thr = 1; bool protein = false;
     std::vector<int> device_list;              // --device-list 2,3: these devices instead of 0 .. N - 1
     std::vector<std::pair<std::string, std::string>> options;      // --option pass=serial: how a filter pass is run (mf_set_option)
@@ -447,6 +450,13 @@ static int bait_main(int argc, char **argv)
         else if (o == "--pair") pair = need("--pair");
         else if (o == "--lib") libpath = need("--lib");
         else if (o == "--report") report = need("--report");
+        else if (o == "--group-report") group_report = need("--group-report");
+        else if (o == "--group-field") {
+            const std::string v = need("--group-field"); char *end = nullptr; const long x = strtol(v.c_str(), &end, 10);
+            if (v.empty() || *end || x < 1 || x > INT_MAX) { fprintf(stderr, "error: --group-field wants a field number from 1\n"); return 1; }
+            group_field = (int)x;
+        }
+        else if (o == "--group-sep") { group_sep = need("--group-sep"); have_sep = true; if (group_sep.empty()) { fprintf(stderr, "error: --group-sep wants a separator\n"); return 1; } }
         else if (o == "-k" || o == "--kmer") k = atoi(need("-k").c_str());
         else if (o == "-t" || o == "--threshold") thr = (unsigned)strtoul(need("-t").c_str(), nullptr, 10);
         else if (o == "--devices") devices = atoi(need("--devices").c_str());
@@ -466,11 +476,15 @@ static int bait_main(int argc, char **argv)
     }
     if (bait.empty() || fq1.empty() || out1.empty() || (fq2.empty() != out2.empty()) || (pair != "either" && pair != "both")) {
         fputs("usage: fastfilter bait --bait BAIT.fa [-k 31] [-t 1] --fq1 R1.fq [--fq2 R2.fq] --out1 O1.fq [--out2 O2.fq]"
-              " [--pair either|both] [--devices N | --device-list D0,D1,..] [--option name=value ..] [--report FILE]\n"
+              " [--pair either|both] [--devices N | --device-list D0,D1,..] [--option name=value ..]\n"
+              "       [--report FILE | --group-report FILE [--group-field N] [--group-sep C]]\n"
               "       fastfilter bait --protein --bait PROTEINS.fa [--code 5] [-k 9] ...   (six-frame peptide k-mers)\n", stderr);
         return 1;
     }
     if (protein && !report.empty()) { fprintf(stderr, "error: --report needs a nucleotide bait (it cannot be combined with --protein)\n"); return 1; }
+    if (!report.empty() && !group_report.empty()) { fprintf(stderr, "error: --report and --group-report cannot be combined\n"); return 1; }
+    if (group_report.empty() && (group_field >= 0 || have_sep)) { fprintf(stderr, "error: --group-field and --group-sep need --group-report\n"); return 1; }
+    if (!have_sep) group_sep = "_";
     if (k == 0) k = protein ? 9 : 31;
     if (libpath.empty()) { const char *e = getenv("MITOFILTER_LIB"); if (e && *e) libpath = e; }          // (as the Python wrapper and filter_v2 do)
     if (libpath.empty()) libpath = exe_dir() + "/../libmitofilter_hip.so";
@@ -496,17 +510,22 @@ static int bait_main(int argc, char **argv)
     std::vector<uint64_t> record_reads;
     std::vector<std::string> record_names;
     int rc;
+    const bool grouped = !group_report.empty();
+    if (grouped) report = group_report;
     if (!report.empty()) {
 #define SYM(name) auto p_##name = (decltype(&name))dlsym(h, #name); if (!p_##name) { fprintf(stderr, "error: %s lacks symbol %s\n", libpath.c_str(), #name); p_mf_kmerset_free(ks); return 2; }
         SYM(mf_device_count) SYM(mf_kmerset_record_count) SYM(mf_kmerset_record_name) SYM(mf_filter_fastq_files_by_record)
+        SYM(mf_kmerset_group_records) SYM(mf_kmerset_group_count) SYM(mf_kmerset_group_name) SYM(mf_filter_fastq_files_by_group)
 #undef SYM
         uint64_t n_rec = 0;
-        rc = p_mf_kmerset_record_count(ks, &n_rec);
+        rc = grouped ? p_mf_kmerset_group_records(ks, group_field > 0 ? group_sep.c_str() : nullptr, group_field > 0 ? group_field : 0) : MF_OK;
+        if (rc == MF_OK) rc = grouped ? p_mf_kmerset_group_count(ks, &n_rec) : p_mf_kmerset_record_count(ks, &n_rec);
+        auto name_of = grouped ? p_mf_kmerset_group_name : p_mf_kmerset_record_name;
         for (uint64_t i = 0; rc == MF_OK && i < n_rec; i++) {
             size_t need = 0;
-            (void)p_mf_kmerset_record_name(ks, i, nullptr, 0, &need);
+            (void)name_of(ks, i, nullptr, 0, &need);
             std::vector<char> buf(need ? need : 1);
-            rc = p_mf_kmerset_record_name(ks, i, buf.data(), buf.size(), nullptr);
+            rc = name_of(ks, i, buf.data(), buf.size(), nullptr);
             record_names.emplace_back(buf.data());
         }
         if (rc == MF_OK && device_list.empty()) {          // (what mf_filter_fastq_files does with a device count: 0 .. N - 1, at most the devices there are)
@@ -514,8 +533,9 @@ static int bait_main(int argc, char **argv)
             for (int i = 0; i < std::min(std::max(devices, 1), std::max(have, 1)); i++) device_list.push_back(i);
         }
         record_reads.assign((size_t)n_rec + 2, 0);
+        auto by = grouped ? p_mf_filter_fastq_files_by_group : p_mf_filter_fastq_files_by_record;
         if (rc == MF_OK)
-            rc = p_mf_filter_fastq_files_by_record(ks, fq1.c_str(), fq2.empty() ? nullptr : fq2.c_str(), out1.c_str(),
+            rc = by(ks, fq1.c_str(), fq2.empty() ? nullptr : fq2.c_str(), out1.c_str(),
                                                    out2.empty() ? nullptr : out2.c_str(), thr, pair == "both" ? MF_PAIR_BOTH : MF_PAIR_EITHER,
                                                    device_list.data(), (int)device_list.size(), record_reads.data(), &kept, &total);
     } else rc = device_list.empty()
@@ -532,7 +552,7 @@ static int bait_main(int argc, char **argv)
         bool ok = f != nullptr;
         if (ok) {
             const size_t n_rec = record_names.size();
-            fputs("record\tname\treads\n", f);
+            fputs(grouped ? "group\tname\treads\n" : "record\tname\treads\n", f);
             for (size_t i = 0; i < n_rec; i++) fprintf(f, "%zu\t%s\t%llu\n", i, record_names[i].c_str(), (unsigned long long)record_reads[i]);
             fprintf(f, "-\t*ambiguous*\t%llu\n-\t*unassigned*\t%llu\n", (unsigned long long)record_reads[n_rec], (unsigned long long)record_reads[n_rec + 1]);
             ok = !ferror(f);

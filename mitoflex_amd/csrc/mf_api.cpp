@@ -132,6 +132,7 @@ struct DevTables {
     KmerSetView view{};
     uint64_t n_keys = 0, n_smers = 0;
     uint32_t *owner = nullptr;          // record owner of every slot of `keys` (mf_assign.h), built by the first call that asks for it
+    uint32_t *gowner = nullptr;         // group owner of every slot for the set's current grouping, likewise (freed when the set is regrouped)
 };
 struct mf_kmerset {
     int k = 0, kw = 1;
@@ -147,8 +148,15 @@ struct mf_kmerset {
     int canon = 0;              // != 0: the screen's tables hold one canonical key per bait s-mer (KmerSetView::canon: 1 sixteen-base samples, 2 shorter)
     bool s8_finish = false;     // a stride-8 set whose threshold-1 passes go through screen + finish (baits beyond ~20 kbp)
     size_t screen_words() const { return ((size_t)1 << bloom_log2w) + ((size_t)1 << stage2_log2w); }
+    // grouping of the records (mf_kmerset_group_records): empty rec_group = identity (each record its own group, named after it)
+    std::vector<uint32_t> rec_group;
+    std::vector<std::string> group_names;
     std::mutex mu;
     std::map<int, DevTables> dev;
+    const std::vector<std::string> &names() const { return kind == MF_KIND_PROTEIN ? pbait.names : bait.names; }
+    uint32_t n_records() const { return (uint32_t)names().size(); }
+    uint32_t n_groups() const { return rec_group.empty() ? n_records() : (uint32_t)group_names.size(); }
+    const std::string &group_name(uint64_t i) const { return rec_group.empty() ? names()[i] : group_names[i]; }
 };
 
 // device temporaries of one build: released on every exit path
@@ -570,7 +578,7 @@ int mf_kmerset_free(mf_kmerset *ks)
 {
     if (!ks) return MF_OK;
     for (auto &kv : ks->dev) {
-        if (hipSetDevice(phys(kv.first)) == hipSuccess) { hipFree(kv.second.keys); hipFree(kv.second.bloom); hipFree(kv.second.stab); hipFree(kv.second.kbloom); hipFree(kv.second.kbloom_co); hipFree(kv.second.plut); hipFree(kv.second.front2); hipFree(kv.second.front3); hipFree(kv.second.pre); hipFree(kv.second.owner); }
+        if (hipSetDevice(phys(kv.first)) == hipSuccess) { hipFree(kv.second.keys); hipFree(kv.second.bloom); hipFree(kv.second.stab); hipFree(kv.second.kbloom); hipFree(kv.second.kbloom_co); hipFree(kv.second.plut); hipFree(kv.second.front2); hipFree(kv.second.front3); hipFree(kv.second.pre); hipFree(kv.second.owner); hipFree(kv.second.gowner); }
     }
     delete ks;
     return MF_OK;
@@ -1081,23 +1089,73 @@ static int owner_table(mf_kmerset *ks, int device, DevTables *T)
     HIPCHK(hipMemcpyAsync(d_words, B.words.data(), B.words.size() * 4, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(d_run, B.runlen.data(), B.runlen.size(), hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(d_start, starts.data(), starts.size() * 8, hipMemcpyHostToDevice, st));
-    HIPCHK(launch_build_owner(BaitView{d_words, B.total, d_run}, d_start, n_rec, T->view, owner, d_hi, st));
+    HIPCHK(launch_build_owner(BaitView{d_words, B.total, d_run}, d_start, n_rec, nullptr, T->view, owner, d_hi, st));
     HIPCHK(hipStreamSynchronize(st));
     tmp.bufs.pop_back();
     T->owner = owner;
     return MF_OK;
 }
 
+// The group-owner table of a set on `device` for its current grouping (nucleotide or protein): made by the first grouped call that asks
+// for it, under the set's lock; mf_kmerset_group_records frees it.  Separate from the record-owner table, which mf_assign keeps using.
+static int group_owner_table(mf_kmerset *ks, int device, DevTables *T)
+{
+    std::lock_guard<std::mutex> lk(ks->mu);
+    if (T->gowner) return MF_OK;
+    DevCtx *ctx; int rc = get_ctx(device, &ctx); if (rc) return rc;
+    hipStream_t st = ctx->stream;
+    const bool prot = ks->kind == MF_KIND_PROTEIN;
+    const std::vector<uint64_t> &rec_len = prot ? ks->pbait.rec_len : ks->bait.rec_len;
+    const uint32_t n_rec = (uint32_t)rec_len.size();
+    std::vector<uint64_t> starts((size_t)n_rec + 1, 0);
+    for (uint32_t j = 0; j < n_rec; j++) starts[j + 1] = starts[j] + rec_len[j];
+    DevScratch tmp;
+    uint32_t *d_hi = nullptr, *d_group = nullptr, *owner = nullptr; uint64_t *d_start = nullptr;
+    HIPCHK(tmp.alloc(d_start, starts.size() * 8));
+    HIPCHK(tmp.alloc(d_hi, ks->slots * 4));
+    HIPCHK(hipMemcpyAsync(d_start, starts.data(), starts.size() * 8, hipMemcpyHostToDevice, st));
+    if (!ks->rec_group.empty()) {
+        HIPCHK(tmp.alloc(d_group, ks->rec_group.size() * 4));
+        HIPCHK(hipMemcpyAsync(d_group, ks->rec_group.data(), ks->rec_group.size() * 4, hipMemcpyHostToDevice, st));
+    }
+    if (prot) {          // the residues and run lengths go up for the build only, as the bait's bases do for the nucleotide table
+        const ProtBaitHost &P = ks->pbait;
+        uint8_t *d_aa = nullptr, *d_run = nullptr;
+        HIPCHK(tmp.alloc(d_aa, P.aa.size()));
+        HIPCHK(tmp.alloc(d_run, P.runlen.size()));
+        HIPCHK(hipMemcpyAsync(d_aa, P.aa.data(), P.aa.size(), hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(d_run, P.runlen.data(), P.runlen.size(), hipMemcpyHostToDevice, st));
+        HIPCHK(tmp.alloc(owner, ks->slots * 4));          // (released with the scratch unless the build completes)
+        HIPCHK(launch_build_powner(d_aa, d_run, P.total, d_start, n_rec, d_group, T->view, owner, d_hi, st));
+    } else {
+        const BaitHost &B = ks->bait;
+        uint32_t *d_words = nullptr; uint8_t *d_run = nullptr;
+        HIPCHK(tmp.alloc(d_words, B.words.size() * 4));
+        HIPCHK(tmp.alloc(d_run, B.runlen.size()));
+        HIPCHK(hipMemcpyAsync(d_words, B.words.data(), B.words.size() * 4, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(d_run, B.runlen.data(), B.runlen.size(), hipMemcpyHostToDevice, st));
+        HIPCHK(tmp.alloc(owner, ks->slots * 4));
+        HIPCHK(launch_build_owner(BaitView{d_words, B.total, d_run}, d_start, n_rec, d_group, T->view, owner, d_hi, st));
+    }
+    HIPCHK(hipStreamSynchronize(st));
+    tmp.bufs.pop_back();
+    T->gowner = owner;
+    return MF_OK;
+}
+
 // Assignment of the reads that passed the filter pass just run on this read set (its bitmap in r->d_bits[r->cur]).  assign_out: n_reads words;
 // record_reads: n_rec + 2 counts; pairs: (read << 32) | record of every passing read, in no particular order.  Each optional.
-static int assign_after_filter(mf_kmerset *ks, mf_reads *r, uint32_t *assign_out, uint64_t *record_reads, std::vector<uint64_t> *pairs)
+// by_group: to the set's groups instead of its records (the group-owner table; n_rec is then the number of groups).
+static int assign_after_filter(mf_kmerset *ks, mf_reads *r, uint32_t *assign_out, uint64_t *record_reads, std::vector<uint64_t> *pairs,
+                               bool by_group = false)
 {
     DevTables *T; int rc = build_on_device(ks, r->device, &T); if (rc) return rc;
-    rc = owner_table(ks, r->device, T); if (rc) return rc;
+    rc = by_group ? group_owner_table(ks, r->device, T) : owner_table(ks, r->device, T); if (rc) return rc;
+    const uint32_t *owner = by_group ? T->gowner : T->owner;
     DevCtx *ctx; rc = get_ctx(r->device, &ctx, r->lane); if (rc) return rc;
     hipStream_t st = ctx->stream;
     const uint64_t n = r->v.n_reads;
-    const uint32_t n_rec = (uint32_t)ks->bait.rec_len.size();
+    const uint32_t n_rec = by_group ? ks->n_groups() : (uint32_t)ks->bait.rec_len.size();
     const size_t n_cnt = (size_t)n_rec + 2;                          // records, ambiguous, the length of the list
     HIPCHK(dev_reserve(r->d_acnt, r->cap_acnt, n_cnt * 8, false));
     HIPCHK(hipMemsetAsync(r->d_acnt, 0, n_cnt * 8, st));
@@ -1106,7 +1164,7 @@ static int assign_after_filter(mf_kmerset *ks, mf_reads *r, uint32_t *assign_out
         if (assign_out) { HIPCHK(dev_reserve(r->d_assign, r->cap_assign, n * 4, true)); HIPCHK(hipMemsetAsync(r->d_assign, 0xFF, n * 4, st)); }
         if (pairs) HIPCHK(dev_reserve(r->d_apairs, r->cap_apairs, n * 8, true));
         HIPCHK(launch_pass_list(r->d_bits[r->cur], n, r->d_alist, r->d_acnt + n_rec + 1, st));
-        HIPCHK(launch_assign(r->v, T->view, T->owner, r->d_alist, r->d_acnt + n_rec + 1, n_rec, assign_out ? r->d_assign : nullptr,
+        HIPCHK(launch_assign(r->v, T->view, owner, r->d_alist, r->d_acnt + n_rec + 1, n_rec, assign_out ? r->d_assign : nullptr,
                              pairs ? r->d_apairs : nullptr, r->d_acnt, ctx->n_cu, st));
     }
     std::vector<unsigned long long> cnt(n_cnt, 0);
@@ -1165,6 +1223,72 @@ int mf_assign(const mf_kmerset *ks_, const mf_reads *reads_, uint32_t threshold,
     return assign_after_filter(ks, r, assign_out, record_reads, nullptr);
 }
 
+// ------------------------------------------------------- group assignment
+int mf_kmerset_group_records(mf_kmerset *ks, const char *sep, int field)
+{
+    if (!ks) return fail(MF_E_ARG, "NULL handle");
+    if (field < 0) return fail(MF_E_ARG, "field %d is negative", field);
+    const bool identity = !sep || field == 0;
+    if (!identity && !*sep) return fail(MF_E_ARG, "the separator is empty");
+    std::vector<uint32_t> rec_group;
+    std::vector<std::string> group_names;
+    if (!identity) {          // the field-th sep-separated token of the name (from 1); the whole name when it has fewer fields
+        const std::string sp = sep;
+        std::map<std::string, uint32_t> index;
+        const std::vector<std::string> &names = ks->names();
+        rec_group.reserve(names.size());
+        for (const std::string &nm : names) {
+            size_t at = 0; int f = 1;
+            while (f < field) { const size_t q = nm.find(sp, at); if (q == std::string::npos) break; at = q + sp.size(); f++; }
+            std::string g = nm;
+            if (f == field) { const size_t q = nm.find(sp, at); g = nm.substr(at, q == std::string::npos ? std::string::npos : q - at); }
+            auto it = index.find(g);
+            if (it == index.end()) { it = index.emplace(g, (uint32_t)group_names.size()).first; group_names.push_back(g); }
+            rec_group.push_back(it->second);
+        }
+    }
+    std::lock_guard<std::mutex> lk(ks->mu);
+    for (auto &kv : ks->dev)
+        if (kv.second.gowner) {
+            HIPCHK(hipSetDevice(phys(kv.first)));
+            HIPCHK(hipFree(kv.second.gowner));
+            kv.second.gowner = nullptr;
+        }
+    ks->rec_group.swap(rec_group);
+    ks->group_names.swap(group_names);
+    return MF_OK;
+}
+
+int mf_kmerset_group_count(const mf_kmerset *ks, uint64_t *n_groups)
+{
+    if (!ks) return fail(MF_E_ARG, "NULL handle");
+    if (!n_groups) return fail(MF_E_ARG, "n_groups is NULL");
+    *n_groups = ks->n_groups();
+    return MF_OK;
+}
+
+int mf_kmerset_group_name(const mf_kmerset *ks, uint64_t i, char *buf, size_t buflen, size_t *needed)
+{
+    if (!ks) return fail(MF_E_ARG, "NULL handle");
+    if (i >= ks->n_groups()) return fail(MF_E_ARG, "group %llu out of range (the set has %llu)", (unsigned long long)i, (unsigned long long)ks->n_groups());
+    const std::string &nm = ks->group_name(i);
+    if (needed) *needed = nm.size() + 1;
+    if (!buf || buflen < nm.size() + 1) return fail(MF_E_ARG, "buffer too small: the name needs %llu bytes", (unsigned long long)(nm.size() + 1));
+    memcpy(buf, nm.c_str(), nm.size() + 1);
+    return MF_OK;
+}
+
+int mf_assign_groups(const mf_kmerset *ks_, const mf_reads *reads_, uint32_t threshold, int mode, uint32_t *out_bits, uint32_t *assign_out,
+                     uint64_t *group_reads, mf_filter_stats_t *stats)
+{
+    mf_kmerset *ks = const_cast<mf_kmerset *>(ks_);
+    mf_reads *r = const_cast<mf_reads *>(reads_);
+    if (!ks || !r) return fail(MF_E_ARG, "NULL handle");
+    int rc = filter_common(ks, r, threshold, mode, out_bits, nullptr, 1, stats);
+    if (rc) return rc;
+    return assign_after_filter(ks, r, assign_out, group_reads, nullptr, true);
+}
+
 } // extern "C"
 
 // ------------------------------------------------------------- file level
@@ -1176,7 +1300,7 @@ static thread_local bool t_ingest_stats_valid = false;
 // tally (optional): the kept reads are counted per bait record as well (mf_filter_fastq_files_by_record), on whichever path takes the input
 static int filter_fastq_files_on(mf_kmerset *ks, const char *fq1, const char *fq2, const char *out1, const char *out2,
                                  uint32_t threshold, int pair_mode, const int *devices, int n_devices, uint64_t *kept, uint64_t *total,
-                                 RecordTally *tally = nullptr)
+                                 RecordTally *tally = nullptr, bool by_group = false)
 {
     if (!ks || !fq1 || !out1) return fail(MF_E_ARG, "NULL argument");
     if ((fq2 == nullptr) != (out2 == nullptr)) return fail(MF_E_ARG, "fq2 and out2 must be given together");
@@ -1210,8 +1334,8 @@ static int filter_fastq_files_on(mf_kmerset *ks, const char *fq1, const char *fq
         }
         if (!(ing && strcmp(ing, "host") == 0) && (force || any_gz || big_plain)) {
             std::string derr; IngestStats is;
-            if (tally) tally->reads_pairs = [ks](mf_reads *R, std::vector<uint64_t> &pairs, std::string &err) -> int {
-                const int rc = assign_after_filter(ks, R, nullptr, nullptr, &pairs);
+            if (tally) tally->reads_pairs = [ks, by_group](mf_reads *R, std::vector<uint64_t> &pairs, std::string &err) -> int {
+                const int rc = assign_after_filter(ks, R, nullptr, nullptr, &pairs, by_group);
                 if (rc != MF_OK) err = t_err;
                 return rc;
             };
@@ -1273,10 +1397,10 @@ static int filter_fastq_files_on(mf_kmerset *ks, const char *fq1, const char *fq
         if (rc != MF_OK) err = t_err;
         return rc;
     };
-    if (tally) tally->worker_pairs = [ks, &arena, &batch_n](int worker, std::vector<uint64_t> &pairs, std::string &err) -> int {
+    if (tally) tally->worker_pairs = [ks, by_group, &arena, &batch_n](int worker, std::vector<uint64_t> &pairs, std::string &err) -> int {
         pairs.clear();
         if (batch_n[(size_t)worker] == 0) return MF_OK;
-        const int rc = assign_after_filter(ks, arena[(size_t)worker], nullptr, nullptr, &pairs);
+        const int rc = assign_after_filter(ks, arena[(size_t)worker], nullptr, nullptr, &pairs, by_group);
         if (rc != MF_OK) err = t_err;
         return rc;
     };
@@ -1331,6 +1455,20 @@ int mf_filter_fastq_files_by_record(mf_kmerset *ks, const char *fq1, const char 
     rc = filter_fastq_files_on(ks, fq1, fq2, out1, out2, threshold, pair_mode, devices, n_devices, kept, total, &tally);
     if (rc) return rc;
     std::copy(tally.counts.begin(), tally.counts.end(), record_reads);
+    return MF_OK;
+}
+
+int mf_filter_fastq_files_by_group(mf_kmerset *ks, const char *fq1, const char *fq2, const char *out1, const char *out2,
+                                   uint32_t threshold, int pair_mode, const int *devices, int n_devices,
+                                   uint64_t *group_reads, uint64_t *kept, uint64_t *total)
+{
+    if (!ks) return fail(MF_E_ARG, "NULL handle");
+    if (!group_reads) return fail(MF_E_ARG, "group_reads is NULL");
+    RecordTally tally;
+    tally.reset(ks->n_groups());
+    const int rc = filter_fastq_files_on(ks, fq1, fq2, out1, out2, threshold, pair_mode, devices, n_devices, kept, total, &tally, true);
+    if (rc) return rc;
+    std::copy(tally.counts.begin(), tally.counts.end(), group_reads);
     return MF_OK;
 }
 

@@ -1,8 +1,10 @@
 // Record assignment of baited reads (gfx950, 64-wide waves).
 //
 //   build_owner_kernel   one thread per bait window: the window's slot in the key table, its record by a binary search over the record
-//                        starts, atomicMin / atomicMax of the record into two slot-indexed arrays; owner_finish_kernel keeps the record
-//                        where both agree and marks the key shared otherwise -- the same table whatever order the windows come in.
+//                        starts (mapped to its group when a record -> group map is given), atomicMin / atomicMax of the result into two
+//                        slot-indexed arrays; owner_finish_kernel keeps the owner where both agree and marks the key shared otherwise --
+//                        the same table whatever order the windows come in.
+//   build_powner_kernel  the same for a protein set: one thread per residue that starts a valid window (peptide key, slot, record, group).
 //   pass_list_kernel     the passing reads of a pass bitmap as a list (one atomic append per non-zero bitmap word).
 //   assign_kernel        one wave per listed read, grid-stride.  Lanes take the read's windows 64 at a time: canonical key, slot,
 //                        owner.  The per-read tally u_j lives in a (record, count) map held one entry per lane in registers; a
@@ -11,6 +13,8 @@
 //                        the 64 smallest records it has seen (a record larger than all of them is skipped, the largest is evicted for
 //                        a smaller newcomer), so after a sweep the map holds exact counts of the smallest records, and the next sweep
 //                        starts behind them.
+//   passign_kernel       the same tally (assign_listed below, shared code) over the (strand, start) windows of a protein set: a lane
+//                        translates its window's kp codons through a 64-entry codon table in LDS into the peptide key.
 #include "mf_assign.h"
 #include "mf_keys_dev.h"
 #include <algorithm>
@@ -19,8 +23,8 @@ namespace mf {
 
 template <int KW>
 __global__ void __launch_bounds__(256)
-build_owner_kernel(BaitView B, const uint64_t *__restrict__ rec_start, uint32_t n_rec, KmerSetView S, uint32_t *__restrict__ lo,
-                   uint32_t *__restrict__ hi)
+build_owner_kernel(BaitView B, const uint64_t *__restrict__ rec_start, uint32_t n_rec, const uint32_t *__restrict__ rec_group, KmerSetView S,
+                   uint32_t *__restrict__ lo, uint32_t *__restrict__ hi)
 {
     const uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= B.total || B.runlen[p] < (uint32_t)S.k) return;          // (runlen: valid bases from p inside its record, capped at 255 >= k)
@@ -28,8 +32,27 @@ build_owner_kernel(BaitView B, const uint64_t *__restrict__ rec_start, uint32_t 
     if (slot == ~0ULL) return;                                          // (cannot happen: every valid window's key is in the set)
     uint32_t a = 0, b = n_rec;                                          // last record that starts at or before p (empty records start where the next does)
     while (b - a > 1) { const uint32_t m = (a + b) >> 1; if (rec_start[m] <= p) a = m; else b = m; }
-    atomicMin(&lo[slot], a);
-    atomicMax(&hi[slot], a);
+    const uint32_t o = rec_group ? rec_group[a] : a;
+    atomicMin(&lo[slot], o);
+    atomicMax(&hi[slot], o);
+}
+
+// protein set: one thread per residue whose run is a whole window; aa / runlen as the table builder takes them (mf_protein.hip)
+__global__ void __launch_bounds__(256)
+build_powner_kernel(const uint8_t *__restrict__ aa, const uint8_t *__restrict__ runlen, uint64_t total, const uint64_t *__restrict__ rec_start,
+                    uint32_t n_rec, const uint32_t *__restrict__ rec_group, KmerSetView S, uint32_t *__restrict__ lo, uint32_t *__restrict__ hi)
+{
+    const uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= total || runlen[p] < (uint32_t)S.k) return;
+    uint64_t v = 0;
+    for (int i = 0; i < S.k; i++) v |= (uint64_t)aa[p + i] << (5 * i);            // first residue least significant
+    const uint64_t slot = table_find(S, Key<1>{v});
+    if (slot == ~0ULL) return;
+    uint32_t a = 0, b = n_rec;
+    while (b - a > 1) { const uint32_t m = (a + b) >> 1; if (rec_start[m] <= p) a = m; else b = m; }
+    const uint32_t o = rec_group ? rec_group[a] : a;
+    atomicMin(&lo[slot], o);
+    atomicMax(&hi[slot], o);
 }
 
 __global__ void owner_finish_kernel(uint32_t *__restrict__ lo, const uint32_t *__restrict__ hi, uint64_t slots)
@@ -86,15 +109,79 @@ __device__ __forceinline__ uint32_t wave_max_u32(uint32_t v)
 constexpr int ASSIGN_BLOCK = 512;
 constexpr uint32_t HIST_MAX = 8192;            // records + 1 up to this: the per-record counts gather in LDS first
 
+// Window sources of assign_listed: begin(r) readies read r and returns its number of windows; owner_at(w) is the owner of window w's
+// key (OWNER_SHARED when the window is not valid or its key is shared).
+
+// nucleotide set: the read's k-windows, canonical keys
 template <int KW>
-__global__ void __launch_bounds__(ASSIGN_BLOCK)
-assign_kernel(ReadsView R, KmerSetView S, const uint32_t *__restrict__ owner, const uint32_t *__restrict__ list,
-              const unsigned long long *__restrict__ n_list_p, uint32_t n_rec, uint32_t *__restrict__ assign, uint64_t *__restrict__ pairs,
-              unsigned long long *__restrict__ counts)
+struct NucWindows {
+    const ReadsView &R; const KmerSetView &S; const uint32_t *__restrict__ owner; const int k;
+    uint64_t b0 = 0; bool hasn = false;
+    __device__ NucWindows(const ReadsView &R_, const KmerSetView &S_, const uint32_t *owner_) : R(R_), S(S_), owner(owner_), k(S_.k) {}
+    __device__ __forceinline__ uint64_t begin(uint32_t r)
+    {
+        uint64_t len;
+        if (R.uniform_len) { b0 = (uint64_t)r * R.uniform_len; len = R.uniform_len; }
+        else { b0 = R.offsets[r]; len = R.offsets[r + 1] - b0; }
+        hasn = (R.has_n[r >> 5] >> (r & 31)) & 1u;
+        return len >= (uint64_t)k ? len - k + 1 : 0;
+    }
+    __device__ __forceinline__ uint32_t owner_at(uint64_t p) const
+    {
+        const uint64_t g = b0 + p;
+        bool valid = true;
+        if (hasn) { const uint64_t ni = npos_lower_bound(R, g); valid = !(ni < R.n_npos && R.npos[ni] < g + (uint64_t)k); }
+        uint32_t o = OWNER_SHARED;
+        if (valid) { const uint64_t slot = table_find(S, canonical_at<KW>(R.words, g, k)); if (slot != ~0ULL) o = owner[slot]; }
+        return o;
+    }
+};
+
+// protein set: the read's (strand, start) windows of kp codons -- starts 0 .. len - 3kp forward, then the same starts on the reverse
+// strand; lut: 64 codon entries, forward residue in bits 0-4, reverse-complement residue in bits 8-12 (31: stop codon)
+struct ProtWindows {
+    const ReadsView &R; const KmerSetView &S; const uint32_t *__restrict__ owner; const uint32_t *lut;
+    uint64_t b0 = 0, np = 0; bool hasn = false;
+    __device__ ProtWindows(const ReadsView &R_, const KmerSetView &S_, const uint32_t *owner_, const uint32_t *lut_) : R(R_), S(S_), owner(owner_), lut(lut_) {}
+    __device__ __forceinline__ uint64_t begin(uint32_t r)
+    {
+        uint64_t len;
+        if (R.uniform_len) { b0 = (uint64_t)r * R.uniform_len; len = R.uniform_len; }
+        else { b0 = R.offsets[r]; len = R.offsets[r + 1] - b0; }
+        hasn = (R.has_n[r >> 5] >> (r & 31)) & 1u;
+        const uint64_t span = 3 * (uint64_t)S.k;
+        np = len >= span ? len - span + 1 : 0;
+        return 2 * np;
+    }
+    __device__ __forceinline__ uint32_t owner_at(uint64_t w) const
+    {
+        const uint32_t kp = (uint32_t)S.k;
+        const bool rev = w >= np;
+        const uint64_t g = b0 + (rev ? w - np : w);
+        if (hasn) { const uint64_t ni = npos_lower_bound(R, g); if (ni < R.n_npos && R.npos[ni] < g + 3 * (uint64_t)kp) return OWNER_SHARED; }
+        const uint32_t sh = rev ? 8u : 0u;
+        uint64_t key = 0;
+        for (uint32_t i = 0; i < kp; i++) {
+            const uint64_t bit = 2 * (g + 3 * i);
+            const uint64_t wi = bit >> 5;
+            const uint32_t c = alignbit(R.words[wi + 1], R.words[wi], (uint32_t)bit & 31) & 63u;
+            const uint32_t res = (lut[c] >> sh) & 31u;
+            if (res == 31u) return OWNER_SHARED;                           // stop codon
+            key |= (uint64_t)res << (5 * (rev ? kp - 1 - i : i));           // the reverse strand's peptide runs towards lower positions
+        }
+        const uint64_t slot = table_find(S, Key<1>{key});
+        return slot != ~0ULL ? owner[slot] : OWNER_SHARED;
+    }
+};
+
+// The listed reads, one wave each (grid-stride), tallied over the windows `src` gives: the result of every read, and the counts.
+template <class Src>
+__device__ __forceinline__ void assign_listed(Src &src, const uint32_t *__restrict__ list, const unsigned long long *__restrict__ n_list_p, uint32_t n_rec,
+                                              uint32_t *__restrict__ assign, uint64_t *__restrict__ pairs, unsigned long long *__restrict__ counts)
 {
+    __shared__ uint32_t s_hist[HIST_MAX];
     // The counts: most reads of a set go to a few records, and same-address atomics serialise across the chip (one per read cost ~2 ms
     // on 166 k passing reads): a wave adds runs of equal results, a workgroup gathers them in LDS and adds its non-zero entries at the end.
-    __shared__ uint32_t s_hist[HIST_MAX];
     const bool lds_hist = n_rec + 1 <= HIST_MAX;
     if (lds_hist) for (uint32_t j = threadIdx.x; j <= n_rec; j += blockDim.x) s_hist[j] = 0;
     __syncthreads();
@@ -103,14 +190,9 @@ assign_kernel(ReadsView R, KmerSetView S, const uint32_t *__restrict__ owner, co
     const int lane = threadIdx.x & 63;
     const uint64_t n_list = *n_list_p;
     const uint64_t n_waves = (uint64_t)gridDim.x * (ASSIGN_BLOCK / 64);
-    const int k = S.k;
     for (uint64_t i = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6; i < n_list; i += n_waves) {
         const uint32_t r = list[i];
-        uint64_t b0, len;
-        if (R.uniform_len) { b0 = (uint64_t)r * R.uniform_len; len = R.uniform_len; }
-        else { b0 = R.offsets[r]; len = R.offsets[r + 1] - b0; }
-        const uint64_t np = len >= (uint64_t)k ? len - k + 1 : 0;
-        const bool hasn = (R.has_n[r >> 5] >> (r & 31)) & 1u;
+        const uint64_t np = src.begin(r);
         uint32_t best_cnt = 0, best_rec = ASSIGN_AMBIGUOUS; bool tie = false;
         uint32_t lo_bound = 0;                       // the records this sweep counts: lo_bound and above
         for (;;) {
@@ -119,15 +201,7 @@ assign_kernel(ReadsView R, KmerSetView S, const uint32_t *__restrict__ owner, co
             for (uint64_t p0 = 0; p0 < np; p0 += 64) {
                 const uint64_t p = p0 + (uint64_t)lane;
                 uint32_t id = OWNER_SHARED;
-                if (p < np) {
-                    const uint64_t g = b0 + p;
-                    bool valid = true;
-                    if (hasn) { const uint64_t ni = npos_lower_bound(R, g); valid = !(ni < R.n_npos && R.npos[ni] < g + (uint64_t)k); }
-                    if (valid) {
-                        const uint64_t slot = table_find(S, canonical_at<KW>(R.words, g, k));
-                        if (slot != ~0ULL) { const uint32_t o = owner[slot]; if (o != OWNER_SHARED && o >= lo_bound) id = o; }
-                    }
-                }
+                if (p < np) { const uint32_t o = src.owner_at(p); if (o != OWNER_SHARED && o >= lo_bound) id = o; }
                 uint64_t pend = __ballot(id != OWNER_SHARED);
                 while (pend) {                                                         // one distinct record a turn (wave-uniform)
                     const uint32_t L = __builtin_amdgcn_readfirstlane(__shfl(id, (int)(__ffsll((long long)pend) - 1)));
@@ -169,19 +243,58 @@ assign_kernel(ReadsView R, KmerSetView S, const uint32_t *__restrict__ owner, co
     if (lds_hist) for (uint32_t j = threadIdx.x; j <= n_rec; j += blockDim.x) if (s_hist[j]) atomicAdd(&counts[j], (unsigned long long)s_hist[j]);
 }
 
+template <int KW>
+__global__ void __launch_bounds__(ASSIGN_BLOCK)
+assign_kernel(ReadsView R, KmerSetView S, const uint32_t *__restrict__ owner, const uint32_t *__restrict__ list,
+              const unsigned long long *__restrict__ n_list_p, uint32_t n_rec, uint32_t *__restrict__ assign, uint64_t *__restrict__ pairs,
+              unsigned long long *__restrict__ counts)
+{
+    NucWindows<KW> src(R, S, owner);
+    assign_listed(src, list, n_list_p, n_rec, assign, pairs, counts);
+}
+
+__global__ void __launch_bounds__(ASSIGN_BLOCK)
+passign_kernel(ReadsView R, KmerSetView S, const uint32_t *__restrict__ owner, const uint32_t *__restrict__ list,
+               const unsigned long long *__restrict__ n_list_p, uint32_t n_rec, uint32_t *__restrict__ assign, uint64_t *__restrict__ pairs,
+               unsigned long long *__restrict__ counts)
+{
+    __shared__ uint32_t s_lut[64];
+    if (threadIdx.x < 64) {              // from the filter's codon table (mf_host.cpp codon_lut_for): residue << 5 (kp - 1), reverse residue
+        const uint4 e = reinterpret_cast<const uint4 *>(S.plut)[threadIdx.x];
+        const uint32_t f = (uint32_t)((((uint64_t)e.y << 32) | e.x) >> (5 * (S.k - 1)));
+        s_lut[threadIdx.x] = (f & 31u) | ((e.z & 31u) << 8);
+    }
+    // (assign_listed synchronises the workgroup before any lane reads s_lut)
+    ProtWindows src(R, S, owner, s_lut);
+    assign_listed(src, list, n_list_p, n_rec, assign, pairs, counts);
+}
+
 static inline unsigned grid_of(uint64_t n, unsigned block) { return (unsigned)((n + block - 1) / block); }
 
-hipError_t launch_build_owner(const BaitView &B, const uint64_t *rec_start, uint32_t n_rec, const KmerSetView &S, uint32_t *owner,
-                              uint32_t *hi_scratch, hipStream_t st)
+hipError_t launch_build_owner(const BaitView &B, const uint64_t *rec_start, uint32_t n_rec, const uint32_t *rec_group, const KmerSetView &S,
+                              uint32_t *owner, uint32_t *hi_scratch, hipStream_t st)
 {
     const uint64_t slots = S.slot_mask + 1;
     hipError_t e = hipMemsetAsync(owner, 0xFF, slots * 4, st);
     if (e == hipSuccess) e = hipMemsetAsync(hi_scratch, 0, slots * 4, st);
     if (e != hipSuccess) return e;
     if (B.total && n_rec) {
-        if (S.kw == 1) hipLaunchKernelGGL(build_owner_kernel<1>, dim3(grid_of(B.total, 256)), dim3(256), 0, st, B, rec_start, n_rec, S, owner, hi_scratch);
-        else hipLaunchKernelGGL(build_owner_kernel<2>, dim3(grid_of(B.total, 256)), dim3(256), 0, st, B, rec_start, n_rec, S, owner, hi_scratch);
+        if (S.kw == 1) hipLaunchKernelGGL(build_owner_kernel<1>, dim3(grid_of(B.total, 256)), dim3(256), 0, st, B, rec_start, n_rec, rec_group, S, owner, hi_scratch);
+        else hipLaunchKernelGGL(build_owner_kernel<2>, dim3(grid_of(B.total, 256)), dim3(256), 0, st, B, rec_start, n_rec, rec_group, S, owner, hi_scratch);
     }
+    hipLaunchKernelGGL(owner_finish_kernel, dim3(grid_of(slots, 256)), dim3(256), 0, st, owner, hi_scratch, slots);
+    return hipGetLastError();
+}
+
+hipError_t launch_build_powner(const uint8_t *aa, const uint8_t *runlen, uint64_t total, const uint64_t *rec_start, uint32_t n_rec,
+                               const uint32_t *rec_group, const KmerSetView &S, uint32_t *owner, uint32_t *hi_scratch, hipStream_t st)
+{
+    const uint64_t slots = S.slot_mask + 1;
+    hipError_t e = hipMemsetAsync(owner, 0xFF, slots * 4, st);
+    if (e == hipSuccess) e = hipMemsetAsync(hi_scratch, 0, slots * 4, st);
+    if (e != hipSuccess) return e;
+    if (total && n_rec)
+        hipLaunchKernelGGL(build_powner_kernel, dim3(grid_of(total, 256)), dim3(256), 0, st, aa, runlen, total, rec_start, n_rec, rec_group, S, owner, hi_scratch);
     hipLaunchKernelGGL(owner_finish_kernel, dim3(grid_of(slots, 256)), dim3(256), 0, st, owner, hi_scratch, slots);
     return hipGetLastError();
 }
@@ -202,7 +315,8 @@ hipError_t launch_assign(const ReadsView &R, const KmerSetView &S, const uint32_
     // more waves than reads
     const uint64_t waves = std::min<uint64_t>((uint64_t)(n_cu > 0 ? n_cu : 1) * 32, R.n_reads);
     const unsigned grid = grid_of(waves, ASSIGN_BLOCK / 64);
-    if (S.kw == 1) hipLaunchKernelGGL(assign_kernel<1>, dim3(grid), dim3(ASSIGN_BLOCK), 0, st, R, S, owner, list, n_list, n_rec, assign, pairs, counts);
+    if (S.prot) hipLaunchKernelGGL(passign_kernel, dim3(grid), dim3(ASSIGN_BLOCK), 0, st, R, S, owner, list, n_list, n_rec, assign, pairs, counts);
+    else if (S.kw == 1) hipLaunchKernelGGL(assign_kernel<1>, dim3(grid), dim3(ASSIGN_BLOCK), 0, st, R, S, owner, list, n_list, n_rec, assign, pairs, counts);
     else hipLaunchKernelGGL(assign_kernel<2>, dim3(grid), dim3(ASSIGN_BLOCK), 0, st, R, S, owner, list, n_list, n_rec, assign, pairs, counts);
     return hipGetLastError();
 }

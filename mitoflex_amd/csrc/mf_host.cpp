@@ -142,15 +142,20 @@ void parse_bait_protein(const char *text, size_t len, ProtBaitHost &out)
     out = ProtBaitHost();
     std::vector<int8_t> codes; codes.reserve(len);
     std::vector<uint64_t> rec_start;
-    bool at_line_start = true, in_header = false, open = false;
+    bool at_line_start = true, in_header = false, open = false, name_done = false;
     for (size_t i = 0; i < len; i++) {
         const unsigned char c = (unsigned char)text[i];
-        if (in_header) { if (c == '\n') { in_header = false; at_line_start = true; } continue; }
-        if (at_line_start && c == '>') { rec_start.push_back(codes.size()); open = true; in_header = true; at_line_start = false; continue; }
+        if (in_header) {
+            if (c == '\n') { in_header = false; at_line_start = true; }
+            else if (c == ' ' || c == '\t' || c == '\r') name_done = true;
+            else if (!name_done) out.names.back().push_back((char)c);
+            continue;
+        }
+        if (at_line_start && c == '>') { rec_start.push_back(codes.size()); out.names.emplace_back(); name_done = false; open = true; in_header = true; at_line_start = false; continue; }
         if (c == '\n') { at_line_start = true; continue; }
         at_line_start = false;
         if (c == '\r' || c == ' ' || c == '\t' || c == '\v' || c == '\f') continue;
-        if (!open) { rec_start.push_back(codes.size()); open = true; }
+        if (!open) { rec_start.push_back(codes.size()); out.names.emplace_back(); open = true; }
         codes.push_back((int8_t)residue_code(c));
     }
     out.total = codes.size();

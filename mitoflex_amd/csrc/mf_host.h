@@ -40,6 +40,7 @@ struct ProtBaitHost {
     std::vector<uint8_t> runlen;    // valid run length from each residue (cap 255), 0 at invalid letters
     uint64_t total = 0;             // residues over all records (invalid ones included)
     std::vector<uint64_t> rec_len;
+    std::vector<std::string> names; // per record, as BaitHost::names
     uint64_t n_windows(int kp) const;
 };
 // same record rules as parse_bait_fasta; anything but the 20 standard residues (either case) is invalid

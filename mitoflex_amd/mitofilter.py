@@ -34,6 +34,7 @@ EXPORTS = (
     "mf_reads_info", "mf_reads_free", "mf_filter", "mf_filter_resident", "mf_filter_resident_passes", "mf_filter_packed",
     "mf_filter_fastq_files", "mf_filter_fastq_files_on", "mf_last_ingest_stats", "mf_h2d_bandwidth", "mf_set_option", "mf_qualfilter_files", "mf_release_cached",
     "mf_kmerset_record_count", "mf_kmerset_record_name", "mf_assign", "mf_filter_fastq_files_by_record",
+    "mf_kmerset_group_records", "mf_kmerset_group_count", "mf_kmerset_group_name", "mf_assign_groups", "mf_filter_fastq_files_by_group",
 )
 
 
@@ -132,6 +133,12 @@ def load(path: Optional[str] = None):
     L.mf_assign.argtypes = [vp, vp, C.c_uint32, C.c_int, vp, vp, vp, C.POINTER(FilterStats)]
     L.mf_filter_fastq_files_by_record.argtypes = [vp, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_uint32, C.c_int,
                                                   C.POINTER(C.c_int), C.c_int, vp, u64p, u64p]
+    L.mf_kmerset_group_records.argtypes = [vp, C.c_char_p, C.c_int]
+    L.mf_kmerset_group_count.argtypes = [vp, u64p]
+    L.mf_kmerset_group_name.argtypes = [vp, C.c_uint64, C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]
+    L.mf_assign_groups.argtypes = [vp, vp, C.c_uint32, C.c_int, vp, vp, vp, C.POINTER(FilterStats)]
+    L.mf_filter_fastq_files_by_group.argtypes = [vp, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_uint32, C.c_int,
+                                                 C.POINTER(C.c_int), C.c_int, vp, u64p, u64p]
     if L.mf_abi_version() != 5:
         raise MitoFilterError("libmitofilter_hip ABI version mismatch")
     _lib = L
@@ -218,6 +225,27 @@ class KmerSet:
             L.mf_kmerset_record_name(self._h, i, None, 0, C.byref(need))
             buf = C.create_string_buffer(max(need.value, 1))
             _chk(L.mf_kmerset_record_name(self._h, i, buf, len(buf), None))
+            names.append(buf.value.decode(errors="replace"))
+        return names
+
+    def group_records(self, sep: Optional[str] = "_", field: int = 4) -> None:
+        """Group the records by the `field`-th `sep`-separated token of their names (from 1; a name with fewer fields is its own
+        group); sep None or field 0: each record its own group (the default).  Protein and nucleotide sets alike.  Must not run
+        while another call uses the set."""
+        _chk(load().mf_kmerset_group_records(self._h, None if sep is None else sep.encode(), int(field)))
+
+    @property
+    def group_names(self) -> list:
+        """Names of the groups, numbered in order of first appearance (the record names under the identity grouping)."""
+        L = load()
+        n = C.c_uint64()
+        _chk(L.mf_kmerset_group_count(self._h, C.byref(n)))
+        names = []
+        for i in range(n.value):
+            need = C.c_size_t()
+            L.mf_kmerset_group_name(self._h, i, None, 0, C.byref(need))
+            buf = C.create_string_buffer(max(need.value, 1))
+            _chk(L.mf_kmerset_group_name(self._h, i, buf, len(buf), None))
             names.append(buf.value.decode(errors="replace"))
         return names
 
@@ -327,6 +355,25 @@ def assign_reads(ks: KmerSet, reads: Reads, threshold: int = 1, mode: int = MODE
     return bits[:(n + 31) // 32], assign[:n], counts
 
 
+def _n_groups(ks: KmerSet) -> int:
+    n = C.c_uint64()
+    _chk(load().mf_kmerset_group_count(ks._h, C.byref(n)))
+    return n.value
+
+
+def assign_groups(ks: KmerSet, reads: Reads, threshold: int = 1, mode: int = MODE_SCREENED):
+    """assign_reads by group of records (KmerSet.group_records), for protein sets too.  -> (bits u32[ceil(n/32)], assign u32[n],
+    counts u64[G + 2]): assign holds a group index, ASSIGN_AMBIGUOUS or ASSIGN_NONE; counts are the reads of each group, then
+    ambiguous, then unassigned."""
+    n = reads.info.n_reads
+    G = _n_groups(ks)
+    bits = np.zeros(max((n + 31) // 32, 1), dtype=np.uint32)
+    assign = np.full(max(n, 1), ASSIGN_NONE, dtype=np.uint32)
+    counts = np.zeros(G + 2, dtype=np.uint64)
+    _chk(load().mf_assign_groups(ks._h, reads._h, threshold, mode, bits.ctypes.data, assign.ctypes.data, counts.ctypes.data, None))
+    return bits[:(n + 31) // 32], assign[:n], counts
+
+
 def filter_resident(ks: KmerSet, reads: Reads, threshold: int = 1, mode: int = MODE_SCREENED, steps: int = 1) -> FilterStats:
     st = FilterStats()
     _chk(load().mf_filter_resident(ks._h, reads._h, threshold, mode, steps, C.byref(st)))
@@ -380,6 +427,20 @@ def filter_fastq_files_by_record(ks: KmerSet, fq1: str, fq2: Optional[str], out1
     kept, total = C.c_uint64(), C.c_uint64()
     _chk(load().mf_filter_fastq_files_by_record(ks._h, _enc(fq1), _enc(fq2), _enc(out1), _enc(out2), threshold, pair_mode,
                                                 arr, len(devices), counts.ctypes.data, C.byref(kept), C.byref(total)))
+    return kept.value, total.value, counts
+
+
+def filter_fastq_files_by_group(ks: KmerSet, fq1: str, fq2: Optional[str], out1: str, out2: Optional[str],
+                                threshold: int = 1, pair_mode: int = PAIR_EITHER, devices: Optional[Sequence[int]] = None,
+                                n_devices: int = 1):
+    """filter_fastq_files_by_record by group of records.  -> (kept, total, counts u64[G + 2])."""
+    if devices is None:
+        devices = list(range(n_devices))
+    arr = (C.c_int * len(devices))(*[int(d) for d in devices])
+    counts = np.zeros(_n_groups(ks) + 2, dtype=np.uint64)
+    kept, total = C.c_uint64(), C.c_uint64()
+    _chk(load().mf_filter_fastq_files_by_group(ks._h, _enc(fq1), _enc(fq2), _enc(out1), _enc(out2), threshold, pair_mode,
+                                               arr, len(devices), counts.ctypes.data, C.byref(kept), C.byref(total)))
     return kept.value, total.value, counts
 
 
