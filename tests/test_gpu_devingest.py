@@ -58,13 +58,13 @@ def fastq_text(seqs, prefix, crlf=False, tail=b"", last_newline=True, seed=7):
     return t
 
 
-def gz_bytes(text, level, members=1):
+def gz_bytes(text, level, members=1, strategy=zlib.Z_DEFAULT_STRATEGY, mem_level=8, wbits=15):
     """one or several gzip members; level 0 = stored blocks only"""
     if members == 1:
-        c = zlib.compressobj(level, zlib.DEFLATED, 31)
+        c = zlib.compressobj(level, zlib.DEFLATED, 16 + wbits, mem_level, strategy)
         return c.compress(text) + c.flush()
     cut = [len(text) * i // members for i in range(members + 1)]
-    return b"".join(gz_bytes(text[cut[i]:cut[i + 1]], level) for i in range(members))
+    return b"".join(gz_bytes(text[cut[i]:cut[i + 1]], level, 1, strategy, mem_level, wbits) for i in range(members))
 
 
 def run_both(mf, ol, bait_path, ks, fq1, fq2, tmp_path, thr=1, pair_mode=0):
@@ -100,6 +100,69 @@ def test_gz_levels_and_seams(mf, ol, bait_text, tmp_path, monkeypatch, level, se
         k, t = run_both(mf, ol, bait, ks, fq1, fq2, tmp_path, 1, pair_mode)
         assert t == 4000 and 0 < k < t
     run_both(mf, ol, bait, ks, fq2, None, tmp_path, 2)
+
+
+ZLIB_KINDS = {       # name: (level, strategy, memLevel, window bits, made of dynamic blocks)
+    "filtered": (6, zlib.Z_FILTERED, 8, 15, True), "huffman_only": (6, zlib.Z_HUFFMAN_ONLY, 8, 15, True), "rle": (6, zlib.Z_RLE, 8, 15, True),
+    "fixed": (6, zlib.Z_FIXED, 8, 15, False), "mem1": (6, zlib.Z_DEFAULT_STRATEGY, 1, 15, True), "mem9_l9": (9, zlib.Z_DEFAULT_STRATEGY, 9, 15, True),
+    "wbits9": (6, zlib.Z_DEFAULT_STRATEGY, 8, 9, True), "wbits12_l1": (1, zlib.Z_DEFAULT_STRATEGY, 8, 12, True),
+}
+
+
+@pytest.mark.parametrize("kind", sorted(ZLIB_KINDS))
+@pytest.mark.parametrize("seams", [False, True])
+def test_gz_strategies_and_windows(mf, ol, bait_text, tmp_path, monkeypatch, kind, seams):
+    """zlib's strategies (filtered, Huffman only, RLE, fixed codes), memLevel 1 (many small blocks) and 9, windows of 512 B and 4 KiB:
+    the oracle's bytes and counts on the device path; for streams of dynamic blocks the chunks behind the first link on the device
+    (not all bridged by the host)"""
+    if seams:
+        for k, v in SEAMS.items():
+            monkeypatch.setenv(k, v)
+    level, strategy, mem, wbits, dynamic = ZLIB_KINDS[kind]
+    bait = str(tmp_path / "bait.fa")
+    open(bait, "w").write(bait_text)
+    ks = mf.KmerSet.from_fasta(bait, 31)
+    fq1, fq2 = str(tmp_path / "z_1.fq.gz"), str(tmp_path / "z_2.fq.gz")
+    open(fq1, "wb").write(gz_bytes(fastq_text(make_reads(bait_text, 6000, seed=61), "z"), level, 1, strategy, mem, wbits))
+    open(fq2, "wb").write(gz_bytes(fastq_text(make_reads(bait_text, 6000, seed=62), "y", crlf=True), level, 1, strategy, mem, wbits))
+    k, t = run_both(mf, ol, bait, ks, fq1, fq2, tmp_path, 1, mf.PAIR_EITHER)
+    st = mf.last_ingest_stats()
+    assert t == 6000 and 0 < k < t and st["path"] == 1
+    if dynamic and seams:
+        assert st["chunks_linked"] >= 2, st
+    k1, t1 = run_both(mf, ol, bait, ks, fq1, None, tmp_path, 2)
+    if kind == "rle" and not seams:
+        monkeypatch.setenv("MF_INGEST", "host")
+        assert mf.filter_fastq_files(ks, fq1, None, str(tmp_path / "h.fq"), None, 2, 0) == (k1, t1)
+        assert open(tmp_path / "h.fq", "rb").read() == open(tmp_path / "g1.fq", "rb").read()
+
+
+@pytest.mark.parametrize("seams", [False, True])
+def test_full_window_matches(mf, ol, bait_text, tmp_path, monkeypatch, seams):
+    """A FASTQ file as libdeflate / ISA-L write them where the data repeat: a block of records padded to exactly 32 768 bytes, repeated,
+    every repeat coded as matches at distance 32 768 (zlib never reaches further back than 32 506), in dynamic blocks: every chunk
+    behind the first begins with markers into the very front of its window (tests/deflate_writer.py)"""
+    from tests import deflate_writer as W
+    if seams:
+        for k, v in SEAMS.items():
+            monkeypatch.setenv(k, v)
+    bait = str(tmp_path / "bait.fa")
+    open(bait, "w").write(bait_text)
+    ks = mf.KmerSet.from_fasta(bait, 31)
+    recs = fastq_text(make_reads(bait_text, 200, seed=71), "w")
+    recs = recs[:recs.rfind(b"@", 0, 32000)]
+    gz, text, _ = W.fastq_full_window(recs, 40, seed=72)
+    fq = str(tmp_path / "w.fq.gz")
+    open(fq, "wb").write(gz)
+    k, t = run_both(mf, ol, bait, ks, fq, None, tmp_path)
+    st = mf.last_ingest_stats()
+    assert t == 40 * (recs.count(b"\n@") + 2) and 0 < k < t and st["path"] == 1
+    if seams:
+        assert st["chunks_linked"] >= 2, st
+    if not seams:
+        monkeypatch.setenv("MF_INGEST", "host")
+        assert mf.filter_fastq_files(ks, fq, None, str(tmp_path / "h.fq"), None) == (k, t)
+        assert open(tmp_path / "h.fq", "rb").read() == open(tmp_path / "g1.fq", "rb").read()
 
 
 @pytest.mark.parametrize("seams", [False, True])
