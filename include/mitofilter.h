@@ -282,12 +282,50 @@ int mf_filter_fastq_files_by_group(mf_kmerset *ks, const char *fq1, const char *
                                    uint32_t threshold, int pair_mode, const int *devices, int n_devices,
                                    uint64_t *group_reads, uint64_t *kept, uint64_t *total);
 
+/* ---- k-mer depth along the bait records: how deep, and how evenly, the baited reads cover each record.  No reference counterpart: the
+ * reference gets a per-contig mean depth from `bwa mem | samtools depth -aa | avgdep` (findmitoscaf/findmitoscaf.py:439-467).
+ * Positions: a set's positions are the letters of its records, concatenated in file order, invalid letters included -- bases of a
+ * nucleotide set, residues of a protein set (mf_kmerset_info's n_windows does not count them; mf_kmerset_record_starts does).  Record j
+ * covers [starts[j], starts[j+1]).
+ * Valid window: position p starts a valid window when the k bases (nucleotide set) or kp residues (protein set) from p lie inside one
+ * record and none of them is invalid (the rule the table builders use).
+ * Counted reads: only the reads that pass (hits >= threshold), as mf_filter decides.
+ * Windows of a read: those of mf_assign_groups -- nucleotide sets, the valid k-windows, canonical keys; protein sets, the (frame, window)
+ * pairs that count as hits.
+ * Depth of a window: the depth of the valid window at p is the number of windows, over all counted reads, whose key equals the key of the
+ * window at p.  Nucleotide keys are canonical, so both strands count.  A key that several bait windows hold (a repeat, a k-mer shared
+ * between records) gives its full count to each of them, like a multi-mapping read; a read that holds a key twice counts twice.
+ * Profile: one uint32_t per position -- the depth of the window that starts there, clamped at 0xFFFFFFFE; MF_DEPTH_NONE where no valid
+ * window starts.
+ * Per-record summary: windows = the record's valid windows, covered = those of depth >= 1, depth_sum / depth_max = the sum and the
+ * maximum of their unclamped depths.  The mean k-mer depth is depth_sum / windows; for reads of length L it is about base depth *
+ * (L - k + 1) / L.  No base-level depth is computed.
+ * File level: every mate that passes its own threshold is counted, whether or not the pair rule keeps its pair; the pair rule decides
+ * only what is written.  A file-level profile therefore equals the sum of the in-memory profiles of the mate-1 and mate-2 read sets,
+ * before clamping.
+ * The per-slot representative table (smallest position whose valid window holds the key) and the per-position table behind it are built
+ * on each device by the first depth call there.  Sets of 2^32 - 1 positions or more: MF_E_ARG. */
+#define MF_DEPTH_NONE 0xFFFFFFFFu
+typedef struct { uint64_t windows, covered, depth_sum, depth_max; } mf_depth_record_t;
+/* R + 1 position offsets, nucleotide and protein sets alike; MF_E_ARG and *needed (may be NULL) when n is too small */
+int mf_kmerset_record_starts(const mf_kmerset *ks, uint64_t *starts, size_t n, size_t *needed);
+/* one pass like mf_filter, then depth; out_bits / profile (starts[R] u32) / records (R entries) / stats each optional */
+int mf_depth(const mf_kmerset *ks, const mf_reads *reads, uint32_t threshold, int mode,
+             uint32_t *out_bits, uint32_t *profile, mf_depth_record_t *records, mf_filter_stats_t *stats);
+/* mf_filter_fastq_files_on plus depth over the whole input; the same ingest path, output files byte-identical to it; profile / records
+ * each optional */
+int mf_filter_fastq_files_depth(mf_kmerset *ks, const char *fq1, const char *fq2, const char *out1, const char *out2,
+                                uint32_t threshold, int pair_mode, const int *devices, int n_devices,
+                                uint32_t *profile, mf_depth_record_t *records, uint64_t *kept, uint64_t *total);
+
 /* Options that select which kernels a filter pass runs (process-wide; every variant gives the same bits and is parity-tested):
  *   pass=default|split|serial   adapt=0|1   finish_streams=0|1|2   screen_streams=1|2   split_pipe=0|1   exact_co=0|1
  * and, read when a k-mer set is BUILT (ABI 5; every form gives the same bits -- tests force them on small baits):
  *   front=-1|0|1|2|3|4 (which screen; -1: by the bait's size)   canon=-1|0|1 (one canonical key per bait s-mer in the screen's tables)
  *   s8_finish=-1|0|1 (k < 28: threshold-1 passes through screen + finish)   front2_log2b=0|6..24   front3_log2b=-1|0|6..27
- *   (MF_FRONT, MF_CANON, MF_S8_FINISH, MF_FRONT2_LOG2B, MF_FRONT3_LOG2B under MF_ENV_KNOBS=1); expect_files=0|1, short_lived=0|1 (ABI 4).
+ *   (MF_FRONT, MF_CANON, MF_S8_FINISH, MF_FRONT2_LOG2B, MF_FRONT3_LOG2B under MF_ENV_KNOBS=1); expect_files=0|1, short_lived=0|1 (ABI 4);
+ *   depth_index=0|1, read when a set's depth tables are built (MF_DEPTH_INDEX): 1 counts depth per table slot instead of per
+ *   representative position -- the same results, kept to measure the scattered atomics against.
  * The library does NOT take these from the environment in a production process: the MF_PASS, MF_ADAPT, MF_FINISH_STREAMS,
  * MF_SCREEN_STREAMS, MF_SPLIT_PIPE and MF_EXACT_CO variables only count when MF_ENV_KNOBS=1 is set beside them (tests, bench.py,
  * profiling scripts).  ABI 3. */

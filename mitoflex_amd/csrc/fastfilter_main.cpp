@@ -13,14 +13,19 @@
 // counterpart):
 //     fastfilter bait --bait BAIT.fa -k 31 [-t 1] --fq1 R1.fq [--fq2 R2.fq]
 //                     --out1 O1.fq [--out2 O2.fq] [--pair either|both] [--devices N]
-//                     [--report FILE | --group-report FILE [--group-field N] [--group-sep C]]
+//                     [--report FILE | --group-report FILE [--group-field N] [--group-sep C]
+//                      | --depth-report FILE [--depth-profile FILE]]
 // which loads libmitofilter_hip.so (HIP kernels, gfx950) and prints the kept
 // read/pair count.  --report writes how many kept reads (mates one by one)
 // each bait record attracted as a TSV (record, name, reads; then the
 // ambiguous and the unassigned reads); the FASTQ outputs are the same.  --group-report does the same per group of records
 // (group, name, reads), for protein baits too: the records themselves, or with --group-field N the N-th --group-sep separated
-// field of the record name (default separator '_'; MT_database headers by gene: --group-field 4).  It has no CPU fallback: without the library or a GPU it
-// exits non-zero, which shell_call turns into a RuntimeError (helper.py:82-86).
+// field of the record name (default separator '_'; MT_database headers by gene: --group-field 4).  --depth-report and --depth-profile
+// (either alone, for protein baits too) write the K-MER depth of the bait records over every mate that passes its own threshold: per
+// record (record, name, length, valid windows, covered windows, mean and max k-mer depth), and per valid window (name, 1-based window
+// start in the record, depth: the three columns of `samtools depth -aa`, but k-mer depth, not base depth; include/mitofilter.h,
+// mf_depth).  It has no CPU fallback: without the library or a GPU it exits non-zero, which shell_call turns into a RuntimeError
+// (helper.py:82-86).
 #include "../../include/mitofilter.h"
 #include "mf_coldtrace.h"
 
@@ -431,7 +436,7 @@ static std::string exe_dir()
 
 static int bait_main(int argc, char **argv)
 {
-    std::string bait, fq1, fq2, out1, out2, pair = "either", libpath, report, group_report, group_sep;
+    std::string bait, fq1, fq2, out1, out2, pair = "either", libpath, report, group_report, group_sep, depth_report, depth_profile;
     int group_field = -1; bool have_sep = false;
     int k = 0, devices = 1, gcode = 5; unsigned thr = 1; bool protein = false;
     std::vector<int> device_list;              // --device-list 2,3: these devices instead of 0 .. N - 1
@@ -451,6 +456,8 @@ static int bait_main(int argc, char **argv)
         else if (o == "--lib") libpath = need("--lib");
         else if (o == "--report") report = need("--report");
         else if (o == "--group-report") group_report = need("--group-report");
+        else if (o == "--depth-report") depth_report = need("--depth-report");
+        else if (o == "--depth-profile") depth_profile = need("--depth-profile");
         else if (o == "--group-field") {
             const std::string v = need("--group-field"); char *end = nullptr; const long x = strtol(v.c_str(), &end, 10);
             if (v.empty() || *end || x < 1 || x > INT_MAX) { fprintf(stderr, "error: --group-field wants a field number from 1\n"); return 1; }
@@ -477,12 +484,14 @@ static int bait_main(int argc, char **argv)
     if (bait.empty() || fq1.empty() || out1.empty() || (fq2.empty() != out2.empty()) || (pair != "either" && pair != "both")) {
         fputs("usage: fastfilter bait --bait BAIT.fa [-k 31] [-t 1] --fq1 R1.fq [--fq2 R2.fq] --out1 O1.fq [--out2 O2.fq]"
               " [--pair either|both] [--devices N | --device-list D0,D1,..] [--option name=value ..]\n"
-              "       [--report FILE | --group-report FILE [--group-field N] [--group-sep C]]\n"
+              "       [--report FILE | --group-report FILE [--group-field N] [--group-sep C] | --depth-report FILE [--depth-profile FILE]]\n"
               "       fastfilter bait --protein --bait PROTEINS.fa [--code 5] [-k 9] ...   (six-frame peptide k-mers)\n", stderr);
         return 1;
     }
     if (protein && !report.empty()) { fprintf(stderr, "error: --report needs a nucleotide bait (it cannot be combined with --protein)\n"); return 1; }
     if (!report.empty() && !group_report.empty()) { fprintf(stderr, "error: --report and --group-report cannot be combined\n"); return 1; }
+    const bool depth = !depth_report.empty() || !depth_profile.empty();
+    if (depth && (!report.empty() || !group_report.empty())) { fprintf(stderr, "error: --depth-report / --depth-profile cannot be combined with --report or --group-report\n"); return 1; }
     if (group_report.empty() && (group_field >= 0 || have_sep)) { fprintf(stderr, "error: --group-field and --group-sep need --group-report\n"); return 1; }
     if (!have_sep) group_sep = "_";
     if (k == 0) k = protein ? 9 : 31;
@@ -512,7 +521,35 @@ static int bait_main(int argc, char **argv)
     int rc;
     const bool grouped = !group_report.empty();
     if (grouped) report = group_report;
-    if (!report.empty()) {
+    std::vector<uint64_t> starts;
+    std::vector<uint32_t> profile;
+    std::vector<mf_depth_record_t> depth_recs;
+    if (depth) {
+#define SYM(name) auto p_##name = (decltype(&name))dlsym(h, #name); if (!p_##name) { fprintf(stderr, "error: %s lacks symbol %s\n", libpath.c_str(), #name); p_mf_kmerset_free(ks); return 2; }
+        SYM(mf_device_count) SYM(mf_kmerset_group_count) SYM(mf_kmerset_group_name) SYM(mf_kmerset_record_starts) SYM(mf_filter_fastq_files_depth)
+#undef SYM
+        uint64_t n_rec = 0;
+        rc = p_mf_kmerset_group_count(ks, &n_rec);          // (the identity grouping: the records' own names, protein sets included)
+        for (uint64_t i = 0; rc == MF_OK && i < n_rec; i++) {
+            size_t need = 0;
+            (void)p_mf_kmerset_group_name(ks, i, nullptr, 0, &need);
+            std::vector<char> buf(need ? need : 1);
+            rc = p_mf_kmerset_group_name(ks, i, buf.data(), buf.size(), nullptr);
+            record_names.emplace_back(buf.data());
+        }
+        starts.assign((size_t)n_rec + 1, 0);
+        if (rc == MF_OK) rc = p_mf_kmerset_record_starts(ks, starts.data(), starts.size(), nullptr);
+        if (rc == MF_OK && device_list.empty()) {
+            const int have = p_mf_device_count();
+            for (int i = 0; i < std::min(std::max(devices, 1), std::max(have, 1)); i++) device_list.push_back(i);
+        }
+        profile.assign(std::max<uint64_t>(starts.back(), 1), 0);
+        depth_recs.assign(std::max<uint64_t>(n_rec, 1), mf_depth_record_t{});
+        if (rc == MF_OK)
+            rc = p_mf_filter_fastq_files_depth(ks, fq1.c_str(), fq2.empty() ? nullptr : fq2.c_str(), out1.c_str(), out2.empty() ? nullptr : out2.c_str(),
+                                               thr, pair == "both" ? MF_PAIR_BOTH : MF_PAIR_EITHER, device_list.data(), (int)device_list.size(),
+                                               profile.data(), depth_recs.data(), &kept, &total);
+    } else if (!report.empty()) {
 #define SYM(name) auto p_##name = (decltype(&name))dlsym(h, #name); if (!p_##name) { fprintf(stderr, "error: %s lacks symbol %s\n", libpath.c_str(), #name); p_mf_kmerset_free(ks); return 2; }
         SYM(mf_device_count) SYM(mf_kmerset_record_count) SYM(mf_kmerset_record_name) SYM(mf_filter_fastq_files_by_record)
         SYM(mf_kmerset_group_records) SYM(mf_kmerset_group_count) SYM(mf_kmerset_group_name) SYM(mf_filter_fastq_files_by_group)
@@ -559,6 +596,31 @@ static int bait_main(int argc, char **argv)
             ok = fclose(f) == 0 && ok;
         }
         if (!ok) { fprintf(stderr, "error: cannot write the report %s\n", report.c_str()); p_mf_kmerset_free(ks); return 3; }
+    }
+    if (!depth_report.empty()) {
+        FILE *f = fopen(depth_report.c_str(), "w");
+        bool ok = f != nullptr;
+        if (ok) {
+            fputs("record\tname\tlength\twindows\tcovered\tmean\tmax\n", f);
+            for (size_t i = 0; i < record_names.size(); i++) {
+                const mf_depth_record_t &d = depth_recs[i];
+                fprintf(f, "%zu\t%s\t%llu\t%llu\t%llu\t%.3f\t%llu\n", i, record_names[i].c_str(), (unsigned long long)(starts[i + 1] - starts[i]),
+                        (unsigned long long)d.windows, (unsigned long long)d.covered, d.windows ? (double)d.depth_sum / (double)d.windows : 0.0,
+                        (unsigned long long)d.depth_max);
+            }
+            ok = !ferror(f);
+            ok = fclose(f) == 0 && ok;
+        }
+        if (!ok) { fprintf(stderr, "error: cannot write the depth report %s\n", depth_report.c_str()); p_mf_kmerset_free(ks); return 3; }
+    }
+    if (!depth_profile.empty()) {
+        FILE *f = fopen(depth_profile.c_str(), "w");
+        bool ok = f != nullptr;
+        for (size_t i = 0; ok && i < record_names.size(); i++)
+            for (uint64_t p = starts[i]; p < starts[i + 1]; p++)
+                if (profile[p] != MF_DEPTH_NONE) fprintf(f, "%s\t%llu\t%u\n", record_names[i].c_str(), (unsigned long long)(p - starts[i] + 1), profile[p]);
+        if (ok) { ok = !ferror(f); ok = fclose(f) == 0 && ok; }
+        if (!ok) { fprintf(stderr, "error: cannot write the depth profile %s\n", depth_profile.c_str()); p_mf_kmerset_free(ks); return 3; }
     }
     printf("%llu\n", (unsigned long long)kept);      // same stdout contract as the contig filter
     // (the outputs are written and closed; what is left is the GPU runtime's teardown -- queues, code objects, a tenth of a second -- which a

@@ -133,6 +133,9 @@ struct DevTables {
     uint64_t n_keys = 0, n_smers = 0;
     uint32_t *owner = nullptr;          // record owner of every slot of `keys` (mf_assign.h), built by the first call that asks for it
     uint32_t *gowner = nullptr;         // group owner of every slot for the set's current grouping, likewise (freed when the set is regrouped)
+    // k-mer depth (mf_depth), built by the first depth call: representative position of every slot, of every bait position's window, and
+    // the profile kernel's work items; dcnt_n counters a pass (the positions, or the slots under depth_index=1)
+    uint32_t *rep = nullptr, *pos_rep = nullptr; DepthItem *ditems = nullptr; uint32_t n_ditems = 0; uint64_t dcnt_n = 0;
 };
 struct mf_kmerset {
     int k = 0, kw = 1;
@@ -157,6 +160,8 @@ struct mf_kmerset {
     uint32_t n_records() const { return (uint32_t)names().size(); }
     uint32_t n_groups() const { return rec_group.empty() ? n_records() : (uint32_t)group_names.size(); }
     const std::string &group_name(uint64_t i) const { return rec_group.empty() ? names()[i] : group_names[i]; }
+    const std::vector<uint64_t> &rec_len() const { return kind == MF_KIND_PROTEIN ? pbait.rec_len : bait.rec_len; }
+    uint64_t positions() const { return kind == MF_KIND_PROTEIN ? pbait.total : bait.total; }       // bases / residues of all records
 };
 
 // device temporaries of one build: released on every exit path
@@ -212,6 +217,9 @@ struct PassOptions {
     std::atomic<int> s8_finish{-1};       // the stride-8 geometries (k < 28) through screen + finish instead of the candidate bitmap: -1 by the bait's size | 0 | 1   "s8_finish"   MF_S8_FINISH
     std::atomic<int> canon{-1};           // -1 by the bait's size | 0 both strands in the screen's tables | 1 one canonical key per s-mer (16-base samples only)             "canon"          MF_CANON
     std::atomic<int> front3_log2b{-1};    // -1 by the bait's size | 0 none | log2 of front3's blocks (6..27)                       "front3_log2b"   MF_FRONT3_LOG2B
+    // read when a set's depth tables are built: 0 depth counters per representative bait position | 1 per slot (the scattered form, kept
+    // to measure against: tools/bench_depth.py)                                                                   "depth_index"    MF_DEPTH_INDEX
+    std::atomic<int> depth_index{0};
 };
 static PassOptions g_opt;
 static int set_option(const char *name, const char *value)
@@ -232,6 +240,7 @@ static int set_option(const char *name, const char *value)
     else if (n == "s8_finish") { if (x < -1 || x > 1) return -1; g_opt.s8_finish = (int)x; }
     else if (n == "canon") { if (x < -1 || x > 1) return -1; g_opt.canon = (int)x; }
     else if (n == "front3_log2b") { if (x < -1 || (x > 0 && x < 6) || x > 27) return -1; g_opt.front3_log2b = (int)x; }
+    else if (n == "depth_index") { if (x < 0 || x > 1) return -1; g_opt.depth_index = (int)x; }
     else return -1;
     return 0;
 }
@@ -242,7 +251,8 @@ static void options_from_env_once()
         if (k && k[0] == '1') {
             static const char *const pairs[][2] = {{"pass", "MF_PASS"}, {"adapt", "MF_ADAPT"}, {"finish_streams", "MF_FINISH_STREAMS"}, {"screen_streams", "MF_SCREEN_STREAMS"},
                                                    {"split_pipe", "MF_SPLIT_PIPE"}, {"exact_co", "MF_EXACT_CO"},
-                                                   {"front", "MF_FRONT"}, {"front2_log2b", "MF_FRONT2_LOG2B"}, {"front3_log2b", "MF_FRONT3_LOG2B"}, {"canon", "MF_CANON"}, {"s8_finish", "MF_S8_FINISH"}};
+                                                   {"front", "MF_FRONT"}, {"front2_log2b", "MF_FRONT2_LOG2B"}, {"front3_log2b", "MF_FRONT3_LOG2B"}, {"canon", "MF_CANON"}, {"s8_finish", "MF_S8_FINISH"},
+                                                   {"depth_index", "MF_DEPTH_INDEX"}};
             for (auto &p : pairs) { const char *v = getenv(p[1]); if (v && *v && set_option(p[0], v) != 0) fprintf(stderr, "libmitofilter_hip: %s=%s is not a value of option '%s' (ignored)\n", p[1], v, p[0]); }
         }
         return true;
@@ -578,7 +588,7 @@ int mf_kmerset_free(mf_kmerset *ks)
 {
     if (!ks) return MF_OK;
     for (auto &kv : ks->dev) {
-        if (hipSetDevice(phys(kv.first)) == hipSuccess) { hipFree(kv.second.keys); hipFree(kv.second.bloom); hipFree(kv.second.stab); hipFree(kv.second.kbloom); hipFree(kv.second.kbloom_co); hipFree(kv.second.plut); hipFree(kv.second.front2); hipFree(kv.second.front3); hipFree(kv.second.pre); hipFree(kv.second.owner); hipFree(kv.second.gowner); }
+        if (hipSetDevice(phys(kv.first)) == hipSuccess) { hipFree(kv.second.keys); hipFree(kv.second.bloom); hipFree(kv.second.stab); hipFree(kv.second.kbloom); hipFree(kv.second.kbloom_co); hipFree(kv.second.plut); hipFree(kv.second.front2); hipFree(kv.second.front3); hipFree(kv.second.pre); hipFree(kv.second.owner); hipFree(kv.second.gowner); hipFree(kv.second.rep); hipFree(kv.second.pos_rep); hipFree(kv.second.ditems); }
     }
     delete ks;
     return MF_OK;
@@ -601,6 +611,7 @@ void reads_release(mf_reads *r)
         }
         hipFree(r->d_hits); hipFree(r->d_npos_blk); hipFree(r->d_off_blk);
         hipFree(r->d_alist); hipFree(r->d_assign); hipFree(r->d_apairs); hipFree(r->d_acnt);
+        hipFree(r->d_dcnt); hipFree(r->d_dtot); hipFree(r->d_drec);
     }
     delete r;
 }
@@ -1291,16 +1302,171 @@ int mf_assign_groups(const mf_kmerset *ks_, const mf_reads *reads_, uint32_t thr
 
 } // extern "C"
 
+// ------------------------------------------------------------------- k-mer depth
+// The depth tables of a set on `device` (nucleotide or protein): made by the first depth call there, under the set's lock.
+static int depth_tables(mf_kmerset *ks, int device, DevTables *T)
+{
+    std::lock_guard<std::mutex> lk(ks->mu);
+    if (T->rep) return MF_OK;
+    const uint64_t total = ks->positions();
+    if (total >= DEPTH_NONE || ks->slots > DEPTH_NONE) return fail(MF_E_ARG, "k-mer depth takes sets of fewer than 2^32 - 1 positions and slots");
+    DevCtx *ctx; int rc = get_ctx(device, &ctx); if (rc) return rc;
+    hipStream_t st = ctx->stream;
+    const bool prot = ks->kind == MF_KIND_PROTEIN;
+    const bool by_slot = g_opt.depth_index.load() == 1;
+    std::vector<DepthItem> items;
+    const std::vector<uint64_t> &rec_len = ks->rec_len();
+    for (uint64_t j = 0, at = 0; j < rec_len.size(); at += rec_len[j], j++)
+        for (uint64_t a = 0; a < rec_len[j]; a += DEPTH_ITEM) items.push_back(DepthItem{at + a, (uint32_t)std::min<uint64_t>(DEPTH_ITEM, rec_len[j] - a), (uint32_t)j});
+    DevScratch tmp;
+    uint32_t *rep = nullptr, *pos_rep = nullptr; DepthItem *d_items = nullptr;
+    const uint64_t n_cnt = by_slot ? std::max<uint64_t>(ks->slots, total) : total;
+    // (the tables are released with the scratch unless the build completes: they go in first, and leave it last)
+    HIPCHK(tmp.alloc(rep, ks->slots * 4));
+    HIPCHK(tmp.alloc(pos_rep, std::max<uint64_t>(total, 1) * 4));
+    HIPCHK(tmp.alloc(d_items, std::max<size_t>(items.size(), 1) * sizeof(DepthItem)));
+    const size_t keep = tmp.bufs.size();
+    if (!items.empty()) HIPCHK(hipMemcpyAsync(d_items, items.data(), items.size() * sizeof(DepthItem), hipMemcpyHostToDevice, st));
+    if (prot) {          // the residues and run lengths go up for the build only
+        const ProtBaitHost &P = ks->pbait;
+        uint8_t *d_aa = nullptr, *d_run = nullptr;
+        HIPCHK(tmp.alloc(d_aa, P.aa.size()));
+        HIPCHK(tmp.alloc(d_run, P.runlen.size()));
+        HIPCHK(hipMemcpyAsync(d_aa, P.aa.data(), P.aa.size(), hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(d_run, P.runlen.data(), P.runlen.size(), hipMemcpyHostToDevice, st));
+        HIPCHK(launch_build_depth(BaitView{nullptr, P.total, d_run}, d_aa, T->view, rep, pos_rep, by_slot, st));
+    } else {
+        const BaitHost &B = ks->bait;
+        uint32_t *d_words = nullptr; uint8_t *d_run = nullptr;
+        HIPCHK(tmp.alloc(d_words, B.words.size() * 4));
+        HIPCHK(tmp.alloc(d_run, B.runlen.size()));
+        HIPCHK(hipMemcpyAsync(d_words, B.words.data(), B.words.size() * 4, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(d_run, B.runlen.data(), B.runlen.size(), hipMemcpyHostToDevice, st));
+        HIPCHK(launch_build_depth(BaitView{d_words, B.total, d_run}, nullptr, T->view, rep, pos_rep, by_slot, st));
+    }
+    HIPCHK(hipStreamSynchronize(st));
+    tmp.bufs.erase(tmp.bufs.begin(), tmp.bufs.begin() + keep);
+    T->rep = rep; T->pos_rep = pos_rep; T->ditems = d_items; T->n_ditems = (uint32_t)items.size(); T->dcnt_n = n_cnt;
+    return MF_OK;
+}
+
+// The windows of the reads that passed the filter pass just run on this read set (its bitmap in r->d_bits[r->cur]) added into tot
+// (T->dcnt_n u64 counters on r's device, which other read sets there may be adding into at the same time).  Ends synchronised.
+static int depth_after_filter(mf_kmerset *ks, mf_reads *r, unsigned long long *tot)
+{
+    DevTables *T; int rc = build_on_device(ks, r->device, &T); if (rc) return rc;
+    rc = depth_tables(ks, r->device, T); if (rc) return rc;
+    DevCtx *ctx; rc = get_ctx(r->device, &ctx, r->lane); if (rc) return rc;
+    hipStream_t st = ctx->stream;
+    const uint64_t n = r->v.n_reads, n_cnt = T->dcnt_n;
+    if (!n || !n_cnt) return MF_OK;
+    // a 32-bit counter holds every window of the read set unless they could number 2^32: then the windows go straight into tot
+    const uint64_t span = ks->kind == MF_KIND_PROTEIN ? 3 * (uint64_t)ks->k : (uint64_t)ks->k;
+    const uint64_t per = r->v.uniform_len ? (r->v.uniform_len >= span ? r->v.uniform_len - span + 1 : 0) : 0;
+    const uint64_t bound = (r->v.uniform_len ? n * per : r->v.total_bases) * (ks->kind == MF_KIND_PROTEIN ? 2 : 1);
+    const bool wide = bound >= DEPTH_NONE;
+    HIPCHK(dev_reserve(r->d_acnt, r->cap_acnt, 8, false));
+    HIPCHK(hipMemsetAsync(r->d_acnt, 0, 8, st));
+    HIPCHK(dev_reserve(r->d_alist, r->cap_alist, n * 4, true));
+    if (!wide) { HIPCHK(dev_reserve(r->d_dcnt, r->cap_dcnt, n_cnt * 4, false)); HIPCHK(hipMemsetAsync(r->d_dcnt, 0, n_cnt * 4, st)); }
+    HIPCHK(launch_pass_list(r->d_bits[r->cur], n, r->d_alist, r->d_acnt, st));
+    HIPCHK(launch_depth_count(r->v, T->view, T->rep, r->d_alist, r->d_acnt, wide ? nullptr : r->d_dcnt, wide ? tot : nullptr, ctx->n_cu, st));
+    if (!wide) HIPCHK(launch_depth_fold(r->d_dcnt, n_cnt, tot, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return MF_OK;
+}
+
+// The profile (ks->positions() u32) and the record summaries (R entries) from the totals tot on `device` (stream st); each optional.
+static int depth_report(mf_kmerset *ks, int device, hipStream_t st, const unsigned long long *tot, uint32_t *d_prof, unsigned long long *d_rec,
+                        uint32_t *profile, mf_depth_record_t *records)
+{
+    DevTables *T; int rc = build_on_device(ks, device, &T); if (rc) return rc;
+    rc = depth_tables(ks, device, T); if (rc) return rc;
+    const uint64_t total = ks->positions(), n_rec = ks->rec_len().size();
+    if (records && n_rec) HIPCHK(hipMemsetAsync(d_rec, 0, n_rec * 32, st));
+    if (profile && total) HIPCHK(hipMemsetAsync(d_prof, 0xFF, total * 4, st));          // (records with no item: none, they are empty)
+    HIPCHK(launch_depth_profile(T->ditems, T->n_ditems, T->pos_rep, tot, profile ? d_prof : nullptr, records ? d_rec : nullptr, st));
+    if (profile && total) HIPCHK(hipMemcpyAsync(profile, d_prof, total * 4, hipMemcpyDeviceToHost, st));
+    if (records && n_rec) HIPCHK(hipMemcpyAsync(records, d_rec, n_rec * 32, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return MF_OK;
+}
+
+extern "C" {
+
+int mf_kmerset_record_starts(const mf_kmerset *ks, uint64_t *starts, size_t n, size_t *needed)
+{
+    if (!ks) return fail(MF_E_ARG, "NULL handle");
+    const std::vector<uint64_t> &len = ks->rec_len();
+    if (needed) *needed = len.size() + 1;
+    if (!starts || n < len.size() + 1) return fail(MF_E_ARG, "buffer too small: the set has %llu records, %llu offsets", (unsigned long long)len.size(), (unsigned long long)(len.size() + 1));
+    starts[0] = 0;
+    for (size_t j = 0; j < len.size(); j++) starts[j + 1] = starts[j] + len[j];
+    return MF_OK;
+}
+
+int mf_depth(const mf_kmerset *ks_, const mf_reads *reads_, uint32_t threshold, int mode, uint32_t *out_bits, uint32_t *profile,
+             mf_depth_record_t *records, mf_filter_stats_t *stats)
+{
+    mf_kmerset *ks = const_cast<mf_kmerset *>(ks_);
+    mf_reads *r = const_cast<mf_reads *>(reads_);
+    if (!ks || !r) return fail(MF_E_ARG, "NULL handle");
+    int rc = filter_common(ks, r, threshold, mode, out_bits, nullptr, 1, stats);
+    if (rc) return rc;
+    DevTables *T; rc = build_on_device(ks, r->device, &T); if (rc) return rc;
+    rc = depth_tables(ks, r->device, T); if (rc) return rc;
+    DevCtx *ctx; rc = get_ctx(r->device, &ctx, r->lane); if (rc) return rc;
+    hipStream_t st = ctx->stream;
+    const uint64_t n_cnt = T->dcnt_n, total = ks->positions(), n_rec = ks->rec_len().size();
+    HIPCHK(dev_reserve(r->d_dtot, r->cap_dtot, std::max<uint64_t>(n_cnt, 1) * 8, false));
+    HIPCHK(hipMemsetAsync(r->d_dtot, 0, std::max<uint64_t>(n_cnt, 1) * 8, st));
+    rc = depth_after_filter(ks, r, r->d_dtot); if (rc) return rc;
+    // (the profile goes through the pass's 32-bit counters, which the totals have taken up)
+    HIPCHK(dev_reserve(r->d_dcnt, r->cap_dcnt, std::max<uint64_t>(std::max(n_cnt, total), 1) * 4, false));
+    HIPCHK(dev_reserve(r->d_drec, r->cap_drec, std::max<uint64_t>(n_rec, 1) * 32, false));
+    return depth_report(ks, r->device, st, r->d_dtot, r->d_dcnt, r->d_drec, profile, records);
+}
+
+} // extern "C"
+
 // ------------------------------------------------------------- file level
 // what the calling thread's last file-level call did (mf_last_ingest_stats)
 static thread_local mf_ingest_stats_t t_ingest_stats;
 static thread_local bool t_ingest_stats_valid = false;
 
+// The 64-bit depth totals of a file-level call with depth: one array per (logical) device, made and zeroed when a batch there first asks
+// for it, shared by the device's workers and lanes (their folds are atomic)
+struct DepthTotals {
+    mf_kmerset *ks = nullptr;
+    std::mutex mu;
+    std::map<int, unsigned long long *> tot;
+    ~DepthTotals() { for (auto &kv : tot) if (hipSetDevice(phys(kv.first)) == hipSuccess) hipFree(kv.second); }
+    int on(int device, unsigned long long **out)
+    {
+        std::lock_guard<std::mutex> lk(mu);
+        auto it = tot.find(device);
+        if (it != tot.end()) { *out = it->second; return MF_OK; }
+        DevTables *T; int rc = build_on_device(ks, device, &T); if (rc) return rc;
+        rc = depth_tables(ks, device, T); if (rc) return rc;
+        DevCtx *ctx; rc = get_ctx(device, &ctx); if (rc) return rc;
+        const size_t bytes = std::max<uint64_t>(T->dcnt_n, 1) * 8;
+        unsigned long long *p = nullptr;
+        HIPCHK(dev_malloc(&p, bytes));
+        tot[device] = p;
+        HIPCHK(hipMemsetAsync(p, 0, bytes, ctx->stream));
+        HIPCHK(hipStreamSynchronize(ctx->stream));
+        *out = p;
+        return MF_OK;
+    }
+    void clear() { for (auto &kv : tot) if (hipSetDevice(phys(kv.first)) == hipSuccess) hipFree(kv.second); tot.clear(); }
+};
+
 // the file-level call on a list of (logical) devices
-// tally (optional): the kept reads are counted per bait record as well (mf_filter_fastq_files_by_record), on whichever path takes the input
+// tally (optional): the kept reads are counted per bait record as well (mf_filter_fastq_files_by_record), on whichever path takes the input;
+// with tally->want_depth, the windows of every mate that passes go into depth's totals instead (mf_filter_fastq_files_depth)
 static int filter_fastq_files_on(mf_kmerset *ks, const char *fq1, const char *fq2, const char *out1, const char *out2,
                                  uint32_t threshold, int pair_mode, const int *devices, int n_devices, uint64_t *kept, uint64_t *total,
-                                 RecordTally *tally = nullptr, bool by_group = false)
+                                 RecordTally *tally = nullptr, bool by_group = false, DepthTotals *depth = nullptr)
 {
     if (!ks || !fq1 || !out1) return fail(MF_E_ARG, "NULL argument");
     if ((fq2 == nullptr) != (out2 == nullptr)) return fail(MF_E_ARG, "fq2 and out2 must be given together");
@@ -1334,7 +1500,14 @@ static int filter_fastq_files_on(mf_kmerset *ks, const char *fq1, const char *fq
         }
         if (!(ing && strcmp(ing, "host") == 0) && (force || any_gz || big_plain)) {
             std::string derr; IngestStats is;
-            if (tally) tally->reads_pairs = [ks, by_group](mf_reads *R, std::vector<uint64_t> &pairs, std::string &err) -> int {
+            if (tally && tally->depth()) tally->reads_depth = [ks, depth](mf_reads *R, std::string &err) -> int {
+                unsigned long long *tot = nullptr;
+                int rc = depth->on(R->device, &tot);
+                if (rc == MF_OK) rc = depth_after_filter(ks, R, tot);
+                if (rc != MF_OK) err = t_err;
+                return rc;
+            };
+            else if (tally) tally->reads_pairs = [ks, by_group](mf_reads *R, std::vector<uint64_t> &pairs, std::string &err) -> int {
                 const int rc = assign_after_filter(ks, R, nullptr, nullptr, &pairs, by_group);
                 if (rc != MF_OK) err = t_err;
                 return rc;
@@ -1353,6 +1526,7 @@ static int filter_fastq_files_on(mf_kmerset *ks, const char *fq1, const char *fq
             }
             if (drc != MF_DEVINGEST_DECLINED) return fail(drc, "%s", derr.c_str());
             if (tally) tally->reset(tally->n_rec);          // (nothing was kept on the path that declined)
+            if (depth) depth->clear();
             if (getenv("MF_PIPE_TIMING")) fprintf(stderr, "[mf device ingest] declined%s%s: the host pipeline takes the input\n", derr.empty() ? "" : ": ", derr.c_str());
         }
     }
@@ -1397,7 +1571,16 @@ static int filter_fastq_files_on(mf_kmerset *ks, const char *fq1, const char *fq
         if (rc != MF_OK) err = t_err;
         return rc;
     };
-    if (tally) tally->worker_pairs = [ks, by_group, &arena, &batch_n](int worker, std::vector<uint64_t> &pairs, std::string &err) -> int {
+    if (tally && tally->depth()) tally->worker_depth = [ks, depth, &arena, &batch_n](int worker, std::string &err) -> int {
+        if (batch_n[(size_t)worker] == 0) return MF_OK;
+        mf_reads *R = arena[(size_t)worker];
+        unsigned long long *tot = nullptr;
+        int rc = depth->on(R->device, &tot);
+        if (rc == MF_OK) rc = depth_after_filter(ks, R, tot);
+        if (rc != MF_OK) err = t_err;
+        return rc;
+    };
+    else if (tally) tally->worker_pairs = [ks, by_group, &arena, &batch_n](int worker, std::vector<uint64_t> &pairs, std::string &err) -> int {
         pairs.clear();
         if (batch_n[(size_t)worker] == 0) return MF_OK;
         const int rc = assign_after_filter(ks, arena[(size_t)worker], nullptr, nullptr, &pairs, by_group);
@@ -1472,10 +1655,43 @@ int mf_filter_fastq_files_by_group(mf_kmerset *ks, const char *fq1, const char *
     return MF_OK;
 }
 
+int mf_filter_fastq_files_depth(mf_kmerset *ks, const char *fq1, const char *fq2, const char *out1, const char *out2,
+                                uint32_t threshold, int pair_mode, const int *devices, int n_devices,
+                                uint32_t *profile, mf_depth_record_t *records, uint64_t *kept, uint64_t *total)
+{
+    if (!ks) return fail(MF_E_ARG, "NULL handle");
+    DepthTotals dt; dt.ks = ks;
+    RecordTally tally; tally.want_depth = true;
+    int rc = filter_fastq_files_on(ks, fq1, fq2, out1, out2, threshold, pair_mode, devices, n_devices, kept, total, &tally, false, &dt);
+    if (rc) return rc;
+    // the devices' totals summed on the host into the first listed device's, then the profile and summary kernels once, there
+    const int dev0 = devices[0];
+    unsigned long long *t0 = nullptr;
+    rc = dt.on(dev0, &t0); if (rc) return rc;
+    DevTables *T; rc = build_on_device(ks, dev0, &T); if (rc) return rc;
+    const uint64_t n_cnt = T->dcnt_n;
+    if (dt.tot.size() > 1 && n_cnt) {
+        std::vector<uint64_t> sum(n_cnt, 0), part(n_cnt);
+        for (auto &kv : dt.tot) {
+            HIPCHK(hipSetDevice(phys(kv.first)));
+            HIPCHK(hipMemcpy(part.data(), kv.second, n_cnt * 8, hipMemcpyDeviceToHost));
+            for (uint64_t i = 0; i < n_cnt; i++) sum[i] += part[i];
+        }
+        HIPCHK(hipSetDevice(phys(dev0)));
+        HIPCHK(hipMemcpy(t0, sum.data(), n_cnt * 8, hipMemcpyHostToDevice));
+    }
+    DevCtx *ctx; rc = get_ctx(dev0, &ctx); if (rc) return rc;
+    DevScratch tmp;
+    uint32_t *d_prof = nullptr; unsigned long long *d_rec = nullptr;
+    HIPCHK(tmp.alloc(d_prof, std::max<uint64_t>(ks->positions(), 1) * 4));
+    HIPCHK(tmp.alloc(d_rec, std::max<uint64_t>(ks->rec_len().size(), 1) * 32));
+    return depth_report(ks, dev0, ctx->stream, t0, d_prof, d_rec, profile, records);
+}
+
 int mf_set_option(const char *name, const char *value)
 {
     options_from_env_once();          // (so that a later first pass does not overwrite what is set here)
-    if (set_option(name, value) != 0) return fail(MF_E_ARG, "unknown option or value: %s=%s (options: pass=default|split|serial, adapt=0|1, finish_streams=0|1|2, screen_streams=1|2, split_pipe=0|1, exact_co=0|1, front=-1|0|1|2|3|4, canon=-1|0|1, s8_finish=-1|0|1, front2_log2b=0|6..24, front3_log2b=-1|0|6..27, expect_files=0|1, short_lived=0|1)", name ? name : "(null)", value ? value : "(null)");
+    if (set_option(name, value) != 0) return fail(MF_E_ARG, "unknown option or value: %s=%s (options: pass=default|split|serial, adapt=0|1, finish_streams=0|1|2, screen_streams=1|2, split_pipe=0|1, exact_co=0|1, front=-1|0|1|2|3|4, canon=-1|0|1, s8_finish=-1|0|1, front2_log2b=0|6..24, front3_log2b=-1|0|6..27, expect_files=0|1, short_lived=0|1, depth_index=0|1)", name ? name : "(null)", value ? value : "(null)");
     return MF_OK;
 }
 

@@ -78,6 +78,10 @@ struct mf_reads {
     // record assignment (mf_assign and the file-level call by record): the passing reads as a list, their records, the counters
     uint32_t *d_alist = nullptr, *d_assign = nullptr; uint64_t *d_apairs = nullptr; unsigned long long *d_acnt = nullptr;
     size_t cap_alist = 0, cap_assign = 0, cap_apairs = 0, cap_acnt = 0;
+    // k-mer depth (mf_depth and the file-level call with depth): a pass's 32-bit counters (then mf_depth's profile), mf_depth's 64-bit
+    // totals and record sums
+    uint32_t *d_dcnt = nullptr; unsigned long long *d_dtot = nullptr, *d_drec = nullptr;
+    size_t cap_dcnt = 0, cap_dtot = 0, cap_drec = 0;
     // capacities (bytes), so that a handle can be refilled batch after batch without touching the allocator
     size_t cap_words = 0, cap_offsets = 0, cap_npos = 0, cap_bitmap = 0, cap_recs = 0, cap_rec_counts = 0, cap_hits = 0, cap_npos_blk = 0, cap_off_blk = 0;
 };

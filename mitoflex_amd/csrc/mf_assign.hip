@@ -15,6 +15,20 @@
 //                        starts behind them.
 //   passign_kernel       the same tally (assign_listed below, shared code) over the (strand, start) windows of a protein set: a lane
 //                        translates its window's kp codons through a 64-entry codon table in LDS into the peptide key.
+//
+// k-mer depth of the bait positions (mf_depth):
+//   build_rep_kernel     one thread per bait position: the slot of the valid window that starts there into pos_rep, and atomicMin of
+//   build_prep_kernel    the position into rep[slot] (protein sets: the peptide key from the residues) -- rep[slot] is the smallest
+//                        position whose valid window holds the key, whatever order the windows come in; rep_finish_kernel then turns
+//                        pos_rep into the representative position of every valid window (DEPTH_NONE where none starts).
+//   depth_kernel         one wave per listed read (grid-stride), its windows 64 at a time: key, slot, rep[slot], atomicAdd of 1 into
+//   pdepth_kernel        cnt[rep].  A read drawn from the bait has consecutive windows on consecutive bait positions, so a wave's
+//                        atomics fall on ~256 contiguous bytes of cnt instead of 64 hashed lines.  The window walks are the assign
+//                        kernels' (NucWindows / ProtWindows), with rep in place of the owner table.  Keys that several lanes of a
+//                        wave hold (low-complexity reads) are added once by count while the first pending key is one of them.
+//   depth_fold_kernel    a pass's 32-bit counters into 64-bit totals (atomics: the totals of a device are shared by its lanes).
+//   depth_profile_kernel one wave per item (a stretch of at most DEPTH_ITEM positions of one record): the profile from pos_rep and the
+//                        totals, the record's windows / covered / sum / max reduced over the wave, one atomic of each per item.
 #include "mf_assign.h"
 #include "mf_keys_dev.h"
 #include <algorithm>
@@ -318,6 +332,195 @@ hipError_t launch_assign(const ReadsView &R, const KmerSetView &S, const uint32_
     if (S.prot) hipLaunchKernelGGL(passign_kernel, dim3(grid), dim3(ASSIGN_BLOCK), 0, st, R, S, owner, list, n_list, n_rec, assign, pairs, counts);
     else if (S.kw == 1) hipLaunchKernelGGL(assign_kernel<1>, dim3(grid), dim3(ASSIGN_BLOCK), 0, st, R, S, owner, list, n_list, n_rec, assign, pairs, counts);
     else hipLaunchKernelGGL(assign_kernel<2>, dim3(grid), dim3(ASSIGN_BLOCK), 0, st, R, S, owner, list, n_list, n_rec, assign, pairs, counts);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------------------------------------ k-mer depth
+template <int KW>
+__global__ void __launch_bounds__(256)
+build_rep_kernel(BaitView B, KmerSetView S, uint32_t *__restrict__ rep, uint32_t *__restrict__ pos_rep)
+{
+    const uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= B.total) return;
+    uint64_t slot = ~0ULL;
+    if (B.runlen[p] >= (uint32_t)S.k) slot = table_find(S, canonical_at<KW>(B.words, p, S.k));
+    if (slot == ~0ULL) { pos_rep[p] = DEPTH_NONE; return; }
+    pos_rep[p] = (uint32_t)slot;
+    atomicMin(&rep[slot], (uint32_t)p);
+}
+
+__global__ void __launch_bounds__(256)
+build_prep_kernel(const uint8_t *__restrict__ aa, const uint8_t *__restrict__ runlen, uint64_t total, KmerSetView S, uint32_t *__restrict__ rep,
+                  uint32_t *__restrict__ pos_rep)
+{
+    const uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= total) return;
+    uint64_t slot = ~0ULL;
+    if (runlen[p] >= (uint32_t)S.k) {
+        uint64_t v = 0;
+        for (int i = 0; i < S.k; i++) v |= (uint64_t)aa[p + i] << (5 * i);
+        slot = table_find(S, Key<1>{v});
+    }
+    if (slot == ~0ULL) { pos_rep[p] = DEPTH_NONE; return; }
+    pos_rep[p] = (uint32_t)slot;
+    atomicMin(&rep[slot], (uint32_t)p);
+}
+
+// by_slot: every key counts in a counter of its own slot (rep[slot] = slot) -- the scattered form, kept to measure against
+__global__ void rep_finish_kernel(uint32_t *__restrict__ rep, uint64_t slots, uint32_t *__restrict__ pos_rep, uint64_t total, int by_slot)
+{
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (by_slot && i < slots) rep[i] = (uint32_t)i;
+    if (i < total) { const uint32_t s = pos_rep[i]; if (s != DEPTH_NONE) pos_rep[i] = by_slot ? s : rep[s]; }
+}
+
+constexpr int DEPTH_BLOCK = 512;
+
+// The windows of the listed reads, one wave a read: one atomic add per window whose key the bait holds
+template <class Src, class Cnt>
+__device__ __forceinline__ void depth_listed(Src &src, const uint32_t *__restrict__ list, const unsigned long long *__restrict__ n_list_p, Cnt *__restrict__ cnt)
+{
+    const int lane = threadIdx.x & 63;
+    const uint64_t n_list = *n_list_p;
+    const uint64_t n_waves = (uint64_t)gridDim.x * (DEPTH_BLOCK / 64);
+    for (uint64_t i = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6; i < n_list; i += n_waves) {
+        const uint64_t np = src.begin(list[i]);
+        for (uint64_t p0 = 0; p0 < np; p0 += 64) {
+            const uint64_t p = p0 + (uint64_t)lane;
+            uint32_t o = p < np ? src.owner_at(p) : OWNER_SHARED;
+            // A run of one key (a microsatellite, poly-A) puts the wave's atomics on a few addresses, and same-address atomics
+            // serialise across the chip (100 ms a pass on 2 % microsatellite reads): while the first pending key is held by several
+            // lanes, one lane adds their count.  A read drawn from the bait leaves after one turn (its first key is unique).
+            uint64_t pend = __ballot(o != OWNER_SHARED);
+            for (int turn = 0; pend && turn < 8; turn++) {
+                const uint32_t L = __builtin_amdgcn_readfirstlane(__shfl(o, (int)(__ffsll((long long)pend) - 1)));
+                const uint64_t same = __ballot(o == L);
+                if (__popcll(same) == 1) break;
+                if ((uint64_t)lane == (uint64_t)(__ffsll((long long)same) - 1)) atomicAdd(&cnt[L], (Cnt)__popcll(same));
+                if (o == L) o = OWNER_SHARED;
+                pend &= ~same;
+            }
+            if (o != OWNER_SHARED) atomicAdd(&cnt[o], (Cnt)1);
+        }
+    }
+}
+
+template <int KW, class Cnt>
+__global__ void __launch_bounds__(DEPTH_BLOCK)
+depth_kernel(ReadsView R, KmerSetView S, const uint32_t *__restrict__ rep, const uint32_t *__restrict__ list,
+             const unsigned long long *__restrict__ n_list_p, Cnt *__restrict__ cnt)
+{
+    NucWindows<KW> src(R, S, rep);
+    depth_listed(src, list, n_list_p, cnt);
+}
+
+template <class Cnt>
+__global__ void __launch_bounds__(DEPTH_BLOCK)
+pdepth_kernel(ReadsView R, KmerSetView S, const uint32_t *__restrict__ rep, const uint32_t *__restrict__ list,
+              const unsigned long long *__restrict__ n_list_p, Cnt *__restrict__ cnt)
+{
+    __shared__ uint32_t s_lut[64];
+    if (threadIdx.x < 64) {              // (as passign_kernel)
+        const uint4 e = reinterpret_cast<const uint4 *>(S.plut)[threadIdx.x];
+        const uint32_t f = (uint32_t)((((uint64_t)e.y << 32) | e.x) >> (5 * (S.k - 1)));
+        s_lut[threadIdx.x] = (f & 31u) | ((e.z & 31u) << 8);
+    }
+    __syncthreads();
+    ProtWindows src(R, S, rep, s_lut);
+    depth_listed(src, list, n_list_p, cnt);
+}
+
+__global__ void __launch_bounds__(256)
+depth_fold_kernel(const uint32_t *__restrict__ cnt, uint64_t n, unsigned long long *__restrict__ tot)
+{
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) { const uint32_t c = cnt[i]; if (c) atomicAdd(&tot[i], (unsigned long long)c); }
+}
+
+__device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+__device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { const unsigned long long t = __shfl_xor(v, o); v = t > v ? t : v; }
+    return v;
+}
+
+__global__ void __launch_bounds__(64)
+depth_profile_kernel(const DepthItem *__restrict__ items, const uint32_t *__restrict__ pos_rep, const unsigned long long *__restrict__ tot,
+                     uint32_t *__restrict__ profile, unsigned long long *__restrict__ rec)
+{
+    const DepthItem it = items[blockIdx.x];
+    unsigned long long w = 0, cov = 0, sum = 0, mx = 0;
+    for (uint32_t i = threadIdx.x; i < it.len; i += 64) {
+        const uint64_t p = it.begin + i;
+        const uint32_t r = pos_rep[p];
+        uint32_t out = DEPTH_NONE;
+        if (r != DEPTH_NONE) {
+            const unsigned long long d = tot[r];
+            w++; cov += d != 0; sum += d; mx = d > mx ? d : mx;
+            out = d < DEPTH_CLAMP ? (uint32_t)d : DEPTH_CLAMP;
+        }
+        if (profile) profile[p] = out;
+    }
+    if (!rec) return;
+    w = wave_sum_u64(w); cov = wave_sum_u64(cov); sum = wave_sum_u64(sum); mx = wave_max_u64(mx);
+    if (threadIdx.x == 0 && w) {
+        unsigned long long *o = rec + 4 * (uint64_t)it.rec;
+        atomicAdd(&o[0], w); atomicAdd(&o[1], cov); atomicAdd(&o[2], sum); atomicMax(&o[3], mx);
+    }
+}
+
+hipError_t launch_build_depth(const BaitView &B, const uint8_t *aa, const KmerSetView &S, uint32_t *rep, uint32_t *pos_rep, bool by_slot,
+                              hipStream_t st)
+{
+    const uint64_t slots = S.slot_mask + 1, total = B.total;
+    hipError_t e = hipMemsetAsync(rep, 0xFF, slots * 4, st);
+    if (e != hipSuccess) return e;
+    if (total) {
+        if (S.prot) hipLaunchKernelGGL(build_prep_kernel, dim3(grid_of(total, 256)), dim3(256), 0, st, aa, B.runlen, total, S, rep, pos_rep);
+        else if (S.kw == 1) hipLaunchKernelGGL(build_rep_kernel<1>, dim3(grid_of(total, 256)), dim3(256), 0, st, B, S, rep, pos_rep);
+        else hipLaunchKernelGGL(build_rep_kernel<2>, dim3(grid_of(total, 256)), dim3(256), 0, st, B, S, rep, pos_rep);
+    }
+    const uint64_t n = std::max<uint64_t>(by_slot ? slots : 0, total);
+    if (n) hipLaunchKernelGGL(rep_finish_kernel, dim3(grid_of(n, 256)), dim3(256), 0, st, rep, slots, pos_rep, total, by_slot ? 1 : 0);
+    return hipGetLastError();
+}
+
+hipError_t launch_depth_count(const ReadsView &R, const KmerSetView &S, const uint32_t *rep, const uint32_t *list, const unsigned long long *n_list,
+                              uint32_t *cnt32, unsigned long long *cnt64, int n_cu, hipStream_t st)
+{
+    if (!R.n_reads) return hipSuccess;
+    const uint64_t waves = std::min<uint64_t>((uint64_t)(n_cu > 0 ? n_cu : 1) * 32, R.n_reads);
+    const unsigned grid = grid_of(waves, DEPTH_BLOCK / 64);
+    if (cnt64) {
+        if (S.prot) hipLaunchKernelGGL(pdepth_kernel<unsigned long long>, dim3(grid), dim3(DEPTH_BLOCK), 0, st, R, S, rep, list, n_list, cnt64);
+        else if (S.kw == 1) hipLaunchKernelGGL((depth_kernel<1, unsigned long long>), dim3(grid), dim3(DEPTH_BLOCK), 0, st, R, S, rep, list, n_list, cnt64);
+        else hipLaunchKernelGGL((depth_kernel<2, unsigned long long>), dim3(grid), dim3(DEPTH_BLOCK), 0, st, R, S, rep, list, n_list, cnt64);
+    } else {
+        if (S.prot) hipLaunchKernelGGL(pdepth_kernel<uint32_t>, dim3(grid), dim3(DEPTH_BLOCK), 0, st, R, S, rep, list, n_list, cnt32);
+        else if (S.kw == 1) hipLaunchKernelGGL((depth_kernel<1, uint32_t>), dim3(grid), dim3(DEPTH_BLOCK), 0, st, R, S, rep, list, n_list, cnt32);
+        else hipLaunchKernelGGL((depth_kernel<2, uint32_t>), dim3(grid), dim3(DEPTH_BLOCK), 0, st, R, S, rep, list, n_list, cnt32);
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_depth_fold(const uint32_t *cnt32, uint64_t n, unsigned long long *tot, hipStream_t st)
+{
+    if (!n) return hipSuccess;
+    hipLaunchKernelGGL(depth_fold_kernel, dim3(grid_of(n, 256)), dim3(256), 0, st, cnt32, n, tot);
+    return hipGetLastError();
+}
+
+hipError_t launch_depth_profile(const DepthItem *items, uint32_t n_items, const uint32_t *pos_rep, const unsigned long long *tot, uint32_t *profile,
+                                unsigned long long *rec, hipStream_t st)
+{
+    if (!n_items) return hipSuccess;
+    hipLaunchKernelGGL(depth_profile_kernel, dim3(n_items), dim3(64), 0, st, items, pos_rep, tot, profile, rec);
     return hipGetLastError();
 }
 

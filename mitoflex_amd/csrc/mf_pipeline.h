@@ -22,6 +22,12 @@ struct RecordTally {
     std::vector<uint64_t> counts;               // n_rec + 2: kept reads (mates one by one) assigned to each record, ambiguous, unassigned
     std::function<int(int worker, std::vector<uint64_t> &pairs, std::string &err)> worker_pairs;       // host pipeline: the batch `worker` has just filtered
     std::function<int(mf_reads *reads, std::vector<uint64_t> &pairs, std::string &err)> reads_pairs;   // device ingest path: a piece's read set
+    // k-mer depth (mf_filter_fastq_files_depth) instead of the pairs, when want_depth is set: the same two places add the batch's passing
+    // reads into the depth counters of its device, and nothing is tallied
+    bool want_depth = false;
+    std::function<int(int worker, std::string &err)> worker_depth;
+    std::function<int(mf_reads *reads, std::string &err)> reads_depth;
+    bool depth() const { return want_depth; }
     std::mutex mu;
     void reset(uint32_t n) { n_rec = n; counts.assign((size_t)n + 2, 0); }
     // one mate's batch of n reads, n_kept of them kept (keep(i): read i is)

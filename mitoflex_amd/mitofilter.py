@@ -24,6 +24,10 @@ PAIR_BOTH = 1
 # record assignment of a read that passes but that no record wins / of a read that does not pass (mf_assign)
 ASSIGN_AMBIGUOUS = 0xFFFFFFFE
 ASSIGN_NONE = 0xFFFFFFFF
+# profile entry of a position where no valid window starts (mf_depth)
+DEPTH_NONE = 0xFFFFFFFF
+# per-record k-mer depth summary (mf_depth_record_t)
+DEPTH_RECORD = np.dtype([("windows", np.uint64), ("covered", np.uint64), ("depth_sum", np.uint64), ("depth_max", np.uint64)])
 
 # every symbol include/mitofilter.h declares (checked by tests/test_abi.py)
 EXPORTS = (
@@ -35,6 +39,7 @@ EXPORTS = (
     "mf_filter_fastq_files", "mf_filter_fastq_files_on", "mf_last_ingest_stats", "mf_h2d_bandwidth", "mf_set_option", "mf_qualfilter_files", "mf_release_cached",
     "mf_kmerset_record_count", "mf_kmerset_record_name", "mf_assign", "mf_filter_fastq_files_by_record",
     "mf_kmerset_group_records", "mf_kmerset_group_count", "mf_kmerset_group_name", "mf_assign_groups", "mf_filter_fastq_files_by_group",
+    "mf_kmerset_record_starts", "mf_depth", "mf_filter_fastq_files_depth",
 )
 
 
@@ -139,6 +144,10 @@ def load(path: Optional[str] = None):
     L.mf_assign_groups.argtypes = [vp, vp, C.c_uint32, C.c_int, vp, vp, vp, C.POINTER(FilterStats)]
     L.mf_filter_fastq_files_by_group.argtypes = [vp, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_uint32, C.c_int,
                                                  C.POINTER(C.c_int), C.c_int, vp, u64p, u64p]
+    L.mf_kmerset_record_starts.argtypes = [vp, vp, C.c_size_t, C.POINTER(C.c_size_t)]
+    L.mf_depth.argtypes = [vp, vp, C.c_uint32, C.c_int, vp, vp, vp, C.POINTER(FilterStats)]
+    L.mf_filter_fastq_files_depth.argtypes = [vp, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_uint32, C.c_int,
+                                              C.POINTER(C.c_int), C.c_int, vp, vp, u64p, u64p]
     if L.mf_abi_version() != 5:
         raise MitoFilterError("libmitofilter_hip ABI version mismatch")
     _lib = L
@@ -248,6 +257,16 @@ class KmerSet:
             _chk(L.mf_kmerset_group_name(self._h, i, buf, len(buf), None))
             names.append(buf.value.decode(errors="replace"))
         return names
+
+    @property
+    def record_starts(self) -> np.ndarray:
+        """u64[R + 1]: record j holds positions (bases, or residues of a protein set) starts[j] .. starts[j + 1] - 1."""
+        L = load()
+        need = C.c_size_t()
+        L.mf_kmerset_record_starts(self._h, None, 0, C.byref(need))
+        out = np.zeros(max(need.value, 1), dtype=np.uint64)
+        _chk(L.mf_kmerset_record_starts(self._h, out.ctypes.data, out.size, None))
+        return out
 
     def export_table(self, device: int = 0) -> np.ndarray:
         i = self.info
@@ -374,6 +393,19 @@ def assign_groups(ks: KmerSet, reads: Reads, threshold: int = 1, mode: int = MOD
     return bits[:(n + 31) // 32], assign[:n], counts
 
 
+def record_depth(ks: KmerSet, reads: Reads, threshold: int = 1, mode: int = MODE_SCREENED):
+    """One filter pass, then the k-mer depth of the bait positions (include/mitofilter.h: mf_depth).  -> (bits u32[ceil(n/32)],
+    profile u32[positions]: depth of the valid window starting at each position, DEPTH_NONE where none does, records: DEPTH_RECORD[R]
+    with the fields windows, covered, depth_sum, depth_max)."""
+    n = reads.info.n_reads
+    starts = ks.record_starts
+    bits = np.zeros(max((n + 31) // 32, 1), dtype=np.uint32)
+    profile = np.zeros(max(int(starts[-1]), 1), dtype=np.uint32)
+    records = np.zeros(max(len(starts) - 1, 1), dtype=DEPTH_RECORD)
+    _chk(load().mf_depth(ks._h, reads._h, threshold, mode, bits.ctypes.data, profile.ctypes.data, records.ctypes.data, None))
+    return bits[:(n + 31) // 32], profile[:int(starts[-1])], records[:len(starts) - 1]
+
+
 def filter_resident(ks: KmerSet, reads: Reads, threshold: int = 1, mode: int = MODE_SCREENED, steps: int = 1) -> FilterStats:
     st = FilterStats()
     _chk(load().mf_filter_resident(ks._h, reads._h, threshold, mode, steps, C.byref(st)))
@@ -442,6 +474,23 @@ def filter_fastq_files_by_group(ks: KmerSet, fq1: str, fq2: Optional[str], out1:
     _chk(load().mf_filter_fastq_files_by_group(ks._h, _enc(fq1), _enc(fq2), _enc(out1), _enc(out2), threshold, pair_mode,
                                                arr, len(devices), counts.ctypes.data, C.byref(kept), C.byref(total)))
     return kept.value, total.value, counts
+
+
+def filter_fastq_files_depth(ks: KmerSet, fq1: str, fq2: Optional[str], out1: str, out2: Optional[str],
+                             threshold: int = 1, pair_mode: int = PAIR_EITHER, devices: Optional[Sequence[int]] = None,
+                             n_devices: int = 1):
+    """filter_fastq_files plus the k-mer depth of the bait positions over every mate that passes its own threshold (the pair rule
+    decides only what is written).  -> (kept, total, profile u32[positions], records DEPTH_RECORD[R])."""
+    if devices is None:
+        devices = list(range(n_devices))
+    arr = (C.c_int * len(devices))(*[int(d) for d in devices])
+    starts = ks.record_starts
+    profile = np.zeros(max(int(starts[-1]), 1), dtype=np.uint32)
+    records = np.zeros(max(len(starts) - 1, 1), dtype=DEPTH_RECORD)
+    kept, total = C.c_uint64(), C.c_uint64()
+    _chk(load().mf_filter_fastq_files_depth(ks._h, _enc(fq1), _enc(fq2), _enc(out1), _enc(out2), threshold, pair_mode, arr, len(devices),
+                                            profile.ctypes.data, records.ctypes.data, C.byref(kept), C.byref(total)))
+    return kept.value, total.value, profile[:int(starts[-1])], records[:len(starts) - 1]
 
 
 def set_option(name: str, value) -> None:
