@@ -6,7 +6,6 @@
 #include "mf_common.h"
 #include "mf_host.h"
 #include "mf_kernels.h"
-#include "mf_assign.h"
 #include "mf_pipeline.h"
 #include "mf_synth.h"
 #include "mf_coldtrace.h"
@@ -40,10 +39,6 @@ int fail(int code, const char *fmt, ...)
     t_err = buf;
     return code;
 }
-#define HIPCHK(call)                                                                                  \
-    do { hipError_t e_ = (call);                                                                      \
-         if (e_ != hipSuccess) return fail(MF_E_HIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); \
-    } while (0)
 
 // --------------------------------------------------------------- device ctx
 static std::mutex g_ctx_mu;
@@ -125,55 +120,10 @@ static int ensure_pipeline_streams(DevCtx *c)
 }
 
 // ------------------------------------------------------------------ kmerset
-struct DevTables {
-    uint64_t *keys = nullptr;
-    uint32_t *bloom = nullptr, *stab = nullptr, *kbloom = nullptr, *kbloom_co = nullptr, *plut = nullptr;    // kbloom_co: own allocation only when it differs from kbloom
-    uint32_t *front2 = nullptr, *front3 = nullptr, *pre = nullptr;      // bait-sized fronts of the large-bait screen (front_mode 1 .. 4); mode 4's one-bit LDS table
-    KmerSetView view{};
-    uint64_t n_keys = 0, n_smers = 0;
-    uint32_t *owner = nullptr;          // record owner of every slot of `keys` (mf_assign.h), built by the first call that asks for it
-    uint32_t *gowner = nullptr;         // group owner of every slot for the set's current grouping, likewise (freed when the set is regrouped)
-    // k-mer depth (mf_depth), built by the first depth call: representative position of every slot, of every bait position's window, and
-    // the profile kernel's work items; dcnt_n counters a pass (the positions, or the slots under depth_index=1)
-    uint32_t *rep = nullptr, *pos_rep = nullptr; DepthItem *ditems = nullptr; uint32_t n_ditems = 0; uint64_t dcnt_n = 0;
-};
-struct mf_kmerset {
-    int k = 0, kw = 1;
-    int kind = MF_KIND_NUCLEOTIDE, genetic_code = 0;   // protein sets: k = residues per key, reads translated with genetic_code
-    ProtBaitHost pbait;
-    uint32_t codon_lut[256] = {0};
-    bool kb_in_lds = true;
-    BaitHost bait;
-    uint64_t n_windows = 0, slots = 0;
-    ScreenGeom geom{0, 0};
-    uint32_t bloom_log2w = 0, stage2_log2w = 0, stab_slots = 0, kb_log2w = 0;
-    uint32_t front_mode = 0, f2_log2b = 0, f3_log2b = 0, pre_log2w = 0;
-    int canon = 0;              // != 0: the screen's tables hold one canonical key per bait s-mer (KmerSetView::canon: 1 sixteen-base samples, 2 shorter)
-    bool s8_finish = false;     // a stride-8 set whose threshold-1 passes go through screen + finish (baits beyond ~20 kbp)
-    size_t screen_words() const { return ((size_t)1 << bloom_log2w) + ((size_t)1 << stage2_log2w); }
-    // grouping of the records (mf_kmerset_group_records): empty rec_group = identity (each record its own group, named after it)
-    std::vector<uint32_t> rec_group;
-    std::vector<std::string> group_names;
-    std::mutex mu;
-    std::map<int, DevTables> dev;
-    const std::vector<std::string> &names() const { return kind == MF_KIND_PROTEIN ? pbait.names : bait.names; }
-    uint32_t n_records() const { return (uint32_t)names().size(); }
-    uint32_t n_groups() const { return rec_group.empty() ? n_records() : (uint32_t)group_names.size(); }
-    const std::string &group_name(uint64_t i) const { return rec_group.empty() ? names()[i] : group_names[i]; }
-    const std::vector<uint64_t> &rec_len() const { return kind == MF_KIND_PROTEIN ? pbait.rec_len : bait.rec_len; }
-    uint64_t positions() const { return kind == MF_KIND_PROTEIN ? pbait.total : bait.total; }       // bases / residues of all records
-};
-
-// device temporaries of one build: released on every exit path
-struct DevScratch {
-    std::vector<void *> bufs;
-    template <class T> hipError_t alloc(T *&p, size_t bytes) { hipError_t e = dev_malloc(&p, bytes); if (e == hipSuccess) bufs.push_back(p); return e; }
-    ~DevScratch() { for (void *p : bufs) hipFree(p); }
-};
 // tables under construction: released unless the build commits them
 struct TablesGuard {
     DevTables *t;
-    ~TablesGuard() { if (t) { hipFree(t->keys); hipFree(t->bloom); hipFree(t->stab); hipFree(t->kbloom); hipFree(t->kbloom_co); hipFree(t->plut); hipFree(t->front2); hipFree(t->front3); hipFree(t->pre); } }
+    ~TablesGuard() { if (t) t->release(); }
 };
 // events of one timing loop
 struct EventList {
@@ -212,10 +162,10 @@ struct PassOptions {
     std::atomic<int> split_pipe{1};       // the candidate-bitmap pass pipelined                                     "split_pipe"      MF_SPLIT_PIPE
     std::atomic<int> exact_co{0};         // the co-resident exact kernel behind every screen (tests)                "exact_co"        MF_EXACT_CO
     // the large-bait screen (read when a k-mer set is BUILT; tests force every form on small baits)
-    std::atomic<int> front{-1};           // -1 by the bait's size | 0 LDS table only | 1 LDS table + front2 | 2 front2 (+ front3) only | 3 LDS table, lone positives through front2   "front"   MF_FRONT
-    std::atomic<int> front2_log2b{0};     // 0 by the bait's size | log2 of front2's 128-bit blocks (6..18)                         "front2_log2b"   MF_FRONT2_LOG2B
+    std::atomic<int> front{-1};           // -1 by the bait's size | 0 LDS table only | 1 LDS table + front2 | 2 front2 (+ front3) only | 3 LDS table, lone positives through front2 | 4 one-bit LDS table, then front2   "front"   MF_FRONT
+    std::atomic<int> front2_log2b{0};     // 0 by the bait's size | log2 of front2's 128-bit blocks (6..24)                         "front2_log2b"   MF_FRONT2_LOG2B
     std::atomic<int> s8_finish{-1};       // the stride-8 geometries (k < 28) through screen + finish instead of the candidate bitmap: -1 by the bait's size | 0 | 1   "s8_finish"   MF_S8_FINISH
-    std::atomic<int> canon{-1};           // -1 by the bait's size | 0 both strands in the screen's tables | 1 one canonical key per s-mer (16-base samples only)             "canon"          MF_CANON
+    std::atomic<int> canon{-1};           // -1 by the bait's size | 0 both strands in the screen's tables | 1 one canonical key per s-mer (s < 16 too)             "canon"          MF_CANON
     std::atomic<int> front3_log2b{-1};    // -1 by the bait's size | 0 none | log2 of front3's blocks (6..27)                       "front3_log2b"   MF_FRONT3_LOG2B
     // read when a set's depth tables are built: 0 depth counters per representative bait position | 1 per slot (the scattered form, kept
     // to measure against: tools/bench_depth.py)                                                                   "depth_index"    MF_DEPTH_INDEX
@@ -259,9 +209,10 @@ static void options_from_env_once()
     }();
     (void)done;
 }
+int depth_index_option() { return g_opt.depth_index.load(); }
 static int pass_kind() { options_from_env_once(); return g_opt.pass; }          // (looked up on every pass: bench.py times the serial form next to the default one in one process)
 
-static int build_on_device(mf_kmerset *ks, int device, DevTables **out)
+int build_on_device(mf_kmerset *ks, int device, DevTables **out)
 {
     std::lock_guard<std::mutex> lk(ks->mu);
     auto it = ks->dev.find(device);
@@ -588,7 +539,7 @@ int mf_kmerset_free(mf_kmerset *ks)
 {
     if (!ks) return MF_OK;
     for (auto &kv : ks->dev) {
-        if (hipSetDevice(phys(kv.first)) == hipSuccess) { hipFree(kv.second.keys); hipFree(kv.second.bloom); hipFree(kv.second.stab); hipFree(kv.second.kbloom); hipFree(kv.second.kbloom_co); hipFree(kv.second.plut); hipFree(kv.second.front2); hipFree(kv.second.front3); hipFree(kv.second.pre); hipFree(kv.second.owner); hipFree(kv.second.gowner); hipFree(kv.second.rep); hipFree(kv.second.pos_rep); hipFree(kv.second.ditems); }
+        if (hipSetDevice(phys(kv.first)) == hipSuccess) kv.second.release();
     }
     delete ks;
     return MF_OK;
@@ -1077,356 +1028,6 @@ int mf_filter_packed(const mf_kmerset *ks, int device, const uint32_t *words, co
     return rc;
 }
 
-// -------------------------------------------------------- record assignment
-// The record-owner table of a set on `device` (its tables are built): made by the first call that asks for it, under the set's lock.
-// Sets that never assign reads never hold one.
-static int owner_table(mf_kmerset *ks, int device, DevTables *T)
-{
-    std::lock_guard<std::mutex> lk(ks->mu);
-    if (T->owner) return MF_OK;
-    DevCtx *ctx; int rc = get_ctx(device, &ctx); if (rc) return rc;
-    hipStream_t st = ctx->stream;
-    const BaitHost &B = ks->bait;
-    const uint32_t n_rec = (uint32_t)B.rec_len.size();
-    std::vector<uint64_t> starts((size_t)n_rec + 1, 0);
-    for (uint32_t j = 0; j < n_rec; j++) starts[j + 1] = starts[j] + B.rec_len[j];
-    DevScratch tmp;
-    uint32_t *d_words = nullptr, *d_hi = nullptr, *owner = nullptr; uint8_t *d_run = nullptr; uint64_t *d_start = nullptr;
-    HIPCHK(tmp.alloc(d_words, B.words.size() * 4));
-    HIPCHK(tmp.alloc(d_run, B.runlen.size()));
-    HIPCHK(tmp.alloc(d_start, starts.size() * 8));
-    HIPCHK(tmp.alloc(d_hi, ks->slots * 4));
-    HIPCHK(tmp.alloc(owner, ks->slots * 4));          // (released with the scratch unless the build completes)
-    HIPCHK(hipMemcpyAsync(d_words, B.words.data(), B.words.size() * 4, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_run, B.runlen.data(), B.runlen.size(), hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_start, starts.data(), starts.size() * 8, hipMemcpyHostToDevice, st));
-    HIPCHK(launch_build_owner(BaitView{d_words, B.total, d_run}, d_start, n_rec, nullptr, T->view, owner, d_hi, st));
-    HIPCHK(hipStreamSynchronize(st));
-    tmp.bufs.pop_back();
-    T->owner = owner;
-    return MF_OK;
-}
-
-// The group-owner table of a set on `device` for its current grouping (nucleotide or protein): made by the first grouped call that asks
-// for it, under the set's lock; mf_kmerset_group_records frees it.  Separate from the record-owner table, which mf_assign keeps using.
-static int group_owner_table(mf_kmerset *ks, int device, DevTables *T)
-{
-    std::lock_guard<std::mutex> lk(ks->mu);
-    if (T->gowner) return MF_OK;
-    DevCtx *ctx; int rc = get_ctx(device, &ctx); if (rc) return rc;
-    hipStream_t st = ctx->stream;
-    const bool prot = ks->kind == MF_KIND_PROTEIN;
-    const std::vector<uint64_t> &rec_len = prot ? ks->pbait.rec_len : ks->bait.rec_len;
-    const uint32_t n_rec = (uint32_t)rec_len.size();
-    std::vector<uint64_t> starts((size_t)n_rec + 1, 0);
-    for (uint32_t j = 0; j < n_rec; j++) starts[j + 1] = starts[j] + rec_len[j];
-    DevScratch tmp;
-    uint32_t *d_hi = nullptr, *d_group = nullptr, *owner = nullptr; uint64_t *d_start = nullptr;
-    HIPCHK(tmp.alloc(d_start, starts.size() * 8));
-    HIPCHK(tmp.alloc(d_hi, ks->slots * 4));
-    HIPCHK(hipMemcpyAsync(d_start, starts.data(), starts.size() * 8, hipMemcpyHostToDevice, st));
-    if (!ks->rec_group.empty()) {
-        HIPCHK(tmp.alloc(d_group, ks->rec_group.size() * 4));
-        HIPCHK(hipMemcpyAsync(d_group, ks->rec_group.data(), ks->rec_group.size() * 4, hipMemcpyHostToDevice, st));
-    }
-    if (prot) {          // the residues and run lengths go up for the build only, as the bait's bases do for the nucleotide table
-        const ProtBaitHost &P = ks->pbait;
-        uint8_t *d_aa = nullptr, *d_run = nullptr;
-        HIPCHK(tmp.alloc(d_aa, P.aa.size()));
-        HIPCHK(tmp.alloc(d_run, P.runlen.size()));
-        HIPCHK(hipMemcpyAsync(d_aa, P.aa.data(), P.aa.size(), hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(d_run, P.runlen.data(), P.runlen.size(), hipMemcpyHostToDevice, st));
-        HIPCHK(tmp.alloc(owner, ks->slots * 4));          // (released with the scratch unless the build completes)
-        HIPCHK(launch_build_powner(d_aa, d_run, P.total, d_start, n_rec, d_group, T->view, owner, d_hi, st));
-    } else {
-        const BaitHost &B = ks->bait;
-        uint32_t *d_words = nullptr; uint8_t *d_run = nullptr;
-        HIPCHK(tmp.alloc(d_words, B.words.size() * 4));
-        HIPCHK(tmp.alloc(d_run, B.runlen.size()));
-        HIPCHK(hipMemcpyAsync(d_words, B.words.data(), B.words.size() * 4, hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(d_run, B.runlen.data(), B.runlen.size(), hipMemcpyHostToDevice, st));
-        HIPCHK(tmp.alloc(owner, ks->slots * 4));
-        HIPCHK(launch_build_owner(BaitView{d_words, B.total, d_run}, d_start, n_rec, d_group, T->view, owner, d_hi, st));
-    }
-    HIPCHK(hipStreamSynchronize(st));
-    tmp.bufs.pop_back();
-    T->gowner = owner;
-    return MF_OK;
-}
-
-// Assignment of the reads that passed the filter pass just run on this read set (its bitmap in r->d_bits[r->cur]).  assign_out: n_reads words;
-// record_reads: n_rec + 2 counts; pairs: (read << 32) | record of every passing read, in no particular order.  Each optional.
-// by_group: to the set's groups instead of its records (the group-owner table; n_rec is then the number of groups).
-static int assign_after_filter(mf_kmerset *ks, mf_reads *r, uint32_t *assign_out, uint64_t *record_reads, std::vector<uint64_t> *pairs,
-                               bool by_group = false)
-{
-    DevTables *T; int rc = build_on_device(ks, r->device, &T); if (rc) return rc;
-    rc = by_group ? group_owner_table(ks, r->device, T) : owner_table(ks, r->device, T); if (rc) return rc;
-    const uint32_t *owner = by_group ? T->gowner : T->owner;
-    DevCtx *ctx; rc = get_ctx(r->device, &ctx, r->lane); if (rc) return rc;
-    hipStream_t st = ctx->stream;
-    const uint64_t n = r->v.n_reads;
-    const uint32_t n_rec = by_group ? ks->n_groups() : (uint32_t)ks->bait.rec_len.size();
-    const size_t n_cnt = (size_t)n_rec + 2;                          // records, ambiguous, the length of the list
-    HIPCHK(dev_reserve(r->d_acnt, r->cap_acnt, n_cnt * 8, false));
-    HIPCHK(hipMemsetAsync(r->d_acnt, 0, n_cnt * 8, st));
-    if (n) {
-        HIPCHK(dev_reserve(r->d_alist, r->cap_alist, n * 4, true));
-        if (assign_out) { HIPCHK(dev_reserve(r->d_assign, r->cap_assign, n * 4, true)); HIPCHK(hipMemsetAsync(r->d_assign, 0xFF, n * 4, st)); }
-        if (pairs) HIPCHK(dev_reserve(r->d_apairs, r->cap_apairs, n * 8, true));
-        HIPCHK(launch_pass_list(r->d_bits[r->cur], n, r->d_alist, r->d_acnt + n_rec + 1, st));
-        HIPCHK(launch_assign(r->v, T->view, owner, r->d_alist, r->d_acnt + n_rec + 1, n_rec, assign_out ? r->d_assign : nullptr,
-                             pairs ? r->d_apairs : nullptr, r->d_acnt, ctx->n_cu, st));
-    }
-    std::vector<unsigned long long> cnt(n_cnt, 0);
-    HIPCHK(hipMemcpyAsync(cnt.data(), r->d_acnt, n_cnt * 8, hipMemcpyDeviceToHost, st));
-    if (assign_out && n) HIPCHK(hipMemcpyAsync(assign_out, r->d_assign, n * 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    const uint64_t listed = cnt[n_rec + 1];
-    if (pairs) {
-        pairs->resize(listed);
-        if (listed) { HIPCHK(hipMemcpyAsync(pairs->data(), r->d_apairs, listed * 8, hipMemcpyDeviceToHost, st)); HIPCHK(hipStreamSynchronize(st)); }
-    }
-    if (record_reads) {
-        for (uint32_t j = 0; j <= n_rec; j++) record_reads[j] = cnt[j];
-        record_reads[n_rec + 1] = n - listed;
-    }
-    return MF_OK;
-}
-
-static int need_nucleotide(const mf_kmerset *ks)
-{
-    if (!ks) return fail(MF_E_ARG, "NULL handle");
-    if (ks->kind != MF_KIND_NUCLEOTIDE) return fail(MF_E_ARG, "record assignment needs a nucleotide bait set");
-    return MF_OK;
-}
-
-extern "C" {
-
-int mf_kmerset_record_count(const mf_kmerset *ks, uint64_t *n_records)
-{
-    int rc = need_nucleotide(ks); if (rc) return rc;
-    if (!n_records) return fail(MF_E_ARG, "n_records is NULL");
-    *n_records = ks->bait.rec_len.size();
-    return MF_OK;
-}
-
-int mf_kmerset_record_name(const mf_kmerset *ks, uint64_t i, char *buf, size_t buflen, size_t *needed)
-{
-    int rc = need_nucleotide(ks); if (rc) return rc;
-    if (i >= ks->bait.names.size()) return fail(MF_E_ARG, "record %llu out of range (the set has %llu)", (unsigned long long)i, (unsigned long long)ks->bait.names.size());
-    const std::string &nm = ks->bait.names[i];
-    if (needed) *needed = nm.size() + 1;
-    if (!buf || buflen < nm.size() + 1) return fail(MF_E_ARG, "buffer too small: the name needs %llu bytes", (unsigned long long)(nm.size() + 1));
-    memcpy(buf, nm.c_str(), nm.size() + 1);
-    return MF_OK;
-}
-
-int mf_assign(const mf_kmerset *ks_, const mf_reads *reads_, uint32_t threshold, int mode, uint32_t *out_bits, uint32_t *assign_out,
-              uint64_t *record_reads, mf_filter_stats_t *stats)
-{
-    mf_kmerset *ks = const_cast<mf_kmerset *>(ks_);
-    mf_reads *r = const_cast<mf_reads *>(reads_);
-    int rc = need_nucleotide(ks); if (rc) return rc;
-    if (!r) return fail(MF_E_ARG, "NULL handle");
-    rc = filter_common(ks, r, threshold, mode, out_bits, nullptr, 1, stats);
-    if (rc) return rc;
-    return assign_after_filter(ks, r, assign_out, record_reads, nullptr);
-}
-
-// ------------------------------------------------------- group assignment
-int mf_kmerset_group_records(mf_kmerset *ks, const char *sep, int field)
-{
-    if (!ks) return fail(MF_E_ARG, "NULL handle");
-    if (field < 0) return fail(MF_E_ARG, "field %d is negative", field);
-    const bool identity = !sep || field == 0;
-    if (!identity && !*sep) return fail(MF_E_ARG, "the separator is empty");
-    std::vector<uint32_t> rec_group;
-    std::vector<std::string> group_names;
-    if (!identity) {          // the field-th sep-separated token of the name (from 1); the whole name when it has fewer fields
-        const std::string sp = sep;
-        std::map<std::string, uint32_t> index;
-        const std::vector<std::string> &names = ks->names();
-        rec_group.reserve(names.size());
-        for (const std::string &nm : names) {
-            size_t at = 0; int f = 1;
-            while (f < field) { const size_t q = nm.find(sp, at); if (q == std::string::npos) break; at = q + sp.size(); f++; }
-            std::string g = nm;
-            if (f == field) { const size_t q = nm.find(sp, at); g = nm.substr(at, q == std::string::npos ? std::string::npos : q - at); }
-            auto it = index.find(g);
-            if (it == index.end()) { it = index.emplace(g, (uint32_t)group_names.size()).first; group_names.push_back(g); }
-            rec_group.push_back(it->second);
-        }
-    }
-    std::lock_guard<std::mutex> lk(ks->mu);
-    for (auto &kv : ks->dev)
-        if (kv.second.gowner) {
-            HIPCHK(hipSetDevice(phys(kv.first)));
-            HIPCHK(hipFree(kv.second.gowner));
-            kv.second.gowner = nullptr;
-        }
-    ks->rec_group.swap(rec_group);
-    ks->group_names.swap(group_names);
-    return MF_OK;
-}
-
-int mf_kmerset_group_count(const mf_kmerset *ks, uint64_t *n_groups)
-{
-    if (!ks) return fail(MF_E_ARG, "NULL handle");
-    if (!n_groups) return fail(MF_E_ARG, "n_groups is NULL");
-    *n_groups = ks->n_groups();
-    return MF_OK;
-}
-
-int mf_kmerset_group_name(const mf_kmerset *ks, uint64_t i, char *buf, size_t buflen, size_t *needed)
-{
-    if (!ks) return fail(MF_E_ARG, "NULL handle");
-    if (i >= ks->n_groups()) return fail(MF_E_ARG, "group %llu out of range (the set has %llu)", (unsigned long long)i, (unsigned long long)ks->n_groups());
-    const std::string &nm = ks->group_name(i);
-    if (needed) *needed = nm.size() + 1;
-    if (!buf || buflen < nm.size() + 1) return fail(MF_E_ARG, "buffer too small: the name needs %llu bytes", (unsigned long long)(nm.size() + 1));
-    memcpy(buf, nm.c_str(), nm.size() + 1);
-    return MF_OK;
-}
-
-int mf_assign_groups(const mf_kmerset *ks_, const mf_reads *reads_, uint32_t threshold, int mode, uint32_t *out_bits, uint32_t *assign_out,
-                     uint64_t *group_reads, mf_filter_stats_t *stats)
-{
-    mf_kmerset *ks = const_cast<mf_kmerset *>(ks_);
-    mf_reads *r = const_cast<mf_reads *>(reads_);
-    if (!ks || !r) return fail(MF_E_ARG, "NULL handle");
-    int rc = filter_common(ks, r, threshold, mode, out_bits, nullptr, 1, stats);
-    if (rc) return rc;
-    return assign_after_filter(ks, r, assign_out, group_reads, nullptr, true);
-}
-
-} // extern "C"
-
-// ------------------------------------------------------------------- k-mer depth
-// The depth tables of a set on `device` (nucleotide or protein): made by the first depth call there, under the set's lock.
-static int depth_tables(mf_kmerset *ks, int device, DevTables *T)
-{
-    std::lock_guard<std::mutex> lk(ks->mu);
-    if (T->rep) return MF_OK;
-    const uint64_t total = ks->positions();
-    if (total >= DEPTH_NONE || ks->slots > DEPTH_NONE) return fail(MF_E_ARG, "k-mer depth takes sets of fewer than 2^32 - 1 positions and slots");
-    DevCtx *ctx; int rc = get_ctx(device, &ctx); if (rc) return rc;
-    hipStream_t st = ctx->stream;
-    const bool prot = ks->kind == MF_KIND_PROTEIN;
-    const bool by_slot = g_opt.depth_index.load() == 1;
-    std::vector<DepthItem> items;
-    const std::vector<uint64_t> &rec_len = ks->rec_len();
-    for (uint64_t j = 0, at = 0; j < rec_len.size(); at += rec_len[j], j++)
-        for (uint64_t a = 0; a < rec_len[j]; a += DEPTH_ITEM) items.push_back(DepthItem{at + a, (uint32_t)std::min<uint64_t>(DEPTH_ITEM, rec_len[j] - a), (uint32_t)j});
-    DevScratch tmp;
-    uint32_t *rep = nullptr, *pos_rep = nullptr; DepthItem *d_items = nullptr;
-    const uint64_t n_cnt = by_slot ? std::max<uint64_t>(ks->slots, total) : total;
-    // (the tables are released with the scratch unless the build completes: they go in first, and leave it last)
-    HIPCHK(tmp.alloc(rep, ks->slots * 4));
-    HIPCHK(tmp.alloc(pos_rep, std::max<uint64_t>(total, 1) * 4));
-    HIPCHK(tmp.alloc(d_items, std::max<size_t>(items.size(), 1) * sizeof(DepthItem)));
-    const size_t keep = tmp.bufs.size();
-    if (!items.empty()) HIPCHK(hipMemcpyAsync(d_items, items.data(), items.size() * sizeof(DepthItem), hipMemcpyHostToDevice, st));
-    if (prot) {          // the residues and run lengths go up for the build only
-        const ProtBaitHost &P = ks->pbait;
-        uint8_t *d_aa = nullptr, *d_run = nullptr;
-        HIPCHK(tmp.alloc(d_aa, P.aa.size()));
-        HIPCHK(tmp.alloc(d_run, P.runlen.size()));
-        HIPCHK(hipMemcpyAsync(d_aa, P.aa.data(), P.aa.size(), hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(d_run, P.runlen.data(), P.runlen.size(), hipMemcpyHostToDevice, st));
-        HIPCHK(launch_build_depth(BaitView{nullptr, P.total, d_run}, d_aa, T->view, rep, pos_rep, by_slot, st));
-    } else {
-        const BaitHost &B = ks->bait;
-        uint32_t *d_words = nullptr; uint8_t *d_run = nullptr;
-        HIPCHK(tmp.alloc(d_words, B.words.size() * 4));
-        HIPCHK(tmp.alloc(d_run, B.runlen.size()));
-        HIPCHK(hipMemcpyAsync(d_words, B.words.data(), B.words.size() * 4, hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(d_run, B.runlen.data(), B.runlen.size(), hipMemcpyHostToDevice, st));
-        HIPCHK(launch_build_depth(BaitView{d_words, B.total, d_run}, nullptr, T->view, rep, pos_rep, by_slot, st));
-    }
-    HIPCHK(hipStreamSynchronize(st));
-    tmp.bufs.erase(tmp.bufs.begin(), tmp.bufs.begin() + keep);
-    T->rep = rep; T->pos_rep = pos_rep; T->ditems = d_items; T->n_ditems = (uint32_t)items.size(); T->dcnt_n = n_cnt;
-    return MF_OK;
-}
-
-// The windows of the reads that passed the filter pass just run on this read set (its bitmap in r->d_bits[r->cur]) added into tot
-// (T->dcnt_n u64 counters on r's device, which other read sets there may be adding into at the same time).  Ends synchronised.
-static int depth_after_filter(mf_kmerset *ks, mf_reads *r, unsigned long long *tot)
-{
-    DevTables *T; int rc = build_on_device(ks, r->device, &T); if (rc) return rc;
-    rc = depth_tables(ks, r->device, T); if (rc) return rc;
-    DevCtx *ctx; rc = get_ctx(r->device, &ctx, r->lane); if (rc) return rc;
-    hipStream_t st = ctx->stream;
-    const uint64_t n = r->v.n_reads, n_cnt = T->dcnt_n;
-    if (!n || !n_cnt) return MF_OK;
-    // a 32-bit counter holds every window of the read set unless they could number 2^32: then the windows go straight into tot
-    const uint64_t span = ks->kind == MF_KIND_PROTEIN ? 3 * (uint64_t)ks->k : (uint64_t)ks->k;
-    const uint64_t per = r->v.uniform_len ? (r->v.uniform_len >= span ? r->v.uniform_len - span + 1 : 0) : 0;
-    const uint64_t bound = (r->v.uniform_len ? n * per : r->v.total_bases) * (ks->kind == MF_KIND_PROTEIN ? 2 : 1);
-    const bool wide = bound >= DEPTH_NONE;
-    HIPCHK(dev_reserve(r->d_acnt, r->cap_acnt, 8, false));
-    HIPCHK(hipMemsetAsync(r->d_acnt, 0, 8, st));
-    HIPCHK(dev_reserve(r->d_alist, r->cap_alist, n * 4, true));
-    if (!wide) { HIPCHK(dev_reserve(r->d_dcnt, r->cap_dcnt, n_cnt * 4, false)); HIPCHK(hipMemsetAsync(r->d_dcnt, 0, n_cnt * 4, st)); }
-    HIPCHK(launch_pass_list(r->d_bits[r->cur], n, r->d_alist, r->d_acnt, st));
-    HIPCHK(launch_depth_count(r->v, T->view, T->rep, r->d_alist, r->d_acnt, wide ? nullptr : r->d_dcnt, wide ? tot : nullptr, ctx->n_cu, st));
-    if (!wide) HIPCHK(launch_depth_fold(r->d_dcnt, n_cnt, tot, st));
-    HIPCHK(hipStreamSynchronize(st));
-    return MF_OK;
-}
-
-// The profile (ks->positions() u32) and the record summaries (R entries) from the totals tot on `device` (stream st); each optional.
-static int depth_report(mf_kmerset *ks, int device, hipStream_t st, const unsigned long long *tot, uint32_t *d_prof, unsigned long long *d_rec,
-                        uint32_t *profile, mf_depth_record_t *records)
-{
-    DevTables *T; int rc = build_on_device(ks, device, &T); if (rc) return rc;
-    rc = depth_tables(ks, device, T); if (rc) return rc;
-    const uint64_t total = ks->positions(), n_rec = ks->rec_len().size();
-    if (records && n_rec) HIPCHK(hipMemsetAsync(d_rec, 0, n_rec * 32, st));
-    if (profile && total) HIPCHK(hipMemsetAsync(d_prof, 0xFF, total * 4, st));          // (records with no item: none, they are empty)
-    HIPCHK(launch_depth_profile(T->ditems, T->n_ditems, T->pos_rep, tot, profile ? d_prof : nullptr, records ? d_rec : nullptr, st));
-    if (profile && total) HIPCHK(hipMemcpyAsync(profile, d_prof, total * 4, hipMemcpyDeviceToHost, st));
-    if (records && n_rec) HIPCHK(hipMemcpyAsync(records, d_rec, n_rec * 32, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    return MF_OK;
-}
-
-extern "C" {
-
-int mf_kmerset_record_starts(const mf_kmerset *ks, uint64_t *starts, size_t n, size_t *needed)
-{
-    if (!ks) return fail(MF_E_ARG, "NULL handle");
-    const std::vector<uint64_t> &len = ks->rec_len();
-    if (needed) *needed = len.size() + 1;
-    if (!starts || n < len.size() + 1) return fail(MF_E_ARG, "buffer too small: the set has %llu records, %llu offsets", (unsigned long long)len.size(), (unsigned long long)(len.size() + 1));
-    starts[0] = 0;
-    for (size_t j = 0; j < len.size(); j++) starts[j + 1] = starts[j] + len[j];
-    return MF_OK;
-}
-
-int mf_depth(const mf_kmerset *ks_, const mf_reads *reads_, uint32_t threshold, int mode, uint32_t *out_bits, uint32_t *profile,
-             mf_depth_record_t *records, mf_filter_stats_t *stats)
-{
-    mf_kmerset *ks = const_cast<mf_kmerset *>(ks_);
-    mf_reads *r = const_cast<mf_reads *>(reads_);
-    if (!ks || !r) return fail(MF_E_ARG, "NULL handle");
-    int rc = filter_common(ks, r, threshold, mode, out_bits, nullptr, 1, stats);
-    if (rc) return rc;
-    DevTables *T; rc = build_on_device(ks, r->device, &T); if (rc) return rc;
-    rc = depth_tables(ks, r->device, T); if (rc) return rc;
-    DevCtx *ctx; rc = get_ctx(r->device, &ctx, r->lane); if (rc) return rc;
-    hipStream_t st = ctx->stream;
-    const uint64_t n_cnt = T->dcnt_n, total = ks->positions(), n_rec = ks->rec_len().size();
-    HIPCHK(dev_reserve(r->d_dtot, r->cap_dtot, std::max<uint64_t>(n_cnt, 1) * 8, false));
-    HIPCHK(hipMemsetAsync(r->d_dtot, 0, std::max<uint64_t>(n_cnt, 1) * 8, st));
-    rc = depth_after_filter(ks, r, r->d_dtot); if (rc) return rc;
-    // (the profile goes through the pass's 32-bit counters, which the totals have taken up)
-    HIPCHK(dev_reserve(r->d_dcnt, r->cap_dcnt, std::max<uint64_t>(std::max(n_cnt, total), 1) * 4, false));
-    HIPCHK(dev_reserve(r->d_drec, r->cap_drec, std::max<uint64_t>(n_rec, 1) * 32, false));
-    return depth_report(ks, r->device, st, r->d_dtot, r->d_dcnt, r->d_drec, profile, records);
-}
-
 } // extern "C"
 
 // ------------------------------------------------------------- file level
@@ -1434,39 +1035,11 @@ int mf_depth(const mf_kmerset *ks_, const mf_reads *reads_, uint32_t threshold, 
 static thread_local mf_ingest_stats_t t_ingest_stats;
 static thread_local bool t_ingest_stats_valid = false;
 
-// The 64-bit depth totals of a file-level call with depth: one array per (logical) device, made and zeroed when a batch there first asks
-// for it, shared by the device's workers and lanes (their folds are atomic)
-struct DepthTotals {
-    mf_kmerset *ks = nullptr;
-    std::mutex mu;
-    std::map<int, unsigned long long *> tot;
-    ~DepthTotals() { for (auto &kv : tot) if (hipSetDevice(phys(kv.first)) == hipSuccess) hipFree(kv.second); }
-    int on(int device, unsigned long long **out)
-    {
-        std::lock_guard<std::mutex> lk(mu);
-        auto it = tot.find(device);
-        if (it != tot.end()) { *out = it->second; return MF_OK; }
-        DevTables *T; int rc = build_on_device(ks, device, &T); if (rc) return rc;
-        rc = depth_tables(ks, device, T); if (rc) return rc;
-        DevCtx *ctx; rc = get_ctx(device, &ctx); if (rc) return rc;
-        const size_t bytes = std::max<uint64_t>(T->dcnt_n, 1) * 8;
-        unsigned long long *p = nullptr;
-        HIPCHK(dev_malloc(&p, bytes));
-        tot[device] = p;
-        HIPCHK(hipMemsetAsync(p, 0, bytes, ctx->stream));
-        HIPCHK(hipStreamSynchronize(ctx->stream));
-        *out = p;
-        return MF_OK;
-    }
-    void clear() { for (auto &kv : tot) if (hipSetDevice(phys(kv.first)) == hipSuccess) hipFree(kv.second); tot.clear(); }
-};
-
 // the file-level call on a list of (logical) devices
-// tally (optional): the kept reads are counted per bait record as well (mf_filter_fastq_files_by_record), on whichever path takes the input;
-// with tally->want_depth, the windows of every mate that passes go into depth's totals instead (mf_filter_fastq_files_depth)
-static int filter_fastq_files_on(mf_kmerset *ks, const char *fq1, const char *fq2, const char *out1, const char *out2,
-                                 uint32_t threshold, int pair_mode, const int *devices, int n_devices, uint64_t *kept, uint64_t *total,
-                                 RecordTally *tally = nullptr, bool by_group = false, DepthTotals *depth = nullptr)
+// report (optional): what the call reports on the reads that pass (mf_report.cpp), on whichever path takes the input: its after_pass runs
+// behind every mate batch's pass, and the kept reads are tallied from the pairs it makes
+int filter_fastq_files_on(mf_kmerset *ks, const char *fq1, const char *fq2, const char *out1, const char *out2,
+                          uint32_t threshold, int pair_mode, const int *devices, int n_devices, uint64_t *kept, uint64_t *total, PassReport *report)
 {
     if (!ks || !fq1 || !out1) return fail(MF_E_ARG, "NULL argument");
     if ((fq2 == nullptr) != (out2 == nullptr)) return fail(MF_E_ARG, "fq2 and out2 must be given together");
@@ -1500,19 +1073,7 @@ static int filter_fastq_files_on(mf_kmerset *ks, const char *fq1, const char *fq
         }
         if (!(ing && strcmp(ing, "host") == 0) && (force || any_gz || big_plain)) {
             std::string derr; IngestStats is;
-            if (tally && tally->depth()) tally->reads_depth = [ks, depth](mf_reads *R, std::string &err) -> int {
-                unsigned long long *tot = nullptr;
-                int rc = depth->on(R->device, &tot);
-                if (rc == MF_OK) rc = depth_after_filter(ks, R, tot);
-                if (rc != MF_OK) err = t_err;
-                return rc;
-            };
-            else if (tally) tally->reads_pairs = [ks, by_group](mf_reads *R, std::vector<uint64_t> &pairs, std::string &err) -> int {
-                const int rc = assign_after_filter(ks, R, nullptr, nullptr, &pairs, by_group);
-                if (rc != MF_OK) err = t_err;
-                return rc;
-            };
-            const int drc = run_device_ingest(ks, fq1, fq2, out1, out2, threshold, pair_mode == MF_PAIR_BOTH, devices, n_devices, kept, total, derr, &is, tally);
+            const int drc = run_device_ingest(ks, fq1, fq2, out1, out2, threshold, pair_mode == MF_PAIR_BOTH, devices, n_devices, kept, total, derr, &is, report);
             if (drc == MF_OK) {
                 mf_ingest_stats_t &o = t_ingest_stats;
                 memset(&o, 0, sizeof o);
@@ -1525,8 +1086,7 @@ static int filter_fastq_files_on(mf_kmerset *ks, const char *fq1, const char *fq
                 return MF_OK;
             }
             if (drc != MF_DEVINGEST_DECLINED) return fail(drc, "%s", derr.c_str());
-            if (tally) tally->reset(tally->n_rec);          // (nothing was kept on the path that declined)
-            if (depth) depth->clear();
+            if (report) report->restart();          // (nothing was kept on the path that declined)
             if (getenv("MF_PIPE_TIMING")) fprintf(stderr, "[mf device ingest] declined%s%s: the host pipeline takes the input\n", derr.empty() ? "" : ": ", derr.c_str());
         }
     }
@@ -1553,10 +1113,10 @@ static int filter_fastq_files_on(mf_kmerset *ks, const char *fq1, const char *fq
     const int lanes = (int)env_u32("MF_WORKERS_PER_DEVICE", 2) < 1 ? 1 : (int)env_u32("MF_WORKERS_PER_DEVICE", 2);
     const int n_workers = n_devices * lanes;
     std::vector<mf_reads *> arena((size_t)n_workers, nullptr);
-    std::vector<uint64_t> batch_n((size_t)n_workers, 0);          // reads of the batch each worker filtered last
-    BatchFilterFn fn = [ks, threshold, n_devices, dev_base, &arena, &batch_n](int worker, const PackedHost &P, uint64_t n, std::vector<uint32_t> &bits, std::string &err) -> int {
+    if (report) report->held.assign((size_t)n_workers, nullptr);
+    BatchFilterFn fn = [ks, threshold, n_devices, dev_base, report, &arena](int worker, const PackedHost &P, uint64_t n, std::vector<uint32_t> &bits, std::string &err) -> int {
         bits.assign((n + 31) / 32 + 1, 0);
-        batch_n[(size_t)worker] = n;
+        if (report) report->held[(size_t)worker] = nullptr;          // (an empty batch, or a pass that fails: nothing to report on)
         if (n == 0) return MF_OK;
         const int device = dev_base + worker % n_devices, lane = worker / n_devices;
         DevCtx *ctx; int rc = get_ctx(device, &ctx, lane);
@@ -1569,27 +1129,12 @@ static int filter_fastq_files_on(mf_kmerset *ks, const char *fq1, const char *fq
                             P.npos.data(), P.npos.size(), ctx);
         if (rc == MF_OK) rc = filter_common(ks, arena[worker], threshold, MF_MODE_SCREENED, bits.data(), nullptr, 1, nullptr);
         if (rc != MF_OK) err = t_err;
-        return rc;
-    };
-    if (tally && tally->depth()) tally->worker_depth = [ks, depth, &arena, &batch_n](int worker, std::string &err) -> int {
-        if (batch_n[(size_t)worker] == 0) return MF_OK;
-        mf_reads *R = arena[(size_t)worker];
-        unsigned long long *tot = nullptr;
-        int rc = depth->on(R->device, &tot);
-        if (rc == MF_OK) rc = depth_after_filter(ks, R, tot);
-        if (rc != MF_OK) err = t_err;
-        return rc;
-    };
-    else if (tally) tally->worker_pairs = [ks, by_group, &arena, &batch_n](int worker, std::vector<uint64_t> &pairs, std::string &err) -> int {
-        pairs.clear();
-        if (batch_n[(size_t)worker] == 0) return MF_OK;
-        const int rc = assign_after_filter(ks, arena[(size_t)worker], nullptr, nullptr, &pairs, by_group);
-        if (rc != MF_OK) err = t_err;
+        else if (report) report->held[(size_t)worker] = arena[worker];          // (this worker's read set holds the mate until its next batch)
         return rc;
     };
     PipelineStats ps; std::string perr;
     const auto t_pipe0 = std::chrono::steady_clock::now();
-    const int rc = run_fastq_pipeline(fq1, fq2, out1, out2, pair_mode == MF_PAIR_BOTH, n_workers, pack_threads, batch_reads, fn, ps, perr, tally);
+    const int rc = run_fastq_pipeline(fq1, fq2, out1, out2, pair_mode == MF_PAIR_BOTH, n_workers, pack_threads, batch_reads, fn, ps, perr, report);
     {
         mf_ingest_stats_t &o = t_ingest_stats;
         memset(&o, 0, sizeof o);
@@ -1609,6 +1154,8 @@ static int filter_fastq_files_on(mf_kmerset *ks, const char *fq1, const char *fq
     return MF_OK;
 }
 
+extern "C" {
+
 int mf_filter_fastq_files(mf_kmerset *ks, const char *fq1, const char *fq2, const char *out1, const char *out2,
                           uint32_t threshold, int pair_mode, int n_devices, uint64_t *kept, uint64_t *total)
 {
@@ -1618,74 +1165,13 @@ int mf_filter_fastq_files(mf_kmerset *ks, const char *fq1, const char *fq2, cons
     if (n_devices > have) n_devices = have;
     std::vector<int> devs((size_t)n_devices);
     for (int i = 0; i < n_devices; i++) devs[(size_t)i] = i;
-    return filter_fastq_files_on(ks, fq1, fq2, out1, out2, threshold, pair_mode, devs.data(), n_devices, kept, total);
+    return filter_fastq_files_on(ks, fq1, fq2, out1, out2, threshold, pair_mode, devs.data(), n_devices, kept, total, nullptr);
 }
 
 int mf_filter_fastq_files_on(mf_kmerset *ks, const char *fq1, const char *fq2, const char *out1, const char *out2,
                              uint32_t threshold, int pair_mode, const int *devices, int n_devices, uint64_t *kept, uint64_t *total)
 {
-    return filter_fastq_files_on(ks, fq1, fq2, out1, out2, threshold, pair_mode, devices, n_devices, kept, total);
-}
-
-int mf_filter_fastq_files_by_record(mf_kmerset *ks, const char *fq1, const char *fq2, const char *out1, const char *out2,
-                                    uint32_t threshold, int pair_mode, const int *devices, int n_devices,
-                                    uint64_t *record_reads, uint64_t *kept, uint64_t *total)
-{
-    int rc = need_nucleotide(ks); if (rc) return rc;
-    if (!record_reads) return fail(MF_E_ARG, "record_reads is NULL");
-    RecordTally tally;
-    tally.reset((uint32_t)ks->bait.rec_len.size());
-    rc = filter_fastq_files_on(ks, fq1, fq2, out1, out2, threshold, pair_mode, devices, n_devices, kept, total, &tally);
-    if (rc) return rc;
-    std::copy(tally.counts.begin(), tally.counts.end(), record_reads);
-    return MF_OK;
-}
-
-int mf_filter_fastq_files_by_group(mf_kmerset *ks, const char *fq1, const char *fq2, const char *out1, const char *out2,
-                                   uint32_t threshold, int pair_mode, const int *devices, int n_devices,
-                                   uint64_t *group_reads, uint64_t *kept, uint64_t *total)
-{
-    if (!ks) return fail(MF_E_ARG, "NULL handle");
-    if (!group_reads) return fail(MF_E_ARG, "group_reads is NULL");
-    RecordTally tally;
-    tally.reset(ks->n_groups());
-    const int rc = filter_fastq_files_on(ks, fq1, fq2, out1, out2, threshold, pair_mode, devices, n_devices, kept, total, &tally, true);
-    if (rc) return rc;
-    std::copy(tally.counts.begin(), tally.counts.end(), group_reads);
-    return MF_OK;
-}
-
-int mf_filter_fastq_files_depth(mf_kmerset *ks, const char *fq1, const char *fq2, const char *out1, const char *out2,
-                                uint32_t threshold, int pair_mode, const int *devices, int n_devices,
-                                uint32_t *profile, mf_depth_record_t *records, uint64_t *kept, uint64_t *total)
-{
-    if (!ks) return fail(MF_E_ARG, "NULL handle");
-    DepthTotals dt; dt.ks = ks;
-    RecordTally tally; tally.want_depth = true;
-    int rc = filter_fastq_files_on(ks, fq1, fq2, out1, out2, threshold, pair_mode, devices, n_devices, kept, total, &tally, false, &dt);
-    if (rc) return rc;
-    // the devices' totals summed on the host into the first listed device's, then the profile and summary kernels once, there
-    const int dev0 = devices[0];
-    unsigned long long *t0 = nullptr;
-    rc = dt.on(dev0, &t0); if (rc) return rc;
-    DevTables *T; rc = build_on_device(ks, dev0, &T); if (rc) return rc;
-    const uint64_t n_cnt = T->dcnt_n;
-    if (dt.tot.size() > 1 && n_cnt) {
-        std::vector<uint64_t> sum(n_cnt, 0), part(n_cnt);
-        for (auto &kv : dt.tot) {
-            HIPCHK(hipSetDevice(phys(kv.first)));
-            HIPCHK(hipMemcpy(part.data(), kv.second, n_cnt * 8, hipMemcpyDeviceToHost));
-            for (uint64_t i = 0; i < n_cnt; i++) sum[i] += part[i];
-        }
-        HIPCHK(hipSetDevice(phys(dev0)));
-        HIPCHK(hipMemcpy(t0, sum.data(), n_cnt * 8, hipMemcpyHostToDevice));
-    }
-    DevCtx *ctx; rc = get_ctx(dev0, &ctx); if (rc) return rc;
-    DevScratch tmp;
-    uint32_t *d_prof = nullptr; unsigned long long *d_rec = nullptr;
-    HIPCHK(tmp.alloc(d_prof, std::max<uint64_t>(ks->positions(), 1) * 4));
-    HIPCHK(tmp.alloc(d_rec, std::max<uint64_t>(ks->rec_len().size(), 1) * 32));
-    return depth_report(ks, dev0, ctx->stream, t0, d_prof, d_rec, profile, records);
+    return filter_fastq_files_on(ks, fq1, fq2, out1, out2, threshold, pair_mode, devices, n_devices, kept, total, nullptr);
 }
 
 int mf_set_option(const char *name, const char *value)

@@ -1,11 +1,17 @@
-// Internals of mf_api.cpp that the device ingest path (mf_devingest.cpp) shares: device contexts, the read-set handle and
-// the filter call.  Not part of the C ABI.
+// Internals of mf_api.cpp that the device ingest path (mf_devingest.cpp) and the reports (mf_report.cpp) share: device contexts, the
+// k-mer set and read-set handles, the filter call and the file-level worker.  Not part of the C ABI.
 #pragma once
 #include "../../include/mitofilter.h"
 #include "mf_common.h"
+#include "mf_host.h"
 #include "mf_kernels.h"
+#include "mf_assign.h"
 #include <hip/hip_runtime.h>
+#include <algorithm>
+#include <map>
+#include <mutex>
 #include <string>
+#include <vector>
 
 // stream2: finish kernels of pipelined passes (stream4: those of every other pass when the finish kernels are what a pass waits for); stream3: every other screen
 struct DevCtx { int device = -1; hipStream_t stream = nullptr, stream2 = nullptr, stream3 = nullptr, stream4 = nullptr; int n_cu = 0; };
@@ -14,6 +20,10 @@ int fail(int code, const char *fmt, ...);               // sets the thread's err
 const std::string &mf_thread_error();
 int phys(int device);                                   // logical -> physical device (MF_FAKE_DEVICES)
 int get_ctx(int device, DevCtx **out, int lane = 0);
+#define HIPCHK(call)                                                                                  \
+    do { hipError_t e_ = (call);                                                                      \
+         if (e_ != hipSuccess) return fail(MF_E_HIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); \
+    } while (0)
 
 // The device ingest path keeps device buffers of earlier calls in a pool per device (mf_devingest.cpp).  Memory that sits there idle must
 // never make another allocation of this library fail: release_cached_device_memory() gives the current device's idle pool buffers (and, with
@@ -43,6 +53,64 @@ template <class T> inline hipError_t dev_reserve(T *&p, size_t &cap, size_t byte
     return e;
 }
 
+
+// ------------------------------------------------------------------ kmerset
+struct DevTables {
+    uint64_t *keys = nullptr;
+    uint32_t *bloom = nullptr, *stab = nullptr, *kbloom = nullptr, *kbloom_co = nullptr, *plut = nullptr;    // kbloom_co: own allocation only when it differs from kbloom
+    uint32_t *front2 = nullptr, *front3 = nullptr, *pre = nullptr;      // bait-sized fronts of the large-bait screen (front_mode 1 .. 4); mode 4's one-bit LDS table
+    mf::KmerSetView view{};
+    uint64_t n_keys = 0, n_smers = 0;
+    uint32_t *owner = nullptr;          // record owner of every slot of `keys` (mf_assign.h), built by the first call that asks for it
+    uint32_t *gowner = nullptr;         // group owner of every slot for the set's current grouping, likewise (freed when the set is regrouped)
+    // k-mer depth (mf_depth), built by the first depth call: representative position of every slot, of every bait position's window, and
+    // the profile kernel's work items; dcnt_n counters a pass (the positions, or the slots under depth_index=1)
+    uint32_t *rep = nullptr, *pos_rep = nullptr; mf::DepthItem *ditems = nullptr; uint32_t n_ditems = 0; uint64_t dcnt_n = 0;
+    // frees one table / every table (the current device is the tables')
+    template <class T> static hipError_t drop(T *&p) { const hipError_t e = hipFree(p); p = nullptr; return e; }
+    void release()
+    {
+        drop(keys); drop(bloom); drop(stab); drop(kbloom); drop(kbloom_co); drop(plut); drop(front2); drop(front3); drop(pre);
+        drop(owner); drop(gowner); drop(rep); drop(pos_rep); drop(ditems);
+    }
+};
+struct mf_kmerset {
+    int k = 0, kw = 1;
+    int kind = MF_KIND_NUCLEOTIDE, genetic_code = 0;   // protein sets: k = residues per key, reads translated with genetic_code
+    mf::ProtBaitHost pbait;
+    uint32_t codon_lut[256] = {0};
+    bool kb_in_lds = true;
+    mf::BaitHost bait;
+    uint64_t n_windows = 0, slots = 0;
+    mf::ScreenGeom geom{0, 0};
+    uint32_t bloom_log2w = 0, stage2_log2w = 0, stab_slots = 0, kb_log2w = 0;
+    uint32_t front_mode = 0, f2_log2b = 0, f3_log2b = 0, pre_log2w = 0;
+    int canon = 0;              // != 0: the screen's tables hold one canonical key per bait s-mer (mf::KmerSetView::canon: 1 sixteen-base samples, 2 shorter)
+    bool s8_finish = false;     // a stride-8 set whose threshold-1 passes go through screen + finish (baits beyond ~20 kbp)
+    size_t screen_words() const { return ((size_t)1 << bloom_log2w) + ((size_t)1 << stage2_log2w); }
+    // grouping of the records (mf_kmerset_group_records): empty rec_group = identity (each record its own group, named after it)
+    std::vector<uint32_t> rec_group;
+    std::vector<std::string> group_names;
+    std::mutex mu;
+    std::map<int, DevTables> dev;
+    const std::vector<std::string> &names() const { return kind == MF_KIND_PROTEIN ? pbait.names : bait.names; }
+    uint32_t n_records() const { return (uint32_t)names().size(); }
+    uint32_t n_groups() const { return rec_group.empty() ? n_records() : (uint32_t)group_names.size(); }
+    const std::string &group_name(uint64_t i) const { return rec_group.empty() ? names()[i] : group_names[i]; }
+    const std::vector<uint64_t> &rec_len() const { return kind == MF_KIND_PROTEIN ? pbait.rec_len : bait.rec_len; }
+    uint64_t positions() const { return kind == MF_KIND_PROTEIN ? pbait.total : bait.total; }       // bases / residues of all records
+};
+
+// device temporaries of one build: released on every exit path
+struct DevScratch {
+    std::vector<void *> bufs;
+    template <class T> hipError_t alloc(T *&p, size_t bytes) { hipError_t e = dev_malloc(&p, bytes); if (e == hipSuccess) bufs.push_back(p); return e; }
+    template <class T> T *release(T *p) { bufs.erase(std::remove(bufs.begin(), bufs.end(), (void *)p), bufs.end()); return p; }     // p outlives the build
+    ~DevScratch() { for (void *p : bufs) hipFree(p); }
+};
+// the tables of a set on `device`, built by the first call that asks for them
+int build_on_device(mf_kmerset *ks, int device, DevTables **out);
+int depth_index_option();          // the "depth_index" option as it is set now (mf_set_option)
 
 // Buffer sets a pipelined pass rotates through.  (Round 2 measured nothing from a third; since the finish kernels of two-word keys run on two streams and
 // outlast a screen, it is worth 4 % of a pass for them: profiles/r06/n_three_sets.txt -- one-word keys keep to two, mf_api.cpp enqueue_pass.  A fourth adds nothing.)
@@ -97,3 +165,7 @@ int reads_finish(mf_reads *r, bool reuse, uint64_t n_words, uint64_t n_reads, ui
 // one or more passes of the filter over a resident read set; out_bits / hits_out may be null (the result stays in r->d_bits[r->cur])
 int filter_common(const mf_kmerset *ks, const mf_reads *reads, uint32_t thr, int mode, uint32_t *out_bits, uint32_t *hits_out, int steps,
                   mf_filter_stats_t *stats, uint64_t *pass_per_step = nullptr);
+// the file-level call on a list of (logical) devices; report: what it reports on the reads that pass (mf_pipeline.h), or null
+namespace mf { struct PassReport; }
+int filter_fastq_files_on(mf_kmerset *ks, const char *fq1, const char *fq2, const char *out1, const char *out2,
+                          uint32_t threshold, int pair_mode, const int *devices, int n_devices, uint64_t *kept, uint64_t *total, mf::PassReport *report);

@@ -186,12 +186,12 @@ struct CallRunning { CallRunning() { g_calls_running++; } ~CallRunning() { g_cal
 
 int run_device_ingest(mf_kmerset *ks, const char *fq1, const char *fq2, const char *out1, const char *out2, uint32_t threshold,
                       bool pair_both, const int *devices, int n_devices, uint64_t *kept, uint64_t *total, std::string &err, IngestStats *stats,
-                      RecordTally *tally)
+                      PassReport *report)
 {
     g_knobs.refresh();          // (the environment as it is now: tests change it between calls of one process)
     CallRunning running;
     Ingest I;
-    I.ks = ks; I.threshold = threshold; I.pair_both = pair_both; I.tally = tally;
+    I.ks = ks; I.threshold = threshold; I.pair_both = pair_both; I.report = report;
     for (int i = 0; i < n_devices; i++) I.devices.push_back(devices[i]);
     const int rc = run_ingest(I, fq1, fq2, out1, out2, err, stats);
     if (rc) return rc;

@@ -22,13 +22,13 @@ struct IngestStats {
     int n_devices = 0, consumers = 0;
 };
 
-struct RecordTally;
+struct PassReport;
 // fq2 / out2 null: single end.  devices: the (logical) devices the slabs of the input are dealt to, round robin.
 // Returns MF_OK, MF_DEVINGEST_DECLINED (no survivor has been written: the caller takes the host pipeline) or an MF_E_* code with err set.
-// tally (optional): per-record counts of the kept reads, from the assignment its reads_pairs makes of every piece (mf_pipeline.h)
+// report (optional): what the call reports on the reads that pass, through its after_pass behind every piece's pass (mf_pipeline.h)
 int run_device_ingest(mf_kmerset *ks, const char *fq1, const char *fq2, const char *out1, const char *out2, uint32_t threshold,
                       bool pair_both, const int *devices, int n_devices, uint64_t *kept, uint64_t *total, std::string &err, IngestStats *stats = nullptr,
-                      RecordTally *tally = nullptr);
+                      PassReport *report = nullptr);
 
 // The same path with the reference's FASTQ quality filter (filter_v2: filter/filter_bin/src/main.rs:188-323) as its job instead of the
 // bait filter: counting, hashing, the de-duplication set, the decisions and the formatting of the kept records run on `device` over

@@ -61,7 +61,7 @@ struct Batch {
     uint64_t n_rec = 0, rec_base = 0, n_text = 0, n_lines = 0;
     int ldev = 0;
     bool filtered = false;               // its pass bits are in the mate's bitmap
-    std::vector<uint64_t> pairs;         // record assignment of its passing reads (Ingest::tally): (record in the batch << 32) | record of the bait
+    std::vector<uint64_t> pairs;         // record assignment of its passing reads (Ingest::report): (record in the batch << 32) | record of the bait
     // the quality filter's job (QualState below): what one pass over the records found, kept with the batch until its turn to be decided
     DevBuf<uint32_t> q_bad, q_sl, q_ql, q_olen; DevBuf<uint8_t> q_fl; DevBuf<uint64_t> q_hash;
     uint64_t q_done = 0;                                  // (Ingest::mu) records of it that have been decided

@@ -10,7 +10,7 @@ namespace {
 struct Ingest {
     mf_kmerset *ks = nullptr; uint32_t threshold = 1; bool pair_both = false; std::vector<int> devices;
     QualState *qual = nullptr;          // set: the job is the quality filter (one device), not the bait filter
-    RecordTally *tally = nullptr;       // set: the kept reads are tallied per bait record as well
+    PassReport *report = nullptr;       // set: the call reports on the reads that pass (mf_pipeline.h)
     Mate m[2]; int nm = 1;
     uint64_t kept = 0, total = 0;
     std::atomic<bool> first_indexed_{false}, first_filtered_{false};
@@ -294,7 +294,7 @@ struct Ingest {
         if (bw + 2 > S.h_bits_cap) { if (S.h_bits) (void)hipHostFree(S.h_bits); S.h_bits = nullptr; S.h_bits_cap = 0; DCHK(hipHostMalloc((void **)&S.h_bits, (bw + bw / 2 + 1024) * 4, hipHostMallocDefault)); S.h_bits_cap = bw + bw / 2 + 1024; }
         rc = filter_common(ks, R, threshold, MF_MODE_SCREENED, S.h_bits, nullptr, 1, nullptr);
         if (rc) { err = mf_thread_error(); return rc; }
-        if (tally) { rc = tally->depth() ? tally->reads_depth(R, err) : tally->reads_pairs(R, Bt.pairs, err); if (rc) return rc; }
+        if (report) { rc = report->after_pass(R, Bt.pairs, err); if (rc) return rc; }
         if (!first_filtered_.exchange(true)) cold_mark("consumer: first piece packed and filtered");
         {
             size_t f = 0, t = 0; const bool got = hipMemGetInfo(&f, &t) == hipSuccess;
@@ -330,7 +330,7 @@ struct Ingest {
         }
         for (size_t j = 0; j < bw; j++) keep_n += (uint64_t)__builtin_popcount(S.h_bits[j]);
         if (mi == 0) kept += keep_n;
-        if (tally && !tally->depth()) { const uint32_t *kb = S.h_bits; tally->add(B.pairs, n_emit, keep_n, [kb](uint64_t i) { return ((kb[i >> 5] >> (i & 31)) & 1u) != 0; }); }
+        if (report) { const uint32_t *kb = S.h_bits; report->add(B.pairs, n_emit, keep_n, [kb](uint64_t i) { return ((kb[i >> 5] >> (i & 31)) & 1u) != 0; }); }
         if (!keep_n) return MF_OK;
         // the survivors are few: their record numbers go up as a list (in place of the mask they were read from), and the kernels
         // that measure and copy them run over the list

@@ -395,7 +395,7 @@ using PairPtr = std::shared_ptr<PairBatch>;
 
 int run_fastq_pipeline(const char *fq1, const char *fq2, const char *out1, const char *out2, bool pair_both,
                        int n_devices, int pack_threads, uint64_t batch_reads, const BatchFilterFn &filter,
-                       PipelineStats &stats, std::string &err, RecordTally *tally)
+                       PipelineStats &stats, std::string &err, PassReport *report)
 {
     const int nm = fq2 ? 2 : 1;
     const char *in_path[2] = {fq1, fq2}, *out_path[2] = {out1, out2};
@@ -491,7 +491,7 @@ int run_fastq_pipeline(const char *fq1, const char *fq2, const char *out1, const
                     std::string e;
                     const uint64_t t0 = now_us();
                     int r = filter(d, pb->packed[m], pb->n, bits[m], e);
-                    if (r == MF_OK && tally) r = tally->depth() ? tally->worker_depth(d, e) : tally->worker_pairs(d, pairs[m], e);      // (the worker's read set still holds this mate)
+                    if (r == MF_OK && report) r = report->after_pass(report->held[d], pairs[m], e);      // (the worker's read set still holds this mate)
                     t_dev += now_us() - t0;
                     if (r != MF_OK) { set_err(r, e); abort_all(); ok = false; }
                 }
@@ -503,7 +503,7 @@ int run_fastq_pipeline(const char *fq1, const char *fq2, const char *out1, const
                     const uint8_t k = (uint8_t)(nm == 2 ? (pair_both ? (a & b) : (a | b)) : a);
                     pb->keep[i] = k; kc += k;
                 }
-                if (tally && !tally->depth()) for (int m = 0; m < nm; m++) tally->add(pairs[m], pb->n, kc, [&](uint64_t i) { return pb->keep[i] != 0; });
+                if (report) for (int m = 0; m < nm; m++) report->add(pairs[m], pb->n, kc, [&](uint64_t i) { return pb->keep[i] != 0; });
                 { std::lock_guard<std::mutex> lk(stat_mu); stats.kept += kc; stats.total += pb->n; stats.batches++; }
                 for (int m = 0; m < nm; m++) if (!q_write[m].push(pb)) { ok = false; break; }
                 if (!ok) break;

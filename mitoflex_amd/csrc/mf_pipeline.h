@@ -13,26 +13,26 @@ struct mf_reads;
 
 namespace mf {
 
-// Per-record counts of the kept reads of a file-level call (mf_filter_fastq_files_by_record).  The library hands the assignment in
-// through the two callbacks; the ingest paths call the one that is theirs right behind a batch's filter pass, on the read set that
-// still holds it, and tally once the pair rule has decided which reads are kept.  Pairs are (read in the batch << 32) | record, the
-// record being 0xFFFFFFFE for a passing read that no record wins; only passing reads have one.
-struct RecordTally {
-    uint32_t n_rec = 0;
+// What a file-level call reports about the reads that pass (mf_report.cpp: reads per record, per group, k-mer depth).  Both ingest paths
+// call after_pass once per mate batch right behind its filter pass, on the worker thread that ran the pass and on the read set that still
+// holds the batch, and tally its pairs once the pair rule has decided which reads are kept.  Pairs are (read in the batch << 32) | record,
+// the record being 0xFFFFFFFE for a passing read that no record wins; only passing reads have one.  A report that counts something else
+// (depth) leaves the pairs empty and is made without counts: it tallies nothing.
+struct PassReport {
+    const uint32_t n_rec;
+    // host pipeline: held[worker] = the read set that holds the batch the worker has just filtered (null: an empty batch), set by the
+    // filter closure, which owns the read sets, and handed to after_pass by the same worker thread
+    std::vector<mf_reads *> held;
     std::vector<uint64_t> counts;               // n_rec + 2: kept reads (mates one by one) assigned to each record, ambiguous, unassigned
-    std::function<int(int worker, std::vector<uint64_t> &pairs, std::string &err)> worker_pairs;       // host pipeline: the batch `worker` has just filtered
-    std::function<int(mf_reads *reads, std::vector<uint64_t> &pairs, std::string &err)> reads_pairs;   // device ingest path: a piece's read set
-    // k-mer depth (mf_filter_fastq_files_depth) instead of the pairs, when want_depth is set: the same two places add the batch's passing
-    // reads into the depth counters of its device, and nothing is tallied
-    bool want_depth = false;
-    std::function<int(int worker, std::string &err)> worker_depth;
-    std::function<int(mf_reads *reads, std::string &err)> reads_depth;
-    bool depth() const { return want_depth; }
     std::mutex mu;
-    void reset(uint32_t n) { n_rec = n; counts.assign((size_t)n + 2, 0); }
+    explicit PassReport(uint32_t n, bool tallies = true) : n_rec(n), counts(tallies ? (size_t)n + 2 : 0, 0) {}
+    virtual ~PassReport() = default;
+    virtual int after_pass(mf_reads *reads, std::vector<uint64_t> &pairs, std::string &err) = 0;
+    virtual void restart() { counts.assign(counts.size(), 0); }          // the path that had taken the input declined it: nothing was kept
     // one mate's batch of n reads, n_kept of them kept (keep(i): read i is)
     template <class KeepFn> void add(const std::vector<uint64_t> &pairs, uint64_t n, uint64_t n_kept, KeepFn keep)
     {
+        if (counts.empty()) return;
         std::lock_guard<std::mutex> lk(mu);
         uint64_t assigned = 0;
         for (const uint64_t pr : pairs) {
@@ -51,7 +51,7 @@ struct PipelineStats { uint64_t kept = 0, total = 0, batches = 0; };
 
 int run_fastq_pipeline(const char *fq1, const char *fq2, const char *out1, const char *out2, bool pair_both,
                        int n_devices, int pack_threads, uint64_t batch_reads, const BatchFilterFn &filter,
-                       PipelineStats &stats, std::string &err, RecordTally *tally = nullptr);
+                       PipelineStats &stats, std::string &err, PassReport *report = nullptr);
 
 // ---------------------------------------------------------------- FASTQ quality filter (filter_v2)
 struct QualParams {

@@ -1,0 +1,435 @@
+// libmitofilter_hip: the reports on the reads that pass the filter -- reads per bait record (mf_assign), per group of records
+// (mf_assign_groups), k-mer depth along the records (mf_depth) -- and their file-level calls.  Each runs behind a filter pass of
+// mf_api.cpp on the read set that still holds the pass's bitmap; the kernels are mf_assign.hip's.
+#include "mf_api_internal.h"
+#include "mf_pipeline.h"
+
+#include <string.h>
+
+using namespace mf;
+
+// record j holds positions [starts[j], starts[j + 1]) of the set (bases or residues): n_rec + 1 offsets
+static std::vector<uint64_t> record_starts(const mf_kmerset *ks)
+{
+    const std::vector<uint64_t> &len = ks->rec_len();
+    std::vector<uint64_t> starts(len.size() + 1, 0);
+    for (size_t j = 0; j < len.size(); j++) starts[j + 1] = starts[j] + len[j];
+    return starts;
+}
+
+// A set's bait on the device for the time of a table build: bases (nucleotide) or residues (protein), run lengths, record starts.
+// Released with the build's other temporaries (tmp) on every exit path.
+struct BaitOnDevice {
+    DevScratch tmp;
+    BaitView view{nullptr, 0, nullptr};          // words: null for a protein set
+    const uint8_t *aa = nullptr;                 // residues: null for a nucleotide set
+    const uint64_t *rec_start = nullptr; uint32_t n_rec = 0;
+    std::vector<uint64_t> starts;                // (the host copy lives as long as the upload may be running)
+    template <class T> int put(const T *&d, const std::vector<T> &h, hipStream_t st)
+    {
+        T *p = nullptr;
+        HIPCHK(tmp.alloc(p, h.size() * sizeof(T)));
+        HIPCHK(hipMemcpyAsync(p, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice, st));
+        d = p;
+        return MF_OK;
+    }
+    int upload(const mf_kmerset *ks, hipStream_t st)
+    {
+        const bool prot = ks->kind == MF_KIND_PROTEIN;
+        starts = record_starts(ks);
+        n_rec = (uint32_t)starts.size() - 1;
+        view.total = ks->positions();
+        int rc = prot ? put(aa, ks->pbait.aa, st) : put(view.words, ks->bait.words, st);
+        if (rc == MF_OK) rc = put(view.runlen, prot ? ks->pbait.runlen : ks->bait.runlen, st);
+        if (rc == MF_OK) rc = put(rec_start, starts, st);
+        return rc;
+    }
+};
+
+// -------------------------------------------------------- record and group assignment
+// The owner table of a set on `device` (its tables are built) in `slot`: T->owner, by record (what mf_assign uses, whatever the set's
+// grouping), or T->gowner with the set's record -> group map, for its current grouping (mf_kmerset_group_records frees it).  Made by the
+// first call that asks for it, under the set's lock; sets that never assign reads never hold one.
+static int owner_table(mf_kmerset *ks, int device, const DevTables *T, uint32_t *&slot, const std::vector<uint32_t> *rec_group)
+{
+    std::lock_guard<std::mutex> lk(ks->mu);
+    if (slot) return MF_OK;
+    DevCtx *ctx; int rc = get_ctx(device, &ctx); if (rc) return rc;
+    hipStream_t st = ctx->stream;
+    BaitOnDevice B;
+    rc = B.upload(ks, st); if (rc) return rc;
+    const uint32_t *d_group = nullptr; uint32_t *d_hi = nullptr, *owner = nullptr;
+    if (rec_group && !rec_group->empty()) { rc = B.put(d_group, *rec_group, st); if (rc) return rc; }
+    HIPCHK(B.tmp.alloc(d_hi, ks->slots * 4));
+    HIPCHK(B.tmp.alloc(owner, ks->slots * 4));
+    HIPCHK(B.aa ? launch_build_powner(B.aa, B.view.runlen, B.view.total, B.rec_start, B.n_rec, d_group, T->view, owner, d_hi, st)
+                : launch_build_owner(B.view, B.rec_start, B.n_rec, d_group, T->view, owner, d_hi, st));
+    HIPCHK(hipStreamSynchronize(st));
+    slot = B.tmp.release(owner);
+    return MF_OK;
+}
+
+// Assignment of the reads that passed the filter pass just run on this read set (its bitmap in r->d_bits[r->cur]).  assign_out: n_reads words;
+// record_reads: n_rec + 2 counts; pairs: (read << 32) | record of every passing read, in no particular order.  Each optional.
+// by_group: to the set's groups instead of its records (the group-owner table; n_rec is then the number of groups).
+static int assign_after_filter(mf_kmerset *ks, mf_reads *r, uint32_t *assign_out, uint64_t *record_reads, std::vector<uint64_t> *pairs, bool by_group)
+{
+    DevTables *T; int rc = build_on_device(ks, r->device, &T); if (rc) return rc;
+    rc = by_group ? owner_table(ks, r->device, T, T->gowner, &ks->rec_group) : owner_table(ks, r->device, T, T->owner, nullptr); if (rc) return rc;
+    const uint32_t *owner = by_group ? T->gowner : T->owner;
+    DevCtx *ctx; rc = get_ctx(r->device, &ctx, r->lane); if (rc) return rc;
+    hipStream_t st = ctx->stream;
+    const uint64_t n = r->v.n_reads;
+    const uint32_t n_rec = by_group ? ks->n_groups() : (uint32_t)ks->bait.rec_len.size();
+    const size_t n_cnt = (size_t)n_rec + 2;                          // records, ambiguous, the length of the list
+    HIPCHK(dev_reserve(r->d_acnt, r->cap_acnt, n_cnt * 8, false));
+    HIPCHK(hipMemsetAsync(r->d_acnt, 0, n_cnt * 8, st));
+    if (n) {
+        HIPCHK(dev_reserve(r->d_alist, r->cap_alist, n * 4, true));
+        if (assign_out) { HIPCHK(dev_reserve(r->d_assign, r->cap_assign, n * 4, true)); HIPCHK(hipMemsetAsync(r->d_assign, 0xFF, n * 4, st)); }
+        if (pairs) HIPCHK(dev_reserve(r->d_apairs, r->cap_apairs, n * 8, true));
+        HIPCHK(launch_pass_list(r->d_bits[r->cur], n, r->d_alist, r->d_acnt + n_rec + 1, st));
+        HIPCHK(launch_assign(r->v, T->view, owner, r->d_alist, r->d_acnt + n_rec + 1, n_rec, assign_out ? r->d_assign : nullptr,
+                             pairs ? r->d_apairs : nullptr, r->d_acnt, ctx->n_cu, st));
+    }
+    std::vector<unsigned long long> cnt(n_cnt, 0);
+    HIPCHK(hipMemcpyAsync(cnt.data(), r->d_acnt, n_cnt * 8, hipMemcpyDeviceToHost, st));
+    if (assign_out && n) HIPCHK(hipMemcpyAsync(assign_out, r->d_assign, n * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    const uint64_t listed = cnt[n_rec + 1];
+    if (pairs) {
+        pairs->resize(listed);
+        if (listed) { HIPCHK(hipMemcpyAsync(pairs->data(), r->d_apairs, listed * 8, hipMemcpyDeviceToHost, st)); HIPCHK(hipStreamSynchronize(st)); }
+    }
+    if (record_reads) {
+        for (uint32_t j = 0; j <= n_rec; j++) record_reads[j] = cnt[j];
+        record_reads[n_rec + 1] = n - listed;
+    }
+    return MF_OK;
+}
+
+static int need_nucleotide(const mf_kmerset *ks)
+{
+    if (!ks) return fail(MF_E_ARG, "NULL handle");
+    if (ks->kind != MF_KIND_NUCLEOTIDE) return fail(MF_E_ARG, "record assignment needs a nucleotide bait set");
+    return MF_OK;
+}
+
+// a record's or group's name into the caller's buffer
+static int copy_name(const std::string &nm, char *buf, size_t buflen, size_t *needed)
+{
+    if (needed) *needed = nm.size() + 1;
+    if (!buf || buflen < nm.size() + 1) return fail(MF_E_ARG, "buffer too small: the name needs %llu bytes", (unsigned long long)(nm.size() + 1));
+    memcpy(buf, nm.c_str(), nm.size() + 1);
+    return MF_OK;
+}
+
+extern "C" {
+
+int mf_kmerset_record_count(const mf_kmerset *ks, uint64_t *n_records)
+{
+    int rc = need_nucleotide(ks); if (rc) return rc;
+    if (!n_records) return fail(MF_E_ARG, "n_records is NULL");
+    *n_records = ks->bait.rec_len.size();
+    return MF_OK;
+}
+
+int mf_kmerset_record_name(const mf_kmerset *ks, uint64_t i, char *buf, size_t buflen, size_t *needed)
+{
+    int rc = need_nucleotide(ks); if (rc) return rc;
+    if (i >= ks->bait.names.size()) return fail(MF_E_ARG, "record %llu out of range (the set has %llu)", (unsigned long long)i, (unsigned long long)ks->bait.names.size());
+    return copy_name(ks->bait.names[i], buf, buflen, needed);
+}
+
+int mf_assign(const mf_kmerset *ks_, const mf_reads *reads_, uint32_t threshold, int mode, uint32_t *out_bits, uint32_t *assign_out,
+              uint64_t *record_reads, mf_filter_stats_t *stats)
+{
+    mf_kmerset *ks = const_cast<mf_kmerset *>(ks_);
+    mf_reads *r = const_cast<mf_reads *>(reads_);
+    int rc = need_nucleotide(ks); if (rc) return rc;
+    if (!r) return fail(MF_E_ARG, "NULL handle");
+    rc = filter_common(ks, r, threshold, mode, out_bits, nullptr, 1, stats);
+    if (rc) return rc;
+    return assign_after_filter(ks, r, assign_out, record_reads, nullptr, false);
+}
+
+// ------------------------------------------------------- group assignment
+int mf_kmerset_group_records(mf_kmerset *ks, const char *sep, int field)
+{
+    if (!ks) return fail(MF_E_ARG, "NULL handle");
+    if (field < 0) return fail(MF_E_ARG, "field %d is negative", field);
+    const bool identity = !sep || field == 0;
+    if (!identity && !*sep) return fail(MF_E_ARG, "the separator is empty");
+    std::vector<uint32_t> rec_group;
+    std::vector<std::string> group_names;
+    if (!identity) {          // the field-th sep-separated token of the name (from 1); the whole name when it has fewer fields
+        const std::string sp = sep;
+        std::map<std::string, uint32_t> index;
+        const std::vector<std::string> &names = ks->names();
+        rec_group.reserve(names.size());
+        for (const std::string &nm : names) {
+            size_t at = 0; int f = 1;
+            while (f < field) { const size_t q = nm.find(sp, at); if (q == std::string::npos) break; at = q + sp.size(); f++; }
+            std::string g = nm;
+            if (f == field) { const size_t q = nm.find(sp, at); g = nm.substr(at, q == std::string::npos ? std::string::npos : q - at); }
+            auto it = index.find(g);
+            if (it == index.end()) { it = index.emplace(g, (uint32_t)group_names.size()).first; group_names.push_back(g); }
+            rec_group.push_back(it->second);
+        }
+    }
+    std::lock_guard<std::mutex> lk(ks->mu);
+    for (auto &kv : ks->dev)
+        if (kv.second.gowner) {
+            HIPCHK(hipSetDevice(phys(kv.first)));
+            HIPCHK(DevTables::drop(kv.second.gowner));
+        }
+    ks->rec_group.swap(rec_group);
+    ks->group_names.swap(group_names);
+    return MF_OK;
+}
+
+int mf_kmerset_group_count(const mf_kmerset *ks, uint64_t *n_groups)
+{
+    if (!ks) return fail(MF_E_ARG, "NULL handle");
+    if (!n_groups) return fail(MF_E_ARG, "n_groups is NULL");
+    *n_groups = ks->n_groups();
+    return MF_OK;
+}
+
+int mf_kmerset_group_name(const mf_kmerset *ks, uint64_t i, char *buf, size_t buflen, size_t *needed)
+{
+    if (!ks) return fail(MF_E_ARG, "NULL handle");
+    if (i >= ks->n_groups()) return fail(MF_E_ARG, "group %llu out of range (the set has %llu)", (unsigned long long)i, (unsigned long long)ks->n_groups());
+    return copy_name(ks->group_name(i), buf, buflen, needed);
+}
+
+int mf_assign_groups(const mf_kmerset *ks_, const mf_reads *reads_, uint32_t threshold, int mode, uint32_t *out_bits, uint32_t *assign_out,
+                     uint64_t *group_reads, mf_filter_stats_t *stats)
+{
+    mf_kmerset *ks = const_cast<mf_kmerset *>(ks_);
+    mf_reads *r = const_cast<mf_reads *>(reads_);
+    if (!ks || !r) return fail(MF_E_ARG, "NULL handle");
+    int rc = filter_common(ks, r, threshold, mode, out_bits, nullptr, 1, stats);
+    if (rc) return rc;
+    return assign_after_filter(ks, r, assign_out, group_reads, nullptr, true);
+}
+
+} // extern "C"
+
+// ------------------------------------------------------------------- k-mer depth
+// The depth tables of a set on `device` (nucleotide or protein): made by the first depth call there, under the set's lock.
+static int depth_tables(mf_kmerset *ks, int device, DevTables *T)
+{
+    std::lock_guard<std::mutex> lk(ks->mu);
+    if (T->rep) return MF_OK;
+    const uint64_t total = ks->positions();
+    if (total >= DEPTH_NONE || ks->slots > DEPTH_NONE) return fail(MF_E_ARG, "k-mer depth takes sets of fewer than 2^32 - 1 positions and slots");
+    DevCtx *ctx; int rc = get_ctx(device, &ctx); if (rc) return rc;
+    hipStream_t st = ctx->stream;
+    const bool by_slot = depth_index_option() == 1;
+    BaitOnDevice B;
+    rc = B.upload(ks, st); if (rc) return rc;
+    std::vector<DepthItem> items;
+    for (uint32_t j = 0; j < B.n_rec; j++)
+        for (uint64_t a = B.starts[j]; a < B.starts[j + 1]; a += DEPTH_ITEM) items.push_back(DepthItem{a, (uint32_t)std::min<uint64_t>(DEPTH_ITEM, B.starts[j + 1] - a), j});
+    uint32_t *rep = nullptr, *pos_rep = nullptr; DepthItem *d_items = nullptr;
+    HIPCHK(B.tmp.alloc(rep, ks->slots * 4));
+    HIPCHK(B.tmp.alloc(pos_rep, std::max<uint64_t>(total, 1) * 4));
+    HIPCHK(B.tmp.alloc(d_items, std::max<size_t>(items.size(), 1) * sizeof(DepthItem)));
+    if (!items.empty()) HIPCHK(hipMemcpyAsync(d_items, items.data(), items.size() * sizeof(DepthItem), hipMemcpyHostToDevice, st));
+    HIPCHK(launch_build_depth(B.view, B.aa, T->view, rep, pos_rep, by_slot, st));
+    HIPCHK(hipStreamSynchronize(st));
+    T->rep = B.tmp.release(rep); T->pos_rep = B.tmp.release(pos_rep); T->ditems = B.tmp.release(d_items);
+    T->n_ditems = (uint32_t)items.size(); T->dcnt_n = by_slot ? std::max<uint64_t>(ks->slots, total) : total;
+    return MF_OK;
+}
+
+// The windows of the reads that passed the filter pass just run on this read set (its bitmap in r->d_bits[r->cur]) added into tot
+// (T->dcnt_n u64 counters on r's device, which other read sets there may be adding into at the same time).  Ends synchronised.
+static int depth_after_filter(mf_kmerset *ks, mf_reads *r, unsigned long long *tot)
+{
+    DevTables *T; int rc = build_on_device(ks, r->device, &T); if (rc) return rc;
+    rc = depth_tables(ks, r->device, T); if (rc) return rc;
+    DevCtx *ctx; rc = get_ctx(r->device, &ctx, r->lane); if (rc) return rc;
+    hipStream_t st = ctx->stream;
+    const uint64_t n = r->v.n_reads, n_cnt = T->dcnt_n;
+    if (!n || !n_cnt) return MF_OK;
+    // a 32-bit counter holds every window of the read set unless they could number 2^32: then the windows go straight into tot
+    const uint64_t span = ks->kind == MF_KIND_PROTEIN ? 3 * (uint64_t)ks->k : (uint64_t)ks->k;
+    const uint64_t per = r->v.uniform_len ? (r->v.uniform_len >= span ? r->v.uniform_len - span + 1 : 0) : 0;
+    const uint64_t bound = (r->v.uniform_len ? n * per : r->v.total_bases) * (ks->kind == MF_KIND_PROTEIN ? 2 : 1);
+    const bool wide = bound >= DEPTH_NONE;
+    HIPCHK(dev_reserve(r->d_acnt, r->cap_acnt, 8, false));
+    HIPCHK(hipMemsetAsync(r->d_acnt, 0, 8, st));
+    HIPCHK(dev_reserve(r->d_alist, r->cap_alist, n * 4, true));
+    if (!wide) { HIPCHK(dev_reserve(r->d_dcnt, r->cap_dcnt, n_cnt * 4, false)); HIPCHK(hipMemsetAsync(r->d_dcnt, 0, n_cnt * 4, st)); }
+    HIPCHK(launch_pass_list(r->d_bits[r->cur], n, r->d_alist, r->d_acnt, st));
+    HIPCHK(launch_depth_count(r->v, T->view, T->rep, r->d_alist, r->d_acnt, wide ? nullptr : r->d_dcnt, wide ? tot : nullptr, ctx->n_cu, st));
+    if (!wide) HIPCHK(launch_depth_fold(r->d_dcnt, n_cnt, tot, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return MF_OK;
+}
+
+// The profile (ks->positions() u32) and the record summaries (R entries) from the totals tot on `device` (stream st); each optional.
+static int depth_report(mf_kmerset *ks, int device, hipStream_t st, const unsigned long long *tot, uint32_t *d_prof, unsigned long long *d_rec,
+                        uint32_t *profile, mf_depth_record_t *records)
+{
+    DevTables *T; int rc = build_on_device(ks, device, &T); if (rc) return rc;
+    rc = depth_tables(ks, device, T); if (rc) return rc;
+    const uint64_t total = ks->positions(), n_rec = ks->rec_len().size();
+    if (records && n_rec) HIPCHK(hipMemsetAsync(d_rec, 0, n_rec * 32, st));
+    if (profile && total) HIPCHK(hipMemsetAsync(d_prof, 0xFF, total * 4, st));          // (records with no item: none, they are empty)
+    HIPCHK(launch_depth_profile(T->ditems, T->n_ditems, T->pos_rep, tot, profile ? d_prof : nullptr, records ? d_rec : nullptr, st));
+    if (profile && total) HIPCHK(hipMemcpyAsync(profile, d_prof, total * 4, hipMemcpyDeviceToHost, st));
+    if (records && n_rec) HIPCHK(hipMemcpyAsync(records, d_rec, n_rec * 32, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return MF_OK;
+}
+
+extern "C" {
+
+int mf_kmerset_record_starts(const mf_kmerset *ks, uint64_t *starts, size_t n, size_t *needed)
+{
+    if (!ks) return fail(MF_E_ARG, "NULL handle");
+    const std::vector<uint64_t> s = record_starts(ks);
+    if (needed) *needed = s.size();
+    if (!starts || n < s.size()) return fail(MF_E_ARG, "buffer too small: the set has %llu records, %llu offsets", (unsigned long long)(s.size() - 1), (unsigned long long)s.size());
+    std::copy(s.begin(), s.end(), starts);
+    return MF_OK;
+}
+
+int mf_depth(const mf_kmerset *ks_, const mf_reads *reads_, uint32_t threshold, int mode, uint32_t *out_bits, uint32_t *profile,
+             mf_depth_record_t *records, mf_filter_stats_t *stats)
+{
+    mf_kmerset *ks = const_cast<mf_kmerset *>(ks_);
+    mf_reads *r = const_cast<mf_reads *>(reads_);
+    if (!ks || !r) return fail(MF_E_ARG, "NULL handle");
+    int rc = filter_common(ks, r, threshold, mode, out_bits, nullptr, 1, stats);
+    if (rc) return rc;
+    DevTables *T; rc = build_on_device(ks, r->device, &T); if (rc) return rc;
+    rc = depth_tables(ks, r->device, T); if (rc) return rc;
+    DevCtx *ctx; rc = get_ctx(r->device, &ctx, r->lane); if (rc) return rc;
+    hipStream_t st = ctx->stream;
+    const uint64_t n_cnt = T->dcnt_n, total = ks->positions(), n_rec = ks->rec_len().size();
+    HIPCHK(dev_reserve(r->d_dtot, r->cap_dtot, std::max<uint64_t>(n_cnt, 1) * 8, false));
+    HIPCHK(hipMemsetAsync(r->d_dtot, 0, std::max<uint64_t>(n_cnt, 1) * 8, st));
+    rc = depth_after_filter(ks, r, r->d_dtot); if (rc) return rc;
+    // (the profile goes through the pass's 32-bit counters, which the totals have taken up)
+    HIPCHK(dev_reserve(r->d_dcnt, r->cap_dcnt, std::max<uint64_t>(std::max(n_cnt, total), 1) * 4, false));
+    HIPCHK(dev_reserve(r->d_drec, r->cap_drec, std::max<uint64_t>(n_rec, 1) * 32, false));
+    return depth_report(ks, r->device, st, r->d_dtot, r->d_dcnt, r->d_drec, profile, records);
+}
+
+} // extern "C"
+
+// ------------------------------------------------------------- file level
+// What filter_fastq_files_on is given to report with: after_pass runs behind every mate batch's filter pass, on the worker thread that ran
+// it, before that worker's read set is filled again (mf_pipeline.h); the host pipeline hands it no read set for an empty batch.
+static int hook_result(int rc, std::string &err) { if (rc != MF_OK) err = mf_thread_error(); return rc; }
+
+// reads per record or per group: the batch's pairs, which the ingest path tallies once the pair rule has decided
+struct AssignReport : PassReport {
+    mf_kmerset *ks; bool by_group;
+    AssignReport(mf_kmerset *ks_, bool by_group_) : PassReport(by_group_ ? ks_->n_groups() : (uint32_t)ks_->bait.rec_len.size()), ks(ks_), by_group(by_group_) {}
+    int after_pass(mf_reads *R, std::vector<uint64_t> &pairs, std::string &err) override { return R ? hook_result(assign_after_filter(ks, R, nullptr, nullptr, &pairs, by_group), err) : MF_OK; }
+};
+
+// K-mer depth: the windows of every mate that passes go into 64-bit totals, one array per (logical) device, made and zeroed when a batch
+// there first asks for it, shared by the device's workers and lanes (their folds are atomic).  No pairs: nothing is tallied.
+struct DepthTotals : PassReport {
+    mf_kmerset *ks;
+    std::mutex tot_mu;
+    std::map<int, unsigned long long *> tot;
+    explicit DepthTotals(mf_kmerset *ks_) : PassReport(0, false), ks(ks_) {}
+    ~DepthTotals() { restart(); }
+    void restart() override { for (auto &kv : tot) if (hipSetDevice(phys(kv.first)) == hipSuccess) hipFree(kv.second); tot.clear(); }
+    int on(int device, unsigned long long **out)
+    {
+        std::lock_guard<std::mutex> lk(tot_mu);
+        auto it = tot.find(device);
+        if (it != tot.end()) { *out = it->second; return MF_OK; }
+        DevTables *T; int rc = build_on_device(ks, device, &T); if (rc) return rc;
+        rc = depth_tables(ks, device, T); if (rc) return rc;
+        DevCtx *ctx; rc = get_ctx(device, &ctx); if (rc) return rc;
+        const size_t bytes = std::max<uint64_t>(T->dcnt_n, 1) * 8;
+        unsigned long long *p = nullptr;
+        HIPCHK(dev_malloc(&p, bytes));
+        tot[device] = p;
+        HIPCHK(hipMemsetAsync(p, 0, bytes, ctx->stream));
+        HIPCHK(hipStreamSynchronize(ctx->stream));
+        *out = p;
+        return MF_OK;
+    }
+    int after_pass(mf_reads *R, std::vector<uint64_t> &, std::string &err) override
+    {
+        if (!R) return MF_OK;
+        unsigned long long *t = nullptr;
+        int rc = on(R->device, &t);
+        if (rc == MF_OK) rc = depth_after_filter(ks, R, t);
+        return hook_result(rc, err);
+    }
+};
+
+static int files_by_owner(mf_kmerset *ks, const char *fq1, const char *fq2, const char *out1, const char *out2, uint32_t threshold, int pair_mode,
+                          const int *devices, int n_devices, bool by_group, uint64_t *counts, uint64_t *kept, uint64_t *total)
+{
+    AssignReport report(ks, by_group);
+    const int rc = filter_fastq_files_on(ks, fq1, fq2, out1, out2, threshold, pair_mode, devices, n_devices, kept, total, &report);
+    if (rc) return rc;
+    std::copy(report.counts.begin(), report.counts.end(), counts);
+    return MF_OK;
+}
+
+extern "C" {
+
+int mf_filter_fastq_files_by_record(mf_kmerset *ks, const char *fq1, const char *fq2, const char *out1, const char *out2,
+                                    uint32_t threshold, int pair_mode, const int *devices, int n_devices,
+                                    uint64_t *record_reads, uint64_t *kept, uint64_t *total)
+{
+    int rc = need_nucleotide(ks); if (rc) return rc;
+    if (!record_reads) return fail(MF_E_ARG, "record_reads is NULL");
+    return files_by_owner(ks, fq1, fq2, out1, out2, threshold, pair_mode, devices, n_devices, false, record_reads, kept, total);
+}
+
+int mf_filter_fastq_files_by_group(mf_kmerset *ks, const char *fq1, const char *fq2, const char *out1, const char *out2,
+                                   uint32_t threshold, int pair_mode, const int *devices, int n_devices,
+                                   uint64_t *group_reads, uint64_t *kept, uint64_t *total)
+{
+    if (!ks) return fail(MF_E_ARG, "NULL handle");
+    if (!group_reads) return fail(MF_E_ARG, "group_reads is NULL");
+    return files_by_owner(ks, fq1, fq2, out1, out2, threshold, pair_mode, devices, n_devices, true, group_reads, kept, total);
+}
+
+int mf_filter_fastq_files_depth(mf_kmerset *ks, const char *fq1, const char *fq2, const char *out1, const char *out2,
+                                uint32_t threshold, int pair_mode, const int *devices, int n_devices,
+                                uint32_t *profile, mf_depth_record_t *records, uint64_t *kept, uint64_t *total)
+{
+    if (!ks) return fail(MF_E_ARG, "NULL handle");
+    DepthTotals dt(ks);
+    int rc = filter_fastq_files_on(ks, fq1, fq2, out1, out2, threshold, pair_mode, devices, n_devices, kept, total, &dt);
+    if (rc) return rc;
+    // the devices' totals summed on the host into the first listed device's, then the profile and summary kernels once, there
+    const int dev0 = devices[0];
+    unsigned long long *t0 = nullptr;
+    rc = dt.on(dev0, &t0); if (rc) return rc;
+    DevTables *T; rc = build_on_device(ks, dev0, &T); if (rc) return rc;
+    const uint64_t n_cnt = T->dcnt_n;
+    if (dt.tot.size() > 1 && n_cnt) {
+        std::vector<uint64_t> sum(n_cnt, 0), part(n_cnt);
+        for (auto &kv : dt.tot) {
+            HIPCHK(hipSetDevice(phys(kv.first)));
+            HIPCHK(hipMemcpy(part.data(), kv.second, n_cnt * 8, hipMemcpyDeviceToHost));
+            for (uint64_t i = 0; i < n_cnt; i++) sum[i] += part[i];
+        }
+        HIPCHK(hipSetDevice(phys(dev0)));
+        HIPCHK(hipMemcpy(t0, sum.data(), n_cnt * 8, hipMemcpyHostToDevice));
+    }
+    DevCtx *ctx; rc = get_ctx(dev0, &ctx); if (rc) return rc;
+    DevScratch tmp;
+    uint32_t *d_prof = nullptr; unsigned long long *d_rec = nullptr;
+    HIPCHK(tmp.alloc(d_prof, std::max<uint64_t>(ks->positions(), 1) * 4));
+    HIPCHK(tmp.alloc(d_rec, std::max<uint64_t>(ks->rec_len().size(), 1) * 32));
+    return depth_report(ks, dev0, ctx->stream, t0, d_prof, d_rec, profile, records);
+}
+
+} // extern "C"

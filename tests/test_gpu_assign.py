@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 from oracle.kmer_bait_ref import _norm, canonical_code, read_fasta_records
+from tests.report_data import eight_record_bait, fasta, mf, mutate, ol  # noqa: F401  (mf, ol: fixtures)
 from tests.util_data import bait_records, bits_to_bool, make_bait, make_protein_bait, make_reads, revcomp, write_fastq
 
 pytestmark = pytest.mark.gpu
@@ -83,45 +84,6 @@ def counts_of(assign, n_rec):
     for a in assign:
         c[n_rec + 1 if a == NONE else n_rec if a == AMB else a] += 1
     return c
-
-
-def mutate(seq, rate, seed):
-    rng = random.Random(seed)
-    s = list(seq)
-    for i in range(len(s)):
-        if rng.random() < rate:
-            s[i] = rng.choice([b for b in "ACGT" if b != s[i]])
-    return "".join(s)
-
-
-def fasta(records):
-    return "".join(">%s\n%s\n" % (n, "\n".join(s[i:i + 70] for i in range(0, len(s), 70))) for n, s in records)
-
-
-def eight_record_bait():
-    """8 records: the synthetic mitogenome, copies mutated at 1 % and 10 %, an exact duplicate (every key of it shared), a record
-    shorter than k, the second record of the synthetic bait (IUPAC codes, N), a 10 % copy of it, an unrelated random record"""
-    r = bait_records(make_bait())
-    g = r[0][:6000]
-    rng = random.Random(5)
-    m1 = mutate(g, 0.01, 1)
-    return fasta([("mito desc", g), ("mito_1pc", m1), ("mito_10pc", mutate(g, 0.10, 2)), ("mito_1pc_dup", m1), ("tiny", "ACGTTGCA"),
-                  ("rec2", r[1]), ("rec2_10pc", mutate(_norm(r[1]).replace("N", "A"), 0.10, 3)), ("rand", "".join(rng.choices("ACGT", k=3000)))])
-
-
-@pytest.fixture(scope="module")
-def mf(built_lib):
-    from mitoflex_amd import mitofilter
-    if mitofilter.device_count() < 1:
-        pytest.fail("no GPU visible: -m gpu tests must run on the MI355X box")
-    return mitofilter
-
-
-@pytest.fixture(scope="module")
-def ol():
-    from oracle import oracle_lib
-    oracle_lib.lib()
-    return oracle_lib
 
 
 @pytest.fixture(scope="module")

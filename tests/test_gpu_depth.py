@@ -17,6 +17,7 @@ import pytest
 from oracle import kmer_bait_ref as kb
 from oracle import prot_bait_ref as pr
 from tests.clade_data import Clade, gene_dna, sample_reads
+from tests.report_data import fasta, keys_nuc, keys_prot, mf, ol, upload  # noqa: F401  (mf, ol: fixtures)
 from tests.util_data import bait_records, bits_to_bool, make_bait, make_reads, revcomp, write_fastq
 
 pytestmark = pytest.mark.gpu
@@ -28,21 +29,6 @@ NONE, CLAMP = 0xFFFFFFFF, 0xFFFFFFFE
 
 
 # ------------------------------------------------------------------ oracle
-def keys_nuc(seq, k):
-    s = kb._norm(seq)
-    return [kb.canonical_code(s[p:p + k]) for p in range(len(s) - k + 1) if "N" not in s[p:p + k]]
-
-
-def keys_prot(seq, kp, code):
-    out = []
-    for pep in pr.six_frames(seq, code):
-        for i in range(len(pep) - kp + 1):
-            v = pr.pep_code(pep[i:i + kp])
-            if v is not None:
-                out.append(v)
-    return out
-
-
 class Oracle:
     """the expected depth of one set: positions, the valid windows and their keys"""
 
@@ -107,10 +93,6 @@ def records_of(prof, starts):
 
 
 # ------------------------------------------------------------------ data
-def fasta(records):
-    return "".join(">%s\n%s\n" % (n, "\n".join(s[i:i + 70] for i in range(0, len(s), 70))) for n, s in records)
-
-
 def depth_bait():
     """records with invalid bases (IUPAC, N), shorter than k, empty, a stretch repeated within a record, k-mers shared between records
     (one of them reverse-complemented), an anonymous leading record, lower case"""
@@ -127,26 +109,6 @@ def depth_reads(text, x, n, seed, uniform):
     seqs = make_reads(text, n, seed=seed, uniform=uniform, mito_frac=0.5)
     seqs = [revcomp(s) if i % 3 == 0 else s for i, s in enumerate(seqs)]
     return seqs + [x + x[:60], revcomp(x + x[:80]), x[:100] + "N" + x[101:150]]          # keys held twice in one read; a ragged one with N
-
-
-@pytest.fixture(scope="module")
-def mf(built_lib):
-    from mitoflex_amd import mitofilter
-    if mitofilter.device_count() < 1:
-        pytest.fail("no GPU visible: -m gpu tests must run on the MI355X box")
-    return mitofilter
-
-
-@pytest.fixture(scope="module")
-def ol():
-    from oracle import oracle_lib
-    oracle_lib.lib()
-    return oracle_lib
-
-
-def upload(mf, ol, seqs):
-    R = ol.OracleReads.from_seqs(seqs)
-    return mf.Reads.from_packed(R.words, R.offsets, R.npos)
 
 
 def check(mf, ks, reads, o, keys, thr, mode=None):

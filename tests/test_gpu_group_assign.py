@@ -16,6 +16,7 @@ import pytest
 from oracle import kmer_bait_ref as kb
 from oracle import prot_bait_ref as pr
 from tests.clade_data import GENES, Clade, gene_dna, sample_reads
+from tests.report_data import eight_record_bait, fasta, keys_nuc, keys_prot, mf, ol, upload  # noqa: F401  (mf, ol: fixtures)
 from tests.util_data import bits_to_bool, make_protein_bait, make_reads, revcomp, write_fastq
 
 pytestmark = pytest.mark.gpu
@@ -84,22 +85,6 @@ def owners_nuc(text, k, rec_group):
     return own
 
 
-def keys_prot(seq, kp, code):
-    """the peptide key of every hits-eligible (frame, window) pair of a read"""
-    out = []
-    for pep in pr.six_frames(seq, code):
-        for i in range(len(pep) - kp + 1):
-            v = pr.pep_code(pep[i:i + kp])
-            if v is not None:
-                out.append(v)
-    return out
-
-
-def keys_nuc(seq, k):
-    s = kb._norm(seq)
-    return [kb.canonical_code(s[p:p + k]) for p in range(len(s) - k + 1) if "N" not in s[p:p + k]]
-
-
 def oracle_assign(read_keys, own, thr, n_groups):
     """read_keys: the window keys of every read -> (passes bool[n], assign u32[n], counts u64[G + 2])"""
     passes = np.zeros(len(read_keys), bool)
@@ -145,15 +130,6 @@ class Oracle:
 
 
 # ------------------------------------------------------------------ data
-def mutate(seq, rate, seed):
-    rng = random.Random(seed)
-    return "".join(rng.choice([b for b in "ACGT" if b != c]) if c in "ACGT" and rng.random() < rate else c for c in seq)
-
-
-def fasta(records):
-    return "".join(">%s\n%s\n" % (n, "\n".join(s[i:i + 70] for i in range(0, len(s), 70))) for n, s in records)
-
-
 def protein_reads(gene_fa, kp, seed, n=600):
     """reads from the gene DNA with ragged lengths, invalid bases, stop codons put in, and reads shorter than 3kp"""
     rng = random.Random(seed)
@@ -174,26 +150,6 @@ def protein_reads(gene_fa, kp, seed, n=600):
     rng2 = random.Random(seed + 1)
     out += ["".join(rng2.choices("ACGT", k=rng2.randint(1, 160))) for _ in range(n // 10)]
     return out
-
-
-@pytest.fixture(scope="module")
-def mf(built_lib):
-    from mitoflex_amd import mitofilter
-    if mitofilter.device_count() < 1:
-        pytest.fail("no GPU visible: -m gpu tests must run on the MI355X box")
-    return mitofilter
-
-
-@pytest.fixture(scope="module")
-def ol():
-    from oracle import oracle_lib
-    oracle_lib.lib()
-    return oracle_lib
-
-
-def upload(mf, ol, seqs):
-    R = ol.OracleReads.from_seqs(seqs)
-    return mf.Reads.from_packed(R.words, R.offsets, R.npos)
 
 
 def check(mf, reads, ks, o, seqs, thr, keys=None, mode=None):
@@ -301,11 +257,6 @@ def test_unseen_species_resolve_by_gene(mf, ol, clade):
 
 
 # ------------------------------------------------------------------ 4. nucleotide sets
-def eight_record_bait():
-    from tests.test_gpu_assign import eight_record_bait as e
-    return e()
-
-
 @pytest.mark.parametrize("k", [21, 31, 41])
 def test_nucleotide_identity_equals_record_assignment(mf, ol, k):
     text = eight_record_bait()

@@ -87,6 +87,43 @@ def test_pipeline_with_stand_in_filter(data, tmp_path, flags):
     assert gzip.open(o, "rt", newline="").read().count("\n") == 4 * kept
 
 
+def expected_tally(s1, s2, both, batch):
+    """What the stand-in report of pipeline_check counts: a passing read at index i of its batch has record i % 4 of three (3: ambiguous);
+    kept mates are counted one by one, a mate kept without passing itself (through its partner) as unassigned."""
+    mates = [s1] if s2 is None else [s1, s2]
+    n = min(len(m) for m in mates)
+    counts = [0] * 5
+    for g in range(n):
+        passes = [m[g][:1] in ("A", "a") for m in mates]
+        if not (all(passes) if both else any(passes)):
+            continue
+        for p in passes:
+            counts[(g % batch) % 4 if p else 4] += 1
+    return counts
+
+
+@pytest.mark.parametrize("flags", [(), ("-fsanitize=address,undefined", "-fno-omit-frame-pointer"), ("-fsanitize=thread",)],
+                         ids=["plain", "asan_ubsan", "tsan"])
+def test_pipeline_report_hook(data, tmp_path, flags):
+    """The report of a file-level call on the host pipeline: the hook runs behind every mate batch's pass and the kept reads are tallied
+    from its pairs under the pair rule -- single end and paired, `either` and `both`, one worker and several."""
+    d, s1, s2 = data
+    exe = build(str(tmp_path), flags)
+    o1, o2 = str(tmp_path / "o1.fq"), str(tmp_path / "o2.fq")
+    for ext in (".fq", ".fq.gz"):
+        for batch, n_dev in ((2_000_000, 1), (700, 1), (64, 3), (333, 4)):
+            for paired, mode in ((False, "either"), (True, "either"), (True, "both")):
+                files = [str(d / ("a_1" + ext)), str(d / ("a_2" + ext)), o1, o2] if paired else [str(d / ("a_1" + ext)), "-", o1, "-"]
+                p = subprocess.run([exe, *files, str(batch), "4", mode, str(n_dev), "report"], capture_output=True)
+                err = p.stderr.decode()
+                assert "Sanitizer" not in err and "runtime error" not in err, err[:2000]
+                want = expected_tally(s1, s2 if paired else None, mode == "both", batch)
+                kept = sum(want) // 2 if paired else sum(want)
+                lines = p.stdout.decode().splitlines()
+                assert lines[0].split() == [str(kept), str(min(len(s1), len(s2)) if paired else len(s1))], (ext, batch, n_dev, paired, mode, lines, err[:500])
+                assert lines[1].split() == ["tally"] + [str(c) for c in want], (ext, batch, n_dev, paired, mode, lines)
+
+
 @pytest.mark.parametrize("flags", [(), ("-fsanitize=thread",)], ids=["plain", "tsan"])
 def test_pipeline_many_devices(data, tmp_path, flags):
     """N device workers with randomised delays (batches come back out of order): output bytes and counts equal the
