@@ -35,19 +35,10 @@ hipError_t launch_pack(const uint8_t *text, const uint64_t *line_start, const ui
                        uint64_t total_bases, uint64_t base, uint32_t *words, uint32_t *inv_cnt, const uint64_t *inv_base, uint64_t *npos, hipStream_t st);
 hipError_t launch_bytes_from_host(void *dst, const void *pinned_src, uint64_t n, hipStream_t st);      // dst[0..n) = pinned host memory, read by a kernel (not the copy engine: that one carries the uploads)
 hipError_t launch_bytes_to_host(void *pinned_dst, const void *src, uint64_t n, hipStream_t st);        // pinned host memory [0..n) = src, written by a kernel; read it after waiting for the stream
-hipError_t launch_add_base(uint64_t *dst, const uint64_t *src, uint64_t n, uint64_t base, hipStream_t st);       // dst[i] = src[i] + base
-// pass bits of one batch (bit i = record i of the batch) into the file-wide bitmap at record index rec_base
-hipError_t launch_store_bits(const uint32_t *batch_bits, uint64_t n_rec, uint32_t *file_bits, uint64_t rec_base, hipStream_t st);
-// output bytes of records [0, n_rec) of a batch whose first record has file index rec_base: header + seq + "+" + qual with LF
-// line ends when kept (bits_a[r] | bits_b[r], or & when both; bits_b may be nullptr), else 0
-hipError_t launch_out_lens(const uint8_t *text, const uint64_t *line_start, uint64_t n_rec, uint64_t rec_base, const uint32_t *bits_a,
-                           const uint32_t *bits_b, int both, uint32_t *out_len, hipStream_t st);
-// the same two steps over a list of records: out_len[i] = output bytes of record sel[i]; the records go to out[out_off[i] ..]
+// the survivors, over a list of records (sel: their indices in the batch): out_len[i] = output bytes of record sel[i] (header + seq +
+// "+" + qual with LF line ends); the records go to out[out_off[i] ..] (out_off = exclusive scan of out_len)
 hipError_t launch_sel_lens(const uint8_t *text, const uint64_t *line_start, const uint32_t *sel, uint64_t n_sel, uint32_t *out_len, hipStream_t st);
 hipError_t launch_sel_gather(const uint8_t *text, const uint64_t *line_start, const uint32_t *sel, uint64_t n_sel, const uint64_t *out_off, uint8_t *out, hipStream_t st);
-// copies the kept records to out[out_off[r] ..] (out_off = exclusive scan of out_len)
-hipError_t launch_gather(const uint8_t *text, const uint64_t *line_start, uint64_t n_rec, const uint32_t *out_len, const uint64_t *out_off,
-                         uint8_t *out, hipStream_t st);
 
 // ---- the FASTQ quality filter (the reference's filter_v2, filter/filter_bin/src/main.rs:188-323) over records of text on the device
 // per-record flags of launch_qual_scan

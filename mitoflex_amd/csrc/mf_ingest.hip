@@ -205,33 +205,8 @@ __global__ __launch_bounds__(256) void pack_kernel(const uint8_t *text, const ui
         for (uint32_t m = inv; m; m &= m - 1) npos[k++] = g0 + (uint32_t)(__ffs(m) - 1);
     }
 }
-__global__ __launch_bounds__(256) void add_base_kernel(uint64_t *dst, const uint64_t *src, uint64_t n, uint64_t base)
-{
-    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i < n) dst[i] = src[i] + base;
-}
 
 // ------------------------------------------------------------------------------------------------------------ survivors
-__global__ __launch_bounds__(256) void store_bits_kernel(const uint32_t *batch_bits, uint64_t n_rec, uint32_t *file_bits, uint64_t rec_base)
-{
-    // one thread per destination word of the file-wide bitmap that the batch touches; the first and the last are shared with
-    // the neighbouring batches (atomic), the ones in between are written whole
-    const uint64_t w_first = rec_base >> 5, w_last = (rec_base + n_rec - 1) >> 5;
-    const uint64_t w = w_first + (uint64_t)blockIdx.x * 256 + threadIdx.x;
-    if (w > w_last) return;
-    const uint32_t sh = (uint32_t)rec_base & 31u;
-    const int64_t j = (int64_t)(w - w_first);                             // destination word j takes batch bits [32 j - sh, 32 j - sh + 32)
-    const uint64_t nw = (n_rec + 31) >> 5;
-    const uint32_t a = j >= 1 && (uint64_t)(j - 1) < nw ? batch_bits[j - 1] : 0, b = (uint64_t)j < nw ? batch_bits[j] : 0;
-    uint32_t v = sh ? (a >> (32 - sh)) | (b << sh) : b;
-    // bits of the destination word that belong to this batch
-    const uint64_t lo = w * 32 > rec_base ? w * 32 : rec_base, hi = (w + 1) * 32 < rec_base + n_rec ? (w + 1) * 32 : rec_base + n_rec;
-    const uint32_t nbits = (uint32_t)(hi - lo), first = (uint32_t)(lo - w * 32);
-    const uint32_t mask = nbits == 32 ? 0xFFFFFFFFu : (((1u << nbits) - 1) << first);
-    v &= mask;
-    if (nbits == 32) file_bits[w] = v; else if (v) atomicOr(&file_bits[w], v);
-}
-
 struct RecSpan { uint64_t h, s, q; uint32_t hl, sl, ql; };
 __device__ __forceinline__ uint32_t line_len(const uint8_t *text, uint64_t a, uint64_t b)     // line [a, b - 1) less a CR in front of the LF
 {
@@ -247,19 +222,7 @@ __device__ __forceinline__ RecSpan rec_span(const uint8_t *text, const uint64_t 
     x.hl = line_len(text, l0, l1); x.sl = line_len(text, l1, l2); x.ql = line_len(text, l3, l4);
     return x;
 }
-__global__ __launch_bounds__(256) void out_lens_kernel(const uint8_t *text, const uint64_t *line_start, uint64_t n_rec, uint64_t rec_base,
-                                                       const uint32_t *bits_a, const uint32_t *bits_b, int both, uint32_t *out_len)
-{
-    const uint64_t r = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-    if (r >= n_rec) return;
-    const uint64_t g = rec_base + r;
-    const uint32_t a = (bits_a[g >> 5] >> (g & 31)) & 1u, b = bits_b ? (bits_b[g >> 5] >> (g & 31)) & 1u : a;
-    const uint32_t keep = both ? (a & b) : (a | b);
-    uint32_t n = 0;
-    if (keep) { const RecSpan x = rec_span(text, line_start, r); n = x.hl + x.sl + x.ql + 5; }      // header LF seq LF '+' LF qual LF
-    out_len[r] = n;
-}
-// the same for a short list of records (sel: their indices, ascending): what survives a bait filter is a fraction of a per cent of
+// the output of a short list of records (sel: their indices, ascending), header + seq + "+" + qual with LF line ends: what survives a bait filter is a fraction of a per cent of
 // the records, and kernels over the list cost nothing beside kernels over every record
 __global__ __launch_bounds__(256) void sel_lens_kernel(const uint8_t *text, const uint64_t *line_start, const uint32_t *sel, uint64_t n_sel, uint32_t *out_len)
 {
@@ -281,21 +244,6 @@ __global__ __launch_bounds__(256) void sel_gather_kernel(const uint8_t *text, co
     if (lane == 0) { o[0] = '\n'; o[1 + x.sl] = '\n'; o[2 + x.sl] = '+'; o[3 + x.sl] = '\n'; o[4 + x.sl + x.ql] = '\n'; }
     o += x.sl + 4;
     for (uint32_t k = lane; k < x.ql; k += 64) o[k] = text[x.q + k];
-}
-__global__ __launch_bounds__(256) void gather_kernel(const uint8_t *text, const uint64_t *line_start, uint64_t n_rec, const uint32_t *out_len,
-                                                     const uint64_t *out_off, uint8_t *out)
-{
-    const uint64_t r = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);        // one wavefront per record
-    if (r >= n_rec || out_len[r] == 0) return;
-    const uint32_t lane = threadIdx.x & 63;
-    const RecSpan x = rec_span(text, line_start, r);
-    uint8_t *o = out + out_off[r];
-    for (uint32_t i = lane; i < x.hl; i += 64) o[i] = text[x.h + i];
-    o += x.hl;
-    for (uint32_t i = lane; i < x.sl; i += 64) o[1 + i] = text[x.s + i];
-    if (lane == 0) { o[0] = '\n'; o[1 + x.sl] = '\n'; o[2 + x.sl] = '+'; o[3 + x.sl] = '\n'; o[4 + x.sl + x.ql] = '\n'; }
-    o += x.sl + 4;
-    for (uint32_t i = lane; i < x.ql; i += 64) o[i] = text[x.q + i];
 }
 
 
@@ -547,29 +495,6 @@ hipError_t launch_bytes_to_host(void *pinned_dst, const void *src, uint64_t n, h
     return hipGetLastError();
 }
 
-hipError_t launch_add_base(uint64_t *dst, const uint64_t *src, uint64_t n, uint64_t base, hipStream_t st)
-{
-    if (!n) return hipSuccess;
-    hipLaunchKernelGGL(add_base_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, st, dst, src, n, base);
-    return hipGetLastError();
-}
-
-hipError_t launch_store_bits(const uint32_t *batch_bits, uint64_t n_rec, uint32_t *file_bits, uint64_t rec_base, hipStream_t st)
-{
-    if (!n_rec) return hipSuccess;
-    const uint64_t nw = ((rec_base + n_rec - 1) >> 5) - (rec_base >> 5) + 1;
-    hipLaunchKernelGGL(store_bits_kernel, dim3((uint32_t)((nw + 255) / 256)), dim3(256), 0, st, batch_bits, n_rec, file_bits, rec_base);
-    return hipGetLastError();
-}
-
-hipError_t launch_out_lens(const uint8_t *text, const uint64_t *line_start, uint64_t n_rec, uint64_t rec_base, const uint32_t *bits_a,
-                           const uint32_t *bits_b, int both, uint32_t *out_len, hipStream_t st)
-{
-    if (!n_rec) return hipSuccess;
-    hipLaunchKernelGGL(out_lens_kernel, dim3((uint32_t)((n_rec + 255) / 256)), dim3(256), 0, st, text, line_start, n_rec, rec_base, bits_a, bits_b, both, out_len);
-    return hipGetLastError();
-}
-
 hipError_t launch_sel_lens(const uint8_t *text, const uint64_t *line_start, const uint32_t *sel, uint64_t n_sel, uint32_t *out_len, hipStream_t st)
 {
     if (!n_sel) return hipSuccess;
@@ -581,14 +506,6 @@ hipError_t launch_sel_gather(const uint8_t *text, const uint64_t *line_start, co
 {
     if (!n_sel) return hipSuccess;
     hipLaunchKernelGGL(sel_gather_kernel, dim3((uint32_t)((n_sel + 3) / 4)), dim3(256), 0, st, text, line_start, sel, n_sel, out_off, out);
-    return hipGetLastError();
-}
-
-hipError_t launch_gather(const uint8_t *text, const uint64_t *line_start, uint64_t n_rec, const uint32_t *out_len, const uint64_t *out_off,
-                         uint8_t *out, hipStream_t st)
-{
-    if (!n_rec) return hipSuccess;
-    hipLaunchKernelGGL(gather_kernel, dim3((uint32_t)((n_rec + 3) / 4)), dim3(256), 0, st, text, line_start, n_rec, out_len, out_off, out);
     return hipGetLastError();
 }
 

@@ -254,8 +254,9 @@ hipError_t launch_qual_scan(const uint8_t *text, const uint64_t *ls, uint64_t n_
             uint32_t fl = 0;
             auto high = [&](uint64_t a, uint32_t l) { for (uint32_t i = 0; i < l; i++) if (text[a + i] >= 0x80) return true; return false; };
             if (high(x.h, x.hl) || high(x.s, x.sl) || high(x.q, x.ql)) fl |= QF_HIGH;
-            if (x.sl < start || x.ql < start) fl |= QF_SHORT;
-            const uint32_t sl = x.sl < start ? 0 : (uint32_t)std::min<uint64_t>(x.sl - start, cap), ql = x.ql < start ? 0 : (uint32_t)std::min<uint64_t>(x.ql - start, cap);
+            const bool too_short = x.sl < start || x.ql < start;          // (the reference panics: the record has no cut strings, mf_ingest.h)
+            if (too_short) fl |= QF_SHORT;
+            const uint32_t sl = too_short ? 0 : (uint32_t)std::min<uint64_t>(x.sl - start, cap), ql = too_short ? 0 : (uint32_t)std::min<uint64_t>(x.ql - start, cap);
             uint64_t n_count = 0; uint32_t b = 0;
             for (uint32_t i = 0; i < sl; i++) n_count += text[x.s + start + i] == 'N';
             for (uint32_t i = 0; i < ql; i++) b += text[x.q + start + i] <= quality;
@@ -280,7 +281,7 @@ hipError_t launch_qual_decide(uint64_t n, bool pe, bool trunc, float limit, cons
             bool drop = false;
             if (!trunc) {
                 drop = (fl1[i] & QF_NFAIL) || (pe && (fl2[i] & QF_NFAIL));
-                if (!drop) { const float cf = (float)(pe ? sl1[i] : ql1[i]) * limit; const uint64_t cutoff = !(cf > 0.0f) ? 0 : (uint64_t)cf; drop = bad1[i] >= cutoff || (pe && bad2[i] >= cutoff); }
+                if (!drop) { const float cf = (float)(pe ? sl1[i] : ql1[i]) * limit; const uint64_t cutoff = !(cf > 0.0f) ? 0 : cf >= 18446744073709551616.0f ? ~0ull : (uint64_t)cf; drop = bad1[i] >= cutoff || (pe && bad2[i] >= cutoff); }
             }
             alive[i] = drop ? 0 : 1;
         }
