@@ -299,7 +299,7 @@ int mf_filter_fastq_files_by_group(mf_kmerset *ks, const char *fq1, const char *
  * window starts.
  * Per-record summary: windows = the record's valid windows, covered = those of depth >= 1, depth_sum / depth_max = the sum and the
  * maximum of their unclamped depths.  The mean k-mer depth is depth_sum / windows; for reads of length L it is about base depth *
- * (L - k + 1) / L.  No base-level depth is computed.
+ * (L - k + 1) / L.  No base-level depth is computed here: mf_place below does.
  * File level: every mate that passes its own threshold is counted, whether or not the pair rule keeps its pair; the pair rule decides
  * only what is written.  A file-level profile therefore equals the sum of the in-memory profiles of the mate-1 and mate-2 read sets,
  * before clamping.
@@ -317,6 +317,54 @@ int mf_depth(const mf_kmerset *ks, const mf_reads *reads, uint32_t threshold, in
 int mf_filter_fastq_files_depth(mf_kmerset *ks, const char *fq1, const char *fq2, const char *out1, const char *out2,
                                 uint32_t threshold, int pair_mode, const int *devices, int n_devices,
                                 uint32_t *profile, mf_depth_record_t *records, uint64_t *kept, uint64_t *total);
+
+/* ---- placement: where on the bait, and on which strand, a baited read lies, and the BASE depth that follows.  Nucleotide sets only:
+ * every call below returns MF_E_ARG for a protein set.  No reference counterpart: the reference places reads with `bwa mem` and gets base
+ * depth from `samtools depth -aa` (findmitoscaf/findmitoscaf.py:439-467).
+ * Positions, records and valid windows are those of the depth section (mf_kmerset_record_starts).
+ * Anchor: a canonical key of the set is an ANCHOR when exactly one valid bait window, over all records, holds it, and that window is not
+ * its own reverse complement.  An anchor has the position p of that window, the record j of that window, and a bait orientation b: 0 when
+ * the bait's forward text of the window is the canonical form, 1 when its reverse complement is.
+ * Votes of a read of length L: every valid k-window at offset o (0 <= o <= L - k) whose canonical key is an anchor casts one vote.  r is 0
+ * when the read's forward text of the window is the canonical form, else 1; strand = b xor r (0: the read lies as the bait's forward
+ * strand, 1: its reverse complement does); start = p - starts[j] - o for strand 0 and p - starts[j] - (L - k - o) for strand 1: the
+ * record coordinate of the leftmost base of the read's footprint, which may be negative.  The vote goes to the candidate (j, strand,
+ * start); two anchors in different records are different candidates even when their global diagonals coincide.
+ * Placement: defined for the reads that pass (hits >= threshold, as mf_filter decides).  The winner is the candidate with strictly the
+ * most votes: record = j, strand, start, end = start + L (exclusive, unclipped), votes = the winner's votes, windows = the read's anchor
+ * windows over all candidates.  record = MF_PLACE_AMBIGUOUS when the read passes but has no anchor window or the largest vote count is
+ * tied; the other fields are then 0, except windows.  record = MF_PLACE_NONE and every other field 0 when the read does not pass.
+ * There is NO handling of indels or clipping: the whole read counts on its winning diagonal.
+ * Base depth: a placed read covers the record positions [max(start, 0), min(end, len_j)) -- never empty, because the winning anchor's
+ * window lies inside the record.  Base depth is one uint32_t per position of the set, invalid letters included (there is no "none"
+ * marker): the number of placed reads that cover it, clamped at 0xFFFFFFFE.
+ * Per record (mf_place_record_t): forward / reverse = the reads placed on the record, by strand; over_begin = those with start < 0;
+ * over_end = those with end > len_j; covered = positions of depth >= 1; base_sum = the sum of the unclamped depths (the mean base depth
+ * is base_sum / len_j).
+ * unplaced: two uint64_t -- the passing reads that are not placed, then the reads that do not pass.  Sum(forward + reverse) + unplaced[0]
+ * + unplaced[1] = n_reads.
+ * File level: as for depth, every mate that passes its own threshold is placed and counted, whether or not the pair rule keeps its pair.
+ * A file-level base depth therefore equals the sum, before clamping, of the in-memory base depths of the mate-1 and mate-2 read sets; the
+ * record summaries add likewise, except covered; unplaced[1] counts mates.  The output files are byte-identical to
+ * mf_filter_fastq_files_on's.
+ * Rejected with MF_E_ARG: sets of 2^31 - 1 positions or more; sets of 2^30 records or more (record and strand share one 32-bit word on
+ * the device, and a record has four counters); read sets holding a read of 2^31 - positions bases or more, positions being the set's
+ * (start and end are 32-bit: no read may end at 2^31 or beyond wherever it lies, which also refuses every read of 2^31 bases or more).
+ * The per-slot anchor table is built on each device by the first placement call there. */
+#define MF_PLACE_AMBIGUOUS 0xFFFFFFFEu
+#define MF_PLACE_NONE      0xFFFFFFFFu
+typedef struct { uint32_t record, strand; int32_t start, end; uint32_t votes, windows; } mf_place_t;
+typedef struct { uint64_t forward, reverse, over_begin, over_end, covered, base_sum; } mf_place_record_t;
+/* one pass like mf_filter, then placement; out_bits / place_out (n_reads entries) / base_depth (starts[R] u32) / records (R entries) /
+ * unplaced (2 u64) / stats each optional */
+int mf_place(const mf_kmerset *ks, const mf_reads *reads, uint32_t threshold, int mode,
+             uint32_t *out_bits, mf_place_t *place_out, uint32_t *base_depth,
+             mf_place_record_t *records, uint64_t *unplaced, mf_filter_stats_t *stats);
+/* mf_filter_fastq_files_on plus placement over the whole input; the same ingest path; base_depth / records / unplaced each optional */
+int mf_filter_fastq_files_placed(mf_kmerset *ks, const char *fq1, const char *fq2, const char *out1, const char *out2,
+                                 uint32_t threshold, int pair_mode, const int *devices, int n_devices,
+                                 uint32_t *base_depth, mf_place_record_t *records, uint64_t *unplaced,
+                                 uint64_t *kept, uint64_t *total);
 
 /* Options that select which kernels a filter pass runs (process-wide; every variant gives the same bits and is parity-tested):
  *   pass=default|split|serial   adapt=0|1   finish_streams=0|1|2   screen_streams=1|2   split_pipe=0|1   exact_co=0|1

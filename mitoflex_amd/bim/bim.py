@@ -102,12 +102,48 @@ def estimate_insert_sizes(fasta_file: str, fq1: str, fq2: str, kmer: int = 31, m
     return hist
 
 
+def pair_insert_sizes_device(fasta_file: str, fq1: str, fq2: str, kmer: int = 31, max_pairs: Optional[int] = None):
+    """Insert size of every pair of (fq1, fq2), int64, -1 where there is none: the two files are loaded onto the device, every mate is
+    placed on the bait by the votes of all its anchor k-mers (mitofilter.place_reads, one call per mate) and mitofilter.pair_inserts
+    joins the mates.  max_pairs: only the first so many pairs (default: all)."""
+    import numpy as np
+    from mitoflex_amd import mitofilter as mf
+    ks = mf.KmerSet.from_fasta(fasta_file, kmer, 0)
+    try:
+        places = []
+        for fq in (fq1, fq2):
+            reads = mf.Reads.from_fastq(fq, 0)
+            try:
+                places.append(mf.place_reads(ks, reads, 1)[1] if reads.info.n_reads else np.zeros(0, dtype=mf.PLACE))
+            finally:
+                reads.close()
+    finally:
+        ks.close()
+    n = min(len(places[0]), len(places[1]))
+    if max_pairs is not None:
+        n = min(n, max_pairs)
+    return mf.pair_inserts(places[0][:n], places[1][:n])
+
+
+def estimate_insert_sizes_device(fasta_file: str, fq1: str, fq2: str, kmer: int = 31, max_pairs: Optional[int] = None) -> Dict[int, int]:
+    """estimate_insert_sizes on the device: the same histogram {size: pairs}, from every pair (by default) and from all anchor
+    k-mers of a mate instead of its first."""
+    import numpy as np
+    sizes = pair_insert_sizes_device(fasta_file, fq1, fq2, kmer, max_pairs)
+    values, counts = np.unique(sizes[sizes > 0], return_counts=True)
+    return {int(v): int(c) for v, c in zip(values, counts)}
+
+
 def kmer_bait_map(threads: int, fasta_file: str, basedir: str, prefix: str,
                   fastq1: str, fastq2: Optional[str], quality: int = 30,
-                  kmer: int = 31, threshold: int = 1, devices: int = 1) -> Tuple[str, str, Optional[str]]:
+                  kmer: int = 31, threshold: int = 1, devices: int = 1, anchors: str = "host") -> Tuple[str, str, Optional[str]]:
     """Drop-in for `bwa_map`: returns (stats, fq1, fq2).  `stats` stands where the BAM path was and is what `cal_insert`
-    takes; `threads` and `quality` are accepted for signature compatibility and ignored."""
+    takes; `threads` and `quality` are accepted for signature compatibility and ignored.  anchors: "host" estimates the insert
+    sizes in Python from the first anchor of each mate of a sample of the kept pairs; "device" places every kept mate on the GPU
+    (estimate_insert_sizes_device)."""
     from mitoflex_amd import mitofilter as mf
+    if anchors not in ("host", "device"):
+        raise ValueError('anchors is "host" or "device"')
     fq1 = path.join(basedir, prefix + ".1.fq")
     fq2 = path.join(basedir, prefix + ".2.fq") if fastq2 is not None else None
     ks = mf.KmerSet.from_fasta(fasta_file, kmer, 0)          # the device-side set builder, once per generation
@@ -116,7 +152,8 @@ def kmer_bait_map(threads: int, fasta_file: str, basedir: str, prefix: str,
     finally:
         ks.close()
     stats = path.join(basedir, prefix + ".bait.stats")
-    hist = estimate_insert_sizes(fasta_file, fq1, fq2, kmer) if fq2 is not None else {}
+    estimate = estimate_insert_sizes_device if anchors == "device" else estimate_insert_sizes
+    hist = estimate(fasta_file, fq1, fq2, kmer) if fq2 is not None else {}
     with open(stats, "w") as f:
         f.write("# insert sizes of kept pairs from k-mer anchors on the bait (mitoflex_amd.bim); samtools-stats IS layout\n")
         for size in sorted(hist):

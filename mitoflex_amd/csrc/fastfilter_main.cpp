@@ -14,7 +14,7 @@
 //     fastfilter bait --bait BAIT.fa -k 31 [-t 1] --fq1 R1.fq [--fq2 R2.fq]
 //                     --out1 O1.fq [--out2 O2.fq] [--pair either|both] [--devices N]
 //                     [--report FILE | --group-report FILE [--group-field N] [--group-sep C]
-//                      | --depth-report FILE [--depth-profile FILE]]
+//                      | --depth-report FILE [--depth-profile FILE] | --place-report FILE [--base-depth FILE]]
 // which loads libmitofilter_hip.so (HIP kernels, gfx950) and prints the kept
 // read/pair count.  --report writes how many kept reads (mates one by one)
 // each bait record attracted as a TSV (record, name, reads; then the
@@ -24,7 +24,10 @@
 // (either alone, for protein baits too) write the K-MER depth of the bait records over every mate that passes its own threshold: per
 // record (record, name, length, valid windows, covered windows, mean and max k-mer depth), and per valid window (name, 1-based window
 // start in the record, depth: the three columns of `samtools depth -aa`, but k-mer depth, not base depth; include/mitofilter.h,
-// mf_depth).  It has no CPU fallback: without the library or a GPU it exits non-zero, which shell_call turns into a RuntimeError
+// mf_depth).  --place-report and --base-depth (either alone, nucleotide baits) write where the passing mates lie on the bait: per record
+// (record, name, length, reads placed forward and reverse, reads hanging over its begin and its end, covered positions, mean and max base
+// depth, and a last line for the passing mates that are not placed), and per position (name, 1-based position, depth: the columns and
+// rows of `samtools depth -aa`; include/mitofilter.h, mf_place).  It has no CPU fallback: without the library or a GPU it exits non-zero, which shell_call turns into a RuntimeError
 // (helper.py:82-86).
 #include "../../include/mitofilter.h"
 #include "mf_coldtrace.h"
@@ -436,7 +439,7 @@ static std::string exe_dir()
 
 static int bait_main(int argc, char **argv)
 {
-    std::string bait, fq1, fq2, out1, out2, pair = "either", libpath, report, group_report, group_sep, depth_report, depth_profile;
+    std::string bait, fq1, fq2, out1, out2, pair = "either", libpath, report, group_report, group_sep, depth_report, depth_profile, place_report, base_depth_file;
     int group_field = -1; bool have_sep = false;
     int k = 0, devices = 1, gcode = 5; unsigned thr = 1; bool protein = false;
     std::vector<int> device_list;              // --device-list 2,3: these devices instead of 0 .. N - 1
@@ -458,6 +461,8 @@ static int bait_main(int argc, char **argv)
         else if (o == "--group-report") group_report = need("--group-report");
         else if (o == "--depth-report") depth_report = need("--depth-report");
         else if (o == "--depth-profile") depth_profile = need("--depth-profile");
+        else if (o == "--place-report") place_report = need("--place-report");
+        else if (o == "--base-depth") base_depth_file = need("--base-depth");
         else if (o == "--group-field") {
             const std::string v = need("--group-field"); char *end = nullptr; const long x = strtol(v.c_str(), &end, 10);
             if (v.empty() || *end || x < 1 || x > INT_MAX) { fprintf(stderr, "error: --group-field wants a field number from 1\n"); return 1; }
@@ -484,7 +489,8 @@ static int bait_main(int argc, char **argv)
     if (bait.empty() || fq1.empty() || out1.empty() || (fq2.empty() != out2.empty()) || (pair != "either" && pair != "both")) {
         fputs("usage: fastfilter bait --bait BAIT.fa [-k 31] [-t 1] --fq1 R1.fq [--fq2 R2.fq] --out1 O1.fq [--out2 O2.fq]"
               " [--pair either|both] [--devices N | --device-list D0,D1,..] [--option name=value ..]\n"
-              "       [--report FILE | --group-report FILE [--group-field N] [--group-sep C] | --depth-report FILE [--depth-profile FILE]]\n"
+              "       [--report FILE | --group-report FILE [--group-field N] [--group-sep C] | --depth-report FILE [--depth-profile FILE]\n"
+              "        | --place-report FILE [--base-depth FILE]]\n"
               "       fastfilter bait --protein --bait PROTEINS.fa [--code 5] [-k 9] ...   (six-frame peptide k-mers)\n", stderr);
         return 1;
     }
@@ -492,6 +498,11 @@ static int bait_main(int argc, char **argv)
     if (!report.empty() && !group_report.empty()) { fprintf(stderr, "error: --report and --group-report cannot be combined\n"); return 1; }
     const bool depth = !depth_report.empty() || !depth_profile.empty();
     if (depth && (!report.empty() || !group_report.empty())) { fprintf(stderr, "error: --depth-report / --depth-profile cannot be combined with --report or --group-report\n"); return 1; }
+    const bool placed = !place_report.empty() || !base_depth_file.empty();
+    if (placed && (depth || protein || !report.empty() || !group_report.empty())) {
+        fprintf(stderr, "error: --place-report / --base-depth need a nucleotide bait and cannot be combined with --report, --group-report, --depth-report, --depth-profile or --protein\n");
+        return 1;
+    }
     if (group_report.empty() && (group_field >= 0 || have_sep)) { fprintf(stderr, "error: --group-field and --group-sep need --group-report\n"); return 1; }
     if (!have_sep) group_sep = "_";
     if (k == 0) k = protein ? 9 : 31;
@@ -524,7 +535,34 @@ static int bait_main(int argc, char **argv)
     std::vector<uint64_t> starts;
     std::vector<uint32_t> profile;
     std::vector<mf_depth_record_t> depth_recs;
-    if (depth) {
+    std::vector<mf_place_record_t> place_recs;
+    uint64_t unplaced[2] = {0, 0};
+    if (placed) {
+#define SYM(name) auto p_##name = (decltype(&name))dlsym(h, #name); if (!p_##name) { fprintf(stderr, "error: %s lacks symbol %s\n", libpath.c_str(), #name); p_mf_kmerset_free(ks); return 2; }
+        SYM(mf_device_count) SYM(mf_kmerset_record_count) SYM(mf_kmerset_record_name) SYM(mf_kmerset_record_starts) SYM(mf_filter_fastq_files_placed)
+#undef SYM
+        uint64_t n_rec = 0;
+        rc = p_mf_kmerset_record_count(ks, &n_rec);
+        for (uint64_t i = 0; rc == MF_OK && i < n_rec; i++) {
+            size_t need = 0;
+            (void)p_mf_kmerset_record_name(ks, i, nullptr, 0, &need);
+            std::vector<char> buf(need ? need : 1);
+            rc = p_mf_kmerset_record_name(ks, i, buf.data(), buf.size(), nullptr);
+            record_names.emplace_back(buf.data());
+        }
+        starts.assign((size_t)n_rec + 1, 0);
+        if (rc == MF_OK) rc = p_mf_kmerset_record_starts(ks, starts.data(), starts.size(), nullptr);
+        if (rc == MF_OK && device_list.empty()) {
+            const int have = p_mf_device_count();
+            for (int i = 0; i < std::min(std::max(devices, 1), std::max(have, 1)); i++) device_list.push_back(i);
+        }
+        profile.assign(std::max<uint64_t>(starts.back(), 1), 0);          // (the base depth: the report's max column needs it too)
+        place_recs.assign(std::max<uint64_t>(n_rec, 1), mf_place_record_t{});
+        if (rc == MF_OK)
+            rc = p_mf_filter_fastq_files_placed(ks, fq1.c_str(), fq2.empty() ? nullptr : fq2.c_str(), out1.c_str(), out2.empty() ? nullptr : out2.c_str(),
+                                                thr, pair == "both" ? MF_PAIR_BOTH : MF_PAIR_EITHER, device_list.data(), (int)device_list.size(),
+                                                profile.data(), place_recs.data(), unplaced, &kept, &total);
+    } else if (depth) {
 #define SYM(name) auto p_##name = (decltype(&name))dlsym(h, #name); if (!p_##name) { fprintf(stderr, "error: %s lacks symbol %s\n", libpath.c_str(), #name); p_mf_kmerset_free(ks); return 2; }
         SYM(mf_device_count) SYM(mf_kmerset_group_count) SYM(mf_kmerset_group_name) SYM(mf_kmerset_record_starts) SYM(mf_filter_fastq_files_depth)
 #undef SYM
@@ -621,6 +659,35 @@ static int bait_main(int argc, char **argv)
                 if (profile[p] != MF_DEPTH_NONE) fprintf(f, "%s\t%llu\t%u\n", record_names[i].c_str(), (unsigned long long)(p - starts[i] + 1), profile[p]);
         if (ok) { ok = !ferror(f); ok = fclose(f) == 0 && ok; }
         if (!ok) { fprintf(stderr, "error: cannot write the depth profile %s\n", depth_profile.c_str()); p_mf_kmerset_free(ks); return 3; }
+    }
+    if (!place_report.empty()) {
+        FILE *f = fopen(place_report.c_str(), "w");
+        bool ok = f != nullptr;
+        if (ok) {
+            fputs("record\tname\tlength\tforward\treverse\tover_begin\tover_end\tcovered\tmean\tmax\n", f);
+            for (size_t i = 0; i < record_names.size(); i++) {
+                const mf_place_record_t &d = place_recs[i];
+                const uint64_t len = starts[i + 1] - starts[i];
+                uint32_t mx = 0;
+                for (uint64_t p = starts[i]; p < starts[i + 1]; p++) mx = std::max(mx, profile[p]);
+                fprintf(f, "%zu\t%s\t%llu\t%llu\t%llu\t%llu\t%llu\t%llu\t%.3f\t%u\n", i, record_names[i].c_str(), (unsigned long long)len,
+                        (unsigned long long)d.forward, (unsigned long long)d.reverse, (unsigned long long)d.over_begin, (unsigned long long)d.over_end,
+                        (unsigned long long)d.covered, len ? (double)d.base_sum / (double)len : 0.0, mx);
+            }
+            fprintf(f, "-\t*unplaced*\t%llu\n", (unsigned long long)unplaced[0]);
+            ok = !ferror(f);
+            ok = fclose(f) == 0 && ok;
+        }
+        if (!ok) { fprintf(stderr, "error: cannot write the placement report %s\n", place_report.c_str()); p_mf_kmerset_free(ks); return 3; }
+    }
+    if (!base_depth_file.empty()) {
+        FILE *f = fopen(base_depth_file.c_str(), "w");
+        bool ok = f != nullptr;
+        for (size_t i = 0; ok && i < record_names.size(); i++)
+            for (uint64_t p = starts[i]; p < starts[i + 1]; p++)
+                fprintf(f, "%s\t%llu\t%u\n", record_names[i].c_str(), (unsigned long long)(p - starts[i] + 1), profile[p]);
+        if (ok) { ok = !ferror(f); ok = fclose(f) == 0 && ok; }
+        if (!ok) { fprintf(stderr, "error: cannot write the base depth %s\n", base_depth_file.c_str()); p_mf_kmerset_free(ks); return 3; }
     }
     printf("%llu\n", (unsigned long long)kept);      // same stdout contract as the contig filter
     // (the outputs are written and closed; what is left is the GPU runtime's teardown -- queues, code objects, a tenth of a second -- which a

@@ -12,7 +12,7 @@
 //                        that carries unique k-mers of more than 64 records is settled exactly by repeated sweeps: a full map keeps
 //                        the 64 smallest records it has seen (a record larger than all of them is skipped, the largest is evicted for
 //                        a smaller newcomer), so after a sweep the map holds exact counts of the smallest records, and the next sweep
-//                        starts behind them.
+//                        starts behind them.  (The tally and the gathering of the counts are mf_tally_dev.h's, shared with mf_place.hip.)
 //   passign_kernel       the same tally (assign_listed below, shared code) over the (strand, start) windows of a protein set: a lane
 //                        translates its window's kp codons through a 64-entry codon table in LDS into the peptide key.
 //
@@ -29,8 +29,7 @@
 //   depth_fold_kernel    a pass's 32-bit counters into 64-bit totals (atomics: the totals of a device are shared by its lanes).
 //   depth_profile_kernel one wave per item (a stretch of at most DEPTH_ITEM positions of one record): the profile from pos_rep and the
 //                        totals, the record's windows / covered / sum / max reduced over the wave, one atomic of each per item.
-#include "mf_assign.h"
-#include "mf_keys_dev.h"
+#include "mf_tally_dev.h"
 #include <algorithm>
 
 namespace mf {
@@ -113,43 +112,7 @@ pass_list_kernel(const uint32_t *__restrict__ bits, uint64_t n_reads, uint32_t *
         for (uint32_t x = v[j]; x; x &= x - 1) list[at++] = (uint32_t)((w0 + j) * 32 + (uint32_t)(__ffs(x) - 1));
 }
 
-__device__ __forceinline__ uint32_t wave_max_u32(uint32_t v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { const uint32_t t = __shfl_xor(v, o); v = t > v ? t : v; }
-    return v;
-}
-
-constexpr int ASSIGN_BLOCK = 512;
-constexpr uint32_t HIST_MAX = 8192;            // records + 1 up to this: the per-record counts gather in LDS first
-
-// Window sources of assign_listed: begin(r) readies read r and returns its number of windows; owner_at(w) is the owner of window w's
-// key (OWNER_SHARED when the window is not valid or its key is shared).
-
-// nucleotide set: the read's k-windows, canonical keys
-template <int KW>
-struct NucWindows {
-    const ReadsView &R; const KmerSetView &S; const uint32_t *__restrict__ owner; const int k;
-    uint64_t b0 = 0; bool hasn = false;
-    __device__ NucWindows(const ReadsView &R_, const KmerSetView &S_, const uint32_t *owner_) : R(R_), S(S_), owner(owner_), k(S_.k) {}
-    __device__ __forceinline__ uint64_t begin(uint32_t r)
-    {
-        uint64_t len;
-        if (R.uniform_len) { b0 = (uint64_t)r * R.uniform_len; len = R.uniform_len; }
-        else { b0 = R.offsets[r]; len = R.offsets[r + 1] - b0; }
-        hasn = (R.has_n[r >> 5] >> (r & 31)) & 1u;
-        return len >= (uint64_t)k ? len - k + 1 : 0;
-    }
-    __device__ __forceinline__ uint32_t owner_at(uint64_t p) const
-    {
-        const uint64_t g = b0 + p;
-        bool valid = true;
-        if (hasn) { const uint64_t ni = npos_lower_bound(R, g); valid = !(ni < R.n_npos && R.npos[ni] < g + (uint64_t)k); }
-        uint32_t o = OWNER_SHARED;
-        if (valid) { const uint64_t slot = table_find(S, canonical_at<KW>(R.words, g, k)); if (slot != ~0ULL) o = owner[slot]; }
-        return o;
-    }
-};
+// (the window walk of a nucleotide set, NucWindows, is mf_tally_dev.h's)
 
 // protein set: the read's (strand, start) windows of kp codons -- starts 0 .. len - 3kp forward, then the same starts on the reverse
 // strand; lut: 64 codon entries, forward residue in bits 0-4, reverse-complement residue in bits 8-12 (31: stop codon)
@@ -194,13 +157,8 @@ __device__ __forceinline__ void assign_listed(Src &src, const uint32_t *__restri
                                               uint32_t *__restrict__ assign, uint64_t *__restrict__ pairs, unsigned long long *__restrict__ counts)
 {
     __shared__ uint32_t s_hist[HIST_MAX];
-    // The counts: most reads of a set go to a few records, and same-address atomics serialise across the chip (one per read cost ~2 ms
-    // on 166 k passing reads): a wave adds runs of equal results, a workgroup gathers them in LDS and adds its non-zero entries at the end.
-    const bool lds_hist = n_rec + 1 <= HIST_MAX;
-    if (lds_hist) for (uint32_t j = threadIdx.x; j <= n_rec; j += blockDim.x) s_hist[j] = 0;
-    __syncthreads();
-    uint32_t run_rec = 0, run_cnt = 0;             // (lane 0) the current run of equal results
-    auto add = [&](uint32_t idx, uint32_t c) { if (lds_hist) atomicAdd(&s_hist[idx], c); else atomicAdd(&counts[idx], (unsigned long long)c); };
+    GatheredCounts cnt(s_hist, counts, n_rec + 1);       // the records, then ambiguous
+    cnt.hist_begin();
     const int lane = threadIdx.x & 63;
     const uint64_t n_list = *n_list_p;
     const uint64_t n_waves = (uint64_t)gridDim.x * (ASSIGN_BLOCK / 64);
@@ -210,51 +168,25 @@ __device__ __forceinline__ void assign_listed(Src &src, const uint32_t *__restri
         uint32_t best_cnt = 0, best_rec = ASSIGN_AMBIGUOUS; bool tie = false;
         uint32_t lo_bound = 0;                       // the records this sweep counts: lo_bound and above
         for (;;) {
-            uint32_t my_rec = OWNER_SHARED, my_cnt = 0;  // map entry `lane` (OWNER_SHARED: empty)
-            uint32_t n_ent = 0; bool overflow = false;
+            WaveTally<uint32_t> tally;
             for (uint64_t p0 = 0; p0 < np; p0 += 64) {
                 const uint64_t p = p0 + (uint64_t)lane;
                 uint32_t id = OWNER_SHARED;
                 if (p < np) { const uint32_t o = src.owner_at(p); if (o != OWNER_SHARED && o >= lo_bound) id = o; }
-                uint64_t pend = __ballot(id != OWNER_SHARED);
-                while (pend) {                                                         // one distinct record a turn (wave-uniform)
-                    const uint32_t L = __builtin_amdgcn_readfirstlane(__shfl(id, (int)(__ffsll((long long)pend) - 1)));
-                    const uint64_t same = __ballot(id == L);
-                    const uint32_t c = (uint32_t)__popcll(same);
-                    pend &= ~same;
-                    const uint64_t hit = __ballot(my_rec == L);
-                    if (hit) { if ((uint64_t)lane == (uint64_t)(__ffsll((long long)hit) - 1)) my_cnt += c; }
-                    else if (n_ent < 64) { if ((uint32_t)lane == n_ent) { my_rec = L; my_cnt = c; } n_ent++; }
-                    else {                                                              // full: keep the 64 smallest records
-                        overflow = true;
-                        const uint32_t mx = wave_max_u32(my_rec);
-                        if (L < mx) { if (my_rec == mx) { my_rec = L; my_cnt = c; } }
-                    }
-                }
+                tally.add(id, lane);
             }
-            // this sweep's winner, folded into the read's
-            const uint32_t cmax = wave_max_u32(my_cnt);
-            if (cmax) {
-                const uint64_t at = __ballot(my_cnt == cmax);
-                const uint32_t rec = __shfl(my_rec, (int)(__ffsll((long long)at) - 1));
-                if (cmax > best_cnt) { best_cnt = cmax; best_rec = rec; tie = __popcll(at) > 1; }
-                else if (cmax == best_cnt) tie = true;
-            }
-            if (!overflow) break;
-            lo_bound = wave_max_u32(my_rec) + 1;         // (a full map: every entry holds a record)
+            tally.fold(best_cnt, best_rec, tie);
+            if (!tally.overflow) break;
+            lo_bound = tally.next_bound();
         }
         const uint32_t res = (best_cnt == 0 || tie) ? ASSIGN_AMBIGUOUS : best_rec;
         if (lane == 0) {
             if (assign) assign[r] = res;
             if (pairs) pairs[i] = ((uint64_t)r << 32) | res;
-            const uint32_t idx = res == ASSIGN_AMBIGUOUS ? n_rec : res;
-            if (run_cnt && idx == run_rec) run_cnt++;
-            else { if (run_cnt) add(run_rec, run_cnt); run_rec = idx; run_cnt = 1; }
+            cnt.bump(res == ASSIGN_AMBIGUOUS ? n_rec : res);
         }
     }
-    if (lane == 0 && run_cnt) add(run_rec, run_cnt);
-    __syncthreads();
-    if (lds_hist) for (uint32_t j = threadIdx.x; j <= n_rec; j += blockDim.x) if (s_hist[j]) atomicAdd(&counts[j], (unsigned long long)s_hist[j]);
+    cnt.hist_end(lane);
 }
 
 template <int KW>
@@ -282,8 +214,6 @@ passign_kernel(ReadsView R, KmerSetView S, const uint32_t *__restrict__ owner, c
     ProtWindows src(R, S, owner, s_lut);
     assign_listed(src, list, n_list_p, n_rec, assign, pairs, counts);
 }
-
-static inline unsigned grid_of(uint64_t n, unsigned block) { return (unsigned)((n + block - 1) / block); }
 
 hipError_t launch_build_owner(const BaitView &B, const uint64_t *rec_start, uint32_t n_rec, const uint32_t *rec_group, const KmerSetView &S,
                               uint32_t *owner, uint32_t *hi_scratch, hipStream_t st)
@@ -435,19 +365,6 @@ depth_fold_kernel(const uint32_t *__restrict__ cnt, uint64_t n, unsigned long lo
 {
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) { const uint32_t c = cnt[i]; if (c) atomicAdd(&tot[i], (unsigned long long)c); }
-}
-
-__device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-__device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { const unsigned long long t = __shfl_xor(v, o); v = t > v ? t : v; }
-    return v;
 }
 
 __global__ void __launch_bounds__(64)

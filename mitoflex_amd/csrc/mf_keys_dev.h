@@ -54,6 +54,39 @@ __device__ __forceinline__ Key<2> canonical_at<2>(const uint32_t *__restrict__ w
     return f ? Key<2>{lo, hi} : Key<2>{rlo, rhi};
 }
 
+// canonical_at, and which text is the canonical form: rev = 0 the forward text of the window, 1 its reverse complement, 2 both (the
+// window is its own reverse complement: even k only)
+template <int KW>
+__device__ __forceinline__ Key<KW> oriented_at(const uint32_t *__restrict__ words, uint64_t g, int k, uint32_t &rev);
+
+template <>
+__device__ __forceinline__ Key<1> oriented_at<1>(const uint32_t *__restrict__ words, uint64_t g, int k, uint32_t &rev)
+{
+    const uint64_t bit = 2 * g;
+    const uint64_t wi = bit >> 5; const uint32_t sh = (uint32_t)bit & 31;
+    const uint32_t w0 = words[wi], w1 = words[wi + 1], w2 = words[wi + 2];
+    uint64_t fwd = ((uint64_t)alignbit(w2, w1, sh) << 32) | alignbit(w1, w0, sh);
+    if (k < 32) fwd &= (1ULL << (2 * k)) - 1;
+    const uint64_t rc = revcomp1(fwd, k);
+    rev = fwd < rc ? 0u : fwd == rc ? 2u : 1u;
+    return Key<1>{fwd < rc ? fwd : rc};
+}
+
+template <>
+__device__ __forceinline__ Key<2> oriented_at<2>(const uint32_t *__restrict__ words, uint64_t g, int k, uint32_t &rev)
+{
+    const uint64_t bit = 2 * g;
+    const uint64_t wi = bit >> 5; const uint32_t sh = (uint32_t)bit & 31;
+    const uint32_t w0 = words[wi], w1 = words[wi + 1], w2 = words[wi + 2], w3 = words[wi + 3], w4 = words[wi + 4];
+    uint64_t lo = ((uint64_t)alignbit(w2, w1, sh) << 32) | alignbit(w1, w0, sh);
+    uint64_t hi = ((uint64_t)alignbit(w4, w3, sh) << 32) | alignbit(w3, w2, sh);
+    hi &= (1ULL << (2 * k - 64)) - 1;                 // 33 <= k <= 63
+    uint64_t rlo, rhi; revcomp2(lo, hi, k, rlo, rhi);
+    const bool f = (hi < rhi) || (hi == rhi && lo < rlo);
+    rev = f ? 0u : (hi == rhi && lo == rlo) ? 2u : 1u;
+    return f ? Key<2>{lo, hi} : Key<2>{rlo, rhi};
+}
+
 __device__ __forceinline__ bool table_contains(const KmerSetView &S, Key<1> v)
 {
     uint64_t slot = hash_key1(v.lo) & S.slot_mask;

@@ -1,0 +1,39 @@
+// Launchers of mf_place.hip: where on the bait, and on which strand, the reads that pass lie (internal to libmitofilter_hip).
+#pragma once
+#include <hip/hip_runtime.h>
+#include "mf_common.h"
+#include "mf_kernels.h"
+
+namespace mf {
+
+constexpr uint32_t ANCHOR_NONE = 0xFFFFFFFFu;        // position of a slot whose key is no anchor
+constexpr uint32_t PLACE_AMBIGUOUS = 0xFFFFFFFEu;    // MF_PLACE_AMBIGUOUS
+constexpr uint32_t PLACE_NONE = 0xFFFFFFFFu;         // MF_PLACE_NONE
+constexpr uint32_t PLACE_CLAMP = 0xFFFFFFFEu;        // the largest base depth reported
+struct alignas(8) Anchor { uint32_t pos, rb; };          // position inside the record (ANCHOR_NONE: no anchor), record << 1 | b
+struct PlaceOut { uint32_t record, strand; int32_t start, end; uint32_t votes, windows; };       // mf_place_t
+
+// Anchor table, indexed by the slot of the key table: anchor[slot] = { the window's position inside its record, record << 1 | b } when
+// exactly one valid bait window holds the key and that window is not its own reverse complement (b: 1 when the bait's reverse
+// complement is the canonical form); { ANCHOR_NONE, 0 } otherwise.  rec_start: n_rec + 1 ascending base offsets on the device.
+// lo / hi: `slots` words of scratch each.  The result does not depend on the order the windows arrive in.  Positions below 2^31 - 1.
+hipError_t launch_build_anchor(const BaitView &B, const uint64_t *rec_start, uint32_t n_rec, const KmerSetView &S, Anchor *anchor, uint32_t *lo,
+                               uint32_t *hi, hipStream_t st);
+// { PLACE_NONE, 0, 0, 0, 0, 0 } into every entry
+hipError_t launch_place_init(PlaceOut *place, uint64_t n_reads, hipStream_t st);
+// the longest read of a ragged read set into *max_len (zeroed by the caller)
+hipError_t launch_max_read_len(const uint64_t *offsets, uint64_t n_reads, unsigned long long *max_len, hipStream_t st);
+// One wave per listed read: every window whose key is an anchor votes for (record, strand, start); the strict winner places the read.
+// place (optional, n_reads entries, initialised): place[read].  diff: B.total + 1 counters that receive +1 at the first and -1 behind
+// the last covered position of every placed read (global positions, two's complement).  counts: 4 * n_rec + 1 counters -- forward,
+// reverse, over_begin, over_end of every record, then the listed reads that are not placed.
+hipError_t launch_place(const ReadsView &R, const KmerSetView &S, const Anchor *anchor, const uint64_t *rec_start, const uint32_t *list,
+                        const unsigned long long *n_list, uint32_t n_rec, PlaceOut *place, unsigned long long *diff, unsigned long long *counts,
+                        int n_cu, hipStream_t st);
+// Base depth from the difference counters: depth[p] = diff[0] + .. + diff[p] for p < total, clamped into `depth` (optional); rec_sums
+// (optional, zeroed by the caller): covered and base_sum of every record, 2 counters each.  partial: place_scan_tiles(total) + 1 words.
+uint64_t place_scan_tiles(uint64_t total);
+hipError_t launch_place_profile(const unsigned long long *diff, uint64_t total, const uint64_t *rec_start, uint32_t n_rec, unsigned long long *partial,
+                                uint32_t *depth, unsigned long long *rec_sums, hipStream_t st);
+
+} // namespace mf

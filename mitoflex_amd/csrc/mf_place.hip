@@ -1,0 +1,279 @@
+// Placement of baited reads on the bait (gfx950, 64-wide waves): position, strand and base depth.
+//
+//   anchor_span_kernel     one thread per bait window: atomicMin / atomicMax of its position into two slot-indexed arrays;
+//   anchor_finish_kernel   one thread per slot keeps the key as an anchor where both agree (exactly one window holds it, whatever order the
+//                          windows came in) and that window is not its own reverse complement: its position inside its record, its
+//                          record (binary search over the record starts) and the bait's orientation go into one 8-byte entry.
+//   place_kernel           one wave per listed read, grid-stride.  Lanes take the read's windows 64 at a time: canonical key and the
+//                          read's orientation together, slot, anchor entry -- one 8-byte gather --, candidate (record, strand, start)
+//                          as a 64-bit key.  The votes are tallied by mf_tally_dev.h's WaveTally (the leader loop and the repeated
+//                          sweeps of assign_kernel, over a wider key).  Lane 0 writes the read's placement, bumps the record's counters
+//                          through the per-wave run and the workgroup's LDS histogram, and adds +1 / -1 into the difference counters at
+//                          the clipped ends of the read's footprint.
+//   place_scan_reduce_kernel, place_scan_partials_kernel, place_profile_kernel
+//                          base depth = inclusive scan of the difference counters (a -1 that lands on the next record's first position
+//                          is right under a global scan: no segmentation): tile sums, their exclusive scan, then per tile the scan, the
+//                          clamp and the records' covered / base_sum (reduced over the wave where a wave lies inside one record).
+#include "mf_place.h"
+#include "mf_tally_dev.h"
+#include <algorithm>
+
+namespace mf {
+
+template <int KW>
+__global__ void __launch_bounds__(256)
+anchor_span_kernel(BaitView B, KmerSetView S, uint32_t *__restrict__ lo, uint32_t *__restrict__ hi)
+{
+    const uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= B.total || B.runlen[p] < (uint32_t)S.k) return;          // (runlen: valid bases from p inside its record, capped at 255 >= k)
+    const uint64_t slot = table_find(S, canonical_at<KW>(B.words, p, S.k));
+    if (slot == ~0ULL) return;                                          // (cannot happen: every valid window's key is in the set)
+    atomicMin(&lo[slot], (uint32_t)p);
+    atomicMax(&hi[slot], (uint32_t)p);
+}
+
+template <int KW>
+__global__ void __launch_bounds__(256)
+anchor_finish_kernel(BaitView B, const uint64_t *__restrict__ rec_start, uint32_t n_rec, int k, const uint32_t *__restrict__ lo,
+                     const uint32_t *__restrict__ hi, Anchor *__restrict__ anchor, uint64_t slots)
+{
+    const uint64_t s = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= slots) return;
+    Anchor out{ANCHOR_NONE, 0u};
+    const uint32_t p = lo[s];
+    if (p != ANCHOR_NONE && p == hi[s]) {                               // (an empty slot: lo all ones, hi 0)
+        uint32_t rev;
+        (void)oriented_at<KW>(B.words, p, k, rev);
+        if (rev != 2u) {
+            uint32_t a = 0, b = n_rec;                                  // last record that starts at or before p
+            while (b - a > 1) { const uint32_t m = (a + b) >> 1; if (rec_start[m] <= p) a = m; else b = m; }
+            out = Anchor{p - (uint32_t)rec_start[a], (a << 1) | rev};
+        }
+    }
+    anchor[s] = out;
+}
+
+__global__ void __launch_bounds__(256) place_init_kernel(PlaceOut *__restrict__ place, uint64_t n)
+{
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) place[i] = PlaceOut{PLACE_NONE, 0u, 0, 0, 0u, 0u};
+}
+
+__global__ void __launch_bounds__(256) max_read_len_kernel(const uint64_t *__restrict__ offsets, uint64_t n, unsigned long long *__restrict__ max_len)
+{
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    unsigned long long len = i < n ? offsets[i + 1] - offsets[i] : 0;
+    len = wave_max_u64(len);
+    if ((threadIdx.x & 63) == 0 && len) atomicMax(max_len, len);
+}
+
+template <int KW>
+__global__ void __launch_bounds__(ASSIGN_BLOCK)
+place_kernel(ReadsView R, KmerSetView S, const Anchor *__restrict__ anchor, const uint64_t *__restrict__ rec_start, const uint32_t *__restrict__ list,
+             const unsigned long long *__restrict__ n_list_p, uint32_t n_rec, PlaceOut *__restrict__ place, unsigned long long *__restrict__ diff,
+             unsigned long long *__restrict__ counts)
+{
+    __shared__ uint32_t s_hist[HIST_MAX];
+    GatheredCounts cnt(s_hist, counts, 4 * n_rec + 1);      // forward, reverse, over_begin, over_end of every record; not placed
+    cnt.hist_begin();
+    NucWindows<KW> src(R, S, nullptr);
+    const int lane = threadIdx.x & 63;
+    const uint64_t n_list = *n_list_p;
+    const uint64_t n_waves = (uint64_t)gridDim.x * (ASSIGN_BLOCK / 64);
+    for (uint64_t i = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6; i < n_list; i += n_waves) {
+        const uint32_t r = list[i];
+        const uint64_t np = src.begin(r);                    // windows; the read has np + k - 1 bases when np > 0
+        uint32_t best_cnt = 0, windows = 0; uint64_t best_key = 0; bool tie = false;
+        uint64_t lo_bound = 0;                               // the candidates this sweep counts: lo_bound and above
+        for (;;) {
+            WaveTally<uint64_t> tally;
+            for (uint64_t p0 = 0; p0 < np; p0 += 64) {
+                const uint64_t p = p0 + (uint64_t)lane;
+                uint64_t id = WaveTally<uint64_t>::NONE;
+                bool voted = false;
+                if (p < np && src.valid_at(p)) {
+                    uint32_t rev;
+                    const uint64_t slot = table_find(S, oriented_at<KW>(R.words, src.b0 + p, S.k, rev));
+                    if (slot != ~0ULL) {
+                        const Anchor a = anchor[slot];
+                        if (a.pos != ANCHOR_NONE) {            // (a window that is its own reverse complement finds no anchor: the build drops them)
+                            const uint32_t rs = a.rb ^ (rev & 1u);   // record << 1 | strand
+                            const uint32_t off = (uint32_t)((rs & 1u) ? np - 1 - p : p);
+                            const uint64_t cand = ((uint64_t)rs << 32) | (uint32_t)((int32_t)a.pos - (int32_t)off);
+                            voted = true;
+                            if (cand >= lo_bound) id = cand;
+                        }
+                    }
+                }
+                if (lo_bound == 0) windows += (uint32_t)__popcll(__ballot(voted));
+                tally.add(id, lane);
+            }
+            tally.fold(best_cnt, best_key, tie);
+            if (!tally.overflow) break;
+            lo_bound = tally.next_bound();
+        }
+        if (lane == 0) {
+            PlaceOut out{PLACE_AMBIGUOUS, 0u, 0, 0, 0u, windows};
+            if (best_cnt && !tie) {
+                const uint32_t rs = (uint32_t)(best_key >> 32), j = rs >> 1;
+                const int64_t start = (int32_t)(uint32_t)best_key, end = start + (int64_t)(np + S.k - 1);
+                const uint64_t s0 = rec_start[j];
+                const int64_t len = (int64_t)(rec_start[j + 1] - s0);
+                out = PlaceOut{j, rs & 1u, (int32_t)start, (int32_t)end, best_cnt, windows};
+                // the winning anchor's window lies inside the record and inside the read: 0 <= begin < last <= len
+                atomicAdd(&diff[s0 + (uint64_t)(start > 0 ? start : 0)], 1ull);
+                atomicAdd(&diff[s0 + (uint64_t)(end < len ? end : len)], ~0ull);
+                cnt.bump(4 * j + (rs & 1u));
+                if (start < 0) cnt.add(4 * j + 2, 1);
+                if (end > len) cnt.add(4 * j + 3, 1);
+            } else cnt.bump(4 * n_rec);
+            if (place) place[r] = out;
+        }
+    }
+    cnt.hist_end(lane);
+}
+
+// ------------------------------------------------------------------------------------------------------------------ base depth
+constexpr uint32_t PS_BLOCK = 256, PS_ITEMS = 16, PS_TILE = PS_BLOCK * PS_ITEMS;
+
+// exclusive prefix of v over the workgroup in thread order; *total = the workgroup's sum
+__device__ __forceinline__ unsigned long long block_exclusive_u64(unsigned long long v, unsigned long long *lds, unsigned long long *total)
+{
+    unsigned long long inc = v;
+    const uint32_t lane = threadIdx.x & 63, w = threadIdx.x >> 6, nw = blockDim.x >> 6;
+    for (int d = 1; d < 64; d <<= 1) { const unsigned long long t = __shfl_up(inc, d); if (lane >= (uint32_t)d) inc += t; }
+    __syncthreads();
+    if (lane == 63) lds[w] = inc;
+    __syncthreads();
+    unsigned long long base = 0, sum = 0;
+    for (uint32_t i = 0; i < nw; i++) { if (i < w) base += lds[i]; sum += lds[i]; }
+    if (total) *total = sum;
+    return base + inc - v;
+}
+
+__global__ void __launch_bounds__(PS_BLOCK)
+place_scan_reduce_kernel(const unsigned long long *__restrict__ diff, uint64_t n, unsigned long long *__restrict__ partial)
+{
+    __shared__ unsigned long long lds[PS_BLOCK / 64];
+    const uint64_t t0 = (uint64_t)blockIdx.x * PS_TILE;
+    unsigned long long s = 0;
+    for (uint32_t k = 0; k < PS_ITEMS; k++) { const uint64_t i = t0 + (uint64_t)k * PS_BLOCK + threadIdx.x; if (i < n) s += diff[i]; }
+    unsigned long long tot;
+    (void)block_exclusive_u64(s, lds, &tot);
+    if (threadIdx.x == 0) partial[blockIdx.x] = tot;
+}
+
+__global__ void __launch_bounds__(PS_BLOCK)
+place_scan_partials_kernel(unsigned long long *__restrict__ partial, uint64_t nb)        // in place, exclusive
+{
+    __shared__ unsigned long long lds[PS_BLOCK / 64];
+    unsigned long long carry = 0;
+    for (uint64_t b0 = 0; b0 < nb; b0 += PS_BLOCK) {
+        const uint64_t i = b0 + threadIdx.x;
+        const unsigned long long v = i < nb ? partial[i] : 0;
+        unsigned long long tot;
+        const unsigned long long ex = block_exclusive_u64(v, lds, &tot);
+        if (i < nb) partial[i] = carry + ex;
+        carry += tot;
+        __syncthreads();
+    }
+}
+
+__global__ void __launch_bounds__(PS_BLOCK)
+place_profile_kernel(const unsigned long long *__restrict__ diff, uint64_t n, const unsigned long long *__restrict__ partial,
+                     const uint64_t *__restrict__ rec_start, uint32_t n_rec, uint32_t *__restrict__ depth, unsigned long long *__restrict__ rec_sums)
+{
+    __shared__ unsigned long long lds[PS_BLOCK / 64];
+    const uint64_t i0 = (uint64_t)blockIdx.x * PS_TILE + (uint64_t)threadIdx.x * PS_ITEMS;
+    unsigned long long v[PS_ITEMS], s = 0;
+#pragma unroll
+    for (uint32_t k = 0; k < PS_ITEMS; k++) { v[k] = i0 + k < n ? diff[i0 + k] : 0; s += v[k]; }
+    unsigned long long run = partial[blockIdx.x] + block_exclusive_u64(s, lds, nullptr);
+    // the thread's positions lie in record j and the records behind it: sums per record, added when the record changes
+    uint32_t j = ~0u; uint64_t j_end = 0;
+    unsigned long long cov = 0, sum = 0;
+    if (rec_sums && i0 < n) {
+        uint32_t a = 0, b = n_rec;                                      // last record that starts at or before i0
+        while (b - a > 1) { const uint32_t m = (a + b) >> 1; if (rec_start[m] <= i0) a = m; else b = m; }
+        j = a; j_end = rec_start[a + 1];
+    }
+#pragma unroll
+    for (uint32_t k = 0; k < PS_ITEMS; k++) {
+        const uint64_t p = i0 + k;
+        run += v[k];
+        if (p >= n) continue;
+        if (depth) depth[p] = run < PLACE_CLAMP ? (uint32_t)run : PLACE_CLAMP;
+        if (!rec_sums) continue;
+        if (p >= j_end) {
+            if (sum) { atomicAdd(&rec_sums[2 * (uint64_t)j], cov); atomicAdd(&rec_sums[2 * (uint64_t)j + 1], sum); }
+            cov = sum = 0;
+            do { j++; j_end = rec_start[j + 1]; } while (p >= j_end);
+        }
+        cov += run != 0; sum += run;
+    }
+    if (!rec_sums) return;
+    // what is left belongs to record j: one add a wave where all its lanes are in the same record (same-address atomics serialise)
+    const uint32_t j0 = __builtin_amdgcn_readfirstlane(j);
+    if (__ballot(j != j0) == 0) {
+        cov = wave_sum_u64(cov); sum = wave_sum_u64(sum);
+        if ((threadIdx.x & 63) == 0 && sum && j != ~0u) { atomicAdd(&rec_sums[2 * (uint64_t)j], cov); atomicAdd(&rec_sums[2 * (uint64_t)j + 1], sum); }
+    } else if (sum) { atomicAdd(&rec_sums[2 * (uint64_t)j], cov); atomicAdd(&rec_sums[2 * (uint64_t)j + 1], sum); }
+}
+
+hipError_t launch_build_anchor(const BaitView &B, const uint64_t *rec_start, uint32_t n_rec, const KmerSetView &S, Anchor *anchor, uint32_t *lo,
+                               uint32_t *hi, hipStream_t st)
+{
+    const uint64_t slots = S.slot_mask + 1;
+    hipError_t e = hipMemsetAsync(lo, 0xFF, slots * 4, st);
+    if (e == hipSuccess) e = hipMemsetAsync(hi, 0, slots * 4, st);
+    if (e != hipSuccess) return e;
+    if (B.total && n_rec) {
+        if (S.kw == 1) hipLaunchKernelGGL(anchor_span_kernel<1>, dim3(grid_of(B.total, 256)), dim3(256), 0, st, B, S, lo, hi);
+        else hipLaunchKernelGGL(anchor_span_kernel<2>, dim3(grid_of(B.total, 256)), dim3(256), 0, st, B, S, lo, hi);
+    }
+    if (S.kw == 1) hipLaunchKernelGGL(anchor_finish_kernel<1>, dim3(grid_of(slots, 256)), dim3(256), 0, st, B, rec_start, n_rec, S.k, lo, hi, anchor, slots);
+    else hipLaunchKernelGGL(anchor_finish_kernel<2>, dim3(grid_of(slots, 256)), dim3(256), 0, st, B, rec_start, n_rec, S.k, lo, hi, anchor, slots);
+    return hipGetLastError();
+}
+
+hipError_t launch_place_init(PlaceOut *place, uint64_t n_reads, hipStream_t st)
+{
+    if (!n_reads) return hipSuccess;
+    hipLaunchKernelGGL(place_init_kernel, dim3(grid_of(n_reads, 256)), dim3(256), 0, st, place, n_reads);
+    return hipGetLastError();
+}
+
+hipError_t launch_max_read_len(const uint64_t *offsets, uint64_t n_reads, unsigned long long *max_len, hipStream_t st)
+{
+    if (!n_reads) return hipSuccess;
+    hipLaunchKernelGGL(max_read_len_kernel, dim3(grid_of(n_reads, 256)), dim3(256), 0, st, offsets, n_reads, max_len);
+    return hipGetLastError();
+}
+
+hipError_t launch_place(const ReadsView &R, const KmerSetView &S, const Anchor *anchor, const uint64_t *rec_start, const uint32_t *list,
+                        const unsigned long long *n_list, uint32_t n_rec, PlaceOut *place, unsigned long long *diff, unsigned long long *counts,
+                        int n_cu, hipStream_t st)
+{
+    if (!R.n_reads) return hipSuccess;
+    // the launch shape of launch_assign: four workgroups (32 waves) a CU at most, never more waves than reads
+    const uint64_t waves = std::min<uint64_t>((uint64_t)(n_cu > 0 ? n_cu : 1) * 32, R.n_reads);
+    const unsigned grid = grid_of(waves, ASSIGN_BLOCK / 64);
+    if (S.kw == 1) hipLaunchKernelGGL(place_kernel<1>, dim3(grid), dim3(ASSIGN_BLOCK), 0, st, R, S, anchor, rec_start, list, n_list, n_rec, place, diff, counts);
+    else hipLaunchKernelGGL(place_kernel<2>, dim3(grid), dim3(ASSIGN_BLOCK), 0, st, R, S, anchor, rec_start, list, n_list, n_rec, place, diff, counts);
+    return hipGetLastError();
+}
+
+uint64_t place_scan_tiles(uint64_t total) { return (total + PS_TILE - 1) / PS_TILE; }
+
+hipError_t launch_place_profile(const unsigned long long *diff, uint64_t total, const uint64_t *rec_start, uint32_t n_rec, unsigned long long *partial,
+                                uint32_t *depth, unsigned long long *rec_sums, hipStream_t st)
+{
+    const uint64_t nb = place_scan_tiles(total);
+    if (!nb || !n_rec) return hipSuccess;
+    hipLaunchKernelGGL(place_scan_reduce_kernel, dim3((unsigned)nb), dim3(PS_BLOCK), 0, st, diff, total, partial);
+    hipLaunchKernelGGL(place_scan_partials_kernel, dim3(1), dim3(PS_BLOCK), 0, st, partial, nb);
+    hipLaunchKernelGGL(place_profile_kernel, dim3((unsigned)nb), dim3(PS_BLOCK), 0, st, diff, total, partial, rec_start, n_rec, depth, rec_sums);
+    return hipGetLastError();
+}
+
+} // namespace mf

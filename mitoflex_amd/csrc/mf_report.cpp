@@ -1,9 +1,11 @@
 // libmitofilter_hip: the reports on the reads that pass the filter -- reads per bait record (mf_assign), per group of records
-// (mf_assign_groups), k-mer depth along the records (mf_depth) -- and their file-level calls.  Each runs behind a filter pass of
-// mf_api.cpp on the read set that still holds the pass's bitmap; the kernels are mf_assign.hip's.
+// (mf_assign_groups), k-mer depth along the records (mf_depth), position, strand and base depth (mf_place) -- and their file-level calls.
+// Each runs behind a filter pass of mf_api.cpp on the read set that still holds the pass's bitmap; the kernels are mf_assign.hip's and
+// mf_place.hip's.
 #include "mf_api_internal.h"
 #include "mf_pipeline.h"
 
+#include <atomic>
 #include <string.h>
 
 using namespace mf;
@@ -322,6 +324,132 @@ int mf_depth(const mf_kmerset *ks_, const mf_reads *reads_, uint32_t threshold, 
 
 } // extern "C"
 
+// ------------------------------------------------------------------- placement
+// The anchor table of a nucleotide set on `device`, and the record starts beside it: made by the first placement call there, under the
+// set's lock.
+static int place_tables(mf_kmerset *ks, int device, DevTables *T)
+{
+    std::lock_guard<std::mutex> lk(ks->mu);
+    if (T->place_built) return MF_OK;
+    if (ks->positions() >= 0x7FFFFFFFull || ks->rec_len().size() >= (1ull << 30))
+        return fail(MF_E_ARG, "placement takes sets of fewer than 2^31 - 1 positions and 2^30 records");
+    DevCtx *ctx; int rc = get_ctx(device, &ctx); if (rc) return rc;
+    hipStream_t st = ctx->stream;
+    BaitOnDevice B;
+    rc = B.upload(ks, st); if (rc) return rc;
+    uint32_t *lo = nullptr, *hi = nullptr; Anchor *anchor = nullptr;
+    HIPCHK(B.tmp.alloc(lo, ks->slots * 4));
+    HIPCHK(B.tmp.alloc(hi, ks->slots * 4));
+    HIPCHK(B.tmp.alloc(anchor, ks->slots * 8));
+    HIPCHK(launch_build_anchor(B.view, B.rec_start, B.n_rec, T->view, anchor, lo, hi, st));
+    HIPCHK(hipStreamSynchronize(st));
+    T->anchor = B.tmp.release(anchor); T->place_starts = B.tmp.release(const_cast<uint64_t *>(B.rec_start));
+    T->place_built = true;
+    return MF_OK;
+}
+
+// counters of a placement: the difference counters (positions + 1), then forward / reverse / over_begin / over_end of every record and
+// the passing reads that are not placed (4 R + 1)
+static size_t place_diff_n(const mf_kmerset *ks) { return (size_t)ks->positions() + 1; }
+static size_t place_cnt_n(const mf_kmerset *ks) { return 4 * ks->rec_len().size() + 1; }
+
+// The reads that passed the filter pass just run on this read set (its bitmap in r->d_bits[r->cur]) placed: their footprints into diff and
+// their records' counters into cnt (on r's device; other read sets there may be adding into them at the same time), their placements
+// into place (optional, initialised, n_reads entries on the device); *listed: how many passed.  Ends synchronised.
+static int place_after_filter(mf_kmerset *ks, mf_reads *r, unsigned long long *diff, unsigned long long *cnt, PlaceOut *place, uint64_t *listed)
+{
+    DevTables *T; int rc = build_on_device(ks, r->device, &T); if (rc) return rc;
+    rc = place_tables(ks, r->device, T); if (rc) return rc;
+    DevCtx *ctx; rc = get_ctx(r->device, &ctx, r->lane); if (rc) return rc;
+    hipStream_t st = ctx->stream;
+    const uint64_t n = r->v.n_reads;
+    *listed = 0;
+    if (!n) return MF_OK;
+    HIPCHK(dev_reserve(r->d_acnt, r->cap_acnt, 8, false));
+    // start and end are 32-bit: a read must end below 2^31 wherever it lies on the bait
+    const uint64_t room = 0x80000000ull - ks->positions();
+    unsigned long long v = 0;
+    bool too_long = r->v.uniform_len >= room;
+    if (!r->v.uniform_len && r->v.total_bases >= room) {          // only then can a ragged set hold such a read
+        HIPCHK(hipMemsetAsync(r->d_acnt, 0, 8, st));
+        HIPCHK(launch_max_read_len(r->v.offsets, n, r->d_acnt, st));
+        HIPCHK(hipMemcpyAsync(&v, r->d_acnt, 8, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        too_long = v >= room;
+    }
+    if (too_long) return fail(MF_E_ARG, "placement takes reads of fewer than 2^31 - positions bases (%llu for this set)", (unsigned long long)room);
+    HIPCHK(hipMemsetAsync(r->d_acnt, 0, 8, st));
+    HIPCHK(dev_reserve(r->d_alist, r->cap_alist, n * 4, true));
+    HIPCHK(launch_pass_list(r->d_bits[r->cur], n, r->d_alist, r->d_acnt, st));
+    HIPCHK(launch_place(r->v, T->view, T->anchor, T->place_starts, r->d_alist, r->d_acnt, (uint32_t)ks->rec_len().size(), place, diff, cnt, ctx->n_cu, st));
+    HIPCHK(hipMemcpyAsync(&v, r->d_acnt, 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    *listed = v;
+    return MF_OK;
+}
+
+// Base depth (ks->positions() u32), the record summaries (R entries) and the passing reads that are not placed from the counters diff /
+// cnt on `device` (stream st); each optional.  work: 2 R + place_scan_tiles + 1 words, d_depth: positions u32, on the device.
+static size_t place_work_n(const mf_kmerset *ks) { return 2 * ks->rec_len().size() + (size_t)place_scan_tiles(ks->positions()) + 1; }
+static int place_report(mf_kmerset *ks, int device, hipStream_t st, const unsigned long long *diff, const unsigned long long *cnt,
+                        unsigned long long *work, uint32_t *d_depth, uint32_t *base_depth, mf_place_record_t *records, uint64_t *unplaced_passing)
+{
+    DevTables *T; int rc = build_on_device(ks, device, &T); if (rc) return rc;
+    rc = place_tables(ks, device, T); if (rc) return rc;
+    const uint64_t total = ks->positions(), n_rec = ks->rec_len().size();
+    std::vector<unsigned long long> h_cnt(place_cnt_n(ks), 0), h_sum(2 * n_rec + 1, 0);
+    if (records && n_rec) HIPCHK(hipMemsetAsync(work, 0, 2 * n_rec * 8, st));
+    if (base_depth || records)
+        HIPCHK(launch_place_profile(diff, total, T->place_starts, (uint32_t)n_rec, work + 2 * n_rec, base_depth ? d_depth : nullptr,
+                                    records ? work : nullptr, st));
+    if (base_depth && total) HIPCHK(hipMemcpyAsync(base_depth, d_depth, total * 4, hipMemcpyDeviceToHost, st));
+    if (records && n_rec) HIPCHK(hipMemcpyAsync(h_sum.data(), work, 2 * n_rec * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(h_cnt.data(), cnt, h_cnt.size() * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (records)
+        for (uint64_t j = 0; j < n_rec; j++)
+            records[j] = mf_place_record_t{h_cnt[4 * j], h_cnt[4 * j + 1], h_cnt[4 * j + 2], h_cnt[4 * j + 3], h_sum[2 * j], h_sum[2 * j + 1]};
+    if (unplaced_passing) *unplaced_passing = h_cnt[4 * n_rec];
+    return MF_OK;
+}
+
+extern "C" {
+
+int mf_place(const mf_kmerset *ks_, const mf_reads *reads_, uint32_t threshold, int mode, uint32_t *out_bits, mf_place_t *place_out,
+             uint32_t *base_depth, mf_place_record_t *records, uint64_t *unplaced, mf_filter_stats_t *stats)
+{
+    static_assert(sizeof(mf_place_t) == 24 && sizeof(PlaceOut) == 24 && sizeof(mf_place_record_t) == 48, "placement records");
+    mf_kmerset *ks = const_cast<mf_kmerset *>(ks_);
+    mf_reads *r = const_cast<mf_reads *>(reads_);
+    if (!ks || !r) return fail(MF_E_ARG, "NULL handle");
+    if (ks->kind != MF_KIND_NUCLEOTIDE) return fail(MF_E_ARG, "placement needs a nucleotide bait set");
+    int rc = filter_common(ks, r, threshold, mode, out_bits, nullptr, 1, stats);
+    if (rc) return rc;
+    DevCtx *ctx; rc = get_ctx(r->device, &ctx, r->lane); if (rc) return rc;
+    hipStream_t st = ctx->stream;
+    const uint64_t n = r->v.n_reads;
+    const size_t n_diff = place_diff_n(ks), n_cnt = place_cnt_n(ks);
+    HIPCHK(dev_reserve(r->d_dtot, r->cap_dtot, n_diff * 8, false));
+    HIPCHK(dev_reserve(r->d_drec, r->cap_drec, (n_cnt + place_work_n(ks)) * 8, false));
+    HIPCHK(dev_reserve(r->d_dcnt, r->cap_dcnt, std::max<uint64_t>(ks->positions(), 1) * 4, false));
+    HIPCHK(hipMemsetAsync(r->d_dtot, 0, n_diff * 8, st));
+    HIPCHK(hipMemsetAsync(r->d_drec, 0, n_cnt * 8, st));
+    if (place_out && n) {
+        HIPCHK(dev_reserve(r->d_place, r->cap_place, n * sizeof(PlaceOut), true));
+        HIPCHK(launch_place_init(r->d_place, n, st));
+    }
+    uint64_t listed = 0;
+    rc = place_after_filter(ks, r, r->d_dtot, r->d_drec, place_out ? r->d_place : nullptr, &listed); if (rc) return rc;
+    if (place_out && n) HIPCHK(hipMemcpyAsync(place_out, r->d_place, n * sizeof(PlaceOut), hipMemcpyDeviceToHost, st));
+    uint64_t not_placed = 0;
+    rc = place_report(ks, r->device, st, r->d_dtot, r->d_drec, r->d_drec + n_cnt, r->d_dcnt, base_depth, records, &not_placed);
+    if (rc) return rc;
+    if (unplaced) { unplaced[0] = not_placed; unplaced[1] = n - listed; }
+    return MF_OK;
+}
+
+} // extern "C"
+
 // ------------------------------------------------------------- file level
 // What filter_fastq_files_on is given to report with: after_pass runs behind every mate batch's filter pass, on the worker thread that ran
 // it, before that worker's read set is filled again (mf_pipeline.h); the host pipeline hands it no read set for an empty batch.
@@ -366,6 +494,50 @@ struct DepthTotals : PassReport {
         unsigned long long *t = nullptr;
         int rc = on(R->device, &t);
         if (rc == MF_OK) rc = depth_after_filter(ks, R, t);
+        return hook_result(rc, err);
+    }
+};
+
+// Placement: the footprints and record counters of every mate that passes go into one array per (logical) device -- difference counters,
+// then record counters --, made and zeroed when a batch there first asks for it, shared by the device's workers and lanes (the kernel's
+// adds are atomic).  No pairs: nothing is tallied.
+struct PlaceTotals : PassReport {
+    mf_kmerset *ks;
+    std::mutex tot_mu;
+    std::map<int, unsigned long long *> tot;
+    std::atomic<uint64_t> mates{0}, passing{0};
+    explicit PlaceTotals(mf_kmerset *ks_) : PassReport(0, false), ks(ks_) {}
+    ~PlaceTotals() { restart(); }
+    void restart() override
+    {
+        for (auto &kv : tot) if (hipSetDevice(phys(kv.first)) == hipSuccess) hipFree(kv.second);
+        tot.clear(); mates = 0; passing = 0;
+    }
+    size_t words() const { return place_diff_n(ks) + place_cnt_n(ks); }
+    int on(int device, unsigned long long **out)
+    {
+        std::lock_guard<std::mutex> lk(tot_mu);
+        auto it = tot.find(device);
+        if (it != tot.end()) { *out = it->second; return MF_OK; }
+        DevTables *T; int rc = build_on_device(ks, device, &T); if (rc) return rc;
+        rc = place_tables(ks, device, T); if (rc) return rc;
+        DevCtx *ctx; rc = get_ctx(device, &ctx); if (rc) return rc;
+        unsigned long long *p = nullptr;
+        HIPCHK(dev_malloc(&p, words() * 8));
+        tot[device] = p;
+        HIPCHK(hipMemsetAsync(p, 0, words() * 8, ctx->stream));
+        HIPCHK(hipStreamSynchronize(ctx->stream));
+        *out = p;
+        return MF_OK;
+    }
+    int after_pass(mf_reads *R, std::vector<uint64_t> &, std::string &err) override
+    {
+        if (!R) return MF_OK;
+        unsigned long long *t = nullptr;
+        uint64_t listed = 0;
+        int rc = on(R->device, &t);
+        if (rc == MF_OK) rc = place_after_filter(ks, R, t, t + place_diff_n(ks), nullptr, &listed);
+        if (rc == MF_OK) { mates += R->v.n_reads; passing += listed; }
         return hook_result(rc, err);
     }
 };
@@ -430,6 +602,42 @@ int mf_filter_fastq_files_depth(mf_kmerset *ks, const char *fq1, const char *fq2
     HIPCHK(tmp.alloc(d_prof, std::max<uint64_t>(ks->positions(), 1) * 4));
     HIPCHK(tmp.alloc(d_rec, std::max<uint64_t>(ks->rec_len().size(), 1) * 32));
     return depth_report(ks, dev0, ctx->stream, t0, d_prof, d_rec, profile, records);
+}
+
+int mf_filter_fastq_files_placed(mf_kmerset *ks, const char *fq1, const char *fq2, const char *out1, const char *out2,
+                                 uint32_t threshold, int pair_mode, const int *devices, int n_devices,
+                                 uint32_t *base_depth, mf_place_record_t *records, uint64_t *unplaced, uint64_t *kept, uint64_t *total)
+{
+    if (!ks) return fail(MF_E_ARG, "NULL handle");
+    if (ks->kind != MF_KIND_NUCLEOTIDE) return fail(MF_E_ARG, "placement needs a nucleotide bait set");
+    PlaceTotals pt(ks);
+    int rc = filter_fastq_files_on(ks, fq1, fq2, out1, out2, threshold, pair_mode, devices, n_devices, kept, total, &pt);
+    if (rc) return rc;
+    // the devices' counters summed on the host into the first listed device's, then the scan and the summaries once, there
+    const int dev0 = devices[0];
+    unsigned long long *t0 = nullptr;
+    rc = pt.on(dev0, &t0); if (rc) return rc;
+    const size_t n_all = pt.words();
+    if (pt.tot.size() > 1) {
+        std::vector<uint64_t> sum(n_all, 0), part(n_all);
+        for (auto &kv : pt.tot) {
+            HIPCHK(hipSetDevice(phys(kv.first)));
+            HIPCHK(hipMemcpy(part.data(), kv.second, n_all * 8, hipMemcpyDeviceToHost));
+            for (size_t i = 0; i < n_all; i++) sum[i] += part[i];
+        }
+        HIPCHK(hipSetDevice(phys(dev0)));
+        HIPCHK(hipMemcpy(t0, sum.data(), n_all * 8, hipMemcpyHostToDevice));
+    }
+    DevCtx *ctx; rc = get_ctx(dev0, &ctx); if (rc) return rc;
+    DevScratch tmp;
+    uint32_t *d_depth = nullptr; unsigned long long *work = nullptr;
+    HIPCHK(tmp.alloc(d_depth, std::max<uint64_t>(ks->positions(), 1) * 4));
+    HIPCHK(tmp.alloc(work, place_work_n(ks) * 8));
+    uint64_t not_placed = 0;
+    rc = place_report(ks, dev0, ctx->stream, t0, t0 + place_diff_n(ks), work, d_depth, base_depth, records, &not_placed);
+    if (rc) return rc;
+    if (unplaced) { unplaced[0] = not_placed; unplaced[1] = pt.mates - pt.passing; }
+    return MF_OK;
 }
 
 } // extern "C"

@@ -28,6 +28,16 @@ ASSIGN_NONE = 0xFFFFFFFF
 DEPTH_NONE = 0xFFFFFFFF
 # per-record k-mer depth summary (mf_depth_record_t)
 DEPTH_RECORD = np.dtype([("windows", np.uint64), ("covered", np.uint64), ("depth_sum", np.uint64), ("depth_max", np.uint64)])
+# placement of a read that passes but that no candidate wins / of a read that does not pass (mf_place)
+PLACE_AMBIGUOUS = 0xFFFFFFFE
+PLACE_NONE = 0xFFFFFFFF
+# per-read placement (mf_place_t) and per-record placement summary (mf_place_record_t)
+PLACE = np.dtype([("record", np.uint32), ("strand", np.uint32), ("start", np.int32), ("end", np.int32), ("votes", np.uint32),
+                  ("windows", np.uint32)])
+PLACE_RECORD = np.dtype([("forward", np.uint64), ("reverse", np.uint64), ("over_begin", np.uint64), ("over_end", np.uint64),
+                         ("covered", np.uint64), ("base_sum", np.uint64)])
+# the largest insert size pair_inserts keeps (bim.estimate_insert_sizes' rule)
+MAX_INSERT = 100000
 
 # every symbol include/mitofilter.h declares (checked by tests/test_abi.py)
 EXPORTS = (
@@ -40,6 +50,7 @@ EXPORTS = (
     "mf_kmerset_record_count", "mf_kmerset_record_name", "mf_assign", "mf_filter_fastq_files_by_record",
     "mf_kmerset_group_records", "mf_kmerset_group_count", "mf_kmerset_group_name", "mf_assign_groups", "mf_filter_fastq_files_by_group",
     "mf_kmerset_record_starts", "mf_depth", "mf_filter_fastq_files_depth",
+    "mf_place", "mf_filter_fastq_files_placed",
 )
 
 
@@ -148,6 +159,9 @@ def load(path: Optional[str] = None):
     L.mf_depth.argtypes = [vp, vp, C.c_uint32, C.c_int, vp, vp, vp, C.POINTER(FilterStats)]
     L.mf_filter_fastq_files_depth.argtypes = [vp, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_uint32, C.c_int,
                                               C.POINTER(C.c_int), C.c_int, vp, vp, u64p, u64p]
+    L.mf_place.argtypes = [vp, vp, C.c_uint32, C.c_int, vp, vp, vp, vp, vp, C.POINTER(FilterStats)]
+    L.mf_filter_fastq_files_placed.argtypes = [vp, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_uint32, C.c_int,
+                                               C.POINTER(C.c_int), C.c_int, vp, vp, vp, u64p, u64p]
     if L.mf_abi_version() != 5:
         raise MitoFilterError("libmitofilter_hip ABI version mismatch")
     _lib = L
@@ -406,6 +420,38 @@ def record_depth(ks: KmerSet, reads: Reads, threshold: int = 1, mode: int = MODE
     return bits[:(n + 31) // 32], profile[:int(starts[-1])], records[:len(starts) - 1]
 
 
+def place_reads(ks: KmerSet, reads: Reads, threshold: int = 1, mode: int = MODE_SCREENED):
+    """One filter pass, then where every passing read lies on the bait (include/mitofilter.h: mf_place).  -> (bits u32[ceil(n/32)],
+    place PLACE[n]: record (or PLACE_AMBIGUOUS / PLACE_NONE), strand, start, end, votes, windows, base_depth u32[positions],
+    records PLACE_RECORD[R], unplaced u64[2]: passing reads that are not placed, reads that do not pass)."""
+    n = reads.info.n_reads
+    starts = ks.record_starts
+    bits = np.zeros(max((n + 31) // 32, 1), dtype=np.uint32)
+    place = np.zeros(max(n, 1), dtype=PLACE)
+    base_depth = np.zeros(max(int(starts[-1]), 1), dtype=np.uint32)
+    records = np.zeros(max(len(starts) - 1, 1), dtype=PLACE_RECORD)
+    unplaced = np.zeros(2, dtype=np.uint64)
+    _chk(load().mf_place(ks._h, reads._h, threshold, mode, bits.ctypes.data, place.ctypes.data, base_depth.ctypes.data,
+                         records.ctypes.data, unplaced.ctypes.data, None))
+    return bits[:(n + 31) // 32], place[:n], base_depth[:int(starts[-1])], records[:len(starts) - 1], unplaced
+
+
+def pair_inserts(place1: np.ndarray, place2: np.ndarray) -> np.ndarray:
+    """Insert size of every pair from the placements of its mates (PLACE arrays of equal length): int64, -1 where there is none.  A
+    pair has one when both mates are placed on the same record on opposite strands: `end` of the reverse mate - `start` of the
+    forward mate, kept when 0 < size <= MAX_INSERT."""
+    if len(place1) != len(place2):
+        raise ValueError("the mates' placements differ in length")
+    rec1, rec2 = place1["record"], place2["record"]
+    ok = (rec1 < PLACE_AMBIGUOUS) & (rec1 == rec2) & (place1["strand"] != place2["strand"])
+    fwd1 = place1["strand"] == 0
+    start = np.where(fwd1, place1["start"], place2["start"]).astype(np.int64)
+    end = np.where(fwd1, place2["end"], place1["end"]).astype(np.int64)
+    size = end - start
+    ok &= (size > 0) & (size <= MAX_INSERT)
+    return np.where(ok, size, -1).astype(np.int64)
+
+
 def filter_resident(ks: KmerSet, reads: Reads, threshold: int = 1, mode: int = MODE_SCREENED, steps: int = 1) -> FilterStats:
     st = FilterStats()
     _chk(load().mf_filter_resident(ks._h, reads._h, threshold, mode, steps, C.byref(st)))
@@ -491,6 +537,26 @@ def filter_fastq_files_depth(ks: KmerSet, fq1: str, fq2: Optional[str], out1: st
     _chk(load().mf_filter_fastq_files_depth(ks._h, _enc(fq1), _enc(fq2), _enc(out1), _enc(out2), threshold, pair_mode, arr, len(devices),
                                             profile.ctypes.data, records.ctypes.data, C.byref(kept), C.byref(total)))
     return kept.value, total.value, profile[:int(starts[-1])], records[:len(starts) - 1]
+
+
+def filter_fastq_files_placed(ks: KmerSet, fq1: str, fq2: Optional[str], out1: str, out2: Optional[str],
+                              threshold: int = 1, pair_mode: int = PAIR_EITHER, devices: Optional[Sequence[int]] = None,
+                              n_devices: int = 1):
+    """filter_fastq_files plus the placement on the bait of every mate that passes its own threshold (the pair rule decides only what
+    is written).  -> (kept, total, base_depth u32[positions], records PLACE_RECORD[R], unplaced u64[2]: passing mates that are not
+    placed, mates that do not pass)."""
+    if devices is None:
+        devices = list(range(n_devices))
+    arr = (C.c_int * len(devices))(*[int(d) for d in devices])
+    starts = ks.record_starts
+    base_depth = np.zeros(max(int(starts[-1]), 1), dtype=np.uint32)
+    records = np.zeros(max(len(starts) - 1, 1), dtype=PLACE_RECORD)
+    unplaced = np.zeros(2, dtype=np.uint64)
+    kept, total = C.c_uint64(), C.c_uint64()
+    _chk(load().mf_filter_fastq_files_placed(ks._h, _enc(fq1), _enc(fq2), _enc(out1), _enc(out2), threshold, pair_mode, arr, len(devices),
+                                             base_depth.ctypes.data, records.ctypes.data, unplaced.ctypes.data, C.byref(kept),
+                                             C.byref(total)))
+    return kept.value, total.value, base_depth[:int(starts[-1])], records[:len(starts) - 1], unplaced
 
 
 def set_option(name: str, value) -> None:
