@@ -366,6 +366,51 @@ int mf_filter_fastq_files_placed(mf_kmerset *ks, const char *fq1, const char *fq
                                  uint32_t *base_depth, mf_place_record_t *records, uint64_t *unplaced,
                                  uint64_t *kept, uint64_t *total);
 
+/* ---- pile-up: which bases the placed reads put on every bait position, the consensus they give and where it differs from the bait.
+ * Nucleotide sets only: every call below returns MF_E_ARG for a protein set.  No reference counterpart: the reference gets this from
+ * `bwa mem` + `samtools mpileup`.
+ * Positions, records and placement are exactly those of the placement section: a pile-up call places the passing reads as mf_place does.
+ * Pile-up: take a placed read of length L with (record j, strand, start).  Its base at read offset i (0 <= i < L) lies at record
+ * coordinate c = start + i for strand 0 and c = start + (L - 1 - i) for strand 1; on strand 1 the letter is complemented, so counts are
+ * always in the bait's forward letters.  The base is counted when 0 <= c < len_j and it is a valid letter: an invalid read base (N)
+ * counts nowhere, and a base that hangs over either end of the record counts nowhere -- in particular NOT in the neighbouring record,
+ * although global positions are contiguous.  Reads that are ambiguous, unplaced or not passing contribute nothing.  Invalid bait
+ * positions still receive counts.  There is no handling of indels or clipping: behind an insertion the shifted bases pile up as
+ * mismatches.  The result is four uint32_t per position of the set, mf_pileup_t { a, c, g, t }, each clamped at 0xFFFFFFFE.
+ * a + c + g + t at a position is at most the position's base depth (mf_place); the two are equal where no covering read has an N there.
+ * Consensus: take min_depth >= 1 (0 is MF_E_ARG).  Per position let d be the unclamped sum of the four counts and m the largest count.
+ * If d >= min_depth and exactly one letter has count m, the position is CALLED and the byte is that letter in upper case; if
+ * d >= min_depth and the maximum is tied, the position is AMBIGUOUS and the byte is 'N'; if d < min_depth the byte is the bait's own
+ * letter in lower case ('n' for an invalid bait letter).  One byte per position: a record's consensus has the record's length and can
+ * be baited with again.
+ * Per record (mf_pileup_record_t): bases = sum of d; matches = sum of the count of the bait's letter, over valid bait positions;
+ * mismatches = sum of d minus that count, over valid bait positions; called = the called positions; ambiguous = the ambiguous
+ * positions; variants = called positions whose bait letter is valid and differs from the call.  bases - matches - mismatches is what
+ * fell on invalid bait letters.
+ * unplaced: as in mf_place.
+ * File level: every mate that passes its own threshold is piled, as for placement.  Counts, bases, matches and mismatches add over mates
+ * and devices before clamping; the consensus, called, ambiguous and variants are computed once from the summed counts.  The output
+ * files are byte-identical to mf_filter_fastq_files_on's.
+ * Limits: placement's limits apply.  The counters take 32 bytes a position on the device: when they cannot be allocated the call
+ * returns MF_E_NOMEM with a message that names the size.
+ * The bait's packed letters are kept on each device, beside the anchor table, by the first pile-up call there. */
+typedef struct { uint32_t a, c, g, t; } mf_pileup_t;
+typedef struct { uint64_t bases, matches, mismatches, called, ambiguous, variants; } mf_pileup_record_t;
+/* one of 'A' 'C' 'G' 'T' 'N' per position (starts[R] bytes), 'N' for an invalid bait letter; MF_E_ARG and *needed (may be NULL) when n
+ * is too small */
+int mf_kmerset_bait_letters(const mf_kmerset *ks, uint8_t *letters, size_t n, size_t *needed);
+/* one pass like mf_filter, then placement and pile-up; out_bits / pileup (starts[R] entries) / consensus (starts[R] bytes) / records
+ * (R entries) / unplaced (2 u64) / stats each optional */
+int mf_pileup(const mf_kmerset *ks, const mf_reads *reads, uint32_t threshold, int mode, uint32_t min_depth,
+              uint32_t *out_bits, mf_pileup_t *pileup, uint8_t *consensus,
+              mf_pileup_record_t *records, uint64_t *unplaced, mf_filter_stats_t *stats);
+/* mf_filter_fastq_files_on plus the pile-up over the whole input; the same ingest path; pileup / consensus / records / unplaced each
+ * optional */
+int mf_filter_fastq_files_pileup(mf_kmerset *ks, const char *fq1, const char *fq2, const char *out1, const char *out2,
+                                 uint32_t threshold, int pair_mode, const int *devices, int n_devices,
+                                 uint32_t min_depth, mf_pileup_t *pileup, uint8_t *consensus,
+                                 mf_pileup_record_t *records, uint64_t *unplaced, uint64_t *kept, uint64_t *total);
+
 /* Options that select which kernels a filter pass runs (process-wide; every variant gives the same bits and is parity-tested):
  *   pass=default|split|serial   adapt=0|1   finish_streams=0|1|2   screen_streams=1|2   split_pipe=0|1   exact_co=0|1
  * and, read when a k-mer set is BUILT (ABI 5; every form gives the same bits -- tests force them on small baits):

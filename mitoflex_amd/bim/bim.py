@@ -31,6 +31,7 @@ with a stand-in assembler whose kept sets equal the oracle's and grow).
 """
 from __future__ import annotations
 
+import tempfile
 from os import path
 from typing import Dict, Iterator, List, Optional, Tuple
 
@@ -159,6 +160,33 @@ def kmer_bait_map(threads: int, fasta_file: str, basedir: str, prefix: str,
         for size in sorted(hist):
             f.write(f"IS\t{size}\t{hist[size]}\t{hist[size]}\t0\t0\n")
     return stats, fq1, fq2
+
+
+def consensus_bait(fasta_file: str, fq1: str, fq2: Optional[str], out_fasta: str, kmer: int = 31, min_depth: int = 3):
+    """A polished bait for the next generation: the reads of (fq1, fq2) -- the kept reads of a bait step -- are placed on the bait
+    `fasta_file` and piled up on the device (mitofilter.filter_fastq_files_pileup), and the consensus is written to `out_fasta` under the
+    bait's record names: the reads' letter where at least `min_depth` bases agree on one, N where the most is tied, the bait's own
+    letter in lower case elsewhere.  Returns the record summaries (mitofilter.PILEUP_RECORD: bases, matches, mismatches, called,
+    ambiguous, variants)."""
+    from mitoflex_amd import mitofilter as mf
+    if min_depth < 1:
+        raise ValueError("min_depth is at least 1")
+    if kmer < 1:
+        raise ValueError("kmer is at least 1")
+    if path.abspath(out_fasta) == path.abspath(fasta_file):
+        raise ValueError("out_fasta would overwrite the bait")
+    ks = mf.KmerSet.from_fasta(fasta_file, kmer, 0)
+    try:
+        names, starts = ks.record_names, ks.record_starts
+        with tempfile.TemporaryDirectory(prefix="consensus_bait_") as tmp:          # (the call writes its kept reads; they are not wanted)
+            _, _, _, consensus, records, _ = mf.filter_fastq_files_pileup(ks, fq1, fq2, path.join(tmp, "k.1.fq"),
+                                                                          path.join(tmp, "k.2.fq") if fq2 is not None else None, 1,
+                                                                          mf.PAIR_EITHER, min_depth=min_depth)
+    finally:
+        ks.close()
+    with open(out_fasta, "w") as f:
+        f.write(mf.consensus_fasta(names, starts, consensus))
+    return records
 
 
 def cal_insert(bam: str, basedir: str, prefix: str) -> float:

@@ -14,7 +14,8 @@
 //     fastfilter bait --bait BAIT.fa -k 31 [-t 1] --fq1 R1.fq [--fq2 R2.fq]
 //                     --out1 O1.fq [--out2 O2.fq] [--pair either|both] [--devices N]
 //                     [--report FILE | --group-report FILE [--group-field N] [--group-sep C]
-//                      | --depth-report FILE [--depth-profile FILE] | --place-report FILE [--base-depth FILE]]
+//                      | --depth-report FILE [--depth-profile FILE] | --place-report FILE [--base-depth FILE]
+//                      | [--pileup FILE] [--consensus FILE] [--variants FILE] [--min-depth N]]
 // which loads libmitofilter_hip.so (HIP kernels, gfx950) and prints the kept
 // read/pair count.  --report writes how many kept reads (mates one by one)
 // each bait record attracted as a TSV (record, name, reads; then the
@@ -27,7 +28,11 @@
 // mf_depth).  --place-report and --base-depth (either alone, nucleotide baits) write where the passing mates lie on the bait: per record
 // (record, name, length, reads placed forward and reverse, reads hanging over its begin and its end, covered positions, mean and max base
 // depth, and a last line for the passing mates that are not placed), and per position (name, 1-based position, depth: the columns and
-// rows of `samtools depth -aa`; include/mitofilter.h, mf_place).  It has no CPU fallback: without the library or a GPU it exits non-zero, which shell_call turns into a RuntimeError
+// rows of `samtools depth -aa`; include/mitofilter.h, mf_place).  --pileup, --consensus and --variants (any of them alone, nucleotide
+// baits) write what the placed mates' bases say: per position (name, 1-based position, bait letter, depth = A + C + G + T, A, C, G, T,
+// in the bait's forward letters), the consensus as FASTA under the bait's record names (called letters in upper case, N where the most
+// is tied, the bait's own letter in lower case below --min-depth, default 1), and the called positions that differ from the bait (name,
+// 1-based position, ref, alt, depth, alt count; include/mitofilter.h, mf_pileup).  It has no CPU fallback: without the library or a GPU it exits non-zero, which shell_call turns into a RuntimeError
 // (helper.py:82-86).
 #include "../../include/mitofilter.h"
 #include "mf_coldtrace.h"
@@ -439,7 +444,9 @@ static std::string exe_dir()
 
 static int bait_main(int argc, char **argv)
 {
-    std::string bait, fq1, fq2, out1, out2, pair = "either", libpath, report, group_report, group_sep, depth_report, depth_profile, place_report, base_depth_file;
+    std::string bait, fq1, fq2, out1, out2, pair = "either", libpath, report, group_report, group_sep, depth_report, depth_profile, place_report, base_depth_file, pileup_file, consensus_file,
+                variants_file;
+    unsigned min_depth = 1; bool have_min_depth = false;
     int group_field = -1; bool have_sep = false;
     int k = 0, devices = 1, gcode = 5; unsigned thr = 1; bool protein = false;
     std::vector<int> device_list;              // --device-list 2,3: these devices instead of 0 .. N - 1
@@ -463,6 +470,14 @@ static int bait_main(int argc, char **argv)
         else if (o == "--depth-profile") depth_profile = need("--depth-profile");
         else if (o == "--place-report") place_report = need("--place-report");
         else if (o == "--base-depth") base_depth_file = need("--base-depth");
+        else if (o == "--pileup") pileup_file = need("--pileup");
+        else if (o == "--consensus") consensus_file = need("--consensus");
+        else if (o == "--variants") variants_file = need("--variants");
+        else if (o == "--min-depth") {
+            const std::string v = need("--min-depth"); char *end = nullptr; const unsigned long x = strtoul(v.c_str(), &end, 10);
+            if (v.empty() || *end || v[0] == '-' || x < 1 || x > 0xFFFFFFFFul) { fprintf(stderr, "error: --min-depth wants a depth from 1\n"); return 1; }
+            min_depth = (unsigned)x; have_min_depth = true;
+        }
         else if (o == "--group-field") {
             const std::string v = need("--group-field"); char *end = nullptr; const long x = strtol(v.c_str(), &end, 10);
             if (v.empty() || *end || x < 1 || x > INT_MAX) { fprintf(stderr, "error: --group-field wants a field number from 1\n"); return 1; }
@@ -490,7 +505,7 @@ static int bait_main(int argc, char **argv)
         fputs("usage: fastfilter bait --bait BAIT.fa [-k 31] [-t 1] --fq1 R1.fq [--fq2 R2.fq] --out1 O1.fq [--out2 O2.fq]"
               " [--pair either|both] [--devices N | --device-list D0,D1,..] [--option name=value ..]\n"
               "       [--report FILE | --group-report FILE [--group-field N] [--group-sep C] | --depth-report FILE [--depth-profile FILE]\n"
-              "        | --place-report FILE [--base-depth FILE]]\n"
+              "        | --place-report FILE [--base-depth FILE] | [--pileup FILE] [--consensus FILE] [--variants FILE] [--min-depth N]]\n"
               "       fastfilter bait --protein --bait PROTEINS.fa [--code 5] [-k 9] ...   (six-frame peptide k-mers)\n", stderr);
         return 1;
     }
@@ -503,6 +518,12 @@ static int bait_main(int argc, char **argv)
         fprintf(stderr, "error: --place-report / --base-depth need a nucleotide bait and cannot be combined with --report, --group-report, --depth-report, --depth-profile or --protein\n");
         return 1;
     }
+    const bool piled = !pileup_file.empty() || !consensus_file.empty() || !variants_file.empty();
+    if (piled && (placed || depth || protein || !report.empty() || !group_report.empty())) {
+        fprintf(stderr, "error: --pileup / --consensus / --variants need a nucleotide bait and cannot be combined with --report, --group-report, --depth-report, --depth-profile, --place-report, --base-depth or --protein\n");
+        return 1;
+    }
+    if (have_min_depth && !piled) { fprintf(stderr, "error: --min-depth needs --pileup, --consensus or --variants\n"); return 1; }
     if (group_report.empty() && (group_field >= 0 || have_sep)) { fprintf(stderr, "error: --group-field and --group-sep need --group-report\n"); return 1; }
     if (!have_sep) group_sep = "_";
     if (k == 0) k = protein ? 9 : 31;
@@ -537,7 +558,37 @@ static int bait_main(int argc, char **argv)
     std::vector<mf_depth_record_t> depth_recs;
     std::vector<mf_place_record_t> place_recs;
     uint64_t unplaced[2] = {0, 0};
-    if (placed) {
+    std::vector<mf_pileup_t> pile;
+    std::vector<uint8_t> consensus, letters;
+    if (piled) {
+#define SYM(name) auto p_##name = (decltype(&name))dlsym(h, #name); if (!p_##name) { fprintf(stderr, "error: %s lacks symbol %s\n", libpath.c_str(), #name); p_mf_kmerset_free(ks); return 2; }
+        SYM(mf_device_count) SYM(mf_kmerset_record_count) SYM(mf_kmerset_record_name) SYM(mf_kmerset_record_starts) SYM(mf_kmerset_bait_letters)
+        SYM(mf_filter_fastq_files_pileup)
+#undef SYM
+        uint64_t n_rec = 0;
+        rc = p_mf_kmerset_record_count(ks, &n_rec);
+        for (uint64_t i = 0; rc == MF_OK && i < n_rec; i++) {
+            size_t need = 0;
+            (void)p_mf_kmerset_record_name(ks, i, nullptr, 0, &need);
+            std::vector<char> buf(need ? need : 1);
+            rc = p_mf_kmerset_record_name(ks, i, buf.data(), buf.size(), nullptr);
+            record_names.emplace_back(buf.data());
+        }
+        starts.assign((size_t)n_rec + 1, 0);
+        if (rc == MF_OK) rc = p_mf_kmerset_record_starts(ks, starts.data(), starts.size(), nullptr);
+        if (rc == MF_OK && device_list.empty()) {
+            const int have = p_mf_device_count();
+            for (int i = 0; i < std::min(std::max(devices, 1), std::max(have, 1)); i++) device_list.push_back(i);
+        }
+        pile.assign(std::max<uint64_t>(starts.back(), 1), mf_pileup_t{});
+        consensus.assign(std::max<uint64_t>(starts.back(), 1), 0);
+        letters.assign(std::max<uint64_t>(starts.back(), 1), 0);
+        if (rc == MF_OK) rc = p_mf_kmerset_bait_letters(ks, letters.data(), letters.size(), nullptr);
+        if (rc == MF_OK)
+            rc = p_mf_filter_fastq_files_pileup(ks, fq1.c_str(), fq2.empty() ? nullptr : fq2.c_str(), out1.c_str(), out2.empty() ? nullptr : out2.c_str(),
+                                                thr, pair == "both" ? MF_PAIR_BOTH : MF_PAIR_EITHER, device_list.data(), (int)device_list.size(),
+                                                min_depth, pile.data(), consensus.data(), nullptr, unplaced, &kept, &total);
+    } else if (placed) {
 #define SYM(name) auto p_##name = (decltype(&name))dlsym(h, #name); if (!p_##name) { fprintf(stderr, "error: %s lacks symbol %s\n", libpath.c_str(), #name); p_mf_kmerset_free(ks); return 2; }
         SYM(mf_device_count) SYM(mf_kmerset_record_count) SYM(mf_kmerset_record_name) SYM(mf_kmerset_record_starts) SYM(mf_filter_fastq_files_placed)
 #undef SYM
@@ -688,6 +739,45 @@ static int bait_main(int argc, char **argv)
                 fprintf(f, "%s\t%llu\t%u\n", record_names[i].c_str(), (unsigned long long)(p - starts[i] + 1), profile[p]);
         if (ok) { ok = !ferror(f); ok = fclose(f) == 0 && ok; }
         if (!ok) { fprintf(stderr, "error: cannot write the base depth %s\n", base_depth_file.c_str()); p_mf_kmerset_free(ks); return 3; }
+    }
+    if (!pileup_file.empty()) {
+        FILE *f = fopen(pileup_file.c_str(), "w");
+        bool ok = f != nullptr;
+        for (size_t i = 0; ok && i < record_names.size(); i++)
+            for (uint64_t p = starts[i]; p < starts[i + 1]; p++) {
+                const mf_pileup_t &c = pile[p];
+                fprintf(f, "%s\t%llu\t%c\t%llu\t%u\t%u\t%u\t%u\n", record_names[i].c_str(), (unsigned long long)(p - starts[i] + 1), (char)letters[p],
+                        (unsigned long long)c.a + c.c + c.g + c.t, c.a, c.c, c.g, c.t);
+            }
+        if (ok) { ok = !ferror(f); ok = fclose(f) == 0 && ok; }
+        if (!ok) { fprintf(stderr, "error: cannot write the pile-up %s\n", pileup_file.c_str()); p_mf_kmerset_free(ks); return 3; }
+    }
+    if (!consensus_file.empty()) {
+        FILE *f = fopen(consensus_file.c_str(), "w");
+        bool ok = f != nullptr;
+        for (size_t i = 0; ok && i < record_names.size(); i++) {
+            fprintf(f, ">%s\n", record_names[i].c_str());
+            for (uint64_t p = starts[i]; p < starts[i + 1]; p += 60) {
+                fwrite(consensus.data() + p, 1, (size_t)std::min<uint64_t>(60, starts[i + 1] - p), f);
+                fputc('\n', f);
+            }
+        }
+        if (ok) { ok = !ferror(f); ok = fclose(f) == 0 && ok; }
+        if (!ok) { fprintf(stderr, "error: cannot write the consensus %s\n", consensus_file.c_str()); p_mf_kmerset_free(ks); return 3; }
+    }
+    if (!variants_file.empty()) {
+        FILE *f = fopen(variants_file.c_str(), "w");
+        bool ok = f != nullptr;
+        for (size_t i = 0; ok && i < record_names.size(); i++)
+            for (uint64_t p = starts[i]; p < starts[i + 1]; p++) {
+                const uint8_t alt = consensus[p], ref = letters[p];
+                if (!(alt == 'A' || alt == 'C' || alt == 'G' || alt == 'T') || ref == 'N' || alt == ref) continue;
+                const mf_pileup_t &c = pile[p];
+                fprintf(f, "%s\t%llu\t%c\t%c\t%llu\t%u\n", record_names[i].c_str(), (unsigned long long)(p - starts[i] + 1), (char)ref, (char)alt,
+                        (unsigned long long)c.a + c.c + c.g + c.t, alt == 'A' ? c.a : alt == 'C' ? c.c : alt == 'G' ? c.g : c.t);
+            }
+        if (ok) { ok = !ferror(f); ok = fclose(f) == 0 && ok; }
+        if (!ok) { fprintf(stderr, "error: cannot write the variants %s\n", variants_file.c_str()); p_mf_kmerset_free(ks); return 3; }
     }
     printf("%llu\n", (unsigned long long)kept);      // same stdout contract as the contig filter
     // (the outputs are written and closed; what is left is the GPU runtime's teardown -- queues, code objects, a tenth of a second -- which a

@@ -69,6 +69,8 @@ struct DevTables {
     uint32_t *rep = nullptr, *pos_rep = nullptr; mf::DepthItem *ditems = nullptr; uint32_t n_ditems = 0; uint64_t dcnt_n = 0;
     // placement (mf_place), built by the first placement call: the anchor of every slot and the record starts (R + 1) the kernels read
     mf::Anchor *anchor = nullptr; uint64_t *place_starts = nullptr; bool place_built = false;
+    // pile-up (mf_pileup), kept by the first pile-up call: the bait's packed bases and run lengths, which the call kernel reads
+    uint32_t *pile_words = nullptr; uint8_t *pile_runlen = nullptr; bool pile_built = false;
     // frees one table / every table (the current device is the tables')
     template <class T> static hipError_t drop(T *&p) { const hipError_t e = hipFree(p); p = nullptr; return e; }
     void release()
@@ -76,6 +78,7 @@ struct DevTables {
         drop(keys); drop(bloom); drop(stab); drop(kbloom); drop(kbloom_co); drop(plut); drop(front2); drop(front3); drop(pre);
         drop(owner); drop(gowner); drop(rep); drop(pos_rep); drop(ditems);
         drop(anchor); drop(place_starts); place_built = false;
+        drop(pile_words); drop(pile_runlen); pile_built = false;
     }
 };
 struct mf_kmerset {
@@ -155,6 +158,8 @@ struct mf_reads {
     uint32_t *d_dcnt = nullptr; unsigned long long *d_dtot = nullptr, *d_drec = nullptr;
     size_t cap_dcnt = 0, cap_dtot = 0, cap_drec = 0;
     // placement (mf_place): the per-read results; its difference counters, record counters and base depth take d_dtot, d_drec and d_dcnt
+    // (mf_pileup: the pile-up counters in front of them in d_dtot, the record sums behind them in d_drec, the called pile-up and the
+    // consensus in d_dcnt)
     mf::PlaceOut *d_place = nullptr; size_t cap_place = 0;
     // capacities (bytes), so that a handle can be refilled batch after batch without touching the allocator
     size_t cap_words = 0, cap_offsets = 0, cap_npos = 0, cap_bitmap = 0, cap_recs = 0, cap_rec_counts = 0, cap_hits = 0, cap_npos_blk = 0, cap_off_blk = 0;

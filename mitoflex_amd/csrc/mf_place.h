@@ -1,4 +1,5 @@
-// Launchers of mf_place.hip: where on the bait, and on which strand, the reads that pass lie (internal to libmitofilter_hip).
+// Launchers of mf_place.hip: where on the bait, and on which strand, the reads that pass lie, and which bases they put on every bait
+// position (internal to libmitofilter_hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include "mf_common.h"
@@ -27,13 +28,25 @@ hipError_t launch_max_read_len(const uint64_t *offsets, uint64_t n_reads, unsign
 // place (optional, n_reads entries, initialised): place[read].  diff: B.total + 1 counters that receive +1 at the first and -1 behind
 // the last covered position of every placed read (global positions, two's complement).  counts: 4 * n_rec + 1 counters -- forward,
 // reverse, over_begin, over_end of every record, then the listed reads that are not placed.
+// pile (optional): 4 * B.total counters, [position][A, C, G, T] -- the pile-up.  Every valid base of a placed read that lies inside its
+// record adds 1 to the counter of its position and letter, complemented on strand 1 (the bait's forward letters); the other outputs
+// are the same with and without it.
 hipError_t launch_place(const ReadsView &R, const KmerSetView &S, const Anchor *anchor, const uint64_t *rec_start, const uint32_t *list,
                         const unsigned long long *n_list, uint32_t n_rec, PlaceOut *place, unsigned long long *diff, unsigned long long *counts,
-                        int n_cu, hipStream_t st);
+                        unsigned long long *pile, int n_cu, hipStream_t st);
 // Base depth from the difference counters: depth[p] = diff[0] + .. + diff[p] for p < total, clamped into `depth` (optional); rec_sums
 // (optional, zeroed by the caller): covered and base_sum of every record, 2 counters each.  partial: place_scan_tiles(total) + 1 words.
 uint64_t place_scan_tiles(uint64_t total);
 hipError_t launch_place_profile(const unsigned long long *diff, uint64_t total, const uint64_t *rec_start, uint32_t n_rec, unsigned long long *partial,
                                 uint32_t *depth, unsigned long long *rec_sums, hipStream_t st);
+
+// The pile-up called, per position p < B.total: out[p] (optional) = the four counters of pile clamped at PLACE_CLAMP; consensus[p]
+// (optional) = the letter with strictly the most bases in upper case when at least min_depth bases lie there, 'N' when the most is tied,
+// else the bait's own letter in lower case ('n' for an invalid one: B.runlen[p] == 0).  rec_sums (optional, zeroed by the caller): bases,
+// matches, mismatches, called, ambiguous, variants of every record, PILE_SUMS counters each.
+constexpr uint32_t PILE_SUMS = 6;
+struct PileOut { uint32_t a, c, g, t; };                 // mf_pileup_t
+hipError_t launch_pileup_call(const unsigned long long *pile, const BaitView &B, const uint64_t *rec_start, uint32_t n_rec, uint32_t min_depth,
+                              PileOut *out, uint8_t *consensus, unsigned long long *rec_sums, hipStream_t st);
 
 } // namespace mf

@@ -1,4 +1,4 @@
-// Placement of baited reads on the bait (gfx950, 64-wide waves): position, strand and base depth.
+// Placement of baited reads on the bait (gfx950, 64-wide waves): position, strand and base depth; the pile-up of their bases.
 //
 //   anchor_span_kernel     one thread per bait window: atomicMin / atomicMax of its position into two slot-indexed arrays;
 //   anchor_finish_kernel   one thread per slot keeps the key as an anchor where both agree (exactly one window holds it, whatever order the
@@ -9,11 +9,15 @@
 //                          as a 64-bit key.  The votes are tallied by mf_tally_dev.h's WaveTally (the leader loop and the repeated
 //                          sweeps of assign_kernel, over a wider key).  Lane 0 writes the read's placement, bumps the record's counters
 //                          through the per-wave run and the workgroup's LDS histogram, and adds +1 / -1 into the difference counters at
-//                          the clipped ends of the read's footprint.
+//                          the clipped ends of the read's footprint.  With PILE the wave then walks the placed read's bases 64 at a time
+//                          (pile_bases): letter from the packed words, N through the read's has_n bit and the invalid-position index,
+//                          complement on strand 1, clip to the record, one 64-bit add into [position][letter].
 //   place_scan_reduce_kernel, place_scan_partials_kernel, place_profile_kernel
 //                          base depth = inclusive scan of the difference counters (a -1 that lands on the next record's first position
 //                          is right under a global scan: no segmentation): tile sums, their exclusive scan, then per tile the scan, the
 //                          clamp and the records' covered / base_sum (reduced over the wave where a wave lies inside one record).
+//   pileup_call_kernel     per position, tiled like place_profile_kernel: the four counters clamped, the consensus byte, the records' six
+//                          sums through the same record walk (RecordWalk).
 #include "mf_place.h"
 #include "mf_tally_dev.h"
 #include <algorithm>
@@ -67,11 +71,28 @@ __global__ void __launch_bounds__(256) max_read_len_kernel(const uint64_t *__res
     if ((threadIdx.x & 63) == 0 && len) atomicMax(max_len, len);
 }
 
-template <int KW>
+// The bases of a read of L bases at b0, placed on strand `strand` with its leftmost base at record coordinate `start` of the record
+// at s0 (len positions), into pile: [position][letter].  The whole wave calls it; lane l takes bases l, l + 64, ..  Consecutive lanes
+// add to consecutive positions: no two lanes of an instruction share a counter.
+__device__ __forceinline__ void pile_bases(const ReadsView &R, uint64_t b0, bool hasn, uint64_t L, uint32_t strand, int64_t start, uint64_t s0,
+                                           int64_t len, unsigned long long *__restrict__ pile, int lane)
+{
+    for (uint64_t i = (uint64_t)lane; i < L; i += 64) {
+        const uint64_t g = b0 + i;
+        if (hasn) { const uint64_t ni = npos_lower_bound(R, g); if (ni < R.n_npos && R.npos[ni] == g) continue; }     // an N counts nowhere
+        uint32_t letter = (R.words[g >> 4] >> (2 * ((uint32_t)g & 15u))) & 3u;
+        int64_t c = start + (int64_t)i;
+        if (strand) { c = start + (int64_t)(L - 1 - i); letter ^= 3u; }
+        if (c < 0 || c >= len) continue;                                                                                // an overhang counts nowhere
+        atomicAdd(&pile[4 * (s0 + (uint64_t)c) + letter], 1ull);
+    }
+}
+
+template <int KW, bool PILE>
 __global__ void __launch_bounds__(ASSIGN_BLOCK)
 place_kernel(ReadsView R, KmerSetView S, const Anchor *__restrict__ anchor, const uint64_t *__restrict__ rec_start, const uint32_t *__restrict__ list,
              const unsigned long long *__restrict__ n_list_p, uint32_t n_rec, PlaceOut *__restrict__ place, unsigned long long *__restrict__ diff,
-             unsigned long long *__restrict__ counts)
+             unsigned long long *__restrict__ counts, unsigned long long *__restrict__ pile)
 {
     __shared__ uint32_t s_hist[HIST_MAX];
     GatheredCounts cnt(s_hist, counts, 4 * n_rec + 1);      // forward, reverse, over_begin, over_end of every record; not placed
@@ -129,6 +150,12 @@ place_kernel(ReadsView R, KmerSetView S, const Anchor *__restrict__ anchor, cons
             } else cnt.bump(4 * n_rec);
             if (place) place[r] = out;
         }
+        if (PILE && best_cnt && !tie) {                      // (the winner is wave-uniform: into scalar registers)
+            const uint32_t rs = __builtin_amdgcn_readfirstlane((uint32_t)(best_key >> 32));
+            const int32_t start = (int32_t)__builtin_amdgcn_readfirstlane((uint32_t)best_key);
+            const uint64_t s0 = rec_start[rs >> 1];
+            pile_bases(R, src.b0, src.hasn, np + S.k - 1, rs & 1u, (int64_t)start, s0, (int64_t)(rec_start[(rs >> 1) + 1] - s0), pile, lane);
+        }
     }
     cnt.hist_end(lane);
 }
@@ -179,6 +206,47 @@ place_scan_partials_kernel(unsigned long long *__restrict__ partial, uint64_t nb
     }
 }
 
+// The record of a thread's run of ascending positions, and the sums it keeps for that record: begin() finds the record of the first
+// position, next(p) flushes the sums and moves on when p lies behind the record, finish() adds what is left -- one add a wave where all
+// its lanes are in the same record (same-address atomics serialise).  rec_sums: N counters a record.
+template <int N>
+struct RecordWalk {
+    const uint64_t *__restrict__ rec_start; unsigned long long *__restrict__ rec_sums;
+    uint32_t j = ~0u; uint64_t j_end = 0;
+    unsigned long long v[N];
+    __device__ __forceinline__ RecordWalk(const uint64_t *rec_start_, unsigned long long *rec_sums_) : rec_start(rec_start_), rec_sums(rec_sums_)
+    {
+#pragma unroll
+        for (int k = 0; k < N; k++) v[k] = 0;
+    }
+    __device__ __forceinline__ void begin(uint32_t n_rec, uint64_t i0)
+    {
+        uint32_t a = 0, b = n_rec;                                      // last record that starts at or before i0
+        while (b - a > 1) { const uint32_t m = (a + b) >> 1; if (rec_start[m] <= i0) a = m; else b = m; }
+        j = a; j_end = rec_start[a + 1];
+    }
+    __device__ __forceinline__ void flush()
+    {
+#pragma unroll
+        for (int k = 0; k < N; k++) { if (v[k]) atomicAdd(&rec_sums[N * (uint64_t)j + k], v[k]); v[k] = 0; }
+    }
+    __device__ __forceinline__ void next(uint64_t p)
+    {
+        if (p < j_end) return;
+        flush();
+        do { j++; j_end = rec_start[j + 1]; } while (p >= j_end);
+    }
+    __device__ __forceinline__ void finish()
+    {
+        const uint32_t j0 = __builtin_amdgcn_readfirstlane(j);
+        if (__ballot(j != j0) == 0) {
+#pragma unroll
+            for (int k = 0; k < N; k++) v[k] = wave_sum_u64(v[k]);
+            if ((threadIdx.x & 63) == 0 && j != ~0u) flush();
+        } else flush();
+    }
+};
+
 __global__ void __launch_bounds__(PS_BLOCK)
 place_profile_kernel(const unsigned long long *__restrict__ diff, uint64_t n, const unsigned long long *__restrict__ partial,
                      const uint64_t *__restrict__ rec_start, uint32_t n_rec, uint32_t *__restrict__ depth, unsigned long long *__restrict__ rec_sums)
@@ -189,14 +257,9 @@ place_profile_kernel(const unsigned long long *__restrict__ diff, uint64_t n, co
 #pragma unroll
     for (uint32_t k = 0; k < PS_ITEMS; k++) { v[k] = i0 + k < n ? diff[i0 + k] : 0; s += v[k]; }
     unsigned long long run = partial[blockIdx.x] + block_exclusive_u64(s, lds, nullptr);
-    // the thread's positions lie in record j and the records behind it: sums per record, added when the record changes
-    uint32_t j = ~0u; uint64_t j_end = 0;
-    unsigned long long cov = 0, sum = 0;
-    if (rec_sums && i0 < n) {
-        uint32_t a = 0, b = n_rec;                                      // last record that starts at or before i0
-        while (b - a > 1) { const uint32_t m = (a + b) >> 1; if (rec_start[m] <= i0) a = m; else b = m; }
-        j = a; j_end = rec_start[a + 1];
-    }
+    // the thread's positions lie in one record and the records behind it: covered and base_sum per record, added when the record changes
+    RecordWalk<2> walk(rec_start, rec_sums);
+    if (rec_sums && i0 < n) walk.begin(n_rec, i0);
 #pragma unroll
     for (uint32_t k = 0; k < PS_ITEMS; k++) {
         const uint64_t p = i0 + k;
@@ -204,20 +267,54 @@ place_profile_kernel(const unsigned long long *__restrict__ diff, uint64_t n, co
         if (p >= n) continue;
         if (depth) depth[p] = run < PLACE_CLAMP ? (uint32_t)run : PLACE_CLAMP;
         if (!rec_sums) continue;
-        if (p >= j_end) {
-            if (sum) { atomicAdd(&rec_sums[2 * (uint64_t)j], cov); atomicAdd(&rec_sums[2 * (uint64_t)j + 1], sum); }
-            cov = sum = 0;
-            do { j++; j_end = rec_start[j + 1]; } while (p >= j_end);
-        }
-        cov += run != 0; sum += run;
+        walk.next(p);
+        walk.v[0] += run != 0; walk.v[1] += run;
     }
-    if (!rec_sums) return;
-    // what is left belongs to record j: one add a wave where all its lanes are in the same record (same-address atomics serialise)
-    const uint32_t j0 = __builtin_amdgcn_readfirstlane(j);
-    if (__ballot(j != j0) == 0) {
-        cov = wave_sum_u64(cov); sum = wave_sum_u64(sum);
-        if ((threadIdx.x & 63) == 0 && sum && j != ~0u) { atomicAdd(&rec_sums[2 * (uint64_t)j], cov); atomicAdd(&rec_sums[2 * (uint64_t)j + 1], sum); }
-    } else if (sum) { atomicAdd(&rec_sums[2 * (uint64_t)j], cov); atomicAdd(&rec_sums[2 * (uint64_t)j + 1], sum); }
+    if (rec_sums) walk.finish();
+}
+
+// The pile-up called.  A thread takes PS_ITEMS positions in a row -- one word of the bait --, a workgroup PS_TILE.
+__global__ void __launch_bounds__(PS_BLOCK)
+pileup_call_kernel(const unsigned long long *__restrict__ pile, BaitView B, const uint64_t *__restrict__ rec_start, uint32_t n_rec, uint32_t min_depth,
+                   PileOut *__restrict__ out, uint8_t *__restrict__ consensus, unsigned long long *__restrict__ rec_sums)
+{
+    static_assert(PS_ITEMS == 16, "a thread's positions are one packed word");
+    const uint64_t n = B.total;
+    const uint64_t i0 = (uint64_t)blockIdx.x * PS_TILE + (uint64_t)threadIdx.x * PS_ITEMS;
+    RecordWalk<(int)PILE_SUMS> walk(rec_start, rec_sums);          // bases, matches, mismatches, called, ambiguous, variants
+    if (rec_sums && i0 < n) walk.begin(n_rec, i0);
+    const uint32_t word = i0 < n ? B.words[i0 >> 4] : 0u;
+    constexpr uint32_t LETTERS = 0x54474341u;                       // "ACGT", letter l in byte l
+#pragma unroll 4
+    for (uint32_t k = 0; k < PS_ITEMS; k++) {
+        const uint64_t p = i0 + k;
+        if (p >= n) break;
+        const ulonglong2 lo = reinterpret_cast<const ulonglong2 *>(pile)[2 * p], hi = reinterpret_cast<const ulonglong2 *>(pile)[2 * p + 1];
+        const unsigned long long c0 = lo.x, c1 = lo.y, c2 = hi.x, c3 = hi.y;
+        const unsigned long long d = c0 + c1 + c2 + c3;
+        // the letter with strictly the most bases
+        unsigned long long m = c0; uint32_t best = 0; bool tied = false;
+        if (c1 > m) { m = c1; best = 1; tied = false; } else if (c1 == m) tied = true;
+        if (c2 > m) { m = c2; best = 2; tied = false; } else if (c2 == m) tied = true;
+        if (c3 > m) { m = c3; best = 3; tied = false; } else if (c3 == m) tied = true;
+        const bool valid = B.runlen[p] != 0;
+        const uint32_t b = (word >> (2 * k)) & 3u;
+        const bool deep = d >= (unsigned long long)min_depth;
+        if (out) out[p] = PileOut{c0 < PLACE_CLAMP ? (uint32_t)c0 : PLACE_CLAMP, c1 < PLACE_CLAMP ? (uint32_t)c1 : PLACE_CLAMP,
+                                  c2 < PLACE_CLAMP ? (uint32_t)c2 : PLACE_CLAMP, c3 < PLACE_CLAMP ? (uint32_t)c3 : PLACE_CLAMP};
+        if (consensus)
+            consensus[p] = (uint8_t)(deep ? (tied ? (uint32_t)'N' : (LETTERS >> (8 * best)) & 255u)
+                                          : (valid ? ((LETTERS >> (8 * b)) & 255u) | 0x20u : (uint32_t)'n'));
+        if (!rec_sums) continue;
+        walk.next(p);
+        const unsigned long long own = b == 0 ? c0 : b == 1 ? c1 : b == 2 ? c2 : c3;
+        walk.v[0] += d;
+        if (valid) { walk.v[1] += own; walk.v[2] += d - own; }
+        walk.v[3] += deep && !tied;
+        walk.v[4] += deep && tied;
+        walk.v[5] += deep && !tied && valid && best != b;
+    }
+    if (rec_sums) walk.finish();
 }
 
 hipError_t launch_build_anchor(const BaitView &B, const uint64_t *rec_start, uint32_t n_rec, const KmerSetView &S, Anchor *anchor, uint32_t *lo,
@@ -252,14 +349,16 @@ hipError_t launch_max_read_len(const uint64_t *offsets, uint64_t n_reads, unsign
 
 hipError_t launch_place(const ReadsView &R, const KmerSetView &S, const Anchor *anchor, const uint64_t *rec_start, const uint32_t *list,
                         const unsigned long long *n_list, uint32_t n_rec, PlaceOut *place, unsigned long long *diff, unsigned long long *counts,
-                        int n_cu, hipStream_t st)
+                        unsigned long long *pile, int n_cu, hipStream_t st)
 {
     if (!R.n_reads) return hipSuccess;
     // the launch shape of launch_assign: four workgroups (32 waves) a CU at most, never more waves than reads
     const uint64_t waves = std::min<uint64_t>((uint64_t)(n_cu > 0 ? n_cu : 1) * 32, R.n_reads);
     const unsigned grid = grid_of(waves, ASSIGN_BLOCK / 64);
-    if (S.kw == 1) hipLaunchKernelGGL(place_kernel<1>, dim3(grid), dim3(ASSIGN_BLOCK), 0, st, R, S, anchor, rec_start, list, n_list, n_rec, place, diff, counts);
-    else hipLaunchKernelGGL(place_kernel<2>, dim3(grid), dim3(ASSIGN_BLOCK), 0, st, R, S, anchor, rec_start, list, n_list, n_rec, place, diff, counts);
+#define PLACE_LAUNCH(KW, PILE) hipLaunchKernelGGL((place_kernel<KW, PILE>), dim3(grid), dim3(ASSIGN_BLOCK), 0, st, R, S, anchor, rec_start, list, n_list, n_rec, place, diff, counts, pile)
+    if (S.kw == 1) { if (pile) PLACE_LAUNCH(1, true); else PLACE_LAUNCH(1, false); }
+    else { if (pile) PLACE_LAUNCH(2, true); else PLACE_LAUNCH(2, false); }
+#undef PLACE_LAUNCH
     return hipGetLastError();
 }
 
@@ -273,6 +372,15 @@ hipError_t launch_place_profile(const unsigned long long *diff, uint64_t total, 
     hipLaunchKernelGGL(place_scan_reduce_kernel, dim3((unsigned)nb), dim3(PS_BLOCK), 0, st, diff, total, partial);
     hipLaunchKernelGGL(place_scan_partials_kernel, dim3(1), dim3(PS_BLOCK), 0, st, partial, nb);
     hipLaunchKernelGGL(place_profile_kernel, dim3((unsigned)nb), dim3(PS_BLOCK), 0, st, diff, total, partial, rec_start, n_rec, depth, rec_sums);
+    return hipGetLastError();
+}
+
+hipError_t launch_pileup_call(const unsigned long long *pile, const BaitView &B, const uint64_t *rec_start, uint32_t n_rec, uint32_t min_depth,
+                              PileOut *out, uint8_t *consensus, unsigned long long *rec_sums, hipStream_t st)
+{
+    const uint64_t nb = place_scan_tiles(B.total);
+    if (!nb || !n_rec) return hipSuccess;
+    hipLaunchKernelGGL(pileup_call_kernel, dim3((unsigned)nb), dim3(PS_BLOCK), 0, st, pile, B, rec_start, n_rec, min_depth, out, consensus, rec_sums);
     return hipGetLastError();
 }
 

@@ -1,5 +1,6 @@
 // libmitofilter_hip: the reports on the reads that pass the filter -- reads per bait record (mf_assign), per group of records
-// (mf_assign_groups), k-mer depth along the records (mf_depth), position, strand and base depth (mf_place) -- and their file-level calls.
+// (mf_assign_groups), k-mer depth along the records (mf_depth), position, strand and base depth (mf_place), base counts, consensus and
+// variants (mf_pileup) -- and their file-level calls.
 // Each runs behind a filter pass of mf_api.cpp on the read set that still holds the pass's bitmap; the kernels are mf_assign.hip's and
 // mf_place.hip's.
 #include "mf_api_internal.h"
@@ -348,15 +349,40 @@ static int place_tables(mf_kmerset *ks, int device, DevTables *T)
     return MF_OK;
 }
 
+// The bait's packed bases and run lengths beside the anchor table: kept by the first pile-up call on `device`, under the set's lock.
+static int pileup_tables(mf_kmerset *ks, int device, DevTables *T)
+{
+    int rc = place_tables(ks, device, T); if (rc) return rc;
+    std::lock_guard<std::mutex> lk(ks->mu);
+    if (T->pile_built) return MF_OK;
+    DevCtx *ctx; rc = get_ctx(device, &ctx); if (rc) return rc;
+    hipStream_t st = ctx->stream;
+    DevScratch tmp;
+    uint32_t *words = nullptr; uint8_t *runlen = nullptr;
+    HIPCHK(tmp.alloc(words, std::max<size_t>(ks->bait.words.size(), 1) * 4));
+    HIPCHK(tmp.alloc(runlen, std::max<size_t>(ks->bait.runlen.size(), 1)));
+    if (!ks->bait.words.empty()) HIPCHK(hipMemcpyAsync(words, ks->bait.words.data(), ks->bait.words.size() * 4, hipMemcpyHostToDevice, st));
+    if (!ks->bait.runlen.empty()) HIPCHK(hipMemcpyAsync(runlen, ks->bait.runlen.data(), ks->bait.runlen.size(), hipMemcpyHostToDevice, st));
+    HIPCHK(hipStreamSynchronize(st));
+    T->pile_words = tmp.release(words); T->pile_runlen = tmp.release(runlen);
+    T->pile_built = true;
+    return MF_OK;
+}
+
 // counters of a placement: the difference counters (positions + 1), then forward / reverse / over_begin / over_end of every record and
-// the passing reads that are not placed (4 R + 1)
+// the passing reads that are not placed (4 R + 1).  A pile-up puts its four counters a position IN FRONT of them (16-byte aligned for
+// the call kernel; a base that a faulty clip let through would still land inside the array).
 static size_t place_diff_n(const mf_kmerset *ks) { return (size_t)ks->positions() + 1; }
 static size_t place_cnt_n(const mf_kmerset *ks) { return 4 * ks->rec_len().size() + 1; }
+static size_t pile_cnt_n(const mf_kmerset *ks) { return 4 * (size_t)ks->positions(); }
+static int pile_nomem(size_t words) { (void)hipGetLastError(); return fail(MF_E_NOMEM, "the pile-up counters need %llu bytes on the device", (unsigned long long)(words * 8)); }
 
 // The reads that passed the filter pass just run on this read set (its bitmap in r->d_bits[r->cur]) placed: their footprints into diff and
 // their records' counters into cnt (on r's device; other read sets there may be adding into them at the same time), their placements
-// into place (optional, initialised, n_reads entries on the device); *listed: how many passed.  Ends synchronised.
-static int place_after_filter(mf_kmerset *ks, mf_reads *r, unsigned long long *diff, unsigned long long *cnt, PlaceOut *place, uint64_t *listed)
+// into place (optional, initialised, n_reads entries on the device), their bases into pile (optional, pile_cnt_n counters); *listed:
+// how many passed.  Ends synchronised.
+static int place_after_filter(mf_kmerset *ks, mf_reads *r, unsigned long long *diff, unsigned long long *cnt, PlaceOut *place, uint64_t *listed,
+                              unsigned long long *pile = nullptr)
 {
     DevTables *T; int rc = build_on_device(ks, r->device, &T); if (rc) return rc;
     rc = place_tables(ks, r->device, T); if (rc) return rc;
@@ -381,7 +407,7 @@ static int place_after_filter(mf_kmerset *ks, mf_reads *r, unsigned long long *d
     HIPCHK(hipMemsetAsync(r->d_acnt, 0, 8, st));
     HIPCHK(dev_reserve(r->d_alist, r->cap_alist, n * 4, true));
     HIPCHK(launch_pass_list(r->d_bits[r->cur], n, r->d_alist, r->d_acnt, st));
-    HIPCHK(launch_place(r->v, T->view, T->anchor, T->place_starts, r->d_alist, r->d_acnt, (uint32_t)ks->rec_len().size(), place, diff, cnt, ctx->n_cu, st));
+    HIPCHK(launch_place(r->v, T->view, T->anchor, T->place_starts, r->d_alist, r->d_acnt, (uint32_t)ks->rec_len().size(), place, diff, cnt, pile, ctx->n_cu, st));
     HIPCHK(hipMemcpyAsync(&v, r->d_acnt, 8, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     *listed = v;
@@ -450,6 +476,88 @@ int mf_place(const mf_kmerset *ks_, const mf_reads *reads_, uint32_t threshold, 
 
 } // extern "C"
 
+// ------------------------------------------------------------------- pile-up
+// The called pile-up (positions entries), the consensus (positions bytes), the record summaries (R entries) and the passing reads that
+// are not placed from the counters pile / cnt on `device` (stream st); each optional.  sums: PILE_SUMS * R words, d_out: positions
+// PileOut, d_cons: positions bytes, on the device.
+static int pileup_report(mf_kmerset *ks, int device, hipStream_t st, const unsigned long long *pile, const unsigned long long *cnt, uint32_t min_depth,
+                         unsigned long long *sums, PileOut *d_out, uint8_t *d_cons, mf_pileup_t *pileup, uint8_t *consensus,
+                         mf_pileup_record_t *records, uint64_t *unplaced_passing)
+{
+    static_assert(sizeof(mf_pileup_t) == 16 && sizeof(PileOut) == 16 && sizeof(mf_pileup_record_t) == 8 * PILE_SUMS, "pile-up records");
+    DevTables *T; int rc = build_on_device(ks, device, &T); if (rc) return rc;
+    rc = pileup_tables(ks, device, T); if (rc) return rc;
+    const uint64_t total = ks->positions(), n_rec = ks->rec_len().size();
+    std::vector<unsigned long long> h_cnt(place_cnt_n(ks), 0);
+    if (records && n_rec) HIPCHK(hipMemsetAsync(sums, 0, PILE_SUMS * n_rec * 8, st));
+    if (pileup || consensus || records)
+        HIPCHK(launch_pileup_call(pile, BaitView{T->pile_words, total, T->pile_runlen}, T->place_starts, (uint32_t)n_rec, min_depth,
+                                  pileup ? d_out : nullptr, consensus ? d_cons : nullptr, records ? sums : nullptr, st));
+    if (pileup && total) HIPCHK(hipMemcpyAsync(pileup, d_out, total * sizeof(PileOut), hipMemcpyDeviceToHost, st));
+    if (consensus && total) HIPCHK(hipMemcpyAsync(consensus, d_cons, total, hipMemcpyDeviceToHost, st));
+    if (records && n_rec) HIPCHK(hipMemcpyAsync(records, sums, PILE_SUMS * n_rec * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(h_cnt.data(), cnt, h_cnt.size() * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (unplaced_passing) *unplaced_passing = h_cnt[4 * n_rec];
+    return MF_OK;
+}
+
+static int pileup_args(const mf_kmerset *ks, uint32_t min_depth)
+{
+    if (min_depth == 0) return fail(MF_E_ARG, "min_depth is 0: a called position needs at least one base");
+    if (!ks) return fail(MF_E_ARG, "NULL handle");
+    if (ks->kind != MF_KIND_NUCLEOTIDE) return fail(MF_E_ARG, "the pile-up needs a nucleotide bait set");
+    return MF_OK;
+}
+
+extern "C" {
+
+int mf_kmerset_bait_letters(const mf_kmerset *ks, uint8_t *letters, size_t n, size_t *needed)
+{
+    if (!ks) return fail(MF_E_ARG, "NULL handle");
+    if (ks->kind != MF_KIND_NUCLEOTIDE) return fail(MF_E_ARG, "bait letters need a nucleotide bait set");
+    const size_t total = (size_t)ks->bait.total;
+    if (needed) *needed = total;
+    if ((!letters && total) || n < total) return fail(MF_E_ARG, "buffer too small: the set has %llu positions", (unsigned long long)total);
+    for (size_t p = 0; p < total; p++)
+        letters[p] = ks->bait.runlen[p] ? (uint8_t)"ACGT"[(ks->bait.words[p >> 4] >> (2 * (p & 15))) & 3u] : (uint8_t)'N';
+    return MF_OK;
+}
+
+int mf_pileup(const mf_kmerset *ks_, const mf_reads *reads_, uint32_t threshold, int mode, uint32_t min_depth, uint32_t *out_bits,
+              mf_pileup_t *pileup, uint8_t *consensus, mf_pileup_record_t *records, uint64_t *unplaced, mf_filter_stats_t *stats)
+{
+    mf_kmerset *ks = const_cast<mf_kmerset *>(ks_);
+    mf_reads *r = const_cast<mf_reads *>(reads_);
+    int rc = pileup_args(ks, min_depth); if (rc) return rc;
+    if (!r) return fail(MF_E_ARG, "NULL handle");
+    rc = filter_common(ks, r, threshold, mode, out_bits, nullptr, 1, stats);
+    if (rc) return rc;
+    DevCtx *ctx; rc = get_ctx(r->device, &ctx, r->lane); if (rc) return rc;
+    hipStream_t st = ctx->stream;
+    const uint64_t n = r->v.n_reads, total = ks->positions(), n_rec = ks->rec_len().size();
+    // d_dtot: pile-up, difference and record counters; d_drec: the record sums; d_dcnt: the called pile-up, then the consensus
+    const size_t n_pile = pile_cnt_n(ks), n_diff = place_diff_n(ks), n_cnt = place_cnt_n(ks), n_all = n_pile + n_diff + n_cnt;
+    const hipError_t e = dev_reserve(r->d_dtot, r->cap_dtot, n_all * 8, false);
+    if (e == hipErrorOutOfMemory) return pile_nomem(n_all);
+    HIPCHK(e);
+    HIPCHK(dev_reserve(r->d_drec, r->cap_drec, std::max<uint64_t>(n_rec, 1) * PILE_SUMS * 8, false));
+    HIPCHK(dev_reserve(r->d_dcnt, r->cap_dcnt, std::max<uint64_t>(total, 1) * (sizeof(PileOut) + 1) + 16, false));
+    HIPCHK(hipMemsetAsync(r->d_dtot, 0, n_all * 8, st));
+    unsigned long long *pile = r->d_dtot, *diff = pile + n_pile, *cnt = diff + n_diff;
+    uint64_t listed = 0;
+    rc = place_after_filter(ks, r, diff, cnt, nullptr, &listed, pile); if (rc) return rc;
+    uint64_t not_placed = 0;
+    PileOut *d_out = reinterpret_cast<PileOut *>(r->d_dcnt);
+    rc = pileup_report(ks, r->device, st, pile, cnt, min_depth, r->d_drec, d_out, reinterpret_cast<uint8_t *>(d_out + total), pileup, consensus, records,
+                       &not_placed);
+    if (rc) return rc;
+    if (unplaced) { unplaced[0] = not_placed; unplaced[1] = n - listed; }
+    return MF_OK;
+}
+
+} // extern "C"
+
 // ------------------------------------------------------------- file level
 // What filter_fastq_files_on is given to report with: after_pass runs behind every mate batch's filter pass, on the worker thread that ran
 // it, before that worker's read set is filled again (mf_pipeline.h); the host pipeline hands it no read set for an empty batch.
@@ -500,20 +608,21 @@ struct DepthTotals : PassReport {
 
 // Placement: the footprints and record counters of every mate that passes go into one array per (logical) device -- difference counters,
 // then record counters --, made and zeroed when a batch there first asks for it, shared by the device's workers and lanes (the kernel's
-// adds are atomic).  No pairs: nothing is tallied.
+// adds are atomic).  No pairs: nothing is tallied.  n_pile: the pile-up counters in front of them (PileupTotals), or 0.
 struct PlaceTotals : PassReport {
     mf_kmerset *ks;
+    const size_t n_pile;
     std::mutex tot_mu;
     std::map<int, unsigned long long *> tot;
     std::atomic<uint64_t> mates{0}, passing{0};
-    explicit PlaceTotals(mf_kmerset *ks_) : PassReport(0, false), ks(ks_) {}
+    explicit PlaceTotals(mf_kmerset *ks_, size_t n_pile_ = 0) : PassReport(0, false), ks(ks_), n_pile(n_pile_) {}
     ~PlaceTotals() { restart(); }
     void restart() override
     {
         for (auto &kv : tot) if (hipSetDevice(phys(kv.first)) == hipSuccess) hipFree(kv.second);
         tot.clear(); mates = 0; passing = 0;
     }
-    size_t words() const { return place_diff_n(ks) + place_cnt_n(ks); }
+    size_t words() const { return n_pile + place_diff_n(ks) + place_cnt_n(ks); }
     int on(int device, unsigned long long **out)
     {
         std::lock_guard<std::mutex> lk(tot_mu);
@@ -523,7 +632,9 @@ struct PlaceTotals : PassReport {
         rc = place_tables(ks, device, T); if (rc) return rc;
         DevCtx *ctx; rc = get_ctx(device, &ctx); if (rc) return rc;
         unsigned long long *p = nullptr;
-        HIPCHK(dev_malloc(&p, words() * 8));
+        const hipError_t e = dev_malloc(&p, words() * 8);
+        if (e == hipErrorOutOfMemory && n_pile) return pile_nomem(words());
+        HIPCHK(e);
         tot[device] = p;
         HIPCHK(hipMemsetAsync(p, 0, words() * 8, ctx->stream));
         HIPCHK(hipStreamSynchronize(ctx->stream));
@@ -536,10 +647,32 @@ struct PlaceTotals : PassReport {
         unsigned long long *t = nullptr;
         uint64_t listed = 0;
         int rc = on(R->device, &t);
-        if (rc == MF_OK) rc = place_after_filter(ks, R, t, t + place_diff_n(ks), nullptr, &listed);
+        if (rc == MF_OK) rc = place_after_filter(ks, R, t + n_pile, t + n_pile + place_diff_n(ks), nullptr, &listed, n_pile ? t : nullptr);
         if (rc == MF_OK) { mates += R->v.n_reads; passing += listed; }
         return hook_result(rc, err);
     }
+    // the devices' counters summed on the host into the first listed device's, which *t0 then names
+    int fold_into(int dev0, unsigned long long **t0)
+    {
+        int rc = on(dev0, t0); if (rc) return rc;
+        const size_t n_all = words();
+        if (tot.size() > 1) {
+            std::vector<uint64_t> sum(n_all, 0), part(n_all);
+            for (auto &kv : tot) {
+                HIPCHK(hipSetDevice(phys(kv.first)));
+                HIPCHK(hipMemcpy(part.data(), kv.second, n_all * 8, hipMemcpyDeviceToHost));
+                for (size_t i = 0; i < n_all; i++) sum[i] += part[i];
+            }
+            HIPCHK(hipSetDevice(phys(dev0)));
+            HIPCHK(hipMemcpy(*t0, sum.data(), n_all * 8, hipMemcpyHostToDevice));
+        }
+        return MF_OK;
+    }
+};
+
+// Pile-up: PlaceTotals whose array grows by the four counters per position.
+struct PileupTotals : PlaceTotals {
+    explicit PileupTotals(mf_kmerset *ks_) : PlaceTotals(ks_, pile_cnt_n(ks_)) {}
 };
 
 static int files_by_owner(mf_kmerset *ks, const char *fq1, const char *fq2, const char *out1, const char *out2, uint32_t threshold, int pair_mode,
@@ -616,18 +749,7 @@ int mf_filter_fastq_files_placed(mf_kmerset *ks, const char *fq1, const char *fq
     // the devices' counters summed on the host into the first listed device's, then the scan and the summaries once, there
     const int dev0 = devices[0];
     unsigned long long *t0 = nullptr;
-    rc = pt.on(dev0, &t0); if (rc) return rc;
-    const size_t n_all = pt.words();
-    if (pt.tot.size() > 1) {
-        std::vector<uint64_t> sum(n_all, 0), part(n_all);
-        for (auto &kv : pt.tot) {
-            HIPCHK(hipSetDevice(phys(kv.first)));
-            HIPCHK(hipMemcpy(part.data(), kv.second, n_all * 8, hipMemcpyDeviceToHost));
-            for (size_t i = 0; i < n_all; i++) sum[i] += part[i];
-        }
-        HIPCHK(hipSetDevice(phys(dev0)));
-        HIPCHK(hipMemcpy(t0, sum.data(), n_all * 8, hipMemcpyHostToDevice));
-    }
+    rc = pt.fold_into(dev0, &t0); if (rc) return rc;
     DevCtx *ctx; rc = get_ctx(dev0, &ctx); if (rc) return rc;
     DevScratch tmp;
     uint32_t *d_depth = nullptr; unsigned long long *work = nullptr;
@@ -635,6 +757,33 @@ int mf_filter_fastq_files_placed(mf_kmerset *ks, const char *fq1, const char *fq
     HIPCHK(tmp.alloc(work, place_work_n(ks) * 8));
     uint64_t not_placed = 0;
     rc = place_report(ks, dev0, ctx->stream, t0, t0 + place_diff_n(ks), work, d_depth, base_depth, records, &not_placed);
+    if (rc) return rc;
+    if (unplaced) { unplaced[0] = not_placed; unplaced[1] = pt.mates - pt.passing; }
+    return MF_OK;
+}
+
+int mf_filter_fastq_files_pileup(mf_kmerset *ks, const char *fq1, const char *fq2, const char *out1, const char *out2,
+                                 uint32_t threshold, int pair_mode, const int *devices, int n_devices, uint32_t min_depth,
+                                 mf_pileup_t *pileup, uint8_t *consensus, mf_pileup_record_t *records, uint64_t *unplaced,
+                                 uint64_t *kept, uint64_t *total)
+{
+    int rc = pileup_args(ks, min_depth); if (rc) return rc;
+    PileupTotals pt(ks);
+    rc = filter_fastq_files_on(ks, fq1, fq2, out1, out2, threshold, pair_mode, devices, n_devices, kept, total, &pt);
+    if (rc) return rc;
+    // the devices' counters summed on the host into the first listed device's, then the call kernel once, there
+    const int dev0 = devices[0];
+    unsigned long long *t0 = nullptr;
+    rc = pt.fold_into(dev0, &t0); if (rc) return rc;
+    DevCtx *ctx; rc = get_ctx(dev0, &ctx); if (rc) return rc;
+    DevScratch tmp;
+    PileOut *d_out = nullptr; uint8_t *d_cons = nullptr; unsigned long long *sums = nullptr;
+    const uint64_t positions = ks->positions();
+    HIPCHK(tmp.alloc(d_out, std::max<uint64_t>(positions, 1) * sizeof(PileOut)));
+    HIPCHK(tmp.alloc(d_cons, std::max<uint64_t>(positions, 1)));
+    HIPCHK(tmp.alloc(sums, std::max<uint64_t>(ks->rec_len().size(), 1) * PILE_SUMS * 8));
+    uint64_t not_placed = 0;
+    rc = pileup_report(ks, dev0, ctx->stream, t0, t0 + pt.n_pile + place_diff_n(ks), min_depth, sums, d_out, d_cons, pileup, consensus, records, &not_placed);
     if (rc) return rc;
     if (unplaced) { unplaced[0] = not_placed; unplaced[1] = pt.mates - pt.passing; }
     return MF_OK;

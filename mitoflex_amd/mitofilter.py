@@ -36,6 +36,12 @@ PLACE = np.dtype([("record", np.uint32), ("strand", np.uint32), ("start", np.int
                   ("windows", np.uint32)])
 PLACE_RECORD = np.dtype([("forward", np.uint64), ("reverse", np.uint64), ("over_begin", np.uint64), ("over_end", np.uint64),
                          ("covered", np.uint64), ("base_sum", np.uint64)])
+# per-position base counts (mf_pileup_t) and per-record pile-up summary (mf_pileup_record_t)
+PILEUP = np.dtype([("a", np.uint32), ("c", np.uint32), ("g", np.uint32), ("t", np.uint32)])
+PILEUP_RECORD = np.dtype([("bases", np.uint64), ("matches", np.uint64), ("mismatches", np.uint64), ("called", np.uint64),
+                          ("ambiguous", np.uint64), ("variants", np.uint64)])
+# a variant position (pileup_variants): pos is 0-based inside the record, ref / alt are letters
+VARIANT = np.dtype([("record", np.uint32), ("pos", np.uint64), ("ref", "S1"), ("alt", "S1"), ("depth", np.uint64), ("alt_count", np.uint64)])
 # the largest insert size pair_inserts keeps (bim.estimate_insert_sizes' rule)
 MAX_INSERT = 100000
 
@@ -51,6 +57,7 @@ EXPORTS = (
     "mf_kmerset_group_records", "mf_kmerset_group_count", "mf_kmerset_group_name", "mf_assign_groups", "mf_filter_fastq_files_by_group",
     "mf_kmerset_record_starts", "mf_depth", "mf_filter_fastq_files_depth",
     "mf_place", "mf_filter_fastq_files_placed",
+    "mf_pileup", "mf_filter_fastq_files_pileup", "mf_kmerset_bait_letters",
 )
 
 
@@ -162,6 +169,10 @@ def load(path: Optional[str] = None):
     L.mf_place.argtypes = [vp, vp, C.c_uint32, C.c_int, vp, vp, vp, vp, vp, C.POINTER(FilterStats)]
     L.mf_filter_fastq_files_placed.argtypes = [vp, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_uint32, C.c_int,
                                                C.POINTER(C.c_int), C.c_int, vp, vp, vp, u64p, u64p]
+    L.mf_pileup.argtypes = [vp, vp, C.c_uint32, C.c_int, C.c_uint32, vp, vp, vp, vp, vp, C.POINTER(FilterStats)]
+    L.mf_filter_fastq_files_pileup.argtypes = [vp, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_uint32, C.c_int,
+                                               C.POINTER(C.c_int), C.c_int, C.c_uint32, vp, vp, vp, vp, u64p, u64p]
+    L.mf_kmerset_bait_letters.argtypes = [vp, vp, C.c_size_t, C.POINTER(C.c_size_t)]
     if L.mf_abi_version() != 5:
         raise MitoFilterError("libmitofilter_hip ABI version mismatch")
     _lib = L
@@ -281,6 +292,16 @@ class KmerSet:
         out = np.zeros(max(need.value, 1), dtype=np.uint64)
         _chk(L.mf_kmerset_record_starts(self._h, out.ctypes.data, out.size, None))
         return out
+
+    @property
+    def bait_letters(self) -> np.ndarray:
+        """u8[positions]: the bait's letter at every position of a nucleotide set, one of A C G T, N for an invalid one."""
+        L = load()
+        need = C.c_size_t()
+        L.mf_kmerset_bait_letters(self._h, None, 0, C.byref(need))
+        out = np.zeros(max(need.value, 1), dtype=np.uint8)
+        _chk(L.mf_kmerset_bait_letters(self._h, out.ctypes.data, out.size, None))
+        return out[:need.value]
 
     def export_table(self, device: int = 0) -> np.ndarray:
         i = self.info
@@ -436,6 +457,68 @@ def place_reads(ks: KmerSet, reads: Reads, threshold: int = 1, mode: int = MODE_
     return bits[:(n + 31) // 32], place[:n], base_depth[:int(starts[-1])], records[:len(starts) - 1], unplaced
 
 
+def pileup_reads(ks: KmerSet, reads: Reads, threshold: int = 1, mode: int = MODE_SCREENED, min_depth: int = 1):
+    """One filter pass, then the placed reads' bases piled on the bait (include/mitofilter.h: mf_pileup).  -> (bits u32[ceil(n/32)],
+    pileup PILEUP[positions]: bases a, c, g, t in the bait's forward letters, consensus u8[positions]: the called letter in upper case,
+    N where the most is tied, the bait's letter in lower case below min_depth, records PILEUP_RECORD[R], unplaced u64[2] as place_reads)."""
+    n = reads.info.n_reads
+    starts = ks.record_starts
+    P, R = int(starts[-1]), len(starts) - 1
+    bits = np.zeros(max((n + 31) // 32, 1), dtype=np.uint32)
+    pileup = np.zeros(max(P, 1), dtype=PILEUP)
+    consensus = np.zeros(max(P, 1), dtype=np.uint8)
+    records = np.zeros(max(R, 1), dtype=PILEUP_RECORD)
+    unplaced = np.zeros(2, dtype=np.uint64)
+    _chk(load().mf_pileup(ks._h, reads._h, threshold, mode, min_depth, bits.ctypes.data, pileup.ctypes.data, consensus.ctypes.data,
+                          records.ctypes.data, unplaced.ctypes.data, None))
+    return bits[:(n + 31) // 32], pileup[:P], consensus[:P], records[:R], unplaced
+
+
+def consensus_fasta(names, starts, consensus, width: int = 60) -> str:
+    """FASTA text of a consensus (u8[positions] or bytes) under the records' names: lines of `width` letters; an empty record gives a
+    header and no sequence line.  Needs no device."""
+    if width < 1:
+        raise ValueError("width is at least 1")
+    if len(starts) != len(names) + 1:
+        raise ValueError("starts has one more entry than names")
+    text = bytes(bytearray(np.asarray(consensus, dtype=np.uint8))) if not isinstance(consensus, (bytes, bytearray)) else bytes(consensus)
+    if len(text) < int(starts[-1]):
+        raise ValueError("the consensus is shorter than the records")
+    out = []
+    for j, name in enumerate(names):
+        out.append(">%s\n" % name)
+        seq = text[int(starts[j]):int(starts[j + 1])].decode("ascii")
+        out.extend(seq[i:i + width] + "\n" for i in range(0, len(seq), width))
+    return "".join(out)
+
+
+def pileup_variants(starts, letters, pileup, consensus) -> np.ndarray:
+    """The variant positions of a pile-up: called positions (an upper-case A, C, G or T in `consensus`) whose bait letter (`letters`, as
+    KmerSet.bait_letters) is valid and differs from the call.  -> VARIANT[n]: record, pos (0-based inside the record), ref, alt,
+    depth = a + c + g + t, alt_count = the bases of the called letter.  Needs no device."""
+    starts = np.asarray(starts, dtype=np.uint64)
+    P = int(starts[-1])
+    letters = np.frombuffer(bytes(letters), dtype=np.uint8)[:P] if isinstance(letters, (bytes, bytearray)) else np.asarray(letters, dtype=np.uint8)[:P]
+    cons = np.frombuffer(bytes(consensus), dtype=np.uint8)[:P] if isinstance(consensus, (bytes, bytearray)) else np.asarray(consensus, dtype=np.uint8)[:P]
+    pileup = np.asarray(pileup)[:P]
+    if not (len(letters) == len(cons) == len(pileup) == P):
+        raise ValueError("letters, pileup and consensus hold one entry per position")
+    counts = np.stack([pileup[f].astype(np.uint64) for f in ("a", "c", "g", "t")], axis=1) if P else np.zeros((0, 4), np.uint64)
+    code = np.full(256, 4, dtype=np.int64)
+    code[list(b"ACGT")] = range(4)
+    call, ref = code[cons], code[letters]
+    at = np.nonzero((call < 4) & (ref < 4) & (call != ref))[0]
+    out = np.zeros(at.size, dtype=VARIANT)
+    rec = np.searchsorted(starts, at, side="right") - 1          # (empty records share a start: the last record that starts at or before)
+    out["record"] = rec
+    out["pos"] = at - starts[rec].astype(np.int64) if at.size else at
+    out["ref"] = letters[at].view("S1")
+    out["alt"] = cons[at].view("S1")
+    out["depth"] = counts[at].sum(axis=1)
+    out["alt_count"] = counts[at, call[at]]
+    return out
+
+
 def pair_inserts(place1: np.ndarray, place2: np.ndarray) -> np.ndarray:
     """Insert size of every pair from the placements of its mates (PLACE arrays of equal length): int64, -1 where there is none.  A
     pair has one when both mates are placed on the same record on opposite strands: `end` of the reverse mate - `start` of the
@@ -557,6 +640,28 @@ def filter_fastq_files_placed(ks: KmerSet, fq1: str, fq2: Optional[str], out1: s
                                              base_depth.ctypes.data, records.ctypes.data, unplaced.ctypes.data, C.byref(kept),
                                              C.byref(total)))
     return kept.value, total.value, base_depth[:int(starts[-1])], records[:len(starts) - 1], unplaced
+
+
+def filter_fastq_files_pileup(ks: KmerSet, fq1: str, fq2: Optional[str], out1: str, out2: Optional[str],
+                              threshold: int = 1, pair_mode: int = PAIR_EITHER, devices: Optional[Sequence[int]] = None,
+                              n_devices: int = 1, min_depth: int = 1):
+    """filter_fastq_files plus the pile-up on the bait of every mate that passes its own threshold (the pair rule decides only what is
+    written).  -> (kept, total, pileup PILEUP[positions], consensus u8[positions], records PILEUP_RECORD[R], unplaced u64[2]: passing
+    mates that are not placed, mates that do not pass)."""
+    if devices is None:
+        devices = list(range(n_devices))
+    arr = (C.c_int * len(devices))(*[int(d) for d in devices])
+    starts = ks.record_starts
+    P, R = int(starts[-1]), len(starts) - 1
+    pileup = np.zeros(max(P, 1), dtype=PILEUP)
+    consensus = np.zeros(max(P, 1), dtype=np.uint8)
+    records = np.zeros(max(R, 1), dtype=PILEUP_RECORD)
+    unplaced = np.zeros(2, dtype=np.uint64)
+    kept, total = C.c_uint64(), C.c_uint64()
+    _chk(load().mf_filter_fastq_files_pileup(ks._h, _enc(fq1), _enc(fq2), _enc(out1), _enc(out2), threshold, pair_mode, arr, len(devices),
+                                             min_depth, pileup.ctypes.data, consensus.ctypes.data, records.ctypes.data,
+                                             unplaced.ctypes.data, C.byref(kept), C.byref(total)))
+    return kept.value, total.value, pileup[:P], consensus[:P], records[:R], unplaced
 
 
 def set_option(name: str, value) -> None:
