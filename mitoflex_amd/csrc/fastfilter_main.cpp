@@ -36,6 +36,7 @@
 // (helper.py:82-86).
 #include "../../include/mitofilter.h"
 #include "mf_coldtrace.h"
+#include "mf_report_text.h"
 
 #include <dlfcn.h>
 #include <limits.h>
@@ -442,66 +443,84 @@ static std::string exe_dir()
     return s == std::string::npos ? "." : p.substr(0, s);
 }
 
-static int bait_main(int argc, char **argv)
-{
+// what the command line asks for (checked: one kind of report at most)
+struct BaitArgs {
     std::string bait, fq1, fq2, out1, out2, pair = "either", libpath, report, group_report, group_sep, depth_report, depth_profile, place_report, base_depth_file, pileup_file, consensus_file,
                 variants_file;
-    unsigned min_depth = 1; bool have_min_depth = false;
-    int group_field = -1; bool have_sep = false;
-    int k = 0, devices = 1, gcode = 5; unsigned thr = 1; bool protein = false;
+    unsigned min_depth = 1, thr = 1;
+    int group_field = -1, k = 0, devices = 1, gcode = 5; bool protein = false;
     std::vector<int> device_list;              // --device-list 2,3: these devices instead of 0 .. N - 1
     std::vector<std::pair<std::string, std::string>> options;      // --option pass=serial: how a filter pass is run (mf_set_option)
+    bool grouped = false, depth = false, placed = false, piled = false;          // which report (grouped: `report` holds --group-report's file)
+};
+
+// what the library's call gave: the arrays the report files are written from
+struct BaitResult {
+    uint64_t kept = 0, total = 0, unplaced[2] = {0, 0};
+    std::vector<std::string> names;          // of the records, or the groups
+    std::vector<uint64_t> starts, counts;
+    std::vector<uint32_t> profile;          // k-mer depth or base depth
+    std::vector<mf_depth_record_t> depth_recs;
+    std::vector<mf_place_record_t> place_recs;
+    std::vector<mf_pileup_t> pile;
+    std::vector<uint8_t> consensus, letters;
+};
+
+// 0, or the exit code of a command line that cannot be run
+static int parse_bait_args(int argc, char **argv, BaitArgs &A)
+{
+    bool have_min_depth = false, have_sep = false;
     for (int a = 2; a < argc; a++) {
         std::string o = argv[a];
         auto need = [&](const char *name) -> std::string {
             if (a + 1 >= argc) { fprintf(stderr, "error: %s requires a value\n", name); exit(1); }
             return argv[++a];
         };
-        if (o == "--bait") bait = need("--bait");
-        else if (o == "--fq1") fq1 = need("--fq1");
-        else if (o == "--fq2") fq2 = need("--fq2");
-        else if (o == "--out1") out1 = need("--out1");
-        else if (o == "--out2") out2 = need("--out2");
-        else if (o == "--pair") pair = need("--pair");
-        else if (o == "--lib") libpath = need("--lib");
-        else if (o == "--report") report = need("--report");
-        else if (o == "--group-report") group_report = need("--group-report");
-        else if (o == "--depth-report") depth_report = need("--depth-report");
-        else if (o == "--depth-profile") depth_profile = need("--depth-profile");
-        else if (o == "--place-report") place_report = need("--place-report");
-        else if (o == "--base-depth") base_depth_file = need("--base-depth");
-        else if (o == "--pileup") pileup_file = need("--pileup");
-        else if (o == "--consensus") consensus_file = need("--consensus");
-        else if (o == "--variants") variants_file = need("--variants");
+        if (o == "--bait") A.bait = need("--bait");
+        else if (o == "--fq1") A.fq1 = need("--fq1");
+        else if (o == "--fq2") A.fq2 = need("--fq2");
+        else if (o == "--out1") A.out1 = need("--out1");
+        else if (o == "--out2") A.out2 = need("--out2");
+        else if (o == "--pair") A.pair = need("--pair");
+        else if (o == "--lib") A.libpath = need("--lib");
+        else if (o == "--report") A.report = need("--report");
+        else if (o == "--group-report") A.group_report = need("--group-report");
+        else if (o == "--depth-report") A.depth_report = need("--depth-report");
+        else if (o == "--depth-profile") A.depth_profile = need("--depth-profile");
+        else if (o == "--place-report") A.place_report = need("--place-report");
+        else if (o == "--base-depth") A.base_depth_file = need("--base-depth");
+        else if (o == "--pileup") A.pileup_file = need("--pileup");
+        else if (o == "--consensus") A.consensus_file = need("--consensus");
+        else if (o == "--variants") A.variants_file = need("--variants");
         else if (o == "--min-depth") {
             const std::string v = need("--min-depth"); char *end = nullptr; const unsigned long x = strtoul(v.c_str(), &end, 10);
             if (v.empty() || *end || v[0] == '-' || x < 1 || x > 0xFFFFFFFFul) { fprintf(stderr, "error: --min-depth wants a depth from 1\n"); return 1; }
-            min_depth = (unsigned)x; have_min_depth = true;
+            A.min_depth = (unsigned)x; have_min_depth = true;
         }
         else if (o == "--group-field") {
             const std::string v = need("--group-field"); char *end = nullptr; const long x = strtol(v.c_str(), &end, 10);
             if (v.empty() || *end || x < 1 || x > INT_MAX) { fprintf(stderr, "error: --group-field wants a field number from 1\n"); return 1; }
-            group_field = (int)x;
+            A.group_field = (int)x;
         }
-        else if (o == "--group-sep") { group_sep = need("--group-sep"); have_sep = true; if (group_sep.empty()) { fprintf(stderr, "error: --group-sep wants a separator\n"); return 1; } }
-        else if (o == "-k" || o == "--kmer") k = atoi(need("-k").c_str());
-        else if (o == "-t" || o == "--threshold") thr = (unsigned)strtoul(need("-t").c_str(), nullptr, 10);
-        else if (o == "--devices") devices = atoi(need("--devices").c_str());
+        else if (o == "--group-sep") { A.group_sep = need("--group-sep"); have_sep = true; if (A.group_sep.empty()) { fprintf(stderr, "error: --group-sep wants a separator\n"); return 1; } }
+        else if (o == "-k" || o == "--kmer") A.k = atoi(need("-k").c_str());
+        else if (o == "-t" || o == "--threshold") A.thr = (unsigned)strtoul(need("-t").c_str(), nullptr, 10);
+        else if (o == "--devices") A.devices = atoi(need("--devices").c_str());
         else if (o == "--device-list") {
             const std::string v = need("--device-list");
-            for (size_t i = 0; i < v.size();) { size_t j = v.find(',', i); if (j == std::string::npos) j = v.size(); if (j > i) device_list.push_back(atoi(v.substr(i, j - i).c_str())); i = j + 1; }
-            if (device_list.empty()) { fprintf(stderr, "error: --device-list wants device numbers separated by commas\n"); return 1; }
+            for (size_t i = 0; i < v.size();) { size_t j = v.find(',', i); if (j == std::string::npos) j = v.size(); if (j > i) A.device_list.push_back(atoi(v.substr(i, j - i).c_str())); i = j + 1; }
+            if (A.device_list.empty()) { fprintf(stderr, "error: --device-list wants device numbers separated by commas\n"); return 1; }
         }
         else if (o == "--option") {
             const std::string v = need("--option"); const size_t eq = v.find('=');
             if (eq == std::string::npos || eq == 0) { fprintf(stderr, "error: --option wants name=value\n"); return 1; }
-            options.emplace_back(v.substr(0, eq), v.substr(eq + 1));
+            A.options.emplace_back(v.substr(0, eq), v.substr(eq + 1));
         }
-        else if (o == "--protein") protein = true;                       // --bait is a protein FASTA (e.g. profile/MT_database/<clade>.fa)
-        else if (o == "--code" || o == "--genetic-code") gcode = atoi(need("--code").c_str());
+        else if (o == "--protein") A.protein = true;                       // --bait is a protein FASTA (e.g. profile/MT_database/<clade>.fa)
+        else if (o == "--code" || o == "--genetic-code") A.gcode = atoi(need("--code").c_str());
         else { fprintf(stderr, "error: unknown option '%s' for fastfilter bait\n", o.c_str()); return 1; }
     }
-    if (bait.empty() || fq1.empty() || out1.empty() || (fq2.empty() != out2.empty()) || (pair != "either" && pair != "both")) {
+    if (A.bait.empty() || A.fq1.empty() || A.out1.empty() || (A.fq2.empty() != A.out2.empty()) || (A.pair != "either" && A.pair != "both")) {
         fputs("usage: fastfilter bait --bait BAIT.fa [-k 31] [-t 1] --fq1 R1.fq [--fq2 R2.fq] --out1 O1.fq [--out2 O2.fq]"
               " [--pair either|both] [--devices N | --device-list D0,D1,..] [--option name=value ..]\n"
               "       [--report FILE | --group-report FILE [--group-field N] [--group-sep C] | --depth-report FILE [--depth-profile FILE]\n"
@@ -509,283 +528,174 @@ static int bait_main(int argc, char **argv)
               "       fastfilter bait --protein --bait PROTEINS.fa [--code 5] [-k 9] ...   (six-frame peptide k-mers)\n", stderr);
         return 1;
     }
-    if (protein && !report.empty()) { fprintf(stderr, "error: --report needs a nucleotide bait (it cannot be combined with --protein)\n"); return 1; }
-    if (!report.empty() && !group_report.empty()) { fprintf(stderr, "error: --report and --group-report cannot be combined\n"); return 1; }
-    const bool depth = !depth_report.empty() || !depth_profile.empty();
-    if (depth && (!report.empty() || !group_report.empty())) { fprintf(stderr, "error: --depth-report / --depth-profile cannot be combined with --report or --group-report\n"); return 1; }
-    const bool placed = !place_report.empty() || !base_depth_file.empty();
-    if (placed && (depth || protein || !report.empty() || !group_report.empty())) {
+    if (A.protein && !A.report.empty()) { fprintf(stderr, "error: --report needs a nucleotide bait (it cannot be combined with --protein)\n"); return 1; }
+    if (!A.report.empty() && !A.group_report.empty()) { fprintf(stderr, "error: --report and --group-report cannot be combined\n"); return 1; }
+    const bool depth = A.depth = !A.depth_report.empty() || !A.depth_profile.empty();
+    if (depth && (!A.report.empty() || !A.group_report.empty())) { fprintf(stderr, "error: --depth-report / --depth-profile cannot be combined with --report or --group-report\n"); return 1; }
+    const bool placed = A.placed = !A.place_report.empty() || !A.base_depth_file.empty();
+    if (placed && (depth || A.protein || !A.report.empty() || !A.group_report.empty())) {
         fprintf(stderr, "error: --place-report / --base-depth need a nucleotide bait and cannot be combined with --report, --group-report, --depth-report, --depth-profile or --protein\n");
         return 1;
     }
-    const bool piled = !pileup_file.empty() || !consensus_file.empty() || !variants_file.empty();
-    if (piled && (placed || depth || protein || !report.empty() || !group_report.empty())) {
+    const bool piled = A.piled = !A.pileup_file.empty() || !A.consensus_file.empty() || !A.variants_file.empty();
+    if (piled && (placed || depth || A.protein || !A.report.empty() || !A.group_report.empty())) {
         fprintf(stderr, "error: --pileup / --consensus / --variants need a nucleotide bait and cannot be combined with --report, --group-report, --depth-report, --depth-profile, --place-report, --base-depth or --protein\n");
         return 1;
     }
     if (have_min_depth && !piled) { fprintf(stderr, "error: --min-depth needs --pileup, --consensus or --variants\n"); return 1; }
-    if (group_report.empty() && (group_field >= 0 || have_sep)) { fprintf(stderr, "error: --group-field and --group-sep need --group-report\n"); return 1; }
-    if (!have_sep) group_sep = "_";
-    if (k == 0) k = protein ? 9 : 31;
-    if (libpath.empty()) { const char *e = getenv("MITOFILTER_LIB"); if (e && *e) libpath = e; }          // (as the Python wrapper and filter_v2 do)
-    if (libpath.empty()) libpath = exe_dir() + "/../libmitofilter_hip.so";
-    mf::cold_mark("fastfilter bait: arguments read");
-    void *h = dlopen(libpath.c_str(), RTLD_NOW | RTLD_LOCAL);
-    if (!h) { fprintf(stderr, "error: cannot load %s: %s (the bait filter has no CPU fallback)\n", libpath.c_str(), dlerror()); return 2; }
-#define SYM(name) auto p_##name = (decltype(&name))dlsym(h, #name); if (!p_##name) { fprintf(stderr, "error: %s lacks symbol %s\n", libpath.c_str(), #name); return 2; }
+    if (A.group_report.empty() && (A.group_field >= 0 || have_sep)) { fprintf(stderr, "error: --group-field and --group-sep need --group-report\n"); return 1; }
+    if (!have_sep) A.group_sep = "_";
+    if (A.k == 0) A.k = A.protein ? 9 : 31;
+    if (A.libpath.empty()) { const char *e = getenv("MITOFILTER_LIB"); if (e && *e) A.libpath = e; }          // (as the Python wrapper and filter_v2 do)
+    if (A.libpath.empty()) A.libpath = exe_dir() + "/../libmitofilter_hip.so";
+    A.grouped = !A.group_report.empty();
+    if (A.grouped) A.report = A.group_report;
+    return 0;
+}
+
+// the names of a set's records or groups (count and name_of: the library's pair of calls for either)
+static int fetch_names(const mf_kmerset *ks, decltype(&mf_kmerset_record_count) count, decltype(&mf_kmerset_record_name) name_of, std::vector<std::string> &names)
+{
+    uint64_t n = 0;
+    int rc = count(ks, &n);
+    for (uint64_t i = 0; rc == MF_OK && i < n; i++) {
+        size_t need = 0;
+        (void)name_of(ks, i, nullptr, 0, &need);
+        std::vector<char> buf(need ? need : 1);
+        rc = name_of(ks, i, buf.data(), buf.size(), nullptr);
+        names.emplace_back(buf.data());
+    }
+    return rc;
+}
+
+static int fetch_starts(const mf_kmerset *ks, decltype(&mf_kmerset_record_starts) record_starts, size_t n_rec, std::vector<uint64_t> &starts)
+{
+    starts.assign(n_rec + 1, 0);
+    return record_starts(ks, starts.data(), starts.size(), nullptr);
+}
+
+// what mf_filter_fastq_files does with a device count: 0 .. N - 1, at most the devices there are
+static void default_devices(decltype(&mf_device_count) device_count, int devices, std::vector<int> &list)
+{
+    if (!list.empty()) return;
+    const int have = device_count();
+    for (int i = 0; i < std::min(std::max(devices, 1), std::max(have, 1)); i++) list.push_back(i);
+}
+
+// Loads the library, builds the bait set and runs the file-level call of the report that is asked for.  0 with *ks and *free_set for
+// the caller to end with, or the exit code (the set is freed).
+static int bait_run(const BaitArgs &A, BaitResult &R, mf_kmerset **ks_out, decltype(&mf_kmerset_free) *free_set)
+{
+    void *h = dlopen(A.libpath.c_str(), RTLD_NOW | RTLD_LOCAL);
+    if (!h) { fprintf(stderr, "error: cannot load %s: %s (the bait filter has no CPU fallback)\n", A.libpath.c_str(), dlerror()); return 2; }
+    mf_kmerset *ks = nullptr;
+    // a symbol of the library, looked up where it is needed; without it the set (if it is built) is freed and the exit code is 2
+#define SYM(name) auto p_##name = (decltype(&name))dlsym(h, #name); if (!p_##name) { fprintf(stderr, "error: %s lacks symbol %s\n", A.libpath.c_str(), #name); if (ks) (*free_set)(ks); return 2; }
     SYM(mf_abi_version) SYM(mf_last_error) SYM(mf_kmerset_build_from_fasta) SYM(mf_kmerset_build_protein_from_fasta)
     SYM(mf_filter_fastq_files) SYM(mf_filter_fastq_files_on) SYM(mf_kmerset_free) SYM(mf_set_option)
-#undef SYM
+    *free_set = p_mf_kmerset_free;
     if (p_mf_abi_version() != MF_ABI_VERSION) { fprintf(stderr, "error: ABI version mismatch\n"); return 2; }
     (void)p_mf_set_option("expect_files", "1"); (void)p_mf_set_option("short_lived", "1");          // (the file-level call's set-up starts beside the bait set's build)
-    for (auto &kv : options) if (p_mf_set_option(kv.first.c_str(), kv.second.c_str()) != MF_OK) { fprintf(stderr, "error: %s\n", p_mf_last_error()); return 1; }
+    for (auto &kv : A.options) if (p_mf_set_option(kv.first.c_str(), kv.second.c_str()) != MF_OK) { fprintf(stderr, "error: %s\n", p_mf_last_error()); return 1; }
     mf::cold_mark("library loaded");
-    mf_kmerset *ks = nullptr;
+    std::vector<int> device_list = A.device_list;
     const int dev0 = device_list.empty() ? 0 : device_list[0];
-    const int brc = protein ? p_mf_kmerset_build_protein_from_fasta(bait.c_str(), k, gcode, dev0, &ks)
-                            : p_mf_kmerset_build_from_fasta(bait.c_str(), k, dev0, &ks);
+    const int brc = A.protein ? p_mf_kmerset_build_protein_from_fasta(A.bait.c_str(), A.k, A.gcode, dev0, &ks)
+                              : p_mf_kmerset_build_from_fasta(A.bait.c_str(), A.k, dev0, &ks);
     if (brc != MF_OK) { fprintf(stderr, "error: %s\n", p_mf_last_error()); return 3; }
     mf::cold_mark("bait set built");
-    uint64_t kept = 0, total = 0;
     setenv("MF_DEVPOOL_GB", "4096", 0);          // (a process that ends with the call gives no device memory back in between: the runtime frees it all at once)
-    std::vector<uint64_t> record_reads;
-    std::vector<std::string> record_names;
+    // the files and the pair rule of every call; `files`: a call on the device list, with its own outputs in the middle
+    const char *fq1 = A.fq1.c_str(), *fq2 = A.fq2.empty() ? nullptr : A.fq2.c_str(), *out1 = A.out1.c_str(), *out2 = A.out2.empty() ? nullptr : A.out2.c_str();
+    const int pair_mode = A.pair == "both" ? MF_PAIR_BOTH : MF_PAIR_EITHER;
+    auto files = [&](auto call, auto... outs) { return call(ks, fq1, fq2, out1, out2, A.thr, pair_mode, device_list.data(), (int)device_list.size(), outs..., &R.kept, &R.total); };
     int rc;
-    const bool grouped = !group_report.empty();
-    if (grouped) report = group_report;
-    std::vector<uint64_t> starts;
-    std::vector<uint32_t> profile;
-    std::vector<mf_depth_record_t> depth_recs;
-    std::vector<mf_place_record_t> place_recs;
-    uint64_t unplaced[2] = {0, 0};
-    std::vector<mf_pileup_t> pile;
-    std::vector<uint8_t> consensus, letters;
-    if (piled) {
-#define SYM(name) auto p_##name = (decltype(&name))dlsym(h, #name); if (!p_##name) { fprintf(stderr, "error: %s lacks symbol %s\n", libpath.c_str(), #name); p_mf_kmerset_free(ks); return 2; }
-        SYM(mf_device_count) SYM(mf_kmerset_record_count) SYM(mf_kmerset_record_name) SYM(mf_kmerset_record_starts) SYM(mf_kmerset_bait_letters)
-        SYM(mf_filter_fastq_files_pileup)
-#undef SYM
-        uint64_t n_rec = 0;
-        rc = p_mf_kmerset_record_count(ks, &n_rec);
-        for (uint64_t i = 0; rc == MF_OK && i < n_rec; i++) {
-            size_t need = 0;
-            (void)p_mf_kmerset_record_name(ks, i, nullptr, 0, &need);
-            std::vector<char> buf(need ? need : 1);
-            rc = p_mf_kmerset_record_name(ks, i, buf.data(), buf.size(), nullptr);
-            record_names.emplace_back(buf.data());
+    if (A.piled || A.placed || A.depth) {
+        SYM(mf_device_count) SYM(mf_kmerset_record_starts)
+        if (A.depth) {          // (the identity grouping: the records' own names, protein sets included)
+            SYM(mf_kmerset_group_count) SYM(mf_kmerset_group_name)
+            rc = fetch_names(ks, p_mf_kmerset_group_count, p_mf_kmerset_group_name, R.names);
+        } else {
+            SYM(mf_kmerset_record_count) SYM(mf_kmerset_record_name)
+            rc = fetch_names(ks, p_mf_kmerset_record_count, p_mf_kmerset_record_name, R.names);
         }
-        starts.assign((size_t)n_rec + 1, 0);
-        if (rc == MF_OK) rc = p_mf_kmerset_record_starts(ks, starts.data(), starts.size(), nullptr);
-        if (rc == MF_OK && device_list.empty()) {
-            const int have = p_mf_device_count();
-            for (int i = 0; i < std::min(std::max(devices, 1), std::max(have, 1)); i++) device_list.push_back(i);
+        if (rc == MF_OK) rc = fetch_starts(ks, p_mf_kmerset_record_starts, R.names.size(), R.starts);
+        if (rc == MF_OK) default_devices(p_mf_device_count, A.devices, device_list);
+        const size_t positions = rc == MF_OK ? (size_t)std::max<uint64_t>(R.starts.back(), 1) : 1, n_rec = std::max<size_t>(R.names.size(), 1);
+        if (A.piled) {
+            SYM(mf_kmerset_bait_letters) SYM(mf_filter_fastq_files_pileup)
+            R.pile.assign(positions, mf_pileup_t{}); R.consensus.assign(positions, 0); R.letters.assign(positions, 0);
+            if (rc == MF_OK) rc = p_mf_kmerset_bait_letters(ks, R.letters.data(), R.letters.size(), nullptr);
+            if (rc == MF_OK) rc = files(p_mf_filter_fastq_files_pileup, A.min_depth, R.pile.data(), R.consensus.data(), (mf_pileup_record_t *)nullptr, R.unplaced);
+        } else if (A.placed) {
+            SYM(mf_filter_fastq_files_placed)
+            R.profile.assign(positions, 0);          // (the base depth: the report's max column needs it too)
+            R.place_recs.assign(n_rec, mf_place_record_t{});
+            if (rc == MF_OK) rc = files(p_mf_filter_fastq_files_placed, R.profile.data(), R.place_recs.data(), R.unplaced);
+        } else {
+            SYM(mf_filter_fastq_files_depth)
+            R.profile.assign(positions, 0);
+            R.depth_recs.assign(n_rec, mf_depth_record_t{});
+            if (rc == MF_OK) rc = files(p_mf_filter_fastq_files_depth, R.profile.data(), R.depth_recs.data());
         }
-        pile.assign(std::max<uint64_t>(starts.back(), 1), mf_pileup_t{});
-        consensus.assign(std::max<uint64_t>(starts.back(), 1), 0);
-        letters.assign(std::max<uint64_t>(starts.back(), 1), 0);
-        if (rc == MF_OK) rc = p_mf_kmerset_bait_letters(ks, letters.data(), letters.size(), nullptr);
-        if (rc == MF_OK)
-            rc = p_mf_filter_fastq_files_pileup(ks, fq1.c_str(), fq2.empty() ? nullptr : fq2.c_str(), out1.c_str(), out2.empty() ? nullptr : out2.c_str(),
-                                                thr, pair == "both" ? MF_PAIR_BOTH : MF_PAIR_EITHER, device_list.data(), (int)device_list.size(),
-                                                min_depth, pile.data(), consensus.data(), nullptr, unplaced, &kept, &total);
-    } else if (placed) {
-#define SYM(name) auto p_##name = (decltype(&name))dlsym(h, #name); if (!p_##name) { fprintf(stderr, "error: %s lacks symbol %s\n", libpath.c_str(), #name); p_mf_kmerset_free(ks); return 2; }
-        SYM(mf_device_count) SYM(mf_kmerset_record_count) SYM(mf_kmerset_record_name) SYM(mf_kmerset_record_starts) SYM(mf_filter_fastq_files_placed)
-#undef SYM
-        uint64_t n_rec = 0;
-        rc = p_mf_kmerset_record_count(ks, &n_rec);
-        for (uint64_t i = 0; rc == MF_OK && i < n_rec; i++) {
-            size_t need = 0;
-            (void)p_mf_kmerset_record_name(ks, i, nullptr, 0, &need);
-            std::vector<char> buf(need ? need : 1);
-            rc = p_mf_kmerset_record_name(ks, i, buf.data(), buf.size(), nullptr);
-            record_names.emplace_back(buf.data());
-        }
-        starts.assign((size_t)n_rec + 1, 0);
-        if (rc == MF_OK) rc = p_mf_kmerset_record_starts(ks, starts.data(), starts.size(), nullptr);
-        if (rc == MF_OK && device_list.empty()) {
-            const int have = p_mf_device_count();
-            for (int i = 0; i < std::min(std::max(devices, 1), std::max(have, 1)); i++) device_list.push_back(i);
-        }
-        profile.assign(std::max<uint64_t>(starts.back(), 1), 0);          // (the base depth: the report's max column needs it too)
-        place_recs.assign(std::max<uint64_t>(n_rec, 1), mf_place_record_t{});
-        if (rc == MF_OK)
-            rc = p_mf_filter_fastq_files_placed(ks, fq1.c_str(), fq2.empty() ? nullptr : fq2.c_str(), out1.c_str(), out2.empty() ? nullptr : out2.c_str(),
-                                                thr, pair == "both" ? MF_PAIR_BOTH : MF_PAIR_EITHER, device_list.data(), (int)device_list.size(),
-                                                profile.data(), place_recs.data(), unplaced, &kept, &total);
-    } else if (depth) {
-#define SYM(name) auto p_##name = (decltype(&name))dlsym(h, #name); if (!p_##name) { fprintf(stderr, "error: %s lacks symbol %s\n", libpath.c_str(), #name); p_mf_kmerset_free(ks); return 2; }
-        SYM(mf_device_count) SYM(mf_kmerset_group_count) SYM(mf_kmerset_group_name) SYM(mf_kmerset_record_starts) SYM(mf_filter_fastq_files_depth)
-#undef SYM
-        uint64_t n_rec = 0;
-        rc = p_mf_kmerset_group_count(ks, &n_rec);          // (the identity grouping: the records' own names, protein sets included)
-        for (uint64_t i = 0; rc == MF_OK && i < n_rec; i++) {
-            size_t need = 0;
-            (void)p_mf_kmerset_group_name(ks, i, nullptr, 0, &need);
-            std::vector<char> buf(need ? need : 1);
-            rc = p_mf_kmerset_group_name(ks, i, buf.data(), buf.size(), nullptr);
-            record_names.emplace_back(buf.data());
-        }
-        starts.assign((size_t)n_rec + 1, 0);
-        if (rc == MF_OK) rc = p_mf_kmerset_record_starts(ks, starts.data(), starts.size(), nullptr);
-        if (rc == MF_OK && device_list.empty()) {
-            const int have = p_mf_device_count();
-            for (int i = 0; i < std::min(std::max(devices, 1), std::max(have, 1)); i++) device_list.push_back(i);
-        }
-        profile.assign(std::max<uint64_t>(starts.back(), 1), 0);
-        depth_recs.assign(std::max<uint64_t>(n_rec, 1), mf_depth_record_t{});
-        if (rc == MF_OK)
-            rc = p_mf_filter_fastq_files_depth(ks, fq1.c_str(), fq2.empty() ? nullptr : fq2.c_str(), out1.c_str(), out2.empty() ? nullptr : out2.c_str(),
-                                               thr, pair == "both" ? MF_PAIR_BOTH : MF_PAIR_EITHER, device_list.data(), (int)device_list.size(),
-                                               profile.data(), depth_recs.data(), &kept, &total);
-    } else if (!report.empty()) {
-#define SYM(name) auto p_##name = (decltype(&name))dlsym(h, #name); if (!p_##name) { fprintf(stderr, "error: %s lacks symbol %s\n", libpath.c_str(), #name); p_mf_kmerset_free(ks); return 2; }
+    } else if (!A.report.empty()) {
         SYM(mf_device_count) SYM(mf_kmerset_record_count) SYM(mf_kmerset_record_name) SYM(mf_filter_fastq_files_by_record)
         SYM(mf_kmerset_group_records) SYM(mf_kmerset_group_count) SYM(mf_kmerset_group_name) SYM(mf_filter_fastq_files_by_group)
+        rc = A.grouped ? p_mf_kmerset_group_records(ks, A.group_field > 0 ? A.group_sep.c_str() : nullptr, A.group_field > 0 ? A.group_field : 0) : MF_OK;
+        if (rc == MF_OK) rc = A.grouped ? fetch_names(ks, p_mf_kmerset_group_count, p_mf_kmerset_group_name, R.names)
+                                        : fetch_names(ks, p_mf_kmerset_record_count, p_mf_kmerset_record_name, R.names);
+        if (rc == MF_OK) default_devices(p_mf_device_count, A.devices, device_list);
+        R.counts.assign(R.names.size() + 2, 0);
+        if (rc == MF_OK) rc = files(A.grouped ? p_mf_filter_fastq_files_by_group : p_mf_filter_fastq_files_by_record, R.counts.data());
+    } else rc = device_list.empty() ? p_mf_filter_fastq_files(ks, fq1, fq2, out1, out2, A.thr, pair_mode, A.devices, &R.kept, &R.total)
+                                    : files(p_mf_filter_fastq_files_on);
 #undef SYM
-        uint64_t n_rec = 0;
-        rc = grouped ? p_mf_kmerset_group_records(ks, group_field > 0 ? group_sep.c_str() : nullptr, group_field > 0 ? group_field : 0) : MF_OK;
-        if (rc == MF_OK) rc = grouped ? p_mf_kmerset_group_count(ks, &n_rec) : p_mf_kmerset_record_count(ks, &n_rec);
-        auto name_of = grouped ? p_mf_kmerset_group_name : p_mf_kmerset_record_name;
-        for (uint64_t i = 0; rc == MF_OK && i < n_rec; i++) {
-            size_t need = 0;
-            (void)name_of(ks, i, nullptr, 0, &need);
-            std::vector<char> buf(need ? need : 1);
-            rc = name_of(ks, i, buf.data(), buf.size(), nullptr);
-            record_names.emplace_back(buf.data());
-        }
-        if (rc == MF_OK && device_list.empty()) {          // (what mf_filter_fastq_files does with a device count: 0 .. N - 1, at most the devices there are)
-            const int have = p_mf_device_count();
-            for (int i = 0; i < std::min(std::max(devices, 1), std::max(have, 1)); i++) device_list.push_back(i);
-        }
-        record_reads.assign((size_t)n_rec + 2, 0);
-        auto by = grouped ? p_mf_filter_fastq_files_by_group : p_mf_filter_fastq_files_by_record;
-        if (rc == MF_OK)
-            rc = by(ks, fq1.c_str(), fq2.empty() ? nullptr : fq2.c_str(), out1.c_str(),
-                                                   out2.empty() ? nullptr : out2.c_str(), thr, pair == "both" ? MF_PAIR_BOTH : MF_PAIR_EITHER,
-                                                   device_list.data(), (int)device_list.size(), record_reads.data(), &kept, &total);
-    } else rc = device_list.empty()
-        ? p_mf_filter_fastq_files(ks, fq1.c_str(), fq2.empty() ? nullptr : fq2.c_str(), out1.c_str(),
-                                  out2.empty() ? nullptr : out2.c_str(), thr, pair == "both" ? MF_PAIR_BOTH : MF_PAIR_EITHER,
-                                  devices, &kept, &total)
-        : p_mf_filter_fastq_files_on(ks, fq1.c_str(), fq2.empty() ? nullptr : fq2.c_str(), out1.c_str(),
-                                     out2.empty() ? nullptr : out2.c_str(), thr, pair == "both" ? MF_PAIR_BOTH : MF_PAIR_EITHER,
-                                     device_list.data(), (int)device_list.size(), &kept, &total);
     if (rc != MF_OK) { fprintf(stderr, "error: %s\n", p_mf_last_error()); p_mf_kmerset_free(ks); return 3; }
+    *ks_out = ks;
+    return 0;
+}
+
+// one report file: open, write (mf_report_text.h), close; false with the message when any of that fails
+template <class Write> static bool write_file(const std::string &path, const char *what, Write write)
+{
+    if (path.empty()) return true;
+    FILE *f = fopen(path.c_str(), "w");
+    bool ok = write(f);
+    if (f) ok = fclose(f) == 0 && ok;
+    if (!ok) fprintf(stderr, "error: cannot write the %s %s\n", what, path.c_str());
+    return ok;
+}
+
+static bool write_reports(const BaitArgs &A, const BaitResult &R)
+{
+    using namespace mf_text;
+    return write_file(A.report, "report", [&](FILE *f) { return write_reads(f, A.grouped, R.names, R.counts.data()); })
+        && write_file(A.depth_report, "depth report", [&](FILE *f) { return write_depth_report(f, R.names, R.starts, R.depth_recs.data()); })
+        && write_file(A.depth_profile, "depth profile", [&](FILE *f) { return write_depth_profile(f, R.names, R.starts, R.profile.data()); })
+        && write_file(A.place_report, "placement report", [&](FILE *f) { return write_place_report(f, R.names, R.starts, R.place_recs.data(), R.profile.data(), R.unplaced[0]); })
+        && write_file(A.base_depth_file, "base depth", [&](FILE *f) { return write_base_depth(f, R.names, R.starts, R.profile.data()); })
+        && write_file(A.pileup_file, "pile-up", [&](FILE *f) { return write_pileup(f, R.names, R.starts, R.letters.data(), R.pile.data()); })
+        && write_file(A.consensus_file, "consensus", [&](FILE *f) { return write_consensus(f, R.names, R.starts, R.consensus.data()); })
+        && write_file(A.variants_file, "variants", [&](FILE *f) { return write_variants(f, R.names, R.starts, R.letters.data(), R.pile.data(), R.consensus.data()); });
+}
+
+static int bait_main(int argc, char **argv)
+{
+    BaitArgs A;
+    if (const int rc = parse_bait_args(argc, argv, A)) return rc;
+    mf::cold_mark("fastfilter bait: arguments read");
+    BaitResult R;
+    mf_kmerset *ks = nullptr; decltype(&mf_kmerset_free) free_set = nullptr;
+    if (const int rc = bait_run(A, R, &ks, &free_set)) return rc;
     mf::cold_mark("files filtered");
-    if (!report.empty()) {
-        FILE *f = fopen(report.c_str(), "w");
-        bool ok = f != nullptr;
-        if (ok) {
-            const size_t n_rec = record_names.size();
-            fputs(grouped ? "group\tname\treads\n" : "record\tname\treads\n", f);
-            for (size_t i = 0; i < n_rec; i++) fprintf(f, "%zu\t%s\t%llu\n", i, record_names[i].c_str(), (unsigned long long)record_reads[i]);
-            fprintf(f, "-\t*ambiguous*\t%llu\n-\t*unassigned*\t%llu\n", (unsigned long long)record_reads[n_rec], (unsigned long long)record_reads[n_rec + 1]);
-            ok = !ferror(f);
-            ok = fclose(f) == 0 && ok;
-        }
-        if (!ok) { fprintf(stderr, "error: cannot write the report %s\n", report.c_str()); p_mf_kmerset_free(ks); return 3; }
-    }
-    if (!depth_report.empty()) {
-        FILE *f = fopen(depth_report.c_str(), "w");
-        bool ok = f != nullptr;
-        if (ok) {
-            fputs("record\tname\tlength\twindows\tcovered\tmean\tmax\n", f);
-            for (size_t i = 0; i < record_names.size(); i++) {
-                const mf_depth_record_t &d = depth_recs[i];
-                fprintf(f, "%zu\t%s\t%llu\t%llu\t%llu\t%.3f\t%llu\n", i, record_names[i].c_str(), (unsigned long long)(starts[i + 1] - starts[i]),
-                        (unsigned long long)d.windows, (unsigned long long)d.covered, d.windows ? (double)d.depth_sum / (double)d.windows : 0.0,
-                        (unsigned long long)d.depth_max);
-            }
-            ok = !ferror(f);
-            ok = fclose(f) == 0 && ok;
-        }
-        if (!ok) { fprintf(stderr, "error: cannot write the depth report %s\n", depth_report.c_str()); p_mf_kmerset_free(ks); return 3; }
-    }
-    if (!depth_profile.empty()) {
-        FILE *f = fopen(depth_profile.c_str(), "w");
-        bool ok = f != nullptr;
-        for (size_t i = 0; ok && i < record_names.size(); i++)
-            for (uint64_t p = starts[i]; p < starts[i + 1]; p++)
-                if (profile[p] != MF_DEPTH_NONE) fprintf(f, "%s\t%llu\t%u\n", record_names[i].c_str(), (unsigned long long)(p - starts[i] + 1), profile[p]);
-        if (ok) { ok = !ferror(f); ok = fclose(f) == 0 && ok; }
-        if (!ok) { fprintf(stderr, "error: cannot write the depth profile %s\n", depth_profile.c_str()); p_mf_kmerset_free(ks); return 3; }
-    }
-    if (!place_report.empty()) {
-        FILE *f = fopen(place_report.c_str(), "w");
-        bool ok = f != nullptr;
-        if (ok) {
-            fputs("record\tname\tlength\tforward\treverse\tover_begin\tover_end\tcovered\tmean\tmax\n", f);
-            for (size_t i = 0; i < record_names.size(); i++) {
-                const mf_place_record_t &d = place_recs[i];
-                const uint64_t len = starts[i + 1] - starts[i];
-                uint32_t mx = 0;
-                for (uint64_t p = starts[i]; p < starts[i + 1]; p++) mx = std::max(mx, profile[p]);
-                fprintf(f, "%zu\t%s\t%llu\t%llu\t%llu\t%llu\t%llu\t%llu\t%.3f\t%u\n", i, record_names[i].c_str(), (unsigned long long)len,
-                        (unsigned long long)d.forward, (unsigned long long)d.reverse, (unsigned long long)d.over_begin, (unsigned long long)d.over_end,
-                        (unsigned long long)d.covered, len ? (double)d.base_sum / (double)len : 0.0, mx);
-            }
-            fprintf(f, "-\t*unplaced*\t%llu\n", (unsigned long long)unplaced[0]);
-            ok = !ferror(f);
-            ok = fclose(f) == 0 && ok;
-        }
-        if (!ok) { fprintf(stderr, "error: cannot write the placement report %s\n", place_report.c_str()); p_mf_kmerset_free(ks); return 3; }
-    }
-    if (!base_depth_file.empty()) {
-        FILE *f = fopen(base_depth_file.c_str(), "w");
-        bool ok = f != nullptr;
-        for (size_t i = 0; ok && i < record_names.size(); i++)
-            for (uint64_t p = starts[i]; p < starts[i + 1]; p++)
-                fprintf(f, "%s\t%llu\t%u\n", record_names[i].c_str(), (unsigned long long)(p - starts[i] + 1), profile[p]);
-        if (ok) { ok = !ferror(f); ok = fclose(f) == 0 && ok; }
-        if (!ok) { fprintf(stderr, "error: cannot write the base depth %s\n", base_depth_file.c_str()); p_mf_kmerset_free(ks); return 3; }
-    }
-    if (!pileup_file.empty()) {
-        FILE *f = fopen(pileup_file.c_str(), "w");
-        bool ok = f != nullptr;
-        for (size_t i = 0; ok && i < record_names.size(); i++)
-            for (uint64_t p = starts[i]; p < starts[i + 1]; p++) {
-                const mf_pileup_t &c = pile[p];
-                fprintf(f, "%s\t%llu\t%c\t%llu\t%u\t%u\t%u\t%u\n", record_names[i].c_str(), (unsigned long long)(p - starts[i] + 1), (char)letters[p],
-                        (unsigned long long)c.a + c.c + c.g + c.t, c.a, c.c, c.g, c.t);
-            }
-        if (ok) { ok = !ferror(f); ok = fclose(f) == 0 && ok; }
-        if (!ok) { fprintf(stderr, "error: cannot write the pile-up %s\n", pileup_file.c_str()); p_mf_kmerset_free(ks); return 3; }
-    }
-    if (!consensus_file.empty()) {
-        FILE *f = fopen(consensus_file.c_str(), "w");
-        bool ok = f != nullptr;
-        for (size_t i = 0; ok && i < record_names.size(); i++) {
-            fprintf(f, ">%s\n", record_names[i].c_str());
-            for (uint64_t p = starts[i]; p < starts[i + 1]; p += 60) {
-                fwrite(consensus.data() + p, 1, (size_t)std::min<uint64_t>(60, starts[i + 1] - p), f);
-                fputc('\n', f);
-            }
-        }
-        if (ok) { ok = !ferror(f); ok = fclose(f) == 0 && ok; }
-        if (!ok) { fprintf(stderr, "error: cannot write the consensus %s\n", consensus_file.c_str()); p_mf_kmerset_free(ks); return 3; }
-    }
-    if (!variants_file.empty()) {
-        FILE *f = fopen(variants_file.c_str(), "w");
-        bool ok = f != nullptr;
-        for (size_t i = 0; ok && i < record_names.size(); i++)
-            for (uint64_t p = starts[i]; p < starts[i + 1]; p++) {
-                const uint8_t alt = consensus[p], ref = letters[p];
-                if (!(alt == 'A' || alt == 'C' || alt == 'G' || alt == 'T') || ref == 'N' || alt == ref) continue;
-                const mf_pileup_t &c = pile[p];
-                fprintf(f, "%s\t%llu\t%c\t%c\t%llu\t%u\n", record_names[i].c_str(), (unsigned long long)(p - starts[i] + 1), (char)ref, (char)alt,
-                        (unsigned long long)c.a + c.c + c.g + c.t, alt == 'A' ? c.a : alt == 'C' ? c.c : alt == 'G' ? c.g : c.t);
-            }
-        if (ok) { ok = !ferror(f); ok = fclose(f) == 0 && ok; }
-        if (!ok) { fprintf(stderr, "error: cannot write the variants %s\n", variants_file.c_str()); p_mf_kmerset_free(ks); return 3; }
-    }
-    printf("%llu\n", (unsigned long long)kept);      // same stdout contract as the contig filter
+    if (!write_reports(A, R)) { free_set(ks); return 3; }
+    printf("%llu\n", (unsigned long long)R.kept);      // same stdout contract as the contig filter
     // (the outputs are written and closed; what is left is the GPU runtime's teardown -- queues, code objects, a tenth of a second -- which a
     // process that is about to be gone has no use for; a profiler writes its files in a finaliser, so not under one)
     fflush(stdout); fflush(stderr);
     const char *pre = getenv("LD_PRELOAD");
     if (!((pre && strstr(pre, "rocprof")) || getenv("ROCPROFILER_REGISTER_FORCE_LOAD") || getenv("ROCP_TOOL_LIBRARIES"))) _exit(0);
-    p_mf_kmerset_free(ks);
+    free_set(ks);
     return 0;
 }
 

@@ -153,14 +153,14 @@ struct mf_reads {
     // record assignment (mf_assign and the file-level call by record): the passing reads as a list, their records, the counters
     uint32_t *d_alist = nullptr, *d_assign = nullptr; uint64_t *d_apairs = nullptr; unsigned long long *d_acnt = nullptr;
     size_t cap_alist = 0, cap_assign = 0, cap_apairs = 0, cap_acnt = 0;
-    // k-mer depth (mf_depth and the file-level call with depth): a pass's 32-bit counters (then mf_depth's profile), mf_depth's 64-bit
-    // totals and record sums
-    uint32_t *d_dcnt = nullptr; unsigned long long *d_dtot = nullptr, *d_drec = nullptr;
-    size_t cap_dcnt = 0, cap_dtot = 0, cap_drec = 0;
-    // placement (mf_place): the per-read results; its difference counters, record counters and base depth take d_dtot, d_drec and d_dcnt
-    // (mf_pileup: the pile-up counters in front of them in d_dtot, the record sums behind them in d_drec, the called pile-up and the
-    // consensus in d_dcnt)
-    mf::PlaceOut *d_place = nullptr; size_t cap_place = 0;
+    // the reports of mf_depth, mf_place and mf_pileup: d_rtot the call's 64-bit totals; d_rsum its 64-bit record sums and the work words
+    // of its report kernel; d_rpos what it holds per position (32-bit counters or depths, or the called pile-up with the consensus behind it)
+    unsigned long long *d_rtot = nullptr, *d_rsum = nullptr; void *d_rpos = nullptr;
+    size_t cap_rtot = 0, cap_rsum = 0, cap_rpos = 0;
+    uint32_t *rpos_u32() const { return static_cast<uint32_t *>(d_rpos); }
+    mf::PileOut *rpos_pile() const { return static_cast<mf::PileOut *>(d_rpos); }
+    uint8_t *rpos_consensus(uint64_t positions) const { return static_cast<uint8_t *>(d_rpos) + positions * sizeof(mf::PileOut); }
+    mf::PlaceOut *d_place = nullptr; size_t cap_place = 0;          // mf_place's per-read results
     // capacities (bytes), so that a handle can be refilled batch after batch without touching the allocator
     size_t cap_words = 0, cap_offsets = 0, cap_npos = 0, cap_bitmap = 0, cap_recs = 0, cap_rec_counts = 0, cap_hits = 0, cap_npos_blk = 0, cap_off_blk = 0;
 };

@@ -265,26 +265,33 @@ static int depth_after_filter(mf_kmerset *ks, mf_reads *r, unsigned long long *t
     HIPCHK(dev_reserve(r->d_acnt, r->cap_acnt, 8, false));
     HIPCHK(hipMemsetAsync(r->d_acnt, 0, 8, st));
     HIPCHK(dev_reserve(r->d_alist, r->cap_alist, n * 4, true));
-    if (!wide) { HIPCHK(dev_reserve(r->d_dcnt, r->cap_dcnt, n_cnt * 4, false)); HIPCHK(hipMemsetAsync(r->d_dcnt, 0, n_cnt * 4, st)); }
+    if (!wide) { HIPCHK(dev_reserve(r->d_rpos, r->cap_rpos, n_cnt * 4, false)); HIPCHK(hipMemsetAsync(r->d_rpos, 0, n_cnt * 4, st)); }
     HIPCHK(launch_pass_list(r->d_bits[r->cur], n, r->d_alist, r->d_acnt, st));
-    HIPCHK(launch_depth_count(r->v, T->view, T->rep, r->d_alist, r->d_acnt, wide ? nullptr : r->d_dcnt, wide ? tot : nullptr, ctx->n_cu, st));
-    if (!wide) HIPCHK(launch_depth_fold(r->d_dcnt, n_cnt, tot, st));
+    HIPCHK(launch_depth_count(r->v, T->view, T->rep, r->d_alist, r->d_acnt, wide ? nullptr : r->rpos_u32(), wide ? tot : nullptr, ctx->n_cu, st));
+    if (!wide) HIPCHK(launch_depth_fold(r->rpos_u32(), n_cnt, tot, st));
     HIPCHK(hipStreamSynchronize(st));
     return MF_OK;
 }
 
+// What a report's last step works in on the device.  A resident call fills it from the read set's cached buffers (dev_reserve: a warm
+// call allocates nothing), a file-level call from temporaries of its own (DevScratch).
+struct DepthScratch {
+    uint32_t *prof; unsigned long long *rec;          // the profile, the record sums
+    static size_t prof_bytes(const mf_kmerset *ks) { return std::max<uint64_t>(ks->positions(), 1) * 4; }
+    static size_t rec_bytes(const mf_kmerset *ks) { return std::max<size_t>(ks->rec_len().size(), 1) * 32; }
+};
+
 // The profile (ks->positions() u32) and the record summaries (R entries) from the totals tot on `device` (stream st); each optional.
-static int depth_report(mf_kmerset *ks, int device, hipStream_t st, const unsigned long long *tot, uint32_t *d_prof, unsigned long long *d_rec,
-                        uint32_t *profile, mf_depth_record_t *records)
+static int depth_report(mf_kmerset *ks, int device, hipStream_t st, const unsigned long long *tot, DepthScratch s, uint32_t *profile, mf_depth_record_t *records)
 {
     DevTables *T; int rc = build_on_device(ks, device, &T); if (rc) return rc;
     rc = depth_tables(ks, device, T); if (rc) return rc;
     const uint64_t total = ks->positions(), n_rec = ks->rec_len().size();
-    if (records && n_rec) HIPCHK(hipMemsetAsync(d_rec, 0, n_rec * 32, st));
-    if (profile && total) HIPCHK(hipMemsetAsync(d_prof, 0xFF, total * 4, st));          // (records with no item: none, they are empty)
-    HIPCHK(launch_depth_profile(T->ditems, T->n_ditems, T->pos_rep, tot, profile ? d_prof : nullptr, records ? d_rec : nullptr, st));
-    if (profile && total) HIPCHK(hipMemcpyAsync(profile, d_prof, total * 4, hipMemcpyDeviceToHost, st));
-    if (records && n_rec) HIPCHK(hipMemcpyAsync(records, d_rec, n_rec * 32, hipMemcpyDeviceToHost, st));
+    if (records && n_rec) HIPCHK(hipMemsetAsync(s.rec, 0, n_rec * 32, st));
+    if (profile && total) HIPCHK(hipMemsetAsync(s.prof, 0xFF, total * 4, st));          // (records with no item: none, they are empty)
+    HIPCHK(launch_depth_profile(T->ditems, T->n_ditems, T->pos_rep, tot, profile ? s.prof : nullptr, records ? s.rec : nullptr, st));
+    if (profile && total) HIPCHK(hipMemcpyAsync(profile, s.prof, total * 4, hipMemcpyDeviceToHost, st));
+    if (records && n_rec) HIPCHK(hipMemcpyAsync(records, s.rec, n_rec * 32, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     return MF_OK;
 }
@@ -313,14 +320,14 @@ int mf_depth(const mf_kmerset *ks_, const mf_reads *reads_, uint32_t threshold, 
     rc = depth_tables(ks, r->device, T); if (rc) return rc;
     DevCtx *ctx; rc = get_ctx(r->device, &ctx, r->lane); if (rc) return rc;
     hipStream_t st = ctx->stream;
-    const uint64_t n_cnt = T->dcnt_n, total = ks->positions(), n_rec = ks->rec_len().size();
-    HIPCHK(dev_reserve(r->d_dtot, r->cap_dtot, std::max<uint64_t>(n_cnt, 1) * 8, false));
-    HIPCHK(hipMemsetAsync(r->d_dtot, 0, std::max<uint64_t>(n_cnt, 1) * 8, st));
-    rc = depth_after_filter(ks, r, r->d_dtot); if (rc) return rc;
-    // (the profile goes through the pass's 32-bit counters, which the totals have taken up)
-    HIPCHK(dev_reserve(r->d_dcnt, r->cap_dcnt, std::max<uint64_t>(std::max(n_cnt, total), 1) * 4, false));
-    HIPCHK(dev_reserve(r->d_drec, r->cap_drec, std::max<uint64_t>(n_rec, 1) * 32, false));
-    return depth_report(ks, r->device, st, r->d_dtot, r->d_dcnt, r->d_drec, profile, records);
+    const uint64_t n_cnt = T->dcnt_n;
+    HIPCHK(dev_reserve(r->d_rtot, r->cap_rtot, std::max<uint64_t>(n_cnt, 1) * 8, false));
+    HIPCHK(hipMemsetAsync(r->d_rtot, 0, std::max<uint64_t>(n_cnt, 1) * 8, st));
+    rc = depth_after_filter(ks, r, r->d_rtot); if (rc) return rc;
+    // (the profile goes through the pass's 32-bit counters, which the totals have taken up: never a smaller buffer than theirs)
+    HIPCHK(dev_reserve(r->d_rpos, r->cap_rpos, std::max<size_t>(n_cnt * 4, DepthScratch::prof_bytes(ks)), false));
+    HIPCHK(dev_reserve(r->d_rsum, r->cap_rsum, DepthScratch::rec_bytes(ks), false));
+    return depth_report(ks, r->device, st, r->d_rtot, DepthScratch{r->rpos_u32(), r->d_rsum}, profile, records);
 }
 
 } // extern "C"
@@ -369,20 +376,26 @@ static int pileup_tables(mf_kmerset *ks, int device, DevTables *T)
     return MF_OK;
 }
 
-// counters of a placement: the difference counters (positions + 1), then forward / reverse / over_begin / over_end of every record and
-// the passing reads that are not placed (4 R + 1).  A pile-up puts its four counters a position IN FRONT of them (16-byte aligned for
-// the call kernel; a base that a faulty clip let through would still land inside the array).
-static size_t place_diff_n(const mf_kmerset *ks) { return (size_t)ks->positions() + 1; }
-static size_t place_cnt_n(const mf_kmerset *ks) { return 4 * ks->rec_len().size() + 1; }
-static size_t pile_cnt_n(const mf_kmerset *ks) { return 4 * (size_t)ks->positions(); }
+// The counters of a placement, one array of 64-bit words: [pile-up counters | difference counters | record counters].  The four pile-up
+// counters a position (only with a pile-up) come FIRST because the call kernel reads them 16 bytes at a time: at the front of an
+// allocation they are aligned whatever the other two counts are (and a base that a faulty clip let through would still land inside the
+// array).  Then the difference counters (positions + 1), then forward / reverse / over_begin / over_end of every record and the passing
+// reads that are not placed (4 R + 1).  Every offset into the array is computed here.
+struct PlaceLayout {
+    size_t n_pile, n_diff, n_cnt;
+    PlaceLayout(const mf_kmerset *ks, bool pileup) : n_pile(pileup ? 4 * (size_t)ks->positions() : 0), n_diff((size_t)ks->positions() + 1), n_cnt(4 * ks->rec_len().size() + 1) {}
+    size_t words() const { return n_pile + n_diff + n_cnt; }
+    unsigned long long *pile(unsigned long long *base) const { return n_pile ? base : nullptr; }
+    unsigned long long *diff(unsigned long long *base) const { return base + n_pile; }
+    unsigned long long *cnt(unsigned long long *base) const { return base + n_pile + n_diff; }
+};
 static int pile_nomem(size_t words) { (void)hipGetLastError(); return fail(MF_E_NOMEM, "the pile-up counters need %llu bytes on the device", (unsigned long long)(words * 8)); }
 
-// The reads that passed the filter pass just run on this read set (its bitmap in r->d_bits[r->cur]) placed: their footprints into diff and
-// their records' counters into cnt (on r's device; other read sets there may be adding into them at the same time), their placements
-// into place (optional, initialised, n_reads entries on the device), their bases into pile (optional, pile_cnt_n counters); *listed:
-// how many passed.  Ends synchronised.
-static int place_after_filter(mf_kmerset *ks, mf_reads *r, unsigned long long *diff, unsigned long long *cnt, PlaceOut *place, uint64_t *listed,
-                              unsigned long long *pile = nullptr)
+// The reads that passed the filter pass just run on this read set (its bitmap in r->d_bits[r->cur]) placed: their footprints, their
+// records' counters and (with a pile-up) their bases into the counters t of layout L (on r's device; other read sets there may be adding
+// into them at the same time), their placements into place (optional, initialised, n_reads entries on the device); *listed: how many
+// passed.  Ends synchronised.
+static int place_after_filter(mf_kmerset *ks, mf_reads *r, const PlaceLayout &L, unsigned long long *t, PlaceOut *place, uint64_t *listed)
 {
     DevTables *T; int rc = build_on_device(ks, r->device, &T); if (rc) return rc;
     rc = place_tables(ks, r->device, T); if (rc) return rc;
@@ -407,35 +420,41 @@ static int place_after_filter(mf_kmerset *ks, mf_reads *r, unsigned long long *d
     HIPCHK(hipMemsetAsync(r->d_acnt, 0, 8, st));
     HIPCHK(dev_reserve(r->d_alist, r->cap_alist, n * 4, true));
     HIPCHK(launch_pass_list(r->d_bits[r->cur], n, r->d_alist, r->d_acnt, st));
-    HIPCHK(launch_place(r->v, T->view, T->anchor, T->place_starts, r->d_alist, r->d_acnt, (uint32_t)ks->rec_len().size(), place, diff, cnt, pile, ctx->n_cu, st));
+    HIPCHK(launch_place(r->v, T->view, T->anchor, T->place_starts, r->d_alist, r->d_acnt, (uint32_t)ks->rec_len().size(), place, L.diff(t), L.cnt(t), L.pile(t),
+                        ctx->n_cu, st));
     HIPCHK(hipMemcpyAsync(&v, r->d_acnt, 8, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     *listed = v;
     return MF_OK;
 }
 
-// Base depth (ks->positions() u32), the record summaries (R entries) and the passing reads that are not placed from the counters diff /
-// cnt on `device` (stream st); each optional.  work: 2 R + place_scan_tiles + 1 words, d_depth: positions u32, on the device.
-static size_t place_work_n(const mf_kmerset *ks) { return 2 * ks->rec_len().size() + (size_t)place_scan_tiles(ks->positions()) + 1; }
-static int place_report(mf_kmerset *ks, int device, hipStream_t st, const unsigned long long *diff, const unsigned long long *cnt,
-                        unsigned long long *work, uint32_t *d_depth, uint32_t *base_depth, mf_place_record_t *records, uint64_t *unplaced_passing)
+struct PlaceScratch {
+    unsigned long long *work; uint32_t *depth;          // the record sums (2 R) and the scan's partials, the base depth
+    static size_t work_bytes(const mf_kmerset *ks) { return (2 * ks->rec_len().size() + (size_t)place_scan_tiles(ks->positions()) + 1) * 8; }
+    static size_t depth_bytes(const mf_kmerset *ks) { return std::max<uint64_t>(ks->positions(), 1) * 4; }
+};
+
+// Base depth (ks->positions() u32), the record summaries (R entries) and unplaced[2] -- the passing reads that are not placed, then
+// not_passing as it is given -- from the counters t of layout L on `device` (stream st); each optional.
+static int place_report(mf_kmerset *ks, int device, hipStream_t st, const PlaceLayout &L, unsigned long long *t, PlaceScratch s, uint32_t *base_depth,
+                        mf_place_record_t *records, uint64_t *unplaced, uint64_t not_passing)
 {
     DevTables *T; int rc = build_on_device(ks, device, &T); if (rc) return rc;
     rc = place_tables(ks, device, T); if (rc) return rc;
     const uint64_t total = ks->positions(), n_rec = ks->rec_len().size();
-    std::vector<unsigned long long> h_cnt(place_cnt_n(ks), 0), h_sum(2 * n_rec + 1, 0);
-    if (records && n_rec) HIPCHK(hipMemsetAsync(work, 0, 2 * n_rec * 8, st));
+    std::vector<unsigned long long> h_cnt(L.n_cnt, 0), h_sum(2 * n_rec + 1, 0);
+    if (records && n_rec) HIPCHK(hipMemsetAsync(s.work, 0, 2 * n_rec * 8, st));
     if (base_depth || records)
-        HIPCHK(launch_place_profile(diff, total, T->place_starts, (uint32_t)n_rec, work + 2 * n_rec, base_depth ? d_depth : nullptr,
-                                    records ? work : nullptr, st));
-    if (base_depth && total) HIPCHK(hipMemcpyAsync(base_depth, d_depth, total * 4, hipMemcpyDeviceToHost, st));
-    if (records && n_rec) HIPCHK(hipMemcpyAsync(h_sum.data(), work, 2 * n_rec * 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(h_cnt.data(), cnt, h_cnt.size() * 8, hipMemcpyDeviceToHost, st));
+        HIPCHK(launch_place_profile(L.diff(t), total, T->place_starts, (uint32_t)n_rec, s.work + 2 * n_rec, base_depth ? s.depth : nullptr,
+                                    records ? s.work : nullptr, st));
+    if (base_depth && total) HIPCHK(hipMemcpyAsync(base_depth, s.depth, total * 4, hipMemcpyDeviceToHost, st));
+    if (records && n_rec) HIPCHK(hipMemcpyAsync(h_sum.data(), s.work, 2 * n_rec * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(h_cnt.data(), L.cnt(t), h_cnt.size() * 8, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     if (records)
         for (uint64_t j = 0; j < n_rec; j++)
             records[j] = mf_place_record_t{h_cnt[4 * j], h_cnt[4 * j + 1], h_cnt[4 * j + 2], h_cnt[4 * j + 3], h_sum[2 * j], h_sum[2 * j + 1]};
-    if (unplaced_passing) *unplaced_passing = h_cnt[4 * n_rec];
+    if (unplaced) { unplaced[0] = h_cnt[4 * n_rec]; unplaced[1] = not_passing; }
     return MF_OK;
 }
 
@@ -454,51 +473,51 @@ int mf_place(const mf_kmerset *ks_, const mf_reads *reads_, uint32_t threshold, 
     DevCtx *ctx; rc = get_ctx(r->device, &ctx, r->lane); if (rc) return rc;
     hipStream_t st = ctx->stream;
     const uint64_t n = r->v.n_reads;
-    const size_t n_diff = place_diff_n(ks), n_cnt = place_cnt_n(ks);
-    HIPCHK(dev_reserve(r->d_dtot, r->cap_dtot, n_diff * 8, false));
-    HIPCHK(dev_reserve(r->d_drec, r->cap_drec, (n_cnt + place_work_n(ks)) * 8, false));
-    HIPCHK(dev_reserve(r->d_dcnt, r->cap_dcnt, std::max<uint64_t>(ks->positions(), 1) * 4, false));
-    HIPCHK(hipMemsetAsync(r->d_dtot, 0, n_diff * 8, st));
-    HIPCHK(hipMemsetAsync(r->d_drec, 0, n_cnt * 8, st));
+    const PlaceLayout L(ks, false);
+    HIPCHK(dev_reserve(r->d_rtot, r->cap_rtot, L.words() * 8, false));
+    HIPCHK(dev_reserve(r->d_rsum, r->cap_rsum, PlaceScratch::work_bytes(ks), false));
+    HIPCHK(dev_reserve(r->d_rpos, r->cap_rpos, PlaceScratch::depth_bytes(ks), false));
+    HIPCHK(hipMemsetAsync(r->d_rtot, 0, L.words() * 8, st));
     if (place_out && n) {
         HIPCHK(dev_reserve(r->d_place, r->cap_place, n * sizeof(PlaceOut), true));
         HIPCHK(launch_place_init(r->d_place, n, st));
     }
     uint64_t listed = 0;
-    rc = place_after_filter(ks, r, r->d_dtot, r->d_drec, place_out ? r->d_place : nullptr, &listed); if (rc) return rc;
+    rc = place_after_filter(ks, r, L, r->d_rtot, place_out ? r->d_place : nullptr, &listed); if (rc) return rc;
     if (place_out && n) HIPCHK(hipMemcpyAsync(place_out, r->d_place, n * sizeof(PlaceOut), hipMemcpyDeviceToHost, st));
-    uint64_t not_placed = 0;
-    rc = place_report(ks, r->device, st, r->d_dtot, r->d_drec, r->d_drec + n_cnt, r->d_dcnt, base_depth, records, &not_placed);
-    if (rc) return rc;
-    if (unplaced) { unplaced[0] = not_placed; unplaced[1] = n - listed; }
-    return MF_OK;
+    return place_report(ks, r->device, st, L, r->d_rtot, PlaceScratch{r->d_rsum, r->rpos_u32()}, base_depth, records, unplaced, n - listed);
 }
 
 } // extern "C"
 
 // ------------------------------------------------------------------- pile-up
-// The called pile-up (positions entries), the consensus (positions bytes), the record summaries (R entries) and the passing reads that
-// are not placed from the counters pile / cnt on `device` (stream st); each optional.  sums: PILE_SUMS * R words, d_out: positions
-// PileOut, d_cons: positions bytes, on the device.
-static int pileup_report(mf_kmerset *ks, int device, hipStream_t st, const unsigned long long *pile, const unsigned long long *cnt, uint32_t min_depth,
-                         unsigned long long *sums, PileOut *d_out, uint8_t *d_cons, mf_pileup_t *pileup, uint8_t *consensus,
-                         mf_pileup_record_t *records, uint64_t *unplaced_passing)
+struct PileScratch {
+    unsigned long long *sums; PileOut *out; uint8_t *cons;          // the record sums (PILE_SUMS R), the called pile-up, the consensus
+    static size_t sums_bytes(const mf_kmerset *ks) { return std::max<size_t>(ks->rec_len().size(), 1) * PILE_SUMS * 8; }
+    static size_t out_bytes(const mf_kmerset *ks) { return std::max<uint64_t>(ks->positions(), 1) * sizeof(PileOut); }
+    static size_t cons_bytes(const mf_kmerset *ks) { return std::max<uint64_t>(ks->positions(), 1); }
+};
+
+// The called pile-up (positions entries), the consensus (positions bytes), the record summaries (R entries) and unplaced[2] -- the
+// passing reads that are not placed, then not_passing as it is given -- from the counters t of layout L on `device` (stream st); each optional.
+static int pileup_report(mf_kmerset *ks, int device, hipStream_t st, const PlaceLayout &L, unsigned long long *t, uint32_t min_depth, PileScratch s,
+                         mf_pileup_t *pileup, uint8_t *consensus, mf_pileup_record_t *records, uint64_t *unplaced, uint64_t not_passing)
 {
     static_assert(sizeof(mf_pileup_t) == 16 && sizeof(PileOut) == 16 && sizeof(mf_pileup_record_t) == 8 * PILE_SUMS, "pile-up records");
     DevTables *T; int rc = build_on_device(ks, device, &T); if (rc) return rc;
     rc = pileup_tables(ks, device, T); if (rc) return rc;
     const uint64_t total = ks->positions(), n_rec = ks->rec_len().size();
-    std::vector<unsigned long long> h_cnt(place_cnt_n(ks), 0);
-    if (records && n_rec) HIPCHK(hipMemsetAsync(sums, 0, PILE_SUMS * n_rec * 8, st));
+    std::vector<unsigned long long> h_cnt(L.n_cnt, 0);
+    if (records && n_rec) HIPCHK(hipMemsetAsync(s.sums, 0, PILE_SUMS * n_rec * 8, st));
     if (pileup || consensus || records)
-        HIPCHK(launch_pileup_call(pile, BaitView{T->pile_words, total, T->pile_runlen}, T->place_starts, (uint32_t)n_rec, min_depth,
-                                  pileup ? d_out : nullptr, consensus ? d_cons : nullptr, records ? sums : nullptr, st));
-    if (pileup && total) HIPCHK(hipMemcpyAsync(pileup, d_out, total * sizeof(PileOut), hipMemcpyDeviceToHost, st));
-    if (consensus && total) HIPCHK(hipMemcpyAsync(consensus, d_cons, total, hipMemcpyDeviceToHost, st));
-    if (records && n_rec) HIPCHK(hipMemcpyAsync(records, sums, PILE_SUMS * n_rec * 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(h_cnt.data(), cnt, h_cnt.size() * 8, hipMemcpyDeviceToHost, st));
+        HIPCHK(launch_pileup_call(L.pile(t), BaitView{T->pile_words, total, T->pile_runlen}, T->place_starts, (uint32_t)n_rec, min_depth,
+                                  pileup ? s.out : nullptr, consensus ? s.cons : nullptr, records ? s.sums : nullptr, st));
+    if (pileup && total) HIPCHK(hipMemcpyAsync(pileup, s.out, total * sizeof(PileOut), hipMemcpyDeviceToHost, st));
+    if (consensus && total) HIPCHK(hipMemcpyAsync(consensus, s.cons, total, hipMemcpyDeviceToHost, st));
+    if (records && n_rec) HIPCHK(hipMemcpyAsync(records, s.sums, PILE_SUMS * n_rec * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(h_cnt.data(), L.cnt(t), h_cnt.size() * 8, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
-    if (unplaced_passing) *unplaced_passing = h_cnt[4 * n_rec];
+    if (unplaced) { unplaced[0] = h_cnt[4 * n_rec]; unplaced[1] = not_passing; }
     return MF_OK;
 }
 
@@ -535,25 +554,17 @@ int mf_pileup(const mf_kmerset *ks_, const mf_reads *reads_, uint32_t threshold,
     if (rc) return rc;
     DevCtx *ctx; rc = get_ctx(r->device, &ctx, r->lane); if (rc) return rc;
     hipStream_t st = ctx->stream;
-    const uint64_t n = r->v.n_reads, total = ks->positions(), n_rec = ks->rec_len().size();
-    // d_dtot: pile-up, difference and record counters; d_drec: the record sums; d_dcnt: the called pile-up, then the consensus
-    const size_t n_pile = pile_cnt_n(ks), n_diff = place_diff_n(ks), n_cnt = place_cnt_n(ks), n_all = n_pile + n_diff + n_cnt;
-    const hipError_t e = dev_reserve(r->d_dtot, r->cap_dtot, n_all * 8, false);
-    if (e == hipErrorOutOfMemory) return pile_nomem(n_all);
+    const PlaceLayout L(ks, true);
+    const hipError_t e = dev_reserve(r->d_rtot, r->cap_rtot, L.words() * 8, false);
+    if (e == hipErrorOutOfMemory) return pile_nomem(L.words());
     HIPCHK(e);
-    HIPCHK(dev_reserve(r->d_drec, r->cap_drec, std::max<uint64_t>(n_rec, 1) * PILE_SUMS * 8, false));
-    HIPCHK(dev_reserve(r->d_dcnt, r->cap_dcnt, std::max<uint64_t>(total, 1) * (sizeof(PileOut) + 1) + 16, false));
-    HIPCHK(hipMemsetAsync(r->d_dtot, 0, n_all * 8, st));
-    unsigned long long *pile = r->d_dtot, *diff = pile + n_pile, *cnt = diff + n_diff;
+    HIPCHK(dev_reserve(r->d_rsum, r->cap_rsum, PileScratch::sums_bytes(ks), false));
+    HIPCHK(dev_reserve(r->d_rpos, r->cap_rpos, PileScratch::out_bytes(ks) + PileScratch::cons_bytes(ks) + 16, false));
+    HIPCHK(hipMemsetAsync(r->d_rtot, 0, L.words() * 8, st));
     uint64_t listed = 0;
-    rc = place_after_filter(ks, r, diff, cnt, nullptr, &listed, pile); if (rc) return rc;
-    uint64_t not_placed = 0;
-    PileOut *d_out = reinterpret_cast<PileOut *>(r->d_dcnt);
-    rc = pileup_report(ks, r->device, st, pile, cnt, min_depth, r->d_drec, d_out, reinterpret_cast<uint8_t *>(d_out + total), pileup, consensus, records,
-                       &not_placed);
-    if (rc) return rc;
-    if (unplaced) { unplaced[0] = not_placed; unplaced[1] = n - listed; }
-    return MF_OK;
+    rc = place_after_filter(ks, r, L, r->d_rtot, nullptr, &listed); if (rc) return rc;
+    return pileup_report(ks, r->device, st, L, r->d_rtot, min_depth, PileScratch{r->d_rsum, r->rpos_pile(), r->rpos_consensus(ks->positions())}, pileup,
+                         consensus, records, unplaced, r->v.n_reads - listed);
 }
 
 } // extern "C"
@@ -570,73 +581,38 @@ struct AssignReport : PassReport {
     int after_pass(mf_reads *R, std::vector<uint64_t> &pairs, std::string &err) override { return R ? hook_result(assign_after_filter(ks, R, nullptr, nullptr, &pairs, by_group), err) : MF_OK; }
 };
 
-// K-mer depth: the windows of every mate that passes go into 64-bit totals, one array per (logical) device, made and zeroed when a batch
-// there first asks for it, shared by the device's workers and lanes (their folds are atomic).  No pairs: nothing is tallied.
-struct DepthTotals : PassReport {
+// Reports that count on the device: what every mate that passes adds goes into 64-bit counters, one array per (logical) device, made and
+// zeroed when a batch there first asks for it (on), shared by the device's workers and lanes (the kernels' adds are atomic), summed on
+// the host at the end (fold_into).  No pairs: nothing is tallied.  A report says which tables of the set its kernels need on a device,
+// how many words its array has there, and what a batch adds.
+struct DeviceTotals : PassReport {
     mf_kmerset *ks;
+    int (*const nomem)(size_t words);          // what a full device is reported with (null: as any failed HIP call)
     std::mutex tot_mu;
     std::map<int, unsigned long long *> tot;
-    explicit DepthTotals(mf_kmerset *ks_) : PassReport(0, false), ks(ks_) {}
-    ~DepthTotals() { restart(); }
-    void restart() override { for (auto &kv : tot) if (hipSetDevice(phys(kv.first)) == hipSuccess) hipFree(kv.second); tot.clear(); }
+    size_t n_words = 0;
+    explicit DeviceTotals(mf_kmerset *ks_, int (*nomem_)(size_t) = nullptr) : PassReport(0, false), ks(ks_), nomem(nomem_) {}
+    ~DeviceTotals() { release(); }
+    void restart() override { release(); }
+    virtual int tables(int device, DevTables *T) = 0;
+    virtual size_t words(const DevTables *T) const = 0;
+    virtual int add(mf_reads *R, unsigned long long *t) = 0;
+    void release() { for (auto &kv : tot) if (hipSetDevice(phys(kv.first)) == hipSuccess) hipFree(kv.second); tot.clear(); }
     int on(int device, unsigned long long **out)
     {
         std::lock_guard<std::mutex> lk(tot_mu);
         auto it = tot.find(device);
         if (it != tot.end()) { *out = it->second; return MF_OK; }
         DevTables *T; int rc = build_on_device(ks, device, &T); if (rc) return rc;
-        rc = depth_tables(ks, device, T); if (rc) return rc;
+        rc = tables(device, T); if (rc) return rc;
         DevCtx *ctx; rc = get_ctx(device, &ctx); if (rc) return rc;
-        const size_t bytes = std::max<uint64_t>(T->dcnt_n, 1) * 8;
+        n_words = std::max<size_t>(words(T), 1);
         unsigned long long *p = nullptr;
-        HIPCHK(dev_malloc(&p, bytes));
-        tot[device] = p;
-        HIPCHK(hipMemsetAsync(p, 0, bytes, ctx->stream));
-        HIPCHK(hipStreamSynchronize(ctx->stream));
-        *out = p;
-        return MF_OK;
-    }
-    int after_pass(mf_reads *R, std::vector<uint64_t> &, std::string &err) override
-    {
-        if (!R) return MF_OK;
-        unsigned long long *t = nullptr;
-        int rc = on(R->device, &t);
-        if (rc == MF_OK) rc = depth_after_filter(ks, R, t);
-        return hook_result(rc, err);
-    }
-};
-
-// Placement: the footprints and record counters of every mate that passes go into one array per (logical) device -- difference counters,
-// then record counters --, made and zeroed when a batch there first asks for it, shared by the device's workers and lanes (the kernel's
-// adds are atomic).  No pairs: nothing is tallied.  n_pile: the pile-up counters in front of them (PileupTotals), or 0.
-struct PlaceTotals : PassReport {
-    mf_kmerset *ks;
-    const size_t n_pile;
-    std::mutex tot_mu;
-    std::map<int, unsigned long long *> tot;
-    std::atomic<uint64_t> mates{0}, passing{0};
-    explicit PlaceTotals(mf_kmerset *ks_, size_t n_pile_ = 0) : PassReport(0, false), ks(ks_), n_pile(n_pile_) {}
-    ~PlaceTotals() { restart(); }
-    void restart() override
-    {
-        for (auto &kv : tot) if (hipSetDevice(phys(kv.first)) == hipSuccess) hipFree(kv.second);
-        tot.clear(); mates = 0; passing = 0;
-    }
-    size_t words() const { return n_pile + place_diff_n(ks) + place_cnt_n(ks); }
-    int on(int device, unsigned long long **out)
-    {
-        std::lock_guard<std::mutex> lk(tot_mu);
-        auto it = tot.find(device);
-        if (it != tot.end()) { *out = it->second; return MF_OK; }
-        DevTables *T; int rc = build_on_device(ks, device, &T); if (rc) return rc;
-        rc = place_tables(ks, device, T); if (rc) return rc;
-        DevCtx *ctx; rc = get_ctx(device, &ctx); if (rc) return rc;
-        unsigned long long *p = nullptr;
-        const hipError_t e = dev_malloc(&p, words() * 8);
-        if (e == hipErrorOutOfMemory && n_pile) return pile_nomem(words());
+        const hipError_t e = dev_malloc(&p, n_words * 8);
+        if (e == hipErrorOutOfMemory && nomem) return nomem(n_words);
         HIPCHK(e);
         tot[device] = p;
-        HIPCHK(hipMemsetAsync(p, 0, words() * 8, ctx->stream));
+        HIPCHK(hipMemsetAsync(p, 0, n_words * 8, ctx->stream));
         HIPCHK(hipStreamSynchronize(ctx->stream));
         *out = p;
         return MF_OK;
@@ -645,34 +621,52 @@ struct PlaceTotals : PassReport {
     {
         if (!R) return MF_OK;
         unsigned long long *t = nullptr;
-        uint64_t listed = 0;
         int rc = on(R->device, &t);
-        if (rc == MF_OK) rc = place_after_filter(ks, R, t + n_pile, t + n_pile + place_diff_n(ks), nullptr, &listed, n_pile ? t : nullptr);
-        if (rc == MF_OK) { mates += R->v.n_reads; passing += listed; }
+        if (rc == MF_OK) rc = add(R, t);
         return hook_result(rc, err);
     }
     // the devices' counters summed on the host into the first listed device's, which *t0 then names
     int fold_into(int dev0, unsigned long long **t0)
     {
         int rc = on(dev0, t0); if (rc) return rc;
-        const size_t n_all = words();
         if (tot.size() > 1) {
-            std::vector<uint64_t> sum(n_all, 0), part(n_all);
+            std::vector<uint64_t> sum(n_words, 0), part(n_words);
             for (auto &kv : tot) {
                 HIPCHK(hipSetDevice(phys(kv.first)));
-                HIPCHK(hipMemcpy(part.data(), kv.second, n_all * 8, hipMemcpyDeviceToHost));
-                for (size_t i = 0; i < n_all; i++) sum[i] += part[i];
+                HIPCHK(hipMemcpy(part.data(), kv.second, n_words * 8, hipMemcpyDeviceToHost));
+                for (size_t i = 0; i < n_words; i++) sum[i] += part[i];
             }
             HIPCHK(hipSetDevice(phys(dev0)));
-            HIPCHK(hipMemcpy(*t0, sum.data(), n_all * 8, hipMemcpyHostToDevice));
+            HIPCHK(hipMemcpy(*t0, sum.data(), n_words * 8, hipMemcpyHostToDevice));
         }
         return MF_OK;
     }
 };
 
-// Pile-up: PlaceTotals whose array grows by the four counters per position.
-struct PileupTotals : PlaceTotals {
-    explicit PileupTotals(mf_kmerset *ks_) : PlaceTotals(ks_, pile_cnt_n(ks_)) {}
+// K-mer depth: the windows of every mate that passes
+struct DepthTotals : DeviceTotals {
+    using DeviceTotals::DeviceTotals;
+    int tables(int device, DevTables *T) override { return depth_tables(ks, device, T); }
+    size_t words(const DevTables *T) const override { return T->dcnt_n; }
+    int add(mf_reads *R, unsigned long long *t) override { return depth_after_filter(ks, R, t); }
+};
+
+// Placement, and with_pileup the pile-up: the footprints, record counters and bases of every mate that passes (PlaceLayout), and how
+// many mates there were and passed
+struct PlaceTotals : DeviceTotals {
+    const PlaceLayout L;
+    std::atomic<uint64_t> mates{0}, passing{0};
+    PlaceTotals(mf_kmerset *ks_, bool with_pileup) : DeviceTotals(ks_, with_pileup ? pile_nomem : nullptr), L(ks_, with_pileup) {}
+    void restart() override { release(); mates = 0; passing = 0; }
+    int tables(int device, DevTables *T) override { return place_tables(ks, device, T); }
+    size_t words(const DevTables *) const override { return L.words(); }
+    int add(mf_reads *R, unsigned long long *t) override
+    {
+        uint64_t listed = 0;
+        const int rc = place_after_filter(ks, R, L, t, nullptr, &listed);
+        if (rc == MF_OK) { mates += R->v.n_reads; passing += listed; }
+        return rc;
+    }
 };
 
 static int files_by_owner(mf_kmerset *ks, const char *fq1, const char *fq2, const char *out1, const char *out2, uint32_t threshold, int pair_mode,
@@ -683,6 +677,17 @@ static int files_by_owner(mf_kmerset *ks, const char *fq1, const char *fq2, cons
     if (rc) return rc;
     std::copy(report.counts.begin(), report.counts.end(), counts);
     return MF_OK;
+}
+
+// The file-level call with a counting report, then its devices' counters summed into the first listed device's (*t0), whose context
+// *ctx is: the report's last step runs once, there.
+static int files_with_totals(mf_kmerset *ks, const char *fq1, const char *fq2, const char *out1, const char *out2, uint32_t threshold, int pair_mode,
+                             const int *devices, int n_devices, uint64_t *kept, uint64_t *total, DeviceTotals &dt, unsigned long long **t0, DevCtx **ctx)
+{
+    int rc = filter_fastq_files_on(ks, fq1, fq2, out1, out2, threshold, pair_mode, devices, n_devices, kept, total, &dt);
+    if (rc == MF_OK) rc = dt.fold_into(devices[0], t0);
+    if (rc == MF_OK) rc = get_ctx(devices[0], ctx);
+    return rc;
 }
 
 extern "C" {
@@ -711,30 +716,14 @@ int mf_filter_fastq_files_depth(mf_kmerset *ks, const char *fq1, const char *fq2
 {
     if (!ks) return fail(MF_E_ARG, "NULL handle");
     DepthTotals dt(ks);
-    int rc = filter_fastq_files_on(ks, fq1, fq2, out1, out2, threshold, pair_mode, devices, n_devices, kept, total, &dt);
+    unsigned long long *t0 = nullptr; DevCtx *ctx = nullptr;
+    const int rc = files_with_totals(ks, fq1, fq2, out1, out2, threshold, pair_mode, devices, n_devices, kept, total, dt, &t0, &ctx);
     if (rc) return rc;
-    // the devices' totals summed on the host into the first listed device's, then the profile and summary kernels once, there
-    const int dev0 = devices[0];
-    unsigned long long *t0 = nullptr;
-    rc = dt.on(dev0, &t0); if (rc) return rc;
-    DevTables *T; rc = build_on_device(ks, dev0, &T); if (rc) return rc;
-    const uint64_t n_cnt = T->dcnt_n;
-    if (dt.tot.size() > 1 && n_cnt) {
-        std::vector<uint64_t> sum(n_cnt, 0), part(n_cnt);
-        for (auto &kv : dt.tot) {
-            HIPCHK(hipSetDevice(phys(kv.first)));
-            HIPCHK(hipMemcpy(part.data(), kv.second, n_cnt * 8, hipMemcpyDeviceToHost));
-            for (uint64_t i = 0; i < n_cnt; i++) sum[i] += part[i];
-        }
-        HIPCHK(hipSetDevice(phys(dev0)));
-        HIPCHK(hipMemcpy(t0, sum.data(), n_cnt * 8, hipMemcpyHostToDevice));
-    }
-    DevCtx *ctx; rc = get_ctx(dev0, &ctx); if (rc) return rc;
     DevScratch tmp;
-    uint32_t *d_prof = nullptr; unsigned long long *d_rec = nullptr;
-    HIPCHK(tmp.alloc(d_prof, std::max<uint64_t>(ks->positions(), 1) * 4));
-    HIPCHK(tmp.alloc(d_rec, std::max<uint64_t>(ks->rec_len().size(), 1) * 32));
-    return depth_report(ks, dev0, ctx->stream, t0, d_prof, d_rec, profile, records);
+    DepthScratch s{nullptr, nullptr};
+    HIPCHK(tmp.alloc(s.prof, DepthScratch::prof_bytes(ks)));
+    HIPCHK(tmp.alloc(s.rec, DepthScratch::rec_bytes(ks)));
+    return depth_report(ks, devices[0], ctx->stream, t0, s, profile, records);
 }
 
 int mf_filter_fastq_files_placed(mf_kmerset *ks, const char *fq1, const char *fq2, const char *out1, const char *out2,
@@ -743,23 +732,15 @@ int mf_filter_fastq_files_placed(mf_kmerset *ks, const char *fq1, const char *fq
 {
     if (!ks) return fail(MF_E_ARG, "NULL handle");
     if (ks->kind != MF_KIND_NUCLEOTIDE) return fail(MF_E_ARG, "placement needs a nucleotide bait set");
-    PlaceTotals pt(ks);
-    int rc = filter_fastq_files_on(ks, fq1, fq2, out1, out2, threshold, pair_mode, devices, n_devices, kept, total, &pt);
+    PlaceTotals pt(ks, false);
+    unsigned long long *t0 = nullptr; DevCtx *ctx = nullptr;
+    const int rc = files_with_totals(ks, fq1, fq2, out1, out2, threshold, pair_mode, devices, n_devices, kept, total, pt, &t0, &ctx);
     if (rc) return rc;
-    // the devices' counters summed on the host into the first listed device's, then the scan and the summaries once, there
-    const int dev0 = devices[0];
-    unsigned long long *t0 = nullptr;
-    rc = pt.fold_into(dev0, &t0); if (rc) return rc;
-    DevCtx *ctx; rc = get_ctx(dev0, &ctx); if (rc) return rc;
     DevScratch tmp;
-    uint32_t *d_depth = nullptr; unsigned long long *work = nullptr;
-    HIPCHK(tmp.alloc(d_depth, std::max<uint64_t>(ks->positions(), 1) * 4));
-    HIPCHK(tmp.alloc(work, place_work_n(ks) * 8));
-    uint64_t not_placed = 0;
-    rc = place_report(ks, dev0, ctx->stream, t0, t0 + place_diff_n(ks), work, d_depth, base_depth, records, &not_placed);
-    if (rc) return rc;
-    if (unplaced) { unplaced[0] = not_placed; unplaced[1] = pt.mates - pt.passing; }
-    return MF_OK;
+    PlaceScratch s{nullptr, nullptr};
+    HIPCHK(tmp.alloc(s.depth, PlaceScratch::depth_bytes(ks)));
+    HIPCHK(tmp.alloc(s.work, PlaceScratch::work_bytes(ks)));
+    return place_report(ks, devices[0], ctx->stream, pt.L, t0, s, base_depth, records, unplaced, pt.mates - pt.passing);
 }
 
 int mf_filter_fastq_files_pileup(mf_kmerset *ks, const char *fq1, const char *fq2, const char *out1, const char *out2,
@@ -768,25 +749,16 @@ int mf_filter_fastq_files_pileup(mf_kmerset *ks, const char *fq1, const char *fq
                                  uint64_t *kept, uint64_t *total)
 {
     int rc = pileup_args(ks, min_depth); if (rc) return rc;
-    PileupTotals pt(ks);
-    rc = filter_fastq_files_on(ks, fq1, fq2, out1, out2, threshold, pair_mode, devices, n_devices, kept, total, &pt);
+    PlaceTotals pt(ks, true);
+    unsigned long long *t0 = nullptr; DevCtx *ctx = nullptr;
+    rc = files_with_totals(ks, fq1, fq2, out1, out2, threshold, pair_mode, devices, n_devices, kept, total, pt, &t0, &ctx);
     if (rc) return rc;
-    // the devices' counters summed on the host into the first listed device's, then the call kernel once, there
-    const int dev0 = devices[0];
-    unsigned long long *t0 = nullptr;
-    rc = pt.fold_into(dev0, &t0); if (rc) return rc;
-    DevCtx *ctx; rc = get_ctx(dev0, &ctx); if (rc) return rc;
     DevScratch tmp;
-    PileOut *d_out = nullptr; uint8_t *d_cons = nullptr; unsigned long long *sums = nullptr;
-    const uint64_t positions = ks->positions();
-    HIPCHK(tmp.alloc(d_out, std::max<uint64_t>(positions, 1) * sizeof(PileOut)));
-    HIPCHK(tmp.alloc(d_cons, std::max<uint64_t>(positions, 1)));
-    HIPCHK(tmp.alloc(sums, std::max<uint64_t>(ks->rec_len().size(), 1) * PILE_SUMS * 8));
-    uint64_t not_placed = 0;
-    rc = pileup_report(ks, dev0, ctx->stream, t0, t0 + pt.n_pile + place_diff_n(ks), min_depth, sums, d_out, d_cons, pileup, consensus, records, &not_placed);
-    if (rc) return rc;
-    if (unplaced) { unplaced[0] = not_placed; unplaced[1] = pt.mates - pt.passing; }
-    return MF_OK;
+    PileScratch s{nullptr, nullptr, nullptr};
+    HIPCHK(tmp.alloc(s.out, PileScratch::out_bytes(ks)));
+    HIPCHK(tmp.alloc(s.cons, PileScratch::cons_bytes(ks)));
+    HIPCHK(tmp.alloc(s.sums, PileScratch::sums_bytes(ks)));
+    return pileup_report(ks, devices[0], ctx->stream, pt.L, t0, min_depth, s, pileup, consensus, records, unplaced, pt.mates - pt.passing);
 }
 
 } // extern "C"

@@ -1,0 +1,117 @@
+// The text of the report files `fastfilter bait` writes: one pure function per format, from the arrays of the file-level calls
+// (include/mitofilter.h) to an open FILE.  names: the records' (or groups') names; starts: names.size() + 1 offsets, record j holds
+// positions [starts[j], starts[j + 1]) of the per-position arrays.  Each returns false when f is null or a write failed.  Host code with no
+// dependency beyond the C ABI header, so that tests/native/report_text_check.cpp holds every format to its bytes without a device.
+#pragma once
+#include "../../include/mitofilter.h"
+
+#include <cstdio>
+#include <string>
+#include <vector>
+
+namespace mf_text {
+
+using Names = std::vector<std::string>;
+using Starts = std::vector<uint64_t>;
+typedef unsigned long long ull;
+
+inline bool written(FILE *f) { return fflush(f) == 0 && !ferror(f); }
+inline ull pile_depth(const mf_pileup_t &c) { return (ull)c.a + c.c + c.g + c.t; }
+
+// --report / --group-report: counts holds names.size() + 2 entries, the last two the ambiguous and the unassigned reads
+inline bool write_reads(FILE *f, bool grouped, const Names &names, const uint64_t *counts)
+{
+    if (!f) return false;
+    const size_t n = names.size();
+    fputs(grouped ? "group\tname\treads\n" : "record\tname\treads\n", f);
+    for (size_t i = 0; i < n; i++) fprintf(f, "%zu\t%s\t%llu\n", i, names[i].c_str(), (ull)counts[i]);
+    fprintf(f, "-\t*ambiguous*\t%llu\n-\t*unassigned*\t%llu\n", (ull)counts[n], (ull)counts[n + 1]);
+    return written(f);
+}
+
+// --depth-report
+inline bool write_depth_report(FILE *f, const Names &names, const Starts &starts, const mf_depth_record_t *recs)
+{
+    if (!f) return false;
+    fputs("record\tname\tlength\twindows\tcovered\tmean\tmax\n", f);
+    for (size_t i = 0; i < names.size(); i++) {
+        const mf_depth_record_t &d = recs[i];
+        fprintf(f, "%zu\t%s\t%llu\t%llu\t%llu\t%.3f\t%llu\n", i, names[i].c_str(), (ull)(starts[i + 1] - starts[i]), (ull)d.windows, (ull)d.covered,
+                d.windows ? (double)d.depth_sum / (double)d.windows : 0.0, (ull)d.depth_max);
+    }
+    return written(f);
+}
+
+// name, 1-based position, depth of every position (skip_none: but those whose depth is MF_DEPTH_NONE)
+inline bool write_positions(FILE *f, const Names &names, const Starts &starts, const uint32_t *depth, bool skip_none)
+{
+    if (!f) return false;
+    for (size_t i = 0; i < names.size(); i++)
+        for (uint64_t p = starts[i]; p < starts[i + 1]; p++)
+            if (!skip_none || depth[p] != MF_DEPTH_NONE) fprintf(f, "%s\t%llu\t%u\n", names[i].c_str(), (ull)(p - starts[i] + 1), depth[p]);
+    return written(f);
+}
+// --depth-profile: the valid windows; --base-depth: every position
+inline bool write_depth_profile(FILE *f, const Names &names, const Starts &starts, const uint32_t *profile) { return write_positions(f, names, starts, profile, true); }
+inline bool write_base_depth(FILE *f, const Names &names, const Starts &starts, const uint32_t *depth) { return write_positions(f, names, starts, depth, false); }
+
+// --place-report: the max column is taken over the record's base depth; not_placed: the passing mates that are not placed
+inline bool write_place_report(FILE *f, const Names &names, const Starts &starts, const mf_place_record_t *recs, const uint32_t *base_depth, uint64_t not_placed)
+{
+    if (!f) return false;
+    fputs("record\tname\tlength\tforward\treverse\tover_begin\tover_end\tcovered\tmean\tmax\n", f);
+    for (size_t i = 0; i < names.size(); i++) {
+        const mf_place_record_t &d = recs[i];
+        const uint64_t len = starts[i + 1] - starts[i];
+        uint32_t mx = 0;
+        for (uint64_t p = starts[i]; p < starts[i + 1]; p++) if (base_depth[p] > mx) mx = base_depth[p];
+        fprintf(f, "%zu\t%s\t%llu\t%llu\t%llu\t%llu\t%llu\t%llu\t%.3f\t%u\n", i, names[i].c_str(), (ull)len, (ull)d.forward, (ull)d.reverse, (ull)d.over_begin,
+                (ull)d.over_end, (ull)d.covered, len ? (double)d.base_sum / (double)len : 0.0, mx);
+    }
+    fprintf(f, "-\t*unplaced*\t%llu\n", (ull)not_placed);
+    return written(f);
+}
+
+// --pileup: name, 1-based position, bait letter, depth = A + C + G + T, A, C, G, T
+inline bool write_pileup(FILE *f, const Names &names, const Starts &starts, const uint8_t *letters, const mf_pileup_t *pile)
+{
+    if (!f) return false;
+    for (size_t i = 0; i < names.size(); i++)
+        for (uint64_t p = starts[i]; p < starts[i + 1]; p++) {
+            const mf_pileup_t &c = pile[p];
+            fprintf(f, "%s\t%llu\t%c\t%llu\t%u\t%u\t%u\t%u\n", names[i].c_str(), (ull)(p - starts[i] + 1), (char)letters[p], pile_depth(c), c.a, c.c, c.g, c.t);
+        }
+    return written(f);
+}
+
+// --consensus: FASTA, 60 letters a line; an empty record has a header and no sequence line
+inline bool write_consensus(FILE *f, const Names &names, const Starts &starts, const uint8_t *consensus)
+{
+    if (!f) return false;
+    for (size_t i = 0; i < names.size(); i++) {
+        fprintf(f, ">%s\n", names[i].c_str());
+        for (uint64_t p = starts[i]; p < starts[i + 1]; p += 60) {
+            const uint64_t left = starts[i + 1] - p;
+            fwrite(consensus + p, 1, (size_t)(left < 60 ? left : 60), f);
+            fputc('\n', f);
+        }
+    }
+    return written(f);
+}
+
+// --variants: the called positions (an upper-case letter) whose bait letter is valid and differs: name, 1-based position, ref, alt, depth, alt count
+inline bool write_variants(FILE *f, const Names &names, const Starts &starts, const uint8_t *letters, const mf_pileup_t *pile, const uint8_t *consensus)
+{
+    if (!f) return false;
+    for (size_t i = 0; i < names.size(); i++)
+        for (uint64_t p = starts[i]; p < starts[i + 1]; p++) {
+            const uint8_t alt = consensus[p], ref = letters[p];
+            if (!(alt == 'A' || alt == 'C' || alt == 'G' || alt == 'T') || ref == 'N' || alt == ref) continue;
+            const mf_pileup_t &c = pile[p];
+            fprintf(f, "%s\t%llu\t%c\t%c\t%llu\t%u\n", names[i].c_str(), (ull)(p - starts[i] + 1), (char)ref, (char)alt, pile_depth(c),
+                    alt == 'A' ? c.a : alt == 'C' ? c.c : alt == 'G' ? c.g : c.t);
+        }
+    return written(f);
+}
+
+} // namespace mf_text

@@ -575,34 +575,38 @@ def filter_fastq_files(ks: KmerSet, fq1: str, fq2: Optional[str], out1: str, out
     return kept.value, total.value
 
 
+def _files_call(name: str, ks: KmerSet, fq1, fq2, out1, out2, threshold, pair_mode, devices, n_devices, *outs) -> Tuple[int, int]:
+    """The file-level call `name` on `devices` (default 0 .. n_devices - 1); outs: what it takes between the device list and the
+    counts.  -> (kept, total)."""
+    if devices is None:
+        devices = list(range(n_devices))
+    arr = (C.c_int * len(devices))(*[int(d) for d in devices])
+    kept, total = C.c_uint64(), C.c_uint64()
+    _chk(getattr(load(), name)(ks._h, _enc(fq1), _enc(fq2), _enc(out1), _enc(out2), threshold, pair_mode, arr, len(devices), *outs,
+                               C.byref(kept), C.byref(total)))
+    return kept.value, total.value
+
+
 def filter_fastq_files_by_record(ks: KmerSet, fq1: str, fq2: Optional[str], out1: str, out2: Optional[str],
                                  threshold: int = 1, pair_mode: int = PAIR_EITHER, devices: Optional[Sequence[int]] = None,
                                  n_devices: int = 1):
     """filter_fastq_files plus the bait record of every kept read.  -> (kept, total, counts u64[R + 2]): kept reads (mates one by
     one) of each record, then ambiguous, then unassigned (a mate kept only through its partner).  devices: an explicit list of
     device indices (instead of 0 .. n_devices - 1)."""
-    if devices is None:
-        devices = list(range(n_devices))
-    arr = (C.c_int * len(devices))(*[int(d) for d in devices])
     counts = np.zeros(_n_records(ks) + 2, dtype=np.uint64)
-    kept, total = C.c_uint64(), C.c_uint64()
-    _chk(load().mf_filter_fastq_files_by_record(ks._h, _enc(fq1), _enc(fq2), _enc(out1), _enc(out2), threshold, pair_mode,
-                                                arr, len(devices), counts.ctypes.data, C.byref(kept), C.byref(total)))
-    return kept.value, total.value, counts
+    kept, total = _files_call("mf_filter_fastq_files_by_record", ks, fq1, fq2, out1, out2, threshold, pair_mode, devices, n_devices,
+                              counts.ctypes.data)
+    return kept, total, counts
 
 
 def filter_fastq_files_by_group(ks: KmerSet, fq1: str, fq2: Optional[str], out1: str, out2: Optional[str],
                                 threshold: int = 1, pair_mode: int = PAIR_EITHER, devices: Optional[Sequence[int]] = None,
                                 n_devices: int = 1):
     """filter_fastq_files_by_record by group of records.  -> (kept, total, counts u64[G + 2])."""
-    if devices is None:
-        devices = list(range(n_devices))
-    arr = (C.c_int * len(devices))(*[int(d) for d in devices])
     counts = np.zeros(_n_groups(ks) + 2, dtype=np.uint64)
-    kept, total = C.c_uint64(), C.c_uint64()
-    _chk(load().mf_filter_fastq_files_by_group(ks._h, _enc(fq1), _enc(fq2), _enc(out1), _enc(out2), threshold, pair_mode,
-                                               arr, len(devices), counts.ctypes.data, C.byref(kept), C.byref(total)))
-    return kept.value, total.value, counts
+    kept, total = _files_call("mf_filter_fastq_files_by_group", ks, fq1, fq2, out1, out2, threshold, pair_mode, devices, n_devices,
+                              counts.ctypes.data)
+    return kept, total, counts
 
 
 def filter_fastq_files_depth(ks: KmerSet, fq1: str, fq2: Optional[str], out1: str, out2: Optional[str],
@@ -610,16 +614,13 @@ def filter_fastq_files_depth(ks: KmerSet, fq1: str, fq2: Optional[str], out1: st
                              n_devices: int = 1):
     """filter_fastq_files plus the k-mer depth of the bait positions over every mate that passes its own threshold (the pair rule
     decides only what is written).  -> (kept, total, profile u32[positions], records DEPTH_RECORD[R])."""
-    if devices is None:
-        devices = list(range(n_devices))
-    arr = (C.c_int * len(devices))(*[int(d) for d in devices])
     starts = ks.record_starts
-    profile = np.zeros(max(int(starts[-1]), 1), dtype=np.uint32)
-    records = np.zeros(max(len(starts) - 1, 1), dtype=DEPTH_RECORD)
-    kept, total = C.c_uint64(), C.c_uint64()
-    _chk(load().mf_filter_fastq_files_depth(ks._h, _enc(fq1), _enc(fq2), _enc(out1), _enc(out2), threshold, pair_mode, arr, len(devices),
-                                            profile.ctypes.data, records.ctypes.data, C.byref(kept), C.byref(total)))
-    return kept.value, total.value, profile[:int(starts[-1])], records[:len(starts) - 1]
+    P, R = int(starts[-1]), len(starts) - 1
+    profile = np.zeros(max(P, 1), dtype=np.uint32)
+    records = np.zeros(max(R, 1), dtype=DEPTH_RECORD)
+    kept, total = _files_call("mf_filter_fastq_files_depth", ks, fq1, fq2, out1, out2, threshold, pair_mode, devices, n_devices,
+                              profile.ctypes.data, records.ctypes.data)
+    return kept, total, profile[:P], records[:R]
 
 
 def filter_fastq_files_placed(ks: KmerSet, fq1: str, fq2: Optional[str], out1: str, out2: Optional[str],
@@ -628,18 +629,14 @@ def filter_fastq_files_placed(ks: KmerSet, fq1: str, fq2: Optional[str], out1: s
     """filter_fastq_files plus the placement on the bait of every mate that passes its own threshold (the pair rule decides only what
     is written).  -> (kept, total, base_depth u32[positions], records PLACE_RECORD[R], unplaced u64[2]: passing mates that are not
     placed, mates that do not pass)."""
-    if devices is None:
-        devices = list(range(n_devices))
-    arr = (C.c_int * len(devices))(*[int(d) for d in devices])
     starts = ks.record_starts
-    base_depth = np.zeros(max(int(starts[-1]), 1), dtype=np.uint32)
-    records = np.zeros(max(len(starts) - 1, 1), dtype=PLACE_RECORD)
+    P, R = int(starts[-1]), len(starts) - 1
+    base_depth = np.zeros(max(P, 1), dtype=np.uint32)
+    records = np.zeros(max(R, 1), dtype=PLACE_RECORD)
     unplaced = np.zeros(2, dtype=np.uint64)
-    kept, total = C.c_uint64(), C.c_uint64()
-    _chk(load().mf_filter_fastq_files_placed(ks._h, _enc(fq1), _enc(fq2), _enc(out1), _enc(out2), threshold, pair_mode, arr, len(devices),
-                                             base_depth.ctypes.data, records.ctypes.data, unplaced.ctypes.data, C.byref(kept),
-                                             C.byref(total)))
-    return kept.value, total.value, base_depth[:int(starts[-1])], records[:len(starts) - 1], unplaced
+    kept, total = _files_call("mf_filter_fastq_files_placed", ks, fq1, fq2, out1, out2, threshold, pair_mode, devices, n_devices,
+                              base_depth.ctypes.data, records.ctypes.data, unplaced.ctypes.data)
+    return kept, total, base_depth[:P], records[:R], unplaced
 
 
 def filter_fastq_files_pileup(ks: KmerSet, fq1: str, fq2: Optional[str], out1: str, out2: Optional[str],
@@ -648,20 +645,15 @@ def filter_fastq_files_pileup(ks: KmerSet, fq1: str, fq2: Optional[str], out1: s
     """filter_fastq_files plus the pile-up on the bait of every mate that passes its own threshold (the pair rule decides only what is
     written).  -> (kept, total, pileup PILEUP[positions], consensus u8[positions], records PILEUP_RECORD[R], unplaced u64[2]: passing
     mates that are not placed, mates that do not pass)."""
-    if devices is None:
-        devices = list(range(n_devices))
-    arr = (C.c_int * len(devices))(*[int(d) for d in devices])
     starts = ks.record_starts
     P, R = int(starts[-1]), len(starts) - 1
     pileup = np.zeros(max(P, 1), dtype=PILEUP)
     consensus = np.zeros(max(P, 1), dtype=np.uint8)
     records = np.zeros(max(R, 1), dtype=PILEUP_RECORD)
     unplaced = np.zeros(2, dtype=np.uint64)
-    kept, total = C.c_uint64(), C.c_uint64()
-    _chk(load().mf_filter_fastq_files_pileup(ks._h, _enc(fq1), _enc(fq2), _enc(out1), _enc(out2), threshold, pair_mode, arr, len(devices),
-                                             min_depth, pileup.ctypes.data, consensus.ctypes.data, records.ctypes.data,
-                                             unplaced.ctypes.data, C.byref(kept), C.byref(total)))
-    return kept.value, total.value, pileup[:P], consensus[:P], records[:R], unplaced
+    kept, total = _files_call("mf_filter_fastq_files_pileup", ks, fq1, fq2, out1, out2, threshold, pair_mode, devices, n_devices,
+                              min_depth, pileup.ctypes.data, consensus.ctypes.data, records.ctypes.data, unplaced.ctypes.data)
+    return kept, total, pileup[:P], consensus[:P], records[:R], unplaced
 
 
 def set_option(name: str, value) -> None:
