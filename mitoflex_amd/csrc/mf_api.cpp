@@ -148,10 +148,7 @@ static uint32_t env_u32(const char *name, uint32_t dflt)
 }
 
 // ----------------------------------------------------------------- options
-// How a screened pass is run.  Default: screen_kernel, then finish_kernel when the threshold is 1 and no hit counts are wanted
-// (mark_kernel + exact_kernel otherwise).  MF_PASS=split: always screen, mark, exact.  MF_PASS=serial: screen + finish
-// without overlapping consecutive passes (for comparison).
-// The switches that select WHICH KERNELS a pass runs live in one options block.  A production process never reads them from the
+// The switches that select WHICH KERNELS a pass runs (how: mf_passplan.h plan_pass) live in one options block.  A production process never reads them from the
 // environment: they are set through mf_set_option (the CLI's --option name=value), or -- for the test suite, bench.py and the profiling
 // scripts -- taken from the MF_* variables when MF_ENV_KNOBS=1 says so.  Every variant is parity-tested (tests/test_gpu_parity.py).
 struct PassOptions {
@@ -210,7 +207,6 @@ static void options_from_env_once()
     (void)done;
 }
 int depth_index_option() { return g_opt.depth_index.load(); }
-static int pass_kind() { options_from_env_once(); return g_opt.pass; }          // (looked up on every pass: bench.py times the serial form next to the default one in one process)
 
 int build_on_device(mf_kmerset *ks, int device, DevTables **out)
 {
@@ -611,8 +607,8 @@ int reads_finish(mf_reads *r, bool reuse, uint64_t n_words, uint64_t n_reads, ui
     r->cand_clean[0] = true;
     for (int i = 1; i < NSETS; i++) r->cand_clean[i] = false;          // (the twins are allocated and cleared on first use)
     for (int i = 0; i < NSETS; i++) {
-        if (!r->d_counters[i]) RCHK(hipHostMalloc(reinterpret_cast<void **>(&r->d_counters[i]), 3 * EXACT_MAX_GRID * 16, hipHostMallocDefault));
-        memset(r->d_counters[i], 0, 3 * EXACT_MAX_GRID * 16);             // (no kernel of this handle is in flight: every call ends synchronised)
+        if (!r->d_counters[i]) RCHK(hipHostMalloc(reinterpret_cast<void **>(&r->d_counters[i]), TallyLayout::bytes(), hipHostMallocDefault));
+        memset(r->d_counters[i], 0, TallyLayout::bytes());             // (no kernel of this handle is in flight: every call ends synchronised)
         RCHK(hipMemsetAsync(r->d_bits[i], 0, r->bitmap_bytes, st));
         if (!r->ev_screen[i]) RCHK(hipEventCreate(&r->ev_screen[i]));         // (attached to dispatches as completion events)
         if (!r->ev_finish[i]) RCHK(hipEventCreate(&r->ev_finish[i]));
@@ -764,129 +760,56 @@ static uint64_t algorithmic_bytes(const ReadsView &V) { return (2 * V.total_base
 
 // enqueue one pass.  ev (when non-null) holds six events that are attached to the kernels themselves (start/stop of
 // screen, mark, exact or finish): each pair reads that dispatch's own duration and the streams carry no extra packets.
-// `overlap`: a threshold-1 pass may leave its finish kernel running on the second stream (filter_common joins the streams).
-// `more`: another pass of the same call follows (its screen kernel is what this pass's later kernels run beside).
+// `overlap`, `more`: mf_passplan.h PassInputs (filter_common joins the streams a pass leaves its later kernels running on).
 // where the kernels of a pass leave their tallies: the buffer set's pinned block -- or, when the caller wants every pass's
 // tally (mf_filter_resident_passes), a block of that pass's own
 static unsigned long long *tally_of(mf_reads *r, int set) { return r->tally_override ? r->tally_override : r->d_counters[set]; }
-
-static int enqueue_pass(mf_reads *r, const KmerSetView &S, uint32_t thr, int mode, bool count_all, DevCtx *ctx, hipEvent_t *ev, bool overlap,
-                        bool more = false)
+// A buffer set's candidate bitmap follows on the set's first use (reads_finish) and is clean from then on: cleared when made, and the exact kernel clears what it consumes
+static int clean_cand(mf_reads *r, int q, hipStream_t st)
 {
-    r->sample_pass = false;
-    hipStream_t st = ctx->stream;
-    const int n_cu = ctx->n_cu;
+    if (!r->d_cand[q]) { size_t c = 0; HIPCHK(dev_reserve(r->d_cand[q], c, r->cap_bitmap, false)); r->cand_clean[q] = false; }
+    if (!r->cand_clean[q]) { HIPCHK(hipMemsetAsync(r->d_cand[q], 0, r->bitmap_bytes, st)); r->cand_clean[q] = true; }
+    return MF_OK;
+}
+static int enqueue_pass(mf_reads *r, const KmerSetView &S, uint32_t thr, int mode, bool count_all, DevCtx *ctx, hipEvent_t *ev, bool overlap, bool more = false)
+{
+    options_from_env_once();          // (the options are read on every pass, once: bench.py times the serial form next to the default one in one process)
+    const PassKnobs knobs{g_opt.pass, g_opt.finish_streams, g_opt.screen_streams, g_opt.split_pipe, g_opt.exact_co, g_opt.s8_finish};
+    const PassInputs in{(int)S.prot, (int)S.s, (int)S.stride, (int)S.kw, (int)S.k, (int)S.s8_finish, thr, mode, count_all, overlap, more, r->fb, r->flip, r->cur, NSETS};
+    const PassPlan P = plan_pass(knobs, in);
+    const int n_cu = ctx->n_cu, q = P.q; const bool finish = P.kind == PassKind::FINISH;
+    hipStream_t const streams[] = {ctx->stream, ctx->stream2, ctx->stream3, ctx->stream4}, ss = streams[(int)P.screen_on], sf = streams[(int)P.later_on];          // (PassStream's order)
+    const hipEvent_t done = P.two_streams ? r->ev_finish[q] : nullptr;          // completes with the pass's last kernel
     KernelTiming tm[3]; const KernelTiming *t0 = nullptr, *t1 = nullptr, *t2 = nullptr;
     if (ev) { for (int i = 0; i < 3; i++) tm[i] = KernelTiming{ev[2 * i], ev[2 * i + 1]}; t0 = &tm[0]; t1 = &tm[1]; t2 = &tm[2]; }
-    const int p = r->cur;
-    if (S.prot) {          // protein-space set: one kernel translates and probes every read (no screen exists in residue space)
-        HIPCHK(launch_pfilter(r->v, S, thr, count_all, r->d_bits[p], r->d_hits, tally_of(r, p), n_cu, st, t2));
-        return MF_OK;
-    }
-    const bool screened = (mode == MF_MODE_SCREENED) && S.s > 0;
-    // (stride-8 geometries, k < 28: twice the samples, several times the records -- measured faster through the candidate bitmap for a bait the LDS table
-    // screens well, 16.5 kbp: k = 21 0.314 against 0.319 ms a pass, k = 25 / 27 0.292 against 0.298.  Beyond ~20 kbp the candidate bitmap's exact kernel is
-    // what a pass waits for -- its LDS k-mer table fills up -- and screen + finish is faster: k = 21 33 kbp 0.50 -> 0.45, 50 kbp 0.74 -> 0.55, 100 kbp
-    // 1.88 -> 1.51, 350 kbp 3.03 -> 1.98, k = 25 100 kbp 1.68 -> 1.21: KmerSetView::s8_finish, profiles/r06/o_stride8_finish.txt)
-    // (round 3, after the stage-1 fields were fixed for 14-base samples: still the faster pass for stride 8 -- k = 21 0.299 vs 0.302-0.309 ms, k = 25 0.278-0.280 vs 0.281-0.283)
-    if (screened && pass_kind() != 1 && !r->prefer_split && thr == 1 && !count_all && (S.stride == 16 || pass_kind() == 2 || (g_opt.s8_finish < 0 ? S.s8_finish != 0 : g_opt.s8_finish == 1))) {
-        // Two launches: the screen records its stage-1 positives (and clears this pass's result bitmap on the side), the
-        // finish kernel settles them and sets the pass bits with atomics.  Pass i works on buffer set i mod 2; its finish
-        // kernel goes to the second stream and runs under the screen of pass i + 1, which uses the other set.
-        // (three buffer sets for pipelined passes: the screen of pass i + 3 waits for the finish kernels of pass i, not of pass i + 1 -- with two sets a
-        // finish chain that outlasts the next screen, as the two-word keys' does, held the screen after that: k = 41 0.243 -> 0.234 ms a pass, k = 63 0.257 -> 0.250 (k = 31
-        // 0.224 -> 0.222, 33 kbp 0.243 -> 0.237), profiles/r06/n_three_sets.txt.  A call of one pass -- a file-level call's batches -- keeps to two.)
-        // (Kept to the two-word keys: for k <= 32 it is worth 1-2 %, and with three sets two or three screens are in flight at a time, so that a launch
-        // lasts twice what a pass takes -- the per-launch figure bench.py's `roofline` reports for the headline would no longer say what the pass does.)
-        const bool two = overlap && pass_kind() == 0;
-        const int q = (p + 1) % (two && S.kw == 2 ? NSETS : 2);
-        if (!r->d_recs[q]) {
-            size_t c0 = 0, c1 = 0;
-            HIPCHK(dev_reserve(r->d_recs[q], c0, r->cap_recs, false));
-            HIPCHK(dev_reserve(r->d_rec_counts[q], c1, r->cap_rec_counts, false));
-        }
-        // The finish kernels are chains of memory latencies.  With few records (the benchmark's 0.5 % bait reads) they are over long
-        // before the next screen is and one stream carries them all; when they are what a pass waits for (bait-rich input: 2 % bait
-        // reads and more, seen in the last call's tallies) those of consecutive passes go to two streams and run side by side --
-        // 2 %: 0.303 -> 0.280 ms per pass, 10 %: 0.666 -> 0.596; at 0.5 % the same costs 2 % (0.208 -> 0.213).  MF_FINISH_STREAMS=1 / 2 forces.
-        const uint32_t fin_streams = (uint32_t)g_opt.finish_streams;
-        // (two-word keys, k >= 33: a finish kernel's probes are twice as long, and one stream's worth of them is not over when the next screen is --
-        // k = 41 0.2369 -> 0.2331 ms a pass, k = 63 0.2960 -> 0.2817: profiles/r05/c_k41_finish_streams_probe.txt)
-        const bool fin2 = fin_streams == 2 || (fin_streams == 0 && (r->finish_two || S.kw == 2));
-        const int odd = (r->flip ^= 1);
-        hipStream_t sf = two ? ((fin2 && odd) ? ctx->stream4 : ctx->stream2) : st;
-        // consecutive screens go to two streams in turn: nothing orders them against each other (different buffer sets), so the
-        // workgroups of the next screen take over the CUs as the last ones of this screen drain (MF_SCREEN_STREAMS=1: one stream)
-        const bool alt = g_opt.screen_streams == 2;
-        hipStream_t ss = (two && alt && odd) ? ctx->stream3 : st;
-        if (two) HIPCHK(hipStreamWaitEvent(ss, r->ev_finish[q], 0));           // the finish kernels of NSETS passes ago read this set
+    if (P.screen) {
+        size_t c0 = 0, c1 = 0;          // (the record list and count buffer of a set beyond the first follow on its first use, too)
+        if (!r->d_recs[q]) { HIPCHK(dev_reserve(r->d_recs[q], c0, r->cap_recs, false)); HIPCHK(dev_reserve(r->d_rec_counts[q], c1, r->cap_rec_counts, false)); }
+        if (P.wait_prev_finish) HIPCHK(hipStreamWaitEvent(ss, r->ev_finish[q], 0));
+        if (P.needs_cand && !finish) { const int rc = clean_cand(r, q, ss); if (rc) return rc; }          // (behind finish: on the later kernels' stream, below)
         // cross-stream order without marker packets in the screen's stream: the events ride on the dispatches themselves
         // (hipExtLaunchKernelGGL completion events); a separately recorded event costs the next dispatch ~5 us
         KernelTiming scr_done{nullptr, r->ev_screen[q]};
-        const KernelTiming *ts = t0 ? t0 : (two ? &scr_done : nullptr);
-        HIPCHK(launch_screen(r->v, S, r->d_recs[q], r->d_rec_counts[q], n_cu, ss, ts, r->d_bits[q], ((r->v.n_reads + 31) / 32 + 3) / 4));
-        if (two) { if (t0) HIPCHK(hipEventRecord(r->ev_screen[q], ss)); HIPCHK(hipStreamWaitEvent(sf, r->ev_screen[q], 0)); }
+        HIPCHK(launch_screen(r->v, S, r->d_recs[q], r->d_rec_counts[q], n_cu, ss, t0 ? t0 : (P.two_streams ? &scr_done : nullptr),
+                             P.screen_clears_bits ? r->d_bits[q] : nullptr, P.screen_clears_bits ? ((r->v.n_reads + 31) / 32 + 3) / 4 : 0));
+        if (P.two_streams) { if (t0) HIPCHK(hipEventRecord(r->ev_screen[q], ss)); HIPCHK(hipStreamWaitEvent(sf, r->ev_screen[q], 0)); }
+    }
 #ifdef MF_DEBUG_KNOBS              // timing experiment: the pass without its finish kernels (WRONG result bits)
-        static const uint32_t nofin = env_u32("MF_NO_FINISH", 0);
-        if (nofin) { if (two) HIPCHK(hipEventRecord(r->ev_finish[q], sf)); } else
+    static const uint32_t nofin = env_u32("MF_NO_FINISH", 0);
+    if (finish && nofin) { if (done) HIPCHK(hipEventRecord(done, sf)); } else
 #endif
-        {
-            // For k >= 48 (runs of four and more samples: fewer reads are settled by a run) phase 1 hands the reads that hold a bait s-mer outside
-            // any run to an exact kernel behind it, which deals a read's windows to eight lanes, instead of counting them on the one lane that met
-            // the s-mer: k = 63 0.283 -> 0.257 ms a pass.  Below that the third launch costs more than the tail it removes (k = 31 0.219 -> 0.226,
-            // k = 41 0.235 -> 0.248, 33 kbp bait 0.228 -> 0.262: profiles/r06/j_finish_exact_ab.txt).  The candidate bitmap of set q is clean
-            // (cleared when made, and the exact kernel clears what it consumes).
-#ifndef MF_FINISH_EXACT
-#define MF_FINISH_EXACT (S.k >= 48)
-#endif
-            uint32_t *cand = nullptr;
-            if (MF_FINISH_EXACT) {
-                if (!r->d_cand[q]) { size_t c = 0; HIPCHK(dev_reserve(r->d_cand[q], c, r->cap_bitmap, false)); r->cand_clean[q] = false; }
-                if (!r->cand_clean[q]) { HIPCHK(hipMemsetAsync(r->d_cand[q], 0, r->bitmap_bytes, sf)); r->cand_clean[q] = true; }
-                cand = r->d_cand[q];
-            }
-            HIPCHK(launch_finish(r->v, S, r->d_recs[q], r->d_rec_counts[q], r->d_bits[q], tally_of(r, q), n_cu, sf, t2, (two && !cand) ? r->ev_finish[q] : nullptr, cand));
-            if (cand) HIPCHK(launch_exact(r->v, S, cand, 1, false, r->d_bits[q], nullptr, tally_of(r, q) + 4 * (size_t)EXACT_MAX_GRID, n_cu, sf, nullptr, more, two ? r->ev_finish[q] : nullptr, true));
-        }
-        r->sample_pass = true;
-        r->cur = q;
-        return MF_OK;
+    if (P.kind == PassKind::PROTEIN) HIPCHK(launch_pfilter(r->v, S, thr, count_all, r->d_bits[P.q_out], r->d_hits, tally_of(r, P.q_out), n_cu, sf, t2));
+    else if (finish) {
+        if (P.exact_behind_finish) { const int rc = clean_cand(r, q, sf); if (rc) return rc; }
+        uint32_t *const cand = P.exact_behind_finish ? r->d_cand[q] : nullptr;
+        HIPCHK(launch_finish(r->v, S, r->d_recs[q], r->d_rec_counts[q], r->d_bits[q], tally_of(r, q), n_cu, sf, t2, cand ? nullptr : done, cand));
+        if (cand) HIPCHK(launch_exact(r->v, S, cand, 1, false, r->d_bits[q], nullptr, tally_of(r, q) + TallyLayout::region(2), n_cu, sf, nullptr, P.exact_coresident, done, true));
+    } else {          // (hit counts come from the one-stream pass alone)
+        uint32_t *const cand = P.needs_cand ? r->d_cand[q] : nullptr;
+        if (P.screen) HIPCHK(launch_mark(r->v, S, r->d_recs[q], r->d_rec_counts[q], cand, n_cu, sf, t1));
+        HIPCHK(launch_exact(r->v, S, cand, thr, count_all, r->d_bits[P.q_out], P.kind == PassKind::ONE_STREAM ? r->d_hits : nullptr, tally_of(r, P.q_out), n_cu, sf, t2, P.exact_coresident, done));
     }
-    // split / exhaustive: no per-pass memsets -- the exact kernel clears the candidate words it consumes, writes every
-    // result word and zeroes unused tally slots
-    const bool split_pipe = g_opt.split_pipe != 0;
-    const bool exact_co = g_opt.exact_co != 0;           // (tests: the co-resident exact kernel behind every screen)
-    if (screened && !count_all && overlap && split_pipe && pass_kind() != 2 && !r->split_serial) {
-        // The three-kernel pass, pipelined like the one above: pass i works on buffer set i mod 2 (records, candidate
-        // bitmap, result bitmap, tallies); its mark and exact kernels go to the second stream and run beside the screen of
-        // pass i + 1.  The exact kernel takes its co-resident form when a screen follows (a screen workgroup holds 128 KiB
-        // of every CU's LDS for the whole pass), its full form behind the last screen of the call.
-        const int q = (p + 1) % (S.kw == 2 ? NSETS : 2);
-        if (!r->d_recs[q]) {
-            size_t c0 = 0, c1 = 0;
-            HIPCHK(dev_reserve(r->d_recs[q], c0, r->cap_recs, false));
-            HIPCHK(dev_reserve(r->d_rec_counts[q], c1, r->cap_rec_counts, false));
-        }
-        if (!r->d_cand[q]) { size_t c = 0; HIPCHK(dev_reserve(r->d_cand[q], c, r->cap_bitmap, false)); r->cand_clean[q] = false; }
-        const bool alt = g_opt.screen_streams == 2;
-        const int odd = (r->flip ^= 1);
-        hipStream_t ss = (alt && odd) ? ctx->stream3 : st, sf = ctx->stream2;
-        HIPCHK(hipStreamWaitEvent(ss, r->ev_finish[q], 0));                    // the exact kernel of NSETS passes ago worked on this set
-        if (!r->cand_clean[q]) { HIPCHK(hipMemsetAsync(r->d_cand[q], 0, r->bitmap_bytes, ss)); r->cand_clean[q] = true; }
-        KernelTiming scr_done{nullptr, r->ev_screen[q]};
-        HIPCHK(launch_screen(r->v, S, r->d_recs[q], r->d_rec_counts[q], n_cu, ss, t0 ? t0 : &scr_done));
-        if (t0) HIPCHK(hipEventRecord(r->ev_screen[q], ss));
-        HIPCHK(hipStreamWaitEvent(sf, r->ev_screen[q], 0));
-        HIPCHK(launch_mark(r->v, S, r->d_recs[q], r->d_rec_counts[q], r->d_cand[q], n_cu, sf, t1));
-        HIPCHK(launch_exact(r->v, S, r->d_cand[q], thr, false, r->d_bits[q], nullptr, tally_of(r, q), n_cu, sf, t2, more || exact_co, r->ev_finish[q]));
-        r->cur = q;
-        return MF_OK;
-    }
-    // one stream, one buffer set (hit counts wanted, the exhaustive mode, MF_PASS=serial)
-    if (screened && !r->cand_clean[0]) { HIPCHK(hipMemsetAsync(r->d_cand[0], 0, r->bitmap_bytes, st)); r->cand_clean[0] = true; }
-    if (screened) HIPCHK(launch_screen(r->v, S, r->d_recs[0], r->d_rec_counts[0], n_cu, st, t0));
-    if (screened) HIPCHK(launch_mark(r->v, S, r->d_recs[0], r->d_rec_counts[0], r->d_cand[0], n_cu, st, t1));
-    HIPCHK(launch_exact(r->v, S, screened ? r->d_cand[0] : nullptr, thr, count_all, r->d_bits[p], r->d_hits, tally_of(r, p), n_cu, st, t2));
+    r->flip = P.flip; r->cur = P.cur; r->sample_pass = P.sample_pass;
     return MF_OK;
 }
 
@@ -929,15 +852,14 @@ int filter_common(const mf_kmerset *ks_, const mf_reads *reads_, uint32_t thr, i
     if (pipelined) HIPCHK(hipStreamWaitEvent(ctx->stream3, e_begin, 0));
     // every pass's own tally block when the caller wants them all (tests: a buffer-set race that corrupted only the middle passes
     // of a pipelined call would not show in the last pass's tally)
-    constexpr size_t TALLY_WORDS = 3 * (size_t)EXACT_MAX_GRID * 2;
     struct PinnedTmp { unsigned long long *p = nullptr; ~PinnedTmp() { if (p) (void)hipHostFree(p); } } all_tallies;
     if (pass_per_step) {
-        HIPCHK(hipHostMalloc(reinterpret_cast<void **>(&all_tallies.p), (size_t)steps * TALLY_WORDS * 8, hipHostMallocDefault));
-        memset(all_tallies.p, 0, (size_t)steps * TALLY_WORDS * 8);
+        HIPCHK(hipHostMalloc(reinterpret_cast<void **>(&all_tallies.p), (size_t)steps * TallyLayout::bytes(), hipHostMallocDefault));
+        memset(all_tallies.p, 0, (size_t)steps * TallyLayout::bytes());
     }
     struct OverrideReset { mf_reads *r; ~OverrideReset() { r->tally_override = nullptr; } } override_reset{r};
     for (int i = 0; i < steps; i++) {
-        if (pass_per_step) r->tally_override = all_tallies.p + (size_t)i * TALLY_WORDS;
+        if (pass_per_step) r->tally_override = all_tallies.p + (size_t)i * TallyLayout::words();
         rc = enqueue_pass(r, T->view, thr, mode, count_all, ctx, n_sampled && i % stride == 0 ? &ev[(size_t)(i / stride) * 6] : nullptr, pipelined, i + 1 < steps);
         if (rc) return rc;
     }
@@ -945,33 +867,16 @@ int filter_common(const mf_kmerset *ks_, const mf_reads *reads_, uint32_t thr, i
     // join: finish kernels still running on the second stream belong to this call (unrecorded events are no-ops)
     for (int i = 0; i < NSETS; i++) HIPCHK(hipStreamWaitEvent(st, r->ev_finish[i], 0));
     HIPCHK(hipEventRecord(e_end, st));
-    const bool two_halves = r->sample_pass;
-    const unsigned long long *part = pass_per_step ? all_tallies.p + (size_t)(steps - 1) * TALLY_WORDS : r->d_counters[r->cur];          // pinned host memory, complete once the stream is
+    const int regions = r->sample_pass ? TallyLayout::REGIONS : 1;          // (a screen + finish pass: phase 0, phase 1, the exact kernel behind them)
+    const unsigned long long *part = pass_per_step ? all_tallies.p + (size_t)(steps - 1) * TallyLayout::words() : r->d_counters[r->cur];          // pinned host memory, complete once the stream is
     if (out_bits) HIPCHK(hipMemcpyAsync(out_bits, r->d_bits[r->cur], ((r->v.n_reads + 31) / 32) * 4, hipMemcpyDeviceToHost, st));
     if (hits_out && r->v.n_reads) HIPCHK(hipMemcpyAsync(hits_out, r->d_hits, r->v.n_reads * 4, hipMemcpyDeviceToHost, st));
     lap("copies");
     HIPCHK(hipStreamSynchronize(st));
     lap("synced");
-    unsigned long long cnt[2] = {0, 0};
-    for (int i = 0; i < (two_halves ? 3 : 1) * EXACT_MAX_GRID; i++) { cnt[0] += part[2 * i]; cnt[1] += part[2 * i + 1]; }          // (a screen + finish pass: phase 0, phase 1, the exact kernel behind them)
-    if (pass_per_step)
-        for (int s = 0; s < steps; s++) {
-            const unsigned long long *q = all_tallies.p + (size_t)s * TALLY_WORDS;
-            uint64_t n = 0;
-            for (int i = 0; i < (two_halves ? 3 : 1) * EXACT_MAX_GRID; i++) n += q[2 * i];
-            pass_per_step[s] = n;
-        }
-    const bool adapt = g_opt.adapt != 0;          // (adapt = 0: measurements of the sample pass on bait-rich input)
-    if (adapt && !T->view.prot && mode == MF_MODE_SCREENED && T->view.s > 0 && r->v.n_reads >= 100000) {
-        // work items per read: ~0.025 at 0.5 % bait reads, 0.4 at 10 %, 0.8 at 20 %.  (Since a run start is left to the first lane that
-        // holds one, the two kinds of pass are within 5 % of each other from 2 % to 100 % bait reads; the switch stays for inputs
-        // that are nearly all bait.)
-        if (r->sample_pass) { if (cnt[1] > r->v.n_reads) r->prefer_split = true; r->finish_two = cnt[1] > r->v.n_reads / 20; }
-        else {                                                                                     // candidate reads per read
-            if (r->prefer_split && cnt[1] < r->v.n_reads / 8) r->prefer_split = false;
-            if (cnt[1] > r->v.n_reads / 20) r->split_serial = true; else if (cnt[1] < r->v.n_reads / 40) r->split_serial = false;
-        }
-    }
+    const TallyLayout::Totals cnt = TallyLayout::sum(part, regions);
+    for (int s = 0; pass_per_step && s < steps; s++) pass_per_step[s] = TallyLayout::sum(all_tallies.p + (size_t)s * TallyLayout::words(), regions).pass;
+    if (g_opt.adapt && !T->view.prot && mode == MF_MODE_SCREENED && T->view.s > 0) r->fb = adapt_after_call(r->fb, r->sample_pass, cnt.cand, r->v.n_reads);          // (adapt = 0: measurements of the sample pass on bait-rich input)
     if (stats) {
         memset(stats, 0, sizeof *stats);
         float tot = 0, scr = 0, mrk = 0, exa = 0, t;
@@ -984,8 +889,8 @@ int filter_common(const mf_kmerset *ks_, const mf_reads *reads_, uint32_t thr, i
             if (screened) { scr += span(e[0], e[1]); mrk += span(e[2], e[3]); }
             exa += span(e[4], e[5]);
         }
-        stats->n_reads = r->v.n_reads; stats->n_pass = cnt[0];
-        stats->n_candidates = (mode == MF_MODE_SCREENED && T->view.s > 0) ? cnt[1] : r->v.n_reads;
+        stats->n_reads = r->v.n_reads; stats->n_pass = cnt.pass;
+        stats->n_candidates = (mode == MF_MODE_SCREENED && T->view.s > 0) ? cnt.cand : r->v.n_reads;
         stats->ms_total = tot / steps;
         if (n_sampled) { stats->ms_screen = scr / n_sampled; stats->ms_mark = mrk / n_sampled; stats->ms_exact = exa / n_sampled; }
         stats->algorithmic_bytes = algorithmic_bytes(r->v);

@@ -135,19 +135,12 @@ struct mf_reads {
     // exists NSETS times and rotates: record lists, result bitmap, tally buffer.  `cur` holds the latest result.
     uint32_t *d_cand[NSETS] = {}, *d_bits[NSETS] = {};
     void *d_recs[NSETS] = {}; uint32_t *d_rec_counts[NSETS] = {};     // stage-1 positive records (screen -> finish / mark)
-    unsigned long long *d_counters[NSETS] = {};                       // 2 * EXACT_MAX_GRID tally pairs each, in pinned HOST memory: the kernels store
-                                                                      // their pair there directly and a call ends without a device-to-host copy
+    unsigned long long *d_counters[NSETS] = {};     // a tally block each (mf::TallyLayout), in pinned HOST memory: the kernels store their pair there directly and a call ends without a device-to-host copy
     hipEvent_t ev_screen[NSETS] = {}, ev_finish[NSETS] = {};          // ordering between the two streams
     hipEvent_t ev_call[2] = {};                                       // begin / end of a call's passes
     bool cand_clean[NSETS] = {}, sample_pass = false;     // sample_pass: the latest pass was a screen + finish one
-    // Bait-rich input (more than a few per cent of the reads are bait reads -- what the `bim` loop enriches towards) is better
-    // served by the candidate-bitmap pass: one thread per stage-1 record means several records per bait read, and the screen
-    // writes them all.  The choice follows the work the last call of this read set (the last batch of this device) saw.
-    bool prefer_split = false;
-    bool finish_two = false;          // bait-rich input (from the last call's tallies): the finish kernels of consecutive passes go to two streams
-    bool split_serial = false;      // ... and with very many candidates (> 5 % of the reads) its kernels do not fit beside the next screen: one stream
-    int cur = 0;
-    int flip = 0;               // parity of the pipelined passes enqueued so far (which of two streams a pass's screen / finish kernels take)
+    mf::PassFeedback fb;        // what the last call's tallies say about the input (mf_passplan.h)
+    int cur = 0, flip = 0;      // flip: parity of the pipelined passes enqueued so far (which of two streams a pass's screen / finish kernels take)
     unsigned long long *tally_override = nullptr;       // set per pass by filter_common when every pass's tally is wanted
     size_t bitmap_bytes = 0;
     // record assignment (mf_assign and the file-level call by record): the passing reads as a list, their records, the counters

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include "mf_common.h"
 #include "mf_kernels_cfg.h"
+#include "mf_passplan.h"
 
 namespace mf {
 
@@ -24,7 +25,7 @@ uint64_t screen_rec_cap_for(const ReadsView &R, int n_cu, int stride);          
 hipError_t launch_screen(const ReadsView &R, const KmerSetView &S, void *recs, uint32_t *rec_counts, int n_cu, hipStream_t st,
                          const KernelTiming *tm = nullptr, uint32_t *clear = nullptr, uint64_t clear_vec4 = 0);
 // threshold 1, no hit counts: two launches of finish_kernel (runs, then the rest) settle every stage-1 record and set the pass
-// bits (bits must be clean).  partials: 3 * EXACT_MAX_GRID tally pairs (phase 0, phase 1, the exact kernel behind them).
+// bits (bits must be clean).  partials: a pass's tally block (TallyLayout: phase 0, phase 1, the exact kernel behind them).
 // done (optional): an event that completes with the last finish kernel
 // cand (optional): a clean candidate bitmap -- phase 1 then marks the reads that hold a bait s-mer outside any run instead of counting their windows itself, and
 // the caller runs launch_exact(cand, thr = 1, merge = true) behind it (third tally region)

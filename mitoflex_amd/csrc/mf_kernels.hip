@@ -1917,7 +1917,7 @@ hipError_t launch_finish(const ReadsView &R, const KmerSetView &S, const void *r
     const int key = screen_grid_key(S.stride, S.front_mode, S.canon);
     const uint64_t lists = screen_grid_for(R, n_cu, key);
     if (lists == 0) {               // (an empty read set) nothing to settle: the tallies read zero and `done` still completes, as in launch_exact
-        (void)hipMemsetAsync(partials, 0, 3 * EXACT_MAX_GRID * 16, st);
+        (void)hipMemsetAsync(partials, 0, TallyLayout::bytes(), st);
         if (done) (void)hipEventRecord(done, st);
         return hipGetLastError();
     }

@@ -458,11 +458,12 @@ def test_bench_plain_run_dumps_what_it_timed(mf, ol, bait_text, tmp_path):
     assert np.array_equal(bits, obits.astype(np.float64))
 
 
-@pytest.mark.parametrize("k", [21, 31, 41])
+@pytest.mark.parametrize("k", [21, 31, 41, 63])
 def test_multi_pass_calls_match_oracle(mf, ol, bait_text, k):
     """A call with several passes pipelines them: the later kernels of pass i run beside the screen of pass i + 1 on a second
     stream, buffer sets rotate, and the exact kernel of all passes but the last takes its co-resident form.  What comes back
-    (the tally of the last pass, and the result bitmap a following single pass leaves) must not depend on any of that."""
+    (the tally of the last pass, and the result bitmap a following single pass leaves) must not depend on any of that.
+    (k = 63: the exact kernel behind the finish kernels, k >= 48, and with it the tally block's third region.)"""
     n = 200_000
     ks = mf.KmerSet.from_text(bait_text, k)
     reads = mf.Reads.synth(n, 150, seed=11, bait_text=bait_text, keep_host=True)
