@@ -411,6 +411,51 @@ int mf_filter_fastq_files_pileup(mf_kmerset *ks, const char *fq1, const char *fq
                                  uint32_t min_depth, mf_pileup_t *pileup, uint8_t *consensus,
                                  mf_pileup_record_t *records, uint64_t *unplaced, uint64_t *kept, uint64_t *total);
 
+/* ---- verification: how well every placed read agrees with the bait along its placement, and an identity cut on that score.
+ * Nucleotide sets only: every call below returns MF_E_ARG for a protein set.  No reference counterpart: the reference reads this off
+ * the NM tag and the CIGAR of `bwa mem`.
+ * Positions, records and placement are exactly those of the placement section, the coordinates of a read's bases those of the pile-up
+ * section.
+ * Score of a placed read: take a read of length L placed at (record j, strand, start).  Its base at read offset i lies at record
+ * coordinate c = start + i for strand 0 and c = start + (L - 1 - i) for strand 1; on strand 1 the letter is complemented.  The base is
+ * COMPARED when 0 <= c < len_j, the read base is a valid letter and the bait letter at c is valid.  A compared base is a MISMATCH when
+ * the oriented read letter differs from the bait letter.  compared and mismatches are the two counts.  The winning anchor's window lies
+ * inside both the read and the record and matches exactly, so compared >= k and mismatches <= compared - k: nothing ever divides by
+ * zero.  Overhangs, read Ns and invalid bait letters are not compared.  There is still no handling of indels: behind an insertion the
+ * shifted bases are mismatches, which is what the score is there to show.
+ * Cut: max_permille in 0 .. 1000 (more is MF_E_ARG).  A placed read is ACCEPTED iff
+ * (uint64_t)mismatches * 1000 <= (uint64_t)max_permille * compared, otherwise REJECTED.  A rejected read contributes NOTHING to base
+ * depth, to forward / reverse / over_begin / over_end, or to the pile-up counters.  It is not "unplaced": its mf_place_t keeps the real
+ * placement, and its mf_score_t says why it was cut.  At max_permille = 1000 every placed read is accepted, and every placement and
+ * pile-up output equals mf_place's and mf_pileup's bit for bit.
+ * Per read (mf_score_t): compared, mismatches; { 0, 0 } for a read that is not placed.
+ * Per record (mf_score_record_t): accepted / rejected = the placed reads of the record on either side of the cut; compared and
+ * mismatches are summed over the ACCEPTED reads; hist[b] counts ALL placed reads of the record, accepted and rejected, with
+ * min(mismatches, MF_SCORE_BINS - 1) == b -- read at 1000 permille, the histogram is what a cut is picked from.
+ * accepted == forward + reverse of the placement record; sum(hist) == accepted + rejected; sum(forward + reverse + rejected) +
+ * unplaced[0] + unplaced[1] == n_reads; compared == matches + mismatches and mismatches == mismatches of the pile-up record.
+ * File level: as for placement, every mate that passes its own threshold is scored, whether or not the pair rule keeps its pair; all
+ * counts add over mates and devices; the consensus is called once from the summed counts.  The output files are byte-identical to
+ * mf_filter_fastq_files_on's: a rejected read is still written.
+ * Limits: placement's limits apply; min_depth == 0 is MF_E_ARG as for the pile-up.  When pileup, consensus and pileup_records are all
+ * NULL a call allocates no pile-up counters and piles nothing.
+ * The bait's validity, one bit a position, is kept on each device beside its packed letters by the first verifying or pile-up call. */
+#define MF_SCORE_BINS 32
+typedef struct { uint32_t compared, mismatches; } mf_score_t;
+typedef struct { uint64_t accepted, rejected, compared, mismatches, hist[MF_SCORE_BINS]; } mf_score_record_t;
+/* one pass like mf_filter, then placement, score, cut and (when asked for) pile-up; out_bits / place_out / score_out (n_reads entries
+ * each) / base_depth (starts[R] u32) / place_records / pileup (starts[R] entries) / consensus (starts[R] bytes) / pileup_records /
+ * score_records (R entries each) / unplaced (2 u64) / stats each optional */
+int mf_verify(const mf_kmerset *ks, const mf_reads *reads, uint32_t threshold, int mode, uint32_t min_depth, uint32_t max_permille,
+              uint32_t *out_bits, mf_place_t *place_out, mf_score_t *score_out, uint32_t *base_depth, mf_place_record_t *place_records,
+              mf_pileup_t *pileup, uint8_t *consensus, mf_pileup_record_t *pileup_records, mf_score_record_t *score_records,
+              uint64_t *unplaced, mf_filter_stats_t *stats);
+/* mf_filter_fastq_files_on plus verified placement and pile-up over the whole input; the same ingest path; every output optional */
+int mf_filter_fastq_files_verified(mf_kmerset *ks, const char *fq1, const char *fq2, const char *out1, const char *out2,
+              uint32_t threshold, int pair_mode, const int *devices, int n_devices, uint32_t min_depth, uint32_t max_permille,
+              uint32_t *base_depth, mf_place_record_t *place_records, mf_pileup_t *pileup, uint8_t *consensus,
+              mf_pileup_record_t *pileup_records, mf_score_record_t *score_records, uint64_t *unplaced, uint64_t *kept, uint64_t *total);
+
 /* Options that select which kernels a filter pass runs (process-wide; every variant gives the same bits and is parity-tested):
  *   pass=default|split|serial   adapt=0|1   finish_streams=0|1|2   screen_streams=1|2   split_pipe=0|1   exact_co=0|1
  * and, read when a k-mer set is BUILT (ABI 5; every form gives the same bits -- tests force them on small baits):

@@ -162,15 +162,21 @@ def kmer_bait_map(threads: int, fasta_file: str, basedir: str, prefix: str,
     return stats, fq1, fq2
 
 
-def consensus_bait(fasta_file: str, fq1: str, fq2: Optional[str], out_fasta: str, kmer: int = 31, min_depth: int = 3):
+def consensus_bait(fasta_file: str, fq1: str, fq2: Optional[str], out_fasta: str, kmer: int = 31, min_depth: int = 3,
+                   max_permille: Optional[int] = None):
     """A polished bait for the next generation: the reads of (fq1, fq2) -- the kept reads of a bait step -- are placed on the bait
     `fasta_file` and piled up on the device (mitofilter.filter_fastq_files_pileup), and the consensus is written to `out_fasta` under the
     bait's record names: the reads' letter where at least `min_depth` bases agree on one, N where the most is tied, the bait's own
     letter in lower case elsewhere.  Returns the record summaries (mitofilter.PILEUP_RECORD: bases, matches, mismatches, called,
-    ambiguous, variants)."""
+    ambiguous, variants).
+    max_permille: when given (0 .. 1000), every placed read is first scored against the bait along its placement and piled only when
+    its mismatches are at most that many per thousand compared bases (mitofilter.filter_fastq_files_verified): reads of a diverged
+    copy -- a NUMT, a paralogue, a contaminant -- then stay out of the polished bait.  None: no read is scored."""
     from mitoflex_amd import mitofilter as mf
     if min_depth < 1:
         raise ValueError("min_depth is at least 1")
+    if max_permille is not None and not 0 <= int(max_permille) <= 1000:
+        raise ValueError("max_permille is a number from 0 to 1000")
     if kmer < 1:
         raise ValueError("kmer is at least 1")
     if path.abspath(out_fasta) == path.abspath(fasta_file):
@@ -179,9 +185,12 @@ def consensus_bait(fasta_file: str, fq1: str, fq2: Optional[str], out_fasta: str
     try:
         names, starts = ks.record_names, ks.record_starts
         with tempfile.TemporaryDirectory(prefix="consensus_bait_") as tmp:          # (the call writes its kept reads; they are not wanted)
-            _, _, _, consensus, records, _ = mf.filter_fastq_files_pileup(ks, fq1, fq2, path.join(tmp, "k.1.fq"),
-                                                                          path.join(tmp, "k.2.fq") if fq2 is not None else None, 1,
-                                                                          mf.PAIR_EITHER, min_depth=min_depth)
+            out1, out2 = path.join(tmp, "k.1.fq"), path.join(tmp, "k.2.fq") if fq2 is not None else None
+            if max_permille is None:
+                _, _, _, consensus, records, _ = mf.filter_fastq_files_pileup(ks, fq1, fq2, out1, out2, 1, mf.PAIR_EITHER, min_depth=min_depth)
+            else:
+                v = mf.filter_fastq_files_verified(ks, fq1, fq2, out1, out2, 1, mf.PAIR_EITHER, min_depth=min_depth, max_permille=int(max_permille))
+                consensus, records = v.consensus, v.pileup_records
     finally:
         ks.close()
     with open(out_fasta, "w") as f:

@@ -16,6 +16,7 @@
 //                     [--report FILE | --group-report FILE [--group-field N] [--group-sep C]
 //                      | --depth-report FILE [--depth-profile FILE] | --place-report FILE [--base-depth FILE]
 //                      | [--pileup FILE] [--consensus FILE] [--variants FILE] [--min-depth N]]
+//                      [--score-report FILE] [--max-mismatch PERMILLE]
 // which loads libmitofilter_hip.so (HIP kernels, gfx950) and prints the kept
 // read/pair count.  --report writes how many kept reads (mates one by one)
 // each bait record attracted as a TSV (record, name, reads; then the
@@ -32,7 +33,11 @@
 // baits) write what the placed mates' bases say: per position (name, 1-based position, bait letter, depth = A + C + G + T, A, C, G, T,
 // in the bait's forward letters), the consensus as FASTA under the bait's record names (called letters in upper case, N where the most
 // is tied, the bait's own letter in lower case below --min-depth, default 1), and the called positions that differ from the bait (name,
-// 1-based position, ref, alt, depth, alt count; include/mitofilter.h, mf_pileup).  It has no CPU fallback: without the library or a GPU it exits non-zero, which shell_call turns into a RuntimeError
+// 1-based position, ref, alt, depth, alt count; include/mitofilter.h, mf_pileup).  --score-report (alone or with
+// either of those two families) writes per record the placed reads' agreement with the bait along their placement: accepted, rejected,
+// compared, mismatches, mismatches per thousand, and a histogram of mismatches per read; --max-mismatch PERMILLE (with one of the two
+// families or with --score-report, 0 .. 1000) keeps every placed read with more mismatches per thousand compared bases out of the base depth, the placement
+// counts and the pile-up (include/mitofilter.h, mf_verify; the output FASTQ files are not changed by it).  It has no CPU fallback: without the library or a GPU it exits non-zero, which shell_call turns into a RuntimeError
 // (helper.py:82-86).
 #include "../../include/mitofilter.h"
 #include "mf_coldtrace.h"
@@ -446,12 +451,13 @@ static std::string exe_dir()
 // what the command line asks for (checked: one kind of report at most)
 struct BaitArgs {
     std::string bait, fq1, fq2, out1, out2, pair = "either", libpath, report, group_report, group_sep, depth_report, depth_profile, place_report, base_depth_file, pileup_file, consensus_file,
-                variants_file;
-    unsigned min_depth = 1, thr = 1;
+                variants_file, score_report;
+    unsigned min_depth = 1, thr = 1, max_permille = 1000;
     int group_field = -1, k = 0, devices = 1, gcode = 5; bool protein = false;
     std::vector<int> device_list;              // --device-list 2,3: these devices instead of 0 .. N - 1
     std::vector<std::pair<std::string, std::string>> options;      // --option pass=serial: how a filter pass is run (mf_set_option)
     bool grouped = false, depth = false, placed = false, piled = false;          // which report (grouped: `report` holds --group-report's file)
+    bool verified = false;                     // --score-report or --max-mismatch: the placed reads are scored (and cut) first
 };
 
 // what the library's call gave: the arrays the report files are written from
@@ -464,12 +470,13 @@ struct BaitResult {
     std::vector<mf_place_record_t> place_recs;
     std::vector<mf_pileup_t> pile;
     std::vector<uint8_t> consensus, letters;
+    std::vector<mf_score_record_t> score_recs;
 };
 
 // 0, or the exit code of a command line that cannot be run
 static int parse_bait_args(int argc, char **argv, BaitArgs &A)
 {
-    bool have_min_depth = false, have_sep = false;
+    bool have_min_depth = false, have_sep = false, have_max_mismatch = false;
     for (int a = 2; a < argc; a++) {
         std::string o = argv[a];
         auto need = [&](const char *name) -> std::string {
@@ -496,6 +503,12 @@ static int parse_bait_args(int argc, char **argv, BaitArgs &A)
             const std::string v = need("--min-depth"); char *end = nullptr; const unsigned long x = strtoul(v.c_str(), &end, 10);
             if (v.empty() || *end || v[0] == '-' || x < 1 || x > 0xFFFFFFFFul) { fprintf(stderr, "error: --min-depth wants a depth from 1\n"); return 1; }
             A.min_depth = (unsigned)x; have_min_depth = true;
+        }
+        else if (o == "--score-report") A.score_report = need("--score-report");
+        else if (o == "--max-mismatch") {
+            const std::string v = need("--max-mismatch"); char *end = nullptr; const unsigned long x = strtoul(v.c_str(), &end, 10);
+            if (v.empty() || *end || v[0] < '0' || v[0] > '9' || x > 1000) { fprintf(stderr, "error: --max-mismatch wants mismatches per thousand compared bases, from 0 to 1000\n"); return 1; }
+            A.max_permille = (unsigned)x; have_max_mismatch = true;
         }
         else if (o == "--group-field") {
             const std::string v = need("--group-field"); char *end = nullptr; const long x = strtol(v.c_str(), &end, 10);
@@ -525,6 +538,7 @@ static int parse_bait_args(int argc, char **argv, BaitArgs &A)
               " [--pair either|both] [--devices N | --device-list D0,D1,..] [--option name=value ..]\n"
               "       [--report FILE | --group-report FILE [--group-field N] [--group-sep C] | --depth-report FILE [--depth-profile FILE]\n"
               "        | --place-report FILE [--base-depth FILE] | [--pileup FILE] [--consensus FILE] [--variants FILE] [--min-depth N]]\n"
+              "       [--score-report FILE] [--max-mismatch PERMILLE]   (with or without the placement or the pile-up reports)\n"
               "       fastfilter bait --protein --bait PROTEINS.fa [--code 5] [-k 9] ...   (six-frame peptide k-mers)\n", stderr);
         return 1;
     }
@@ -543,6 +557,15 @@ static int parse_bait_args(int argc, char **argv, BaitArgs &A)
         return 1;
     }
     if (have_min_depth && !piled) { fprintf(stderr, "error: --min-depth needs --pileup, --consensus or --variants\n"); return 1; }
+    if (have_max_mismatch && !placed && !piled && A.score_report.empty()) {
+        fprintf(stderr, "error: --max-mismatch needs --place-report, --base-depth, --pileup, --consensus, --variants or --score-report\n");
+        return 1;
+    }
+    if (!A.score_report.empty() && (depth || A.protein || !A.report.empty() || !A.group_report.empty())) {
+        fprintf(stderr, "error: --score-report needs a nucleotide bait and cannot be combined with --report, --group-report, --depth-report, --depth-profile or --protein\n");
+        return 1;
+    }
+    A.verified = have_max_mismatch || !A.score_report.empty();
     if (A.group_report.empty() && (A.group_field >= 0 || have_sep)) { fprintf(stderr, "error: --group-field and --group-sep need --group-report\n"); return 1; }
     if (!have_sep) A.group_sep = "_";
     if (A.k == 0) A.k = A.protein ? 9 : 31;
@@ -610,7 +633,7 @@ static int bait_run(const BaitArgs &A, BaitResult &R, mf_kmerset **ks_out, declt
     const int pair_mode = A.pair == "both" ? MF_PAIR_BOTH : MF_PAIR_EITHER;
     auto files = [&](auto call, auto... outs) { return call(ks, fq1, fq2, out1, out2, A.thr, pair_mode, device_list.data(), (int)device_list.size(), outs..., &R.kept, &R.total); };
     int rc;
-    if (A.piled || A.placed || A.depth) {
+    if (A.piled || A.placed || A.depth || A.verified) {
         SYM(mf_device_count) SYM(mf_kmerset_record_starts)
         if (A.depth) {          // (the identity grouping: the records' own names, protein sets included)
             SYM(mf_kmerset_group_count) SYM(mf_kmerset_group_name)
@@ -622,7 +645,16 @@ static int bait_run(const BaitArgs &A, BaitResult &R, mf_kmerset **ks_out, declt
         if (rc == MF_OK) rc = fetch_starts(ks, p_mf_kmerset_record_starts, R.names.size(), R.starts);
         if (rc == MF_OK) default_devices(p_mf_device_count, A.devices, device_list);
         const size_t positions = rc == MF_OK ? (size_t)std::max<uint64_t>(R.starts.back(), 1) : 1, n_rec = std::max<size_t>(R.names.size(), 1);
-        if (A.piled) {
+        if (A.verified) {          // the placed reads scored and cut; then what the family asks for, from the accepted ones
+            SYM(mf_kmerset_bait_letters) SYM(mf_filter_fastq_files_verified)
+            R.score_recs.assign(n_rec, mf_score_record_t{});
+            if (A.piled) { R.pile.assign(positions, mf_pileup_t{}); R.consensus.assign(positions, 0); R.letters.assign(positions, 0); }
+            if (A.placed) { R.profile.assign(positions, 0); R.place_recs.assign(n_rec, mf_place_record_t{}); }
+            if (rc == MF_OK && A.piled) rc = p_mf_kmerset_bait_letters(ks, R.letters.data(), R.letters.size(), nullptr);
+            if (rc == MF_OK)
+                rc = files(p_mf_filter_fastq_files_verified, A.min_depth, A.max_permille, A.placed ? R.profile.data() : nullptr, A.placed ? R.place_recs.data() : nullptr,
+                           A.piled ? R.pile.data() : nullptr, A.piled ? R.consensus.data() : nullptr, (mf_pileup_record_t *)nullptr, R.score_recs.data(), R.unplaced);
+        } else if (A.piled) {
             SYM(mf_kmerset_bait_letters) SYM(mf_filter_fastq_files_pileup)
             R.pile.assign(positions, mf_pileup_t{}); R.consensus.assign(positions, 0); R.letters.assign(positions, 0);
             if (rc == MF_OK) rc = p_mf_kmerset_bait_letters(ks, R.letters.data(), R.letters.size(), nullptr);
@@ -676,7 +708,8 @@ static bool write_reports(const BaitArgs &A, const BaitResult &R)
         && write_file(A.base_depth_file, "base depth", [&](FILE *f) { return write_base_depth(f, R.names, R.starts, R.profile.data()); })
         && write_file(A.pileup_file, "pile-up", [&](FILE *f) { return write_pileup(f, R.names, R.starts, R.letters.data(), R.pile.data()); })
         && write_file(A.consensus_file, "consensus", [&](FILE *f) { return write_consensus(f, R.names, R.starts, R.consensus.data()); })
-        && write_file(A.variants_file, "variants", [&](FILE *f) { return write_variants(f, R.names, R.starts, R.letters.data(), R.pile.data(), R.consensus.data()); });
+        && write_file(A.variants_file, "variants", [&](FILE *f) { return write_variants(f, R.names, R.starts, R.letters.data(), R.pile.data(), R.consensus.data()); })
+        && write_file(A.score_report, "score report", [&](FILE *f) { return write_score_report(f, R.names, R.starts, R.score_recs.data()); });
 }
 
 static int bait_main(int argc, char **argv)

@@ -69,8 +69,11 @@ struct DevTables {
     uint32_t *rep = nullptr, *pos_rep = nullptr; mf::DepthItem *ditems = nullptr; uint32_t n_ditems = 0; uint64_t dcnt_n = 0;
     // placement (mf_place), built by the first placement call: the anchor of every slot and the record starts (R + 1) the kernels read
     mf::Anchor *anchor = nullptr; uint64_t *place_starts = nullptr; bool place_built = false;
-    // pile-up (mf_pileup), kept by the first pile-up call: the bait's packed bases and run lengths, which the call kernel reads
-    uint32_t *pile_words = nullptr; uint8_t *pile_runlen = nullptr; bool pile_built = false;
+    // pile-up (mf_pileup), kept by the first pile-up call: the bait's packed bases and run lengths, which the call kernel reads, and the
+    // bait's validity one bit a position, which the verifying placement reads beside the bases (pile_words_n / pile_valid_n words, each
+    // padded by one)
+    uint32_t *pile_words = nullptr; uint8_t *pile_runlen = nullptr; uint32_t *pile_valid = nullptr; bool pile_built = false;
+    uint64_t pile_words_n = 0, pile_valid_n = 0;
     // frees one table / every table (the current device is the tables')
     template <class T> static hipError_t drop(T *&p) { const hipError_t e = hipFree(p); p = nullptr; return e; }
     void release()
@@ -78,7 +81,7 @@ struct DevTables {
         drop(keys); drop(bloom); drop(stab); drop(kbloom); drop(kbloom_co); drop(plut); drop(front2); drop(front3); drop(pre);
         drop(owner); drop(gowner); drop(rep); drop(pos_rep); drop(ditems);
         drop(anchor); drop(place_starts); place_built = false;
-        drop(pile_words); drop(pile_runlen); pile_built = false;
+        drop(pile_words); drop(pile_runlen); drop(pile_valid); pile_built = false;
     }
 };
 struct mf_kmerset {
@@ -154,6 +157,7 @@ struct mf_reads {
     mf::PileOut *rpos_pile() const { return static_cast<mf::PileOut *>(d_rpos); }
     uint8_t *rpos_consensus(uint64_t positions) const { return static_cast<uint8_t *>(d_rpos) + positions * sizeof(mf::PileOut); }
     mf::PlaceOut *d_place = nullptr; size_t cap_place = 0;          // mf_place's per-read results
+    mf::ScoreOut *d_score = nullptr; size_t cap_score = 0;          // mf_verify's per-read scores
     // capacities (bytes), so that a handle can be refilled batch after batch without touching the allocator
     size_t cap_words = 0, cap_offsets = 0, cap_npos = 0, cap_bitmap = 0, cap_recs = 0, cap_rec_counts = 0, cap_hits = 0, cap_npos_blk = 0, cap_off_blk = 0;
 };

@@ -13,6 +13,16 @@ constexpr uint32_t PLACE_NONE = 0xFFFFFFFFu;         // MF_PLACE_NONE
 constexpr uint32_t PLACE_CLAMP = 0xFFFFFFFEu;        // the largest base depth reported
 struct alignas(8) Anchor { uint32_t pos, rb; };          // position inside the record (ANCHOR_NONE: no anchor), record << 1 | b
 struct PlaceOut { uint32_t record, strand; int32_t start, end; uint32_t votes, windows; };       // mf_place_t
+struct ScoreOut { uint32_t compared, mismatches; };      // mf_score_t
+constexpr uint32_t SCORE_BINS = 32;                      // MF_SCORE_BINS
+constexpr uint32_t SCORE_GATHERED = 1 + SCORE_BINS;      // counters a record that a verifying launch gathers behind placement's: rejected, the bins
+// What a verifying launch takes beside a placing one.  bait_words / bait_valid: the bait's packed letters and its validity, one bit a
+// position; *_last: the index of each array's last word (the 16-base compare clamps to it).  score (optional): n_reads entries, zeroed.
+// sums: compared, mismatches of every record, 2 counters each, summed over the ACCEPTED reads.
+struct PlaceVerify {
+    const uint32_t *bait_words; uint64_t bait_words_last; const uint32_t *bait_valid; uint64_t bait_valid_last;
+    uint32_t max_permille; ScoreOut *score; unsigned long long *sums;
+};
 
 // Anchor table, indexed by the slot of the key table: anchor[slot] = { the window's position inside its record, record << 1 | b } when
 // exactly one valid bait window holds the key and that window is not its own reverse complement (b: 1 when the bait's reverse
@@ -31,9 +41,13 @@ hipError_t launch_max_read_len(const uint64_t *offsets, uint64_t n_reads, unsign
 // pile (optional): 4 * B.total counters, [position][A, C, G, T] -- the pile-up.  Every valid base of a placed read that lies inside its
 // record adds 1 to the counter of its position and letter, complemented on strand 1 (the bait's forward letters); the other outputs
 // are the same with and without it.
+// verify (optional): every placed read is scored against the bait along its placement before anything of it is counted (mf_score.h), and
+// one whose mismatches * 1000 exceed max_permille * compared is REJECTED: it adds to no counter above, only to its record's `rejected`.
+// counts then holds SCORE_GATHERED * n_rec counters more behind the 4 * n_rec + 1: rejected and the SCORE_BINS bins of min(mismatches, 31)
+// of every record's placed reads, accepted or not.
 hipError_t launch_place(const ReadsView &R, const KmerSetView &S, const Anchor *anchor, const uint64_t *rec_start, const uint32_t *list,
                         const unsigned long long *n_list, uint32_t n_rec, PlaceOut *place, unsigned long long *diff, unsigned long long *counts,
-                        unsigned long long *pile, int n_cu, hipStream_t st);
+                        unsigned long long *pile, const PlaceVerify *verify, int n_cu, hipStream_t st);
 // Base depth from the difference counters: depth[p] = diff[0] + .. + diff[p] for p < total, clamped into `depth` (optional); rec_sums
 // (optional, zeroed by the caller): covered and base_sum of every record, 2 counters each.  partial: place_scan_tiles(total) + 1 words.
 uint64_t place_scan_tiles(uint64_t total);

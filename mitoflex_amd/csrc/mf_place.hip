@@ -12,6 +12,11 @@
 //                          the clipped ends of the read's footprint.  With PILE the wave then walks the placed read's bases 64 at a time
 //                          (pile_bases): letter from the packed words, N through the read's has_n bit and the invalid-position index,
 //                          complement on strand 1, clip to the record, one 64-bit add into [position][letter].
+//                          With VERIFY the wave first scores the winner against the bait (score_read, mf_score.h): lanes take the
+//                          clipped footprint sixteen bases at a time -- the read's word funnel-shifted (mirrored and complemented on
+//                          strand 1) against the bait's, masked by length, clip and the bait's validity bits --, one wave reduction,
+//                          then the cut; a rejected read keeps its placement and its score and bumps only `rejected` and its bin,
+//                          and pile_bases does not run for it.
 //   place_scan_reduce_kernel, place_scan_partials_kernel, place_profile_kernel
 //                          base depth = inclusive scan of the difference counters (a -1 that lands on the next record's first position
 //                          is right under a global scan: no segmentation): tile sums, their exclusive scan, then per tile the scan, the
@@ -20,6 +25,7 @@
 //                          sums through the same record walk (RecordWalk).
 #include "mf_place.h"
 #include "mf_tally_dev.h"
+#include "mf_score.h"
 #include <algorithm>
 
 namespace mf {
@@ -88,19 +94,51 @@ __device__ __forceinline__ void pile_bases(const ReadsView &R, uint64_t b0, bool
     }
 }
 
-template <int KW, bool PILE>
+// What a verifying launch is given beside a placing one (nothing otherwise: the plain instantiations take no argument more than before).
+template <bool VERIFY> struct VerifyArgs {};
+template <> struct VerifyArgs<true> {
+    ScoreBait bait; uint32_t max_permille;
+    ScoreOut *__restrict__ score;                  // optional, n_reads entries, zeroed
+    unsigned long long *__restrict__ sums;         // compared, mismatches of every record's accepted reads
+};
+
+// The score of the placed read (mf_score.h): lanes take the clipped footprint sixteen bases at a time, a read with an invalid base goes
+// base by base; one wave reduction of the packed pair.  Every lane returns the read's (mismatches << 32) | compared.
+__device__ __forceinline__ unsigned long long score_read(const ReadsView &R, uint64_t b0, bool hasn, uint64_t L, uint32_t strand, int64_t start, uint64_t s0,
+                                                         int64_t len, const ScoreBait &B, int lane)
+{
+    unsigned long long acc = 0;
+    if (!hasn) {
+        int64_t lo, hi;
+        score_footprint(L, start, len, lo, hi);
+        const uint64_t chunks = (uint64_t)(hi - lo + 15) >> 4;
+        const uint64_t r_last = R.n_words ? R.n_words - 1 : 0;
+        for (uint64_t t = (uint64_t)lane; t < chunks; t += 64) acc += score_chunk16(R.words, r_last, b0, L, strand, start, B, s0, lo, hi, t);
+    } else {
+        for (uint64_t i = (uint64_t)lane; i < L; i += 64) {
+            const uint64_t g = b0 + i, ni = npos_lower_bound(R, g);
+            if (ni < R.n_npos && R.npos[ni] == g) continue;                                                             // an N is not compared
+            acc += score_base(R.words, b0, L, strand, start, B, s0, len, i);
+        }
+    }
+    return wave_sum_u64(acc);
+}
+
+template <int KW, bool PILE, bool VERIFY>
 __global__ void __launch_bounds__(ASSIGN_BLOCK)
 place_kernel(ReadsView R, KmerSetView S, const Anchor *__restrict__ anchor, const uint64_t *__restrict__ rec_start, const uint32_t *__restrict__ list,
              const unsigned long long *__restrict__ n_list_p, uint32_t n_rec, PlaceOut *__restrict__ place, unsigned long long *__restrict__ diff,
-             unsigned long long *__restrict__ counts, unsigned long long *__restrict__ pile)
+             unsigned long long *__restrict__ counts, unsigned long long *__restrict__ pile, VerifyArgs<VERIFY> V)
 {
     __shared__ uint32_t s_hist[HIST_MAX];
-    GatheredCounts cnt(s_hist, counts, 4 * n_rec + 1);      // forward, reverse, over_begin, over_end of every record; not placed
+    // forward, reverse, over_begin, over_end of every record; not placed; with VERIFY behind them rejected and the 32 bins of every record
+    GatheredCounts cnt(s_hist, counts, 4 * n_rec + 1 + (VERIFY ? SCORE_GATHERED * n_rec : 0u));
     cnt.hist_begin();
     NucWindows<KW> src(R, S, nullptr);
     const int lane = threadIdx.x & 63;
     const uint64_t n_list = *n_list_p;
     const uint64_t n_waves = (uint64_t)gridDim.x * (ASSIGN_BLOCK / 64);
+    uint32_t sum_j = 0; unsigned long long sum_v = 0;        // (lane 0, VERIFY) the packed sums of a run of accepted reads on one record
     for (uint64_t i = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6; i < n_list; i += n_waves) {
         const uint32_t r = list[i];
         const uint64_t np = src.begin(r);                    // windows; the read has np + k - 1 bases when np > 0
@@ -133,6 +171,19 @@ place_kernel(ReadsView R, KmerSetView S, const Anchor *__restrict__ anchor, cons
             if (!tally.overflow) break;
             lo_bound = tally.next_bound();
         }
+        // VERIFY: the read is scored before anything of it is counted; a rejected read then counts nowhere but in rejected and its bin
+        uint32_t compared = 0, mismatches = 0; bool accept = true;
+        if constexpr (VERIFY) {
+            if (best_cnt && !tie) {                          // (the winner is wave-uniform: into scalar registers)
+                const uint32_t rs = __builtin_amdgcn_readfirstlane((uint32_t)(best_key >> 32));
+                const int32_t start = (int32_t)__builtin_amdgcn_readfirstlane((uint32_t)best_key);
+                const uint64_t s0 = rec_start[rs >> 1];
+                const unsigned long long sc = score_read(R, src.b0, src.hasn, np + S.k - 1, rs & 1u, (int64_t)start, s0, (int64_t)(rec_start[(rs >> 1) + 1] - s0),
+                                                         V.bait, lane);
+                compared = __builtin_amdgcn_readfirstlane((uint32_t)sc); mismatches = __builtin_amdgcn_readfirstlane((uint32_t)(sc >> 32));
+                accept = score_accepts(compared, mismatches, V.max_permille);
+            }
+        }
         if (lane == 0) {
             PlaceOut out{PLACE_AMBIGUOUS, 0u, 0, 0, 0u, windows};
             if (best_cnt && !tie) {
@@ -141,22 +192,40 @@ place_kernel(ReadsView R, KmerSetView S, const Anchor *__restrict__ anchor, cons
                 const uint64_t s0 = rec_start[j];
                 const int64_t len = (int64_t)(rec_start[j + 1] - s0);
                 out = PlaceOut{j, rs & 1u, (int32_t)start, (int32_t)end, best_cnt, windows};
-                // the winning anchor's window lies inside the record and inside the read: 0 <= begin < last <= len
-                atomicAdd(&diff[s0 + (uint64_t)(start > 0 ? start : 0)], 1ull);
-                atomicAdd(&diff[s0 + (uint64_t)(end < len ? end : len)], ~0ull);
-                cnt.bump(4 * j + (rs & 1u));
-                if (start < 0) cnt.add(4 * j + 2, 1);
-                if (end > len) cnt.add(4 * j + 3, 1);
+                if (accept) {
+                    // the winning anchor's window lies inside the record and inside the read: 0 <= begin < last <= len
+                    atomicAdd(&diff[s0 + (uint64_t)(start > 0 ? start : 0)], 1ull);
+                    atomicAdd(&diff[s0 + (uint64_t)(end < len ? end : len)], ~0ull);
+                    cnt.bump(4 * j + (rs & 1u));
+                    if (start < 0) cnt.add(4 * j + 2, 1);
+                    if (end > len) cnt.add(4 * j + 3, 1);
+                }
+                if constexpr (VERIFY) {
+                    const uint32_t g0 = 4 * n_rec + 1 + SCORE_GATHERED * j;
+                    if (!accept) cnt.add(g0, 1);
+                    cnt.add(g0 + 1 + (mismatches < SCORE_BINS - 1 ? mismatches : SCORE_BINS - 1), 1);
+                    if (accept) {
+                        if (sum_v && sum_j != j) { atomicAdd(&V.sums[2 * sum_j], sum_v & 0xFFFFFFFFull); atomicAdd(&V.sums[2 * sum_j + 1], sum_v >> 32); sum_v = 0; }
+                        // (a run's packed halves stay below 2^32: flushed before either could carry)
+                        if ((sum_v & 0xFFFFFFFFull) + compared > 0xFFFFFFFFull || (sum_v >> 32) + mismatches > 0xFFFFFFFFull) {
+                            atomicAdd(&V.sums[2 * sum_j], sum_v & 0xFFFFFFFFull); atomicAdd(&V.sums[2 * sum_j + 1], sum_v >> 32); sum_v = 0;
+                        }
+                        sum_j = j; sum_v += ((unsigned long long)mismatches << 32) | compared;
+                    }
+                    if (V.score) V.score[r] = ScoreOut{compared, mismatches};
+                }
             } else cnt.bump(4 * n_rec);
             if (place) place[r] = out;
         }
-        if (PILE && best_cnt && !tie) {                      // (the winner is wave-uniform: into scalar registers)
+        if (PILE && best_cnt && !tie && accept) {            // (the winner is wave-uniform: into scalar registers)
             const uint32_t rs = __builtin_amdgcn_readfirstlane((uint32_t)(best_key >> 32));
             const int32_t start = (int32_t)__builtin_amdgcn_readfirstlane((uint32_t)best_key);
             const uint64_t s0 = rec_start[rs >> 1];
             pile_bases(R, src.b0, src.hasn, np + S.k - 1, rs & 1u, (int64_t)start, s0, (int64_t)(rec_start[(rs >> 1) + 1] - s0), pile, lane);
         }
     }
+    if constexpr (VERIFY)
+        if (lane == 0 && sum_v) { atomicAdd(&V.sums[2 * sum_j], sum_v & 0xFFFFFFFFull); atomicAdd(&V.sums[2 * sum_j + 1], sum_v >> 32); }
     cnt.hist_end(lane);
 }
 
@@ -349,15 +418,24 @@ hipError_t launch_max_read_len(const uint64_t *offsets, uint64_t n_reads, unsign
 
 hipError_t launch_place(const ReadsView &R, const KmerSetView &S, const Anchor *anchor, const uint64_t *rec_start, const uint32_t *list,
                         const unsigned long long *n_list, uint32_t n_rec, PlaceOut *place, unsigned long long *diff, unsigned long long *counts,
-                        unsigned long long *pile, int n_cu, hipStream_t st)
+                        unsigned long long *pile, const PlaceVerify *verify, int n_cu, hipStream_t st)
 {
     if (!R.n_reads) return hipSuccess;
     // the launch shape of launch_assign: four workgroups (32 waves) a CU at most, never more waves than reads
     const uint64_t waves = std::min<uint64_t>((uint64_t)(n_cu > 0 ? n_cu : 1) * 32, R.n_reads);
     const unsigned grid = grid_of(waves, ASSIGN_BLOCK / 64);
-#define PLACE_LAUNCH(KW, PILE) hipLaunchKernelGGL((place_kernel<KW, PILE>), dim3(grid), dim3(ASSIGN_BLOCK), 0, st, R, S, anchor, rec_start, list, n_list, n_rec, place, diff, counts, pile)
-    if (S.kw == 1) { if (pile) PLACE_LAUNCH(1, true); else PLACE_LAUNCH(1, false); }
-    else { if (pile) PLACE_LAUNCH(2, true); else PLACE_LAUNCH(2, false); }
+#define PLACE_LAUNCH(KW, PILE, VERIFY, V) hipLaunchKernelGGL((place_kernel<KW, PILE, VERIFY>), dim3(grid), dim3(ASSIGN_BLOCK), 0, st, R, S, anchor, rec_start, list, n_list, n_rec, place, diff, counts, pile, V)
+    if (verify) {
+        VerifyArgs<true> V;
+        V.bait = ScoreBait{verify->bait_words, verify->bait_words_last, verify->bait_valid, verify->bait_valid_last};
+        V.max_permille = verify->max_permille; V.score = verify->score; V.sums = verify->sums;
+        if (S.kw == 1) { if (pile) PLACE_LAUNCH(1, true, true, V); else PLACE_LAUNCH(1, false, true, V); }
+        else { if (pile) PLACE_LAUNCH(2, true, true, V); else PLACE_LAUNCH(2, false, true, V); }
+    } else {
+        const VerifyArgs<false> V;
+        if (S.kw == 1) { if (pile) PLACE_LAUNCH(1, true, false, V); else PLACE_LAUNCH(1, false, false, V); }
+        else { if (pile) PLACE_LAUNCH(2, true, false, V); else PLACE_LAUNCH(2, false, false, V); }
+    }
 #undef PLACE_LAUNCH
     return hipGetLastError();
 }

@@ -1,6 +1,6 @@
 // libmitofilter_hip: the reports on the reads that pass the filter -- reads per bait record (mf_assign), per group of records
 // (mf_assign_groups), k-mer depth along the records (mf_depth), position, strand and base depth (mf_place), base counts, consensus and
-// variants (mf_pileup) -- and their file-level calls.
+// variants (mf_pileup), per-read mismatches and an identity cut on the placed reads (mf_verify) -- and their file-level calls.
 // Each runs behind a filter pass of mf_api.cpp on the read set that still holds the pass's bitmap; the kernels are mf_assign.hip's and
 // mf_place.hip's.
 #include "mf_api_internal.h"
@@ -356,7 +356,9 @@ static int place_tables(mf_kmerset *ks, int device, DevTables *T)
     return MF_OK;
 }
 
-// The bait's packed bases and run lengths beside the anchor table: kept by the first pile-up call on `device`, under the set's lock.
+// The bait's packed bases and run lengths beside the anchor table, and its validity one bit a position (runlen != 0): kept by the first
+// pile-up or verifying call on `device`, under the set's lock.  The packed bases and the validity bits are each padded by a zero word:
+// the second word of the 16-base compare's funnel read (mf_score.h) exists wherever its first does.
 static int pileup_tables(mf_kmerset *ks, int device, DevTables *T)
 {
     int rc = place_tables(ks, device, T); if (rc) return rc;
@@ -365,13 +367,20 @@ static int pileup_tables(mf_kmerset *ks, int device, DevTables *T)
     DevCtx *ctx; rc = get_ctx(device, &ctx); if (rc) return rc;
     hipStream_t st = ctx->stream;
     DevScratch tmp;
-    uint32_t *words = nullptr; uint8_t *runlen = nullptr;
-    HIPCHK(tmp.alloc(words, std::max<size_t>(ks->bait.words.size(), 1) * 4));
+    uint32_t *words = nullptr, *valid = nullptr; uint8_t *runlen = nullptr;
+    const size_t total = (size_t)ks->bait.total, n_words = std::max(ks->bait.words.size(), (total + 15) / 16) + 1, n_valid = (total + 31) / 32 + 1;
+    std::vector<uint32_t> h_valid(n_valid, 0);
+    for (size_t p = 0; p < total; p++) if (ks->bait.runlen[p]) h_valid[p >> 5] |= 1u << (p & 31);
+    HIPCHK(tmp.alloc(words, n_words * 4));
+    HIPCHK(tmp.alloc(valid, n_valid * 4));
     HIPCHK(tmp.alloc(runlen, std::max<size_t>(ks->bait.runlen.size(), 1)));
+    HIPCHK(hipMemsetAsync(words, 0, n_words * 4, st));
     if (!ks->bait.words.empty()) HIPCHK(hipMemcpyAsync(words, ks->bait.words.data(), ks->bait.words.size() * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(valid, h_valid.data(), n_valid * 4, hipMemcpyHostToDevice, st));
     if (!ks->bait.runlen.empty()) HIPCHK(hipMemcpyAsync(runlen, ks->bait.runlen.data(), ks->bait.runlen.size(), hipMemcpyHostToDevice, st));
     HIPCHK(hipStreamSynchronize(st));
-    T->pile_words = tmp.release(words); T->pile_runlen = tmp.release(runlen);
+    T->pile_words = tmp.release(words); T->pile_runlen = tmp.release(runlen); T->pile_valid = tmp.release(valid);
+    T->pile_words_n = n_words; T->pile_valid_n = n_valid;
     T->pile_built = true;
     return MF_OK;
 }
@@ -380,25 +389,42 @@ static int pileup_tables(mf_kmerset *ks, int device, DevTables *T)
 // counters a position (only with a pile-up) come FIRST because the call kernel reads them 16 bytes at a time: at the front of an
 // allocation they are aligned whatever the other two counts are (and a base that a faulty clip let through would still land inside the
 // array).  Then the difference counters (positions + 1), then forward / reverse / over_begin / over_end of every record and the passing
-// reads that are not placed (4 R + 1).  Every offset into the array is computed here.
+// reads that are not placed (4 R + 1).  A verifying placement keeps a fourth section behind them: rejected and the MF_SCORE_BINS bins of
+// every record (what the kernel gathers with the record counters, SCORE_GATHERED R), then compared and mismatches of every record (2 R).
+// Every offset into the array is computed here.
 struct PlaceLayout {
-    size_t n_pile, n_diff, n_cnt;
-    PlaceLayout(const mf_kmerset *ks, bool pileup) : n_pile(pileup ? 4 * (size_t)ks->positions() : 0), n_diff((size_t)ks->positions() + 1), n_cnt(4 * ks->rec_len().size() + 1) {}
-    size_t words() const { return n_pile + n_diff + n_cnt; }
+    size_t n_pile, n_diff, n_cnt, n_rec; bool verify; uint32_t max_permille;
+    PlaceLayout(const mf_kmerset *ks, bool pileup, bool verify_ = false, uint32_t max_permille_ = 1000)
+        : n_pile(pileup ? 4 * (size_t)ks->positions() : 0), n_diff((size_t)ks->positions() + 1), n_cnt(4 * ks->rec_len().size() + 1), n_rec(ks->rec_len().size()),
+          verify(verify_), max_permille(max_permille_) {}
+    size_t n_score() const { return verify ? ((size_t)SCORE_GATHERED + 2) * n_rec : 0; }
+    size_t words() const { return n_pile + n_diff + n_cnt + n_score(); }
     unsigned long long *pile(unsigned long long *base) const { return n_pile ? base : nullptr; }
     unsigned long long *diff(unsigned long long *base) const { return base + n_pile; }
     unsigned long long *cnt(unsigned long long *base) const { return base + n_pile + n_diff; }
+    unsigned long long *score_sums(unsigned long long *base) const { return cnt(base) + n_cnt + (size_t)SCORE_GATHERED * n_rec; }
+    // the score section as it is downloaded (n_score() words from cnt(base) + n_cnt) into the records; accepted from the placement counters
+    void score_records(const unsigned long long *h_cnt, mf_score_record_t *out) const
+    {
+        const unsigned long long *g = h_cnt + n_cnt, *sums = g + (size_t)SCORE_GATHERED * n_rec;
+        for (size_t j = 0; j < n_rec; j++) {
+            out[j].accepted = h_cnt[4 * j] + h_cnt[4 * j + 1]; out[j].rejected = g[SCORE_GATHERED * j];
+            out[j].compared = sums[2 * j]; out[j].mismatches = sums[2 * j + 1];
+            for (uint32_t b = 0; b < SCORE_BINS; b++) out[j].hist[b] = g[SCORE_GATHERED * j + 1 + b];
+        }
+    }
 };
 static int pile_nomem(size_t words) { (void)hipGetLastError(); return fail(MF_E_NOMEM, "the pile-up counters need %llu bytes on the device", (unsigned long long)(words * 8)); }
 
 // The reads that passed the filter pass just run on this read set (its bitmap in r->d_bits[r->cur]) placed: their footprints, their
 // records' counters and (with a pile-up) their bases into the counters t of layout L (on r's device; other read sets there may be adding
 // into them at the same time), their placements into place (optional, initialised, n_reads entries on the device); *listed: how many
-// passed.  Ends synchronised.
-static int place_after_filter(mf_kmerset *ks, mf_reads *r, const PlaceLayout &L, unsigned long long *t, PlaceOut *place, uint64_t *listed)
+// passed.  A verifying layout: every placed read is scored first and cut at L.max_permille; score (optional, zeroed, n_reads entries on
+// the device) takes the scores.  Ends synchronised.
+static int place_after_filter(mf_kmerset *ks, mf_reads *r, const PlaceLayout &L, unsigned long long *t, PlaceOut *place, ScoreOut *score, uint64_t *listed)
 {
     DevTables *T; int rc = build_on_device(ks, r->device, &T); if (rc) return rc;
-    rc = place_tables(ks, r->device, T); if (rc) return rc;
+    rc = L.verify ? pileup_tables(ks, r->device, T) : place_tables(ks, r->device, T); if (rc) return rc;
     DevCtx *ctx; rc = get_ctx(r->device, &ctx, r->lane); if (rc) return rc;
     hipStream_t st = ctx->stream;
     const uint64_t n = r->v.n_reads;
@@ -420,8 +446,10 @@ static int place_after_filter(mf_kmerset *ks, mf_reads *r, const PlaceLayout &L,
     HIPCHK(hipMemsetAsync(r->d_acnt, 0, 8, st));
     HIPCHK(dev_reserve(r->d_alist, r->cap_alist, n * 4, true));
     HIPCHK(launch_pass_list(r->d_bits[r->cur], n, r->d_alist, r->d_acnt, st));
+    PlaceVerify pv{};
+    if (L.verify) pv = PlaceVerify{T->pile_words, T->pile_words_n - 1, T->pile_valid, T->pile_valid_n - 1, L.max_permille, score, L.score_sums(t)};
     HIPCHK(launch_place(r->v, T->view, T->anchor, T->place_starts, r->d_alist, r->d_acnt, (uint32_t)ks->rec_len().size(), place, L.diff(t), L.cnt(t), L.pile(t),
-                        ctx->n_cu, st));
+                        L.verify ? &pv : nullptr, ctx->n_cu, st));
     HIPCHK(hipMemcpyAsync(&v, r->d_acnt, 8, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     *listed = v;
@@ -483,7 +511,7 @@ int mf_place(const mf_kmerset *ks_, const mf_reads *reads_, uint32_t threshold, 
         HIPCHK(launch_place_init(r->d_place, n, st));
     }
     uint64_t listed = 0;
-    rc = place_after_filter(ks, r, L, r->d_rtot, place_out ? r->d_place : nullptr, &listed); if (rc) return rc;
+    rc = place_after_filter(ks, r, L, r->d_rtot, place_out ? r->d_place : nullptr, nullptr, &listed); if (rc) return rc;
     if (place_out && n) HIPCHK(hipMemcpyAsync(place_out, r->d_place, n * sizeof(PlaceOut), hipMemcpyDeviceToHost, st));
     return place_report(ks, r->device, st, L, r->d_rtot, PlaceScratch{r->d_rsum, r->rpos_u32()}, base_depth, records, unplaced, n - listed);
 }
@@ -562,9 +590,92 @@ int mf_pileup(const mf_kmerset *ks_, const mf_reads *reads_, uint32_t threshold,
     HIPCHK(dev_reserve(r->d_rpos, r->cap_rpos, PileScratch::out_bytes(ks) + PileScratch::cons_bytes(ks) + 16, false));
     HIPCHK(hipMemsetAsync(r->d_rtot, 0, L.words() * 8, st));
     uint64_t listed = 0;
-    rc = place_after_filter(ks, r, L, r->d_rtot, nullptr, &listed); if (rc) return rc;
+    rc = place_after_filter(ks, r, L, r->d_rtot, nullptr, nullptr, &listed); if (rc) return rc;
     return pileup_report(ks, r->device, st, L, r->d_rtot, min_depth, PileScratch{r->d_rsum, r->rpos_pile(), r->rpos_consensus(ks->positions())}, pileup,
                          consensus, records, unplaced, r->v.n_reads - listed);
+}
+
+} // extern "C"
+
+// ------------------------------------------------------------------- verification
+// What verify_report works in: placement's and the pile-up's scratch side by side.  A resident call lays both out in the read set's report
+// buffers (d_rsum: the work words, then the pile-up's sums; d_rpos: the called pile-up, the base depth, the consensus).
+struct VerifyScratch {
+    PlaceScratch place; PileScratch pile;
+    static size_t sums_bytes(const mf_kmerset *ks) { return PlaceScratch::work_bytes(ks) + PileScratch::sums_bytes(ks); }
+    static size_t pos_bytes(const mf_kmerset *ks) { return PileScratch::out_bytes(ks) + PlaceScratch::depth_bytes(ks) + PileScratch::cons_bytes(ks) + 16; }
+    VerifyScratch(const mf_kmerset *ks, unsigned long long *sums, void *pos)
+        : place{sums, reinterpret_cast<uint32_t *>(static_cast<uint8_t *>(pos) + PileScratch::out_bytes(ks))},
+          pile{sums + PlaceScratch::work_bytes(ks) / 8, static_cast<PileOut *>(pos),
+               static_cast<uint8_t *>(pos) + PileScratch::out_bytes(ks) + PlaceScratch::depth_bytes(ks)} {}
+};
+
+// Every report of a verifying placement from the counters t of layout L on `device` (stream st): placement's (place_report), the
+// pile-up's where the layout holds one (pileup_report), the records' scores.  Each optional.
+static int verify_report(mf_kmerset *ks, int device, hipStream_t st, const PlaceLayout &L, unsigned long long *t, uint32_t min_depth, const VerifyScratch &s,
+                         uint32_t *base_depth, mf_place_record_t *place_records, mf_pileup_t *pileup, uint8_t *consensus, mf_pileup_record_t *pileup_records,
+                         mf_score_record_t *score_records, uint64_t *unplaced, uint64_t not_passing)
+{
+    static_assert(sizeof(mf_score_t) == 8 && sizeof(ScoreOut) == 8 && sizeof(mf_score_record_t) == 8 * (4 + MF_SCORE_BINS) && MF_SCORE_BINS == SCORE_BINS, "score records");
+    int rc = place_report(ks, device, st, L, t, s.place, base_depth, place_records, unplaced, not_passing); if (rc) return rc;
+    if (L.n_pile && (pileup || consensus || pileup_records)) {
+        rc = pileup_report(ks, device, st, L, t, min_depth, s.pile, pileup, consensus, pileup_records, nullptr, not_passing); if (rc) return rc;
+    }
+    if (score_records && L.n_rec) {
+        std::vector<unsigned long long> h_cnt(L.n_cnt + L.n_score(), 0);
+        HIPCHK(hipMemcpyAsync(h_cnt.data(), L.cnt(t), h_cnt.size() * 8, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        L.score_records(h_cnt.data(), score_records);
+    }
+    return MF_OK;
+}
+
+static int verify_args(const mf_kmerset *ks, uint32_t min_depth, uint32_t max_permille)
+{
+    if (max_permille > 1000) return fail(MF_E_ARG, "max_permille is %u: the cut is a number from 0 to 1000", max_permille);
+    if (min_depth == 0) return fail(MF_E_ARG, "min_depth is 0: a called position needs at least one base");
+    if (!ks) return fail(MF_E_ARG, "NULL handle");
+    if (ks->kind != MF_KIND_NUCLEOTIDE) return fail(MF_E_ARG, "verification needs a nucleotide bait set");
+    return MF_OK;
+}
+
+extern "C" {
+
+int mf_verify(const mf_kmerset *ks_, const mf_reads *reads_, uint32_t threshold, int mode, uint32_t min_depth, uint32_t max_permille,
+              uint32_t *out_bits, mf_place_t *place_out, mf_score_t *score_out, uint32_t *base_depth, mf_place_record_t *place_records,
+              mf_pileup_t *pileup, uint8_t *consensus, mf_pileup_record_t *pileup_records, mf_score_record_t *score_records,
+              uint64_t *unplaced, mf_filter_stats_t *stats)
+{
+    mf_kmerset *ks = const_cast<mf_kmerset *>(ks_);
+    mf_reads *r = const_cast<mf_reads *>(reads_);
+    int rc = verify_args(ks, min_depth, max_permille); if (rc) return rc;
+    if (!r) return fail(MF_E_ARG, "NULL handle");
+    rc = filter_common(ks, r, threshold, mode, out_bits, nullptr, 1, stats);
+    if (rc) return rc;
+    DevCtx *ctx; rc = get_ctx(r->device, &ctx, r->lane); if (rc) return rc;
+    hipStream_t st = ctx->stream;
+    const uint64_t n = r->v.n_reads;
+    const PlaceLayout L(ks, pileup || consensus || pileup_records, true, max_permille);
+    const hipError_t e = dev_reserve(r->d_rtot, r->cap_rtot, L.words() * 8, false);
+    if (e == hipErrorOutOfMemory && L.n_pile) return pile_nomem(L.words());
+    HIPCHK(e);
+    HIPCHK(dev_reserve(r->d_rsum, r->cap_rsum, VerifyScratch::sums_bytes(ks), false));
+    HIPCHK(dev_reserve(r->d_rpos, r->cap_rpos, VerifyScratch::pos_bytes(ks), false));
+    HIPCHK(hipMemsetAsync(r->d_rtot, 0, L.words() * 8, st));
+    if (place_out && n) {
+        HIPCHK(dev_reserve(r->d_place, r->cap_place, n * sizeof(PlaceOut), true));
+        HIPCHK(launch_place_init(r->d_place, n, st));
+    }
+    if (score_out && n) {
+        HIPCHK(dev_reserve(r->d_score, r->cap_score, n * sizeof(ScoreOut), true));
+        HIPCHK(hipMemsetAsync(r->d_score, 0, n * sizeof(ScoreOut), st));
+    }
+    uint64_t listed = 0;
+    rc = place_after_filter(ks, r, L, r->d_rtot, place_out ? r->d_place : nullptr, score_out ? r->d_score : nullptr, &listed); if (rc) return rc;
+    if (place_out && n) HIPCHK(hipMemcpyAsync(place_out, r->d_place, n * sizeof(PlaceOut), hipMemcpyDeviceToHost, st));
+    if (score_out && n) HIPCHK(hipMemcpyAsync(score_out, r->d_score, n * sizeof(ScoreOut), hipMemcpyDeviceToHost, st));
+    return verify_report(ks, r->device, st, L, r->d_rtot, min_depth, VerifyScratch(ks, r->d_rsum, r->d_rpos), base_depth, place_records, pileup, consensus,
+                         pileup_records, score_records, unplaced, n - listed);
 }
 
 } // extern "C"
@@ -652,18 +763,19 @@ struct DepthTotals : DeviceTotals {
 };
 
 // Placement, and with_pileup the pile-up: the footprints, record counters and bases of every mate that passes (PlaceLayout), and how
-// many mates there were and passed
+// many mates there were and passed.  verify: the placed reads are scored and cut at max_permille first (mf_verify).
 struct PlaceTotals : DeviceTotals {
     const PlaceLayout L;
     std::atomic<uint64_t> mates{0}, passing{0};
-    PlaceTotals(mf_kmerset *ks_, bool with_pileup) : DeviceTotals(ks_, with_pileup ? pile_nomem : nullptr), L(ks_, with_pileup) {}
+    PlaceTotals(mf_kmerset *ks_, bool with_pileup, bool verify = false, uint32_t max_permille = 1000)
+        : DeviceTotals(ks_, with_pileup ? pile_nomem : nullptr), L(ks_, with_pileup, verify, max_permille) {}
     void restart() override { release(); mates = 0; passing = 0; }
-    int tables(int device, DevTables *T) override { return place_tables(ks, device, T); }
+    int tables(int device, DevTables *T) override { return L.verify ? pileup_tables(ks, device, T) : place_tables(ks, device, T); }
     size_t words(const DevTables *) const override { return L.words(); }
     int add(mf_reads *R, unsigned long long *t) override
     {
         uint64_t listed = 0;
-        const int rc = place_after_filter(ks, R, L, t, nullptr, &listed);
+        const int rc = place_after_filter(ks, R, L, t, nullptr, nullptr, &listed);
         if (rc == MF_OK) { mates += R->v.n_reads; passing += listed; }
         return rc;
     }
@@ -759,6 +871,24 @@ int mf_filter_fastq_files_pileup(mf_kmerset *ks, const char *fq1, const char *fq
     HIPCHK(tmp.alloc(s.cons, PileScratch::cons_bytes(ks)));
     HIPCHK(tmp.alloc(s.sums, PileScratch::sums_bytes(ks)));
     return pileup_report(ks, devices[0], ctx->stream, pt.L, t0, min_depth, s, pileup, consensus, records, unplaced, pt.mates - pt.passing);
+}
+
+int mf_filter_fastq_files_verified(mf_kmerset *ks, const char *fq1, const char *fq2, const char *out1, const char *out2,
+                                   uint32_t threshold, int pair_mode, const int *devices, int n_devices, uint32_t min_depth, uint32_t max_permille,
+                                   uint32_t *base_depth, mf_place_record_t *place_records, mf_pileup_t *pileup, uint8_t *consensus,
+                                   mf_pileup_record_t *pileup_records, mf_score_record_t *score_records, uint64_t *unplaced, uint64_t *kept, uint64_t *total)
+{
+    int rc = verify_args(ks, min_depth, max_permille); if (rc) return rc;
+    PlaceTotals pt(ks, pileup || consensus || pileup_records, true, max_permille);
+    unsigned long long *t0 = nullptr; DevCtx *ctx = nullptr;
+    rc = files_with_totals(ks, fq1, fq2, out1, out2, threshold, pair_mode, devices, n_devices, kept, total, pt, &t0, &ctx);
+    if (rc) return rc;
+    DevScratch tmp;
+    unsigned long long *sums = nullptr; uint8_t *pos = nullptr;
+    HIPCHK(tmp.alloc(sums, VerifyScratch::sums_bytes(ks)));
+    HIPCHK(tmp.alloc(pos, VerifyScratch::pos_bytes(ks)));
+    return verify_report(ks, devices[0], ctx->stream, pt.L, t0, min_depth, VerifyScratch(ks, sums, pos), base_depth, place_records, pileup, consensus,
+                         pileup_records, score_records, unplaced, pt.mates - pt.passing);
 }
 
 } // extern "C"

@@ -114,4 +114,23 @@ inline bool write_variants(FILE *f, const Names &names, const Starts &starts, co
     return written(f);
 }
 
+// --score-report: per record the placed reads on either side of the cut, the compared and mismatching bases of the accepted ones, their
+// mismatches per thousand compared bases (0.000 when nothing was compared), then the MF_SCORE_BINS bins of min(mismatches, 31) over ALL
+// placed reads
+inline bool write_score_report(FILE *f, const Names &names, const Starts &starts, const mf_score_record_t *recs)
+{
+    if (!f) return false;
+    fputs("record\tname\tlength\taccepted\trejected\tcompared\tmismatches\tpermille", f);
+    for (int b = 0; b < MF_SCORE_BINS; b++) fprintf(f, b == MF_SCORE_BINS - 1 ? "\tmm%d+" : "\tmm%d", b);
+    fputc('\n', f);
+    for (size_t i = 0; i < names.size(); i++) {
+        const mf_score_record_t &d = recs[i];
+        fprintf(f, "%zu\t%s\t%llu\t%llu\t%llu\t%llu\t%llu\t%.3f", i, names[i].c_str(), (ull)(starts[i + 1] - starts[i]), (ull)d.accepted, (ull)d.rejected,
+                (ull)d.compared, (ull)d.mismatches, d.compared ? 1000.0 * (double)d.mismatches / (double)d.compared : 0.0);
+        for (int b = 0; b < MF_SCORE_BINS; b++) fprintf(f, "\t%llu", (ull)d.hist[b]);
+        fputc('\n', f);
+    }
+    return written(f);
+}
+
 } // namespace mf_text

@@ -40,6 +40,11 @@ PLACE_RECORD = np.dtype([("forward", np.uint64), ("reverse", np.uint64), ("over_
 PILEUP = np.dtype([("a", np.uint32), ("c", np.uint32), ("g", np.uint32), ("t", np.uint32)])
 PILEUP_RECORD = np.dtype([("bases", np.uint64), ("matches", np.uint64), ("mismatches", np.uint64), ("called", np.uint64),
                           ("ambiguous", np.uint64), ("variants", np.uint64)])
+# per-read score of a placed read against the bait (mf_score_t) and per-record summary of the scores and the cut (mf_score_record_t)
+SCORE_BINS = 32
+SCORE = np.dtype([("compared", np.uint32), ("mismatches", np.uint32)])
+SCORE_RECORD = np.dtype([("accepted", np.uint64), ("rejected", np.uint64), ("compared", np.uint64), ("mismatches", np.uint64),
+                         ("hist", np.uint64, (SCORE_BINS,))])
 # a variant position (pileup_variants): pos is 0-based inside the record, ref / alt are letters
 VARIANT = np.dtype([("record", np.uint32), ("pos", np.uint64), ("ref", "S1"), ("alt", "S1"), ("depth", np.uint64), ("alt_count", np.uint64)])
 # the largest insert size pair_inserts keeps (bim.estimate_insert_sizes' rule)
@@ -58,6 +63,7 @@ EXPORTS = (
     "mf_kmerset_record_starts", "mf_depth", "mf_filter_fastq_files_depth",
     "mf_place", "mf_filter_fastq_files_placed",
     "mf_pileup", "mf_filter_fastq_files_pileup", "mf_kmerset_bait_letters",
+    "mf_verify", "mf_filter_fastq_files_verified",
 )
 
 
@@ -173,6 +179,9 @@ def load(path: Optional[str] = None):
     L.mf_filter_fastq_files_pileup.argtypes = [vp, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_uint32, C.c_int,
                                                C.POINTER(C.c_int), C.c_int, C.c_uint32, vp, vp, vp, vp, u64p, u64p]
     L.mf_kmerset_bait_letters.argtypes = [vp, vp, C.c_size_t, C.POINTER(C.c_size_t)]
+    L.mf_verify.argtypes = [vp, vp, C.c_uint32, C.c_int, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(FilterStats)]
+    L.mf_filter_fastq_files_verified.argtypes = [vp, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_uint32, C.c_int,
+                                                 C.POINTER(C.c_int), C.c_int, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp, vp, u64p, u64p]
     if L.mf_abi_version() != 5:
         raise MitoFilterError("libmitofilter_hip ABI version mismatch")
     _lib = L
@@ -474,6 +483,61 @@ def pileup_reads(ks: KmerSet, reads: Reads, threshold: int = 1, mode: int = MODE
     return bits[:(n + 31) // 32], pileup[:P], consensus[:P], records[:R], unplaced
 
 
+class Verified:
+    """What a verifying call gives (include/mitofilter.h, verification).  verify_reads fills bits, place PLACE[n] and score SCORE[n];
+    filter_fastq_files_verified fills kept and total; the fields a call does not fill are None.  Both give base_depth u32[positions],
+    place_records PLACE_RECORD[R], score_records SCORE_RECORD[R], unplaced u64[2] and, unless the call ran with pileup=False (then
+    None), pileup PILEUP[positions], consensus u8[positions] and pileup_records PILEUP_RECORD[R]."""
+    __slots__ = ("bits", "kept", "total", "place", "score", "base_depth", "place_records", "pileup", "consensus", "pileup_records",
+                 "score_records", "unplaced")
+
+    def __init__(self, **fields):
+        for name in self.__slots__:
+            setattr(self, name, fields.pop(name, None))
+        if fields:
+            raise TypeError("unknown field(s): %s" % ", ".join(sorted(fields)))
+
+    def __repr__(self):
+        return "Verified(%s)" % ", ".join(name for name in self.__slots__ if getattr(self, name) is not None)
+
+
+def _verify_outputs(ks: KmerSet, pileup: bool):
+    """the per-position and per-record arrays of a verifying call, and their pointers in the C order (NULL for what pileup=False leaves out)"""
+    starts = ks.record_starts
+    P, R = int(starts[-1]), len(starts) - 1
+    a = {"base_depth": np.zeros(max(P, 1), dtype=np.uint32), "place_records": np.zeros(max(R, 1), dtype=PLACE_RECORD),
+         "pileup": np.zeros(max(P, 1), dtype=PILEUP) if pileup else None, "consensus": np.zeros(max(P, 1), dtype=np.uint8) if pileup else None,
+         "pileup_records": np.zeros(max(R, 1), dtype=PILEUP_RECORD) if pileup else None,
+         "score_records": np.zeros(max(R, 1), dtype=SCORE_RECORD), "unplaced": np.zeros(2, dtype=np.uint64)}
+    order = ("base_depth", "place_records", "pileup", "consensus", "pileup_records", "score_records", "unplaced")
+    ptrs = [a[f].ctypes.data if a[f] is not None else None for f in order]
+    size = {"base_depth": P, "pileup": P, "consensus": P, "place_records": R, "pileup_records": R, "score_records": R, "unplaced": 2}
+    return a, ptrs, lambda: {f: (a[f][:size[f]] if a[f] is not None else None) for f in order}
+
+
+def _check_cut(min_depth: int, max_permille: int):
+    if not 0 <= int(max_permille) <= 1000:
+        raise ValueError("max_permille is a number from 0 to 1000")
+    if int(min_depth) < 1:
+        raise ValueError("min_depth is at least 1")
+
+
+def verify_reads(ks: KmerSet, reads: Reads, threshold: int = 1, mode: int = MODE_SCREENED, min_depth: int = 1, max_permille: int = 1000,
+                 pileup: bool = True) -> Verified:
+    """One filter pass, then every placed read scored against the bait along its placement and cut at max_permille mismatches per
+    thousand compared bases; what is accepted gives base depth and (pileup=True) the pile-up (include/mitofilter.h: mf_verify).
+    -> Verified with bits, place, score and the shared fields."""
+    _check_cut(min_depth, max_permille)
+    n = reads.info.n_reads
+    bits = np.zeros(max((n + 31) // 32, 1), dtype=np.uint32)
+    place = np.zeros(max(n, 1), dtype=PLACE)
+    score = np.zeros(max(n, 1), dtype=SCORE)
+    _, ptrs, result = _verify_outputs(ks, pileup)
+    _chk(load().mf_verify(ks._h, reads._h, threshold, mode, min_depth, max_permille, bits.ctypes.data, place.ctypes.data, score.ctypes.data,
+                          *ptrs, None))
+    return Verified(bits=bits[:(n + 31) // 32], place=place[:n], score=score[:n], **result())
+
+
 def consensus_fasta(names, starts, consensus, width: int = 60) -> str:
     """FASTA text of a consensus (u8[positions] or bytes) under the records' names: lines of `width` letters; an empty record gives a
     header and no sequence line.  Needs no device."""
@@ -654,6 +718,19 @@ def filter_fastq_files_pileup(ks: KmerSet, fq1: str, fq2: Optional[str], out1: s
     kept, total = _files_call("mf_filter_fastq_files_pileup", ks, fq1, fq2, out1, out2, threshold, pair_mode, devices, n_devices,
                               min_depth, pileup.ctypes.data, consensus.ctypes.data, records.ctypes.data, unplaced.ctypes.data)
     return kept, total, pileup[:P], consensus[:P], records[:R], unplaced
+
+
+def filter_fastq_files_verified(ks: KmerSet, fq1: str, fq2: Optional[str], out1: str, out2: Optional[str],
+                                threshold: int = 1, pair_mode: int = PAIR_EITHER, devices: Optional[Sequence[int]] = None,
+                                n_devices: int = 1, min_depth: int = 1, max_permille: int = 1000, pileup: bool = True) -> Verified:
+    """filter_fastq_files plus verified placement and (pileup=True) pile-up of every mate that passes its own threshold: the placed
+    mates are scored against the bait and cut at max_permille (the pair rule decides only what is written; a rejected mate is still
+    written).  -> Verified with kept, total and the shared fields."""
+    _check_cut(min_depth, max_permille)
+    _, ptrs, result = _verify_outputs(ks, pileup)
+    kept, total = _files_call("mf_filter_fastq_files_verified", ks, fq1, fq2, out1, out2, threshold, pair_mode, devices, n_devices,
+                              min_depth, max_permille, *ptrs)
+    return Verified(kept=kept, total=total, **result())
 
 
 def set_option(name: str, value) -> None:
