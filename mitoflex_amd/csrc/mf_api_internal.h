@@ -149,13 +149,12 @@ struct mf_reads {
     // record assignment (mf_assign and the file-level call by record): the passing reads as a list, their records, the counters
     uint32_t *d_alist = nullptr, *d_assign = nullptr; uint64_t *d_apairs = nullptr; unsigned long long *d_acnt = nullptr;
     size_t cap_alist = 0, cap_assign = 0, cap_apairs = 0, cap_acnt = 0;
-    // the reports of mf_depth, mf_place and mf_pileup: d_rtot the call's 64-bit totals; d_rsum its 64-bit record sums and the work words
-    // of its report kernel; d_rpos what it holds per position (32-bit counters or depths, or the called pile-up with the consensus behind it)
+    // the reports of mf_depth and of the placement family: d_rtot the call's 64-bit totals; d_rsum its 64-bit record sums and the work
+    // words of its report kernels; d_rpos what it holds per position (mf_depth: 32-bit counters, then the profile; the placement family:
+    // the sections of ReportScratch, mf_placelayout.h, in both)
     unsigned long long *d_rtot = nullptr, *d_rsum = nullptr; void *d_rpos = nullptr;
     size_t cap_rtot = 0, cap_rsum = 0, cap_rpos = 0;
     uint32_t *rpos_u32() const { return static_cast<uint32_t *>(d_rpos); }
-    mf::PileOut *rpos_pile() const { return static_cast<mf::PileOut *>(d_rpos); }
-    uint8_t *rpos_consensus(uint64_t positions) const { return static_cast<uint8_t *>(d_rpos) + positions * sizeof(mf::PileOut); }
     mf::PlaceOut *d_place = nullptr; size_t cap_place = 0;          // mf_place's per-read results
     mf::ScoreOut *d_score = nullptr; size_t cap_score = 0;          // mf_verify's per-read scores
     // capacities (bytes), so that a handle can be refilled batch after batch without touching the allocator

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include "mf_common.h"
 #include "mf_kernels.h"
+#include "mf_placelayout.h"          // SCORE_BINS, SCORE_GATHERED, PILE_SUMS: what the kernels share with the host's layout
 
 namespace mf {
 
@@ -14,8 +15,6 @@ constexpr uint32_t PLACE_CLAMP = 0xFFFFFFFEu;        // the largest base depth r
 struct alignas(8) Anchor { uint32_t pos, rb; };          // position inside the record (ANCHOR_NONE: no anchor), record << 1 | b
 struct PlaceOut { uint32_t record, strand; int32_t start, end; uint32_t votes, windows; };       // mf_place_t
 struct ScoreOut { uint32_t compared, mismatches; };      // mf_score_t
-constexpr uint32_t SCORE_BINS = 32;                      // MF_SCORE_BINS
-constexpr uint32_t SCORE_GATHERED = 1 + SCORE_BINS;      // counters a record that a verifying launch gathers behind placement's: rejected, the bins
 // What a verifying launch takes beside a placing one.  bait_words / bait_valid: the bait's packed letters and its validity, one bit a
 // position; *_last: the index of each array's last word (the 16-base compare clamps to it).  score (optional): n_reads entries, zeroed.
 // sums: compared, mismatches of every record, 2 counters each, summed over the ACCEPTED reads.
@@ -58,7 +57,6 @@ hipError_t launch_place_profile(const unsigned long long *diff, uint64_t total, 
 // (optional) = the letter with strictly the most bases in upper case when at least min_depth bases lie there, 'N' when the most is tied,
 // else the bait's own letter in lower case ('n' for an invalid one: B.runlen[p] == 0).  rec_sums (optional, zeroed by the caller): bases,
 // matches, mismatches, called, ambiguous, variants of every record, PILE_SUMS counters each.
-constexpr uint32_t PILE_SUMS = 6;
 struct PileOut { uint32_t a, c, g, t; };                 // mf_pileup_t
 hipError_t launch_pileup_call(const unsigned long long *pile, const BaitView &B, const uint64_t *rec_start, uint32_t n_rec, uint32_t min_depth,
                               PileOut *out, uint8_t *consensus, unsigned long long *rec_sums, hipStream_t st);

@@ -1,0 +1,72 @@
+// Where a placement-family call (mf_place, mf_pileup, mf_verify and their file-level calls) keeps what on the device: the counters its
+// kernels add into (PlaceLayout) and what its report works in (ReportScratch), as pure functions of plain values.  Host-only (no HIP
+// include): tests/test_placelayout.py holds every offset here to a restatement of its own without a device.
+#pragma once
+#include "../../include/mitofilter.h"
+#include <stddef.h>
+#include <algorithm>
+namespace mf {
+constexpr uint32_t SCORE_BINS = 32;                      // MF_SCORE_BINS
+constexpr uint32_t SCORE_GATHERED = 1 + SCORE_BINS;      // counters a record that a verifying launch gathers behind placement's: rejected, the bins
+constexpr uint32_t PILE_SUMS = 6;                        // counters a record of the call kernel's sums: the fields of mf_pileup_record_t
+
+// The counters of a placement, one array of 64-bit words: [pile-up counters | difference counters | record counters].  The four pile-up
+// counters a position (only with a pile-up) come FIRST because the call kernel reads them 16 bytes at a time: at the front of an
+// allocation they are aligned whatever the other two counts are (and a base that a faulty clip let through would still land inside the
+// array).  Then the difference counters (positions + 1), then forward / reverse / over_begin / over_end of every record and the passing
+// reads that are not placed (4 R + 1).  A verifying placement keeps a fourth section behind them: rejected and the MF_SCORE_BINS bins of
+// every record (what the kernel gathers with the record counters, SCORE_GATHERED R), then compared and mismatches of every record (2 R).
+// Every offset into the array is computed here.
+struct PlaceLayout {
+    size_t n_pile, n_diff, n_cnt, n_rec; bool verify; uint32_t max_permille;
+    PlaceLayout(uint64_t positions, size_t n_rec_, bool pileup, bool verify_, uint32_t max_permille_)
+        : n_pile(pileup ? 4 * (size_t)positions : 0), n_diff((size_t)positions + 1), n_cnt(4 * n_rec_ + 1), n_rec(n_rec_), verify(verify_), max_permille(max_permille_) {}
+    size_t n_score() const { return verify ? ((size_t)SCORE_GATHERED + 2) * n_rec : 0; }
+    size_t words() const { return n_pile + n_diff + n_cnt + n_score(); }
+    unsigned long long *pile(unsigned long long *base) const { return n_pile ? base : nullptr; }
+    unsigned long long *diff(unsigned long long *base) const { return base + n_pile; }
+    unsigned long long *cnt(unsigned long long *base) const { return base + n_pile + n_diff; }
+    unsigned long long *score_sums(unsigned long long *base) const { return cnt(base) + n_cnt + (size_t)SCORE_GATHERED * n_rec; }
+    // the score section as it is downloaded (n_score() words from cnt(base) + n_cnt) into the records; accepted from the placement counters
+    void score_records(const unsigned long long *h_cnt, mf_score_record_t *out) const
+    {
+        const unsigned long long *g = h_cnt + n_cnt, *sums = g + (size_t)SCORE_GATHERED * n_rec;
+        for (size_t j = 0; j < n_rec; j++) {
+            out[j].accepted = h_cnt[4 * j] + h_cnt[4 * j + 1]; out[j].rejected = g[SCORE_GATHERED * j];
+            out[j].compared = sums[2 * j]; out[j].mismatches = sums[2 * j + 1];
+            for (uint32_t b = 0; b < SCORE_BINS; b++) out[j].hist[b] = g[SCORE_GATHERED * j + 1 + b];
+        }
+    }
+};
+
+// What the report of a placement works in, two device buffers cut into sections (byte offset and size; an absent section has size 0).
+// The "sums" buffer (64-bit words): placement's work words -- covered and base_sum of every record (2 R), then the scan's partials
+// (scan_tiles + 1, scan_tiles being place_scan_tiles(positions)) -- then the pile-up's record sums (PILE_SUMS a record).  The
+// "positions" buffer: the called pile-up FIRST, because the call kernel writes it 16 bytes an entry, then the base depth (u32), then the
+// consensus (bytes), then 16 spare bytes behind it.  place: base depth or placement records are asked for; pile: the layout holds a
+// pile-up.  A resident call cuts the sections out of the read set's cached buffers (d_rsum, d_rpos), a file-level call out of two
+// temporaries of its own.  Every offset is computed here.
+struct ReportScratch {
+    struct Section {
+        size_t off = 0, bytes = 0;
+        template <class T> T *in(void *buf) const { return bytes ? reinterpret_cast<T *>(static_cast<uint8_t *>(buf) + off) : nullptr; }
+    };
+    Section work, pile_sums;                           // of the sums buffer
+    Section pile_out, depth, consensus, spare;         // of the positions buffer
+    size_t sums_bytes, pos_bytes;
+    ReportScratch(uint64_t positions, size_t n_rec, uint64_t scan_tiles, bool place, bool pile)
+    {
+        const size_t P = (size_t)std::max<uint64_t>(positions, 1), R = std::max<size_t>(n_rec, 1);
+        size_t at = 0;
+        auto put = [&at](Section &s, size_t bytes) { s.off = at; s.bytes = bytes; at += bytes; };
+        put(work, place ? (2 * n_rec + (size_t)scan_tiles + 1) * 8 : 0);
+        put(pile_sums, pile ? PILE_SUMS * R * 8 : 0);
+        sums_bytes = at; at = 0;
+        put(pile_out, pile ? P * sizeof(mf_pileup_t) : 0);
+        put(depth, place ? P * 4 : 0);
+        put(consensus, pile ? P : 0);
+        put(spare, pile ? 16 : 0);
+        pos_bytes = at;
+    }
+};
+} // namespace mf

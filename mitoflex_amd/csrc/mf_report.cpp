@@ -385,36 +385,40 @@ static int pileup_tables(mf_kmerset *ks, int device, DevTables *T)
     return MF_OK;
 }
 
-// The counters of a placement, one array of 64-bit words: [pile-up counters | difference counters | record counters].  The four pile-up
-// counters a position (only with a pile-up) come FIRST because the call kernel reads them 16 bytes at a time: at the front of an
-// allocation they are aligned whatever the other two counts are (and a base that a faulty clip let through would still land inside the
-// array).  Then the difference counters (positions + 1), then forward / reverse / over_begin / over_end of every record and the passing
-// reads that are not placed (4 R + 1).  A verifying placement keeps a fourth section behind them: rejected and the MF_SCORE_BINS bins of
-// every record (what the kernel gathers with the record counters, SCORE_GATHERED R), then compared and mismatches of every record (2 R).
-// Every offset into the array is computed here.
-struct PlaceLayout {
-    size_t n_pile, n_diff, n_cnt, n_rec; bool verify; uint32_t max_permille;
-    PlaceLayout(const mf_kmerset *ks, bool pileup, bool verify_ = false, uint32_t max_permille_ = 1000)
-        : n_pile(pileup ? 4 * (size_t)ks->positions() : 0), n_diff((size_t)ks->positions() + 1), n_cnt(4 * ks->rec_len().size() + 1), n_rec(ks->rec_len().size()),
-          verify(verify_), max_permille(max_permille_) {}
-    size_t n_score() const { return verify ? ((size_t)SCORE_GATHERED + 2) * n_rec : 0; }
-    size_t words() const { return n_pile + n_diff + n_cnt + n_score(); }
-    unsigned long long *pile(unsigned long long *base) const { return n_pile ? base : nullptr; }
-    unsigned long long *diff(unsigned long long *base) const { return base + n_pile; }
-    unsigned long long *cnt(unsigned long long *base) const { return base + n_pile + n_diff; }
-    unsigned long long *score_sums(unsigned long long *base) const { return cnt(base) + n_cnt + (size_t)SCORE_GATHERED * n_rec; }
-    // the score section as it is downloaded (n_score() words from cnt(base) + n_cnt) into the records; accepted from the placement counters
-    void score_records(const unsigned long long *h_cnt, mf_score_record_t *out) const
+static int pile_nomem(size_t words) { (void)hipGetLastError(); return fail(MF_E_NOMEM, "the pile-up counters need %llu bytes on the device", (unsigned long long)(words * 8)); }
+
+// Everything a call of the placement family is asked for: mf_place, mf_pileup, mf_verify and their file-level calls are each one of
+// these and one call of a driver below.  family: the name the messages use.  with_pileup: the layout holds pile-up counters.  A family
+// that takes no cut leaves min_depth and max_permille as they are here.  Every output is optional; a file-level call has no per-read ones.
+struct PlaceRequest {
+    const char *family; bool verify, with_pileup;
+    uint32_t min_depth = 1, max_permille = 1000;
+    mf_place_t *place_out = nullptr; mf_score_t *score_out = nullptr;
+    uint32_t *base_depth = nullptr; mf_place_record_t *place_records = nullptr;
+    mf_pileup_t *pileup = nullptr; uint8_t *consensus = nullptr; mf_pileup_record_t *pileup_records = nullptr;
+    mf_score_record_t *score_records = nullptr; uint64_t *unplaced = nullptr;
+    // the one argument check of the family (a resident call checks its read set behind it)
+    int check(const mf_kmerset *ks) const
     {
-        const unsigned long long *g = h_cnt + n_cnt, *sums = g + (size_t)SCORE_GATHERED * n_rec;
-        for (size_t j = 0; j < n_rec; j++) {
-            out[j].accepted = h_cnt[4 * j] + h_cnt[4 * j + 1]; out[j].rejected = g[SCORE_GATHERED * j];
-            out[j].compared = sums[2 * j]; out[j].mismatches = sums[2 * j + 1];
-            for (uint32_t b = 0; b < SCORE_BINS; b++) out[j].hist[b] = g[SCORE_GATHERED * j + 1 + b];
-        }
+        if (max_permille > 1000) return fail(MF_E_ARG, "max_permille is %u: the cut is a number from 0 to 1000", max_permille);
+        if (min_depth == 0) return fail(MF_E_ARG, "min_depth is 0: a called position needs at least one base");
+        if (!ks) return fail(MF_E_ARG, "NULL handle");
+        if (ks->kind != MF_KIND_NUCLEOTIDE) return fail(MF_E_ARG, "%s needs a nucleotide bait set", family);
+        return MF_OK;
+    }
+    PlaceLayout layout(const mf_kmerset *ks) const { return PlaceLayout(ks->positions(), ks->rec_len().size(), with_pileup, verify, max_permille); }
+    ReportScratch scratch(const mf_kmerset *ks) const
+    {
+        return ReportScratch(ks->positions(), ks->rec_len().size(), place_scan_tiles(ks->positions()), base_depth || place_records, with_pileup);
     }
 };
-static int pile_nomem(size_t words) { (void)hipGetLastError(); return fail(MF_E_NOMEM, "the pile-up counters need %llu bytes on the device", (unsigned long long)(words * 8)); }
+
+// the tables on `device` that the kernels of a placement of layout L read
+static int placement_tables(mf_kmerset *ks, int device, const PlaceLayout &L, DevTables **T)
+{
+    int rc = build_on_device(ks, device, T); if (rc) return rc;
+    return L.verify || L.n_pile ? pileup_tables(ks, device, *T) : place_tables(ks, device, *T);
+}
 
 // The reads that passed the filter pass just run on this read set (its bitmap in r->d_bits[r->cur]) placed: their footprints, their
 // records' counters and (with a pile-up) their bases into the counters t of layout L (on r's device; other read sets there may be adding
@@ -423,8 +427,7 @@ static int pile_nomem(size_t words) { (void)hipGetLastError(); return fail(MF_E_
 // the device) takes the scores.  Ends synchronised.
 static int place_after_filter(mf_kmerset *ks, mf_reads *r, const PlaceLayout &L, unsigned long long *t, PlaceOut *place, ScoreOut *score, uint64_t *listed)
 {
-    DevTables *T; int rc = build_on_device(ks, r->device, &T); if (rc) return rc;
-    rc = L.verify ? pileup_tables(ks, r->device, T) : place_tables(ks, r->device, T); if (rc) return rc;
+    DevTables *T; int rc = placement_tables(ks, r->device, L, &T); if (rc) return rc;
     DevCtx *ctx; rc = get_ctx(r->device, &ctx, r->lane); if (rc) return rc;
     hipStream_t st = ctx->stream;
     const uint64_t n = r->v.n_reads;
@@ -456,105 +459,81 @@ static int place_after_filter(mf_kmerset *ks, mf_reads *r, const PlaceLayout &L,
     return MF_OK;
 }
 
-struct PlaceScratch {
-    unsigned long long *work; uint32_t *depth;          // the record sums (2 R) and the scan's partials, the base depth
-    static size_t work_bytes(const mf_kmerset *ks) { return (2 * ks->rec_len().size() + (size_t)place_scan_tiles(ks->positions()) + 1) * 8; }
-    static size_t depth_bytes(const mf_kmerset *ks) { return std::max<uint64_t>(ks->positions(), 1) * 4; }
-};
-
-// Base depth (ks->positions() u32), the record summaries (R entries) and unplaced[2] -- the passing reads that are not placed, then
-// not_passing as it is given -- from the counters t of layout L on `device` (stream st); each optional.
-static int place_report(mf_kmerset *ks, int device, hipStream_t st, const PlaceLayout &L, unsigned long long *t, PlaceScratch s, uint32_t *base_depth,
-                        mf_place_record_t *records, uint64_t *unplaced, uint64_t not_passing)
+// Every report the request q asks for from the counters t of layout L on `device` (stream st), worked out in the sections S of the two
+// scratch buffers sums and pos: base depth (positions u32) and placement's record summaries, the called pile-up (positions entries), the
+// consensus (positions bytes) and the pile-up's record summaries, the records' scores, and unplaced[2] -- the passing reads that are not
+// placed, then not_passing as it is given.  Both kernels and every copy are enqueued, then the stream is waited for once.
+static int placement_report(mf_kmerset *ks, int device, hipStream_t st, const PlaceLayout &L, unsigned long long *t, const PlaceRequest &q,
+                            const ReportScratch &S, unsigned long long *sums, void *pos, uint64_t not_passing)
 {
-    DevTables *T; int rc = build_on_device(ks, device, &T); if (rc) return rc;
-    rc = place_tables(ks, device, T); if (rc) return rc;
-    const uint64_t total = ks->positions(), n_rec = ks->rec_len().size();
-    std::vector<unsigned long long> h_cnt(L.n_cnt, 0), h_sum(2 * n_rec + 1, 0);
-    if (records && n_rec) HIPCHK(hipMemsetAsync(s.work, 0, 2 * n_rec * 8, st));
-    if (base_depth || records)
-        HIPCHK(launch_place_profile(L.diff(t), total, T->place_starts, (uint32_t)n_rec, s.work + 2 * n_rec, base_depth ? s.depth : nullptr,
-                                    records ? s.work : nullptr, st));
-    if (base_depth && total) HIPCHK(hipMemcpyAsync(base_depth, s.depth, total * 4, hipMemcpyDeviceToHost, st));
-    if (records && n_rec) HIPCHK(hipMemcpyAsync(h_sum.data(), s.work, 2 * n_rec * 8, hipMemcpyDeviceToHost, st));
+    static_assert(sizeof(mf_place_t) == 24 && sizeof(PlaceOut) == 24 && sizeof(mf_place_record_t) == 48, "placement records");
+    static_assert(sizeof(mf_pileup_t) == 16 && sizeof(PileOut) == 16 && sizeof(mf_pileup_record_t) == 8 * PILE_SUMS, "pile-up records");
+    static_assert(sizeof(mf_score_t) == 8 && sizeof(ScoreOut) == 8 && sizeof(mf_score_record_t) == 8 * (4 + MF_SCORE_BINS) && MF_SCORE_BINS == SCORE_BINS, "score records");
+    DevTables *T; int rc = placement_tables(ks, device, L, &T); if (rc) return rc;
+    const uint64_t total = ks->positions(), n_rec = L.n_rec;
+    std::vector<unsigned long long> h_cnt(L.n_cnt + (q.score_records ? L.n_score() : 0), 0), h_sum(2 * n_rec + 1, 0);
+    if (q.base_depth || q.place_records) {
+        unsigned long long *work = S.work.in<unsigned long long>(sums); uint32_t *depth = S.depth.in<uint32_t>(pos);
+        if (q.place_records && n_rec) HIPCHK(hipMemsetAsync(work, 0, 2 * n_rec * 8, st));
+        HIPCHK(launch_place_profile(L.diff(t), total, T->place_starts, (uint32_t)n_rec, work + 2 * n_rec, q.base_depth ? depth : nullptr,
+                                    q.place_records ? work : nullptr, st));
+        if (q.base_depth && total) HIPCHK(hipMemcpyAsync(q.base_depth, depth, total * 4, hipMemcpyDeviceToHost, st));
+        if (q.place_records && n_rec) HIPCHK(hipMemcpyAsync(h_sum.data(), work, 2 * n_rec * 8, hipMemcpyDeviceToHost, st));
+    }
+    if (q.with_pileup && (q.pileup || q.consensus || q.pileup_records)) {
+        unsigned long long *psums = S.pile_sums.in<unsigned long long>(sums); PileOut *out = S.pile_out.in<PileOut>(pos); uint8_t *cons = S.consensus.in<uint8_t>(pos);
+        if (q.pileup_records && n_rec) HIPCHK(hipMemsetAsync(psums, 0, PILE_SUMS * n_rec * 8, st));
+        HIPCHK(launch_pileup_call(L.pile(t), BaitView{T->pile_words, total, T->pile_runlen}, T->place_starts, (uint32_t)n_rec, q.min_depth,
+                                  q.pileup ? out : nullptr, q.consensus ? cons : nullptr, q.pileup_records ? psums : nullptr, st));
+        if (q.pileup && total) HIPCHK(hipMemcpyAsync(q.pileup, out, total * sizeof(PileOut), hipMemcpyDeviceToHost, st));
+        if (q.consensus && total) HIPCHK(hipMemcpyAsync(q.consensus, cons, total, hipMemcpyDeviceToHost, st));
+        if (q.pileup_records && n_rec) HIPCHK(hipMemcpyAsync(q.pileup_records, psums, PILE_SUMS * n_rec * 8, hipMemcpyDeviceToHost, st));
+    }
     HIPCHK(hipMemcpyAsync(h_cnt.data(), L.cnt(t), h_cnt.size() * 8, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
-    if (records)
+    if (q.place_records)
         for (uint64_t j = 0; j < n_rec; j++)
-            records[j] = mf_place_record_t{h_cnt[4 * j], h_cnt[4 * j + 1], h_cnt[4 * j + 2], h_cnt[4 * j + 3], h_sum[2 * j], h_sum[2 * j + 1]};
-    if (unplaced) { unplaced[0] = h_cnt[4 * n_rec]; unplaced[1] = not_passing; }
+            q.place_records[j] = mf_place_record_t{h_cnt[4 * j], h_cnt[4 * j + 1], h_cnt[4 * j + 2], h_cnt[4 * j + 3], h_sum[2 * j], h_sum[2 * j + 1]};
+    if (q.score_records) L.score_records(h_cnt.data(), q.score_records);
+    if (q.unplaced) { q.unplaced[0] = h_cnt[4 * n_rec]; q.unplaced[1] = not_passing; }
     return MF_OK;
 }
 
-extern "C" {
-
-int mf_place(const mf_kmerset *ks_, const mf_reads *reads_, uint32_t threshold, int mode, uint32_t *out_bits, mf_place_t *place_out,
-             uint32_t *base_depth, mf_place_record_t *records, uint64_t *unplaced, mf_filter_stats_t *stats)
+// The resident call of the family: one filter pass, the passing reads placed into the read set's cached buffers, the report.
+static int placement_resident(const mf_kmerset *ks_, const mf_reads *reads_, uint32_t threshold, int mode, uint32_t *out_bits, mf_filter_stats_t *stats,
+                              const PlaceRequest &q)
 {
-    static_assert(sizeof(mf_place_t) == 24 && sizeof(PlaceOut) == 24 && sizeof(mf_place_record_t) == 48, "placement records");
     mf_kmerset *ks = const_cast<mf_kmerset *>(ks_);
     mf_reads *r = const_cast<mf_reads *>(reads_);
-    if (!ks || !r) return fail(MF_E_ARG, "NULL handle");
-    if (ks->kind != MF_KIND_NUCLEOTIDE) return fail(MF_E_ARG, "placement needs a nucleotide bait set");
-    int rc = filter_common(ks, r, threshold, mode, out_bits, nullptr, 1, stats);
+    int rc = q.check(ks); if (rc) return rc;
+    if (!r) return fail(MF_E_ARG, "NULL handle");
+    rc = filter_common(ks, r, threshold, mode, out_bits, nullptr, 1, stats);
     if (rc) return rc;
     DevCtx *ctx; rc = get_ctx(r->device, &ctx, r->lane); if (rc) return rc;
     hipStream_t st = ctx->stream;
     const uint64_t n = r->v.n_reads;
-    const PlaceLayout L(ks, false);
-    HIPCHK(dev_reserve(r->d_rtot, r->cap_rtot, L.words() * 8, false));
-    HIPCHK(dev_reserve(r->d_rsum, r->cap_rsum, PlaceScratch::work_bytes(ks), false));
-    HIPCHK(dev_reserve(r->d_rpos, r->cap_rpos, PlaceScratch::depth_bytes(ks), false));
+    const PlaceLayout L = q.layout(ks);
+    const ReportScratch S = q.scratch(ks);
+    const hipError_t e = dev_reserve(r->d_rtot, r->cap_rtot, L.words() * 8, false);
+    if (e == hipErrorOutOfMemory && q.with_pileup) return pile_nomem(L.words());
+    HIPCHK(e);
+    HIPCHK(dev_reserve(r->d_rsum, r->cap_rsum, S.sums_bytes, false));
+    HIPCHK(dev_reserve(r->d_rpos, r->cap_rpos, S.pos_bytes, false));
     HIPCHK(hipMemsetAsync(r->d_rtot, 0, L.words() * 8, st));
-    if (place_out && n) {
+    PlaceOut *d_place = nullptr; ScoreOut *d_score = nullptr;
+    if (q.place_out && n) {
         HIPCHK(dev_reserve(r->d_place, r->cap_place, n * sizeof(PlaceOut), true));
-        HIPCHK(launch_place_init(r->d_place, n, st));
+        HIPCHK(launch_place_init(d_place = r->d_place, n, st));
+    }
+    if (q.score_out && n) {
+        HIPCHK(dev_reserve(r->d_score, r->cap_score, n * sizeof(ScoreOut), true));
+        HIPCHK(hipMemsetAsync(d_score = r->d_score, 0, n * sizeof(ScoreOut), st));
     }
     uint64_t listed = 0;
-    rc = place_after_filter(ks, r, L, r->d_rtot, place_out ? r->d_place : nullptr, nullptr, &listed); if (rc) return rc;
-    if (place_out && n) HIPCHK(hipMemcpyAsync(place_out, r->d_place, n * sizeof(PlaceOut), hipMemcpyDeviceToHost, st));
-    return place_report(ks, r->device, st, L, r->d_rtot, PlaceScratch{r->d_rsum, r->rpos_u32()}, base_depth, records, unplaced, n - listed);
-}
-
-} // extern "C"
-
-// ------------------------------------------------------------------- pile-up
-struct PileScratch {
-    unsigned long long *sums; PileOut *out; uint8_t *cons;          // the record sums (PILE_SUMS R), the called pile-up, the consensus
-    static size_t sums_bytes(const mf_kmerset *ks) { return std::max<size_t>(ks->rec_len().size(), 1) * PILE_SUMS * 8; }
-    static size_t out_bytes(const mf_kmerset *ks) { return std::max<uint64_t>(ks->positions(), 1) * sizeof(PileOut); }
-    static size_t cons_bytes(const mf_kmerset *ks) { return std::max<uint64_t>(ks->positions(), 1); }
-};
-
-// The called pile-up (positions entries), the consensus (positions bytes), the record summaries (R entries) and unplaced[2] -- the
-// passing reads that are not placed, then not_passing as it is given -- from the counters t of layout L on `device` (stream st); each optional.
-static int pileup_report(mf_kmerset *ks, int device, hipStream_t st, const PlaceLayout &L, unsigned long long *t, uint32_t min_depth, PileScratch s,
-                         mf_pileup_t *pileup, uint8_t *consensus, mf_pileup_record_t *records, uint64_t *unplaced, uint64_t not_passing)
-{
-    static_assert(sizeof(mf_pileup_t) == 16 && sizeof(PileOut) == 16 && sizeof(mf_pileup_record_t) == 8 * PILE_SUMS, "pile-up records");
-    DevTables *T; int rc = build_on_device(ks, device, &T); if (rc) return rc;
-    rc = pileup_tables(ks, device, T); if (rc) return rc;
-    const uint64_t total = ks->positions(), n_rec = ks->rec_len().size();
-    std::vector<unsigned long long> h_cnt(L.n_cnt, 0);
-    if (records && n_rec) HIPCHK(hipMemsetAsync(s.sums, 0, PILE_SUMS * n_rec * 8, st));
-    if (pileup || consensus || records)
-        HIPCHK(launch_pileup_call(L.pile(t), BaitView{T->pile_words, total, T->pile_runlen}, T->place_starts, (uint32_t)n_rec, min_depth,
-                                  pileup ? s.out : nullptr, consensus ? s.cons : nullptr, records ? s.sums : nullptr, st));
-    if (pileup && total) HIPCHK(hipMemcpyAsync(pileup, s.out, total * sizeof(PileOut), hipMemcpyDeviceToHost, st));
-    if (consensus && total) HIPCHK(hipMemcpyAsync(consensus, s.cons, total, hipMemcpyDeviceToHost, st));
-    if (records && n_rec) HIPCHK(hipMemcpyAsync(records, s.sums, PILE_SUMS * n_rec * 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(h_cnt.data(), L.cnt(t), h_cnt.size() * 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    if (unplaced) { unplaced[0] = h_cnt[4 * n_rec]; unplaced[1] = not_passing; }
-    return MF_OK;
-}
-
-static int pileup_args(const mf_kmerset *ks, uint32_t min_depth)
-{
-    if (min_depth == 0) return fail(MF_E_ARG, "min_depth is 0: a called position needs at least one base");
-    if (!ks) return fail(MF_E_ARG, "NULL handle");
-    if (ks->kind != MF_KIND_NUCLEOTIDE) return fail(MF_E_ARG, "the pile-up needs a nucleotide bait set");
-    return MF_OK;
+    rc = place_after_filter(ks, r, L, r->d_rtot, d_place, d_score, &listed); if (rc) return rc;
+    if (d_place) HIPCHK(hipMemcpyAsync(q.place_out, d_place, n * sizeof(PlaceOut), hipMemcpyDeviceToHost, st));
+    if (d_score) HIPCHK(hipMemcpyAsync(q.score_out, d_score, n * sizeof(ScoreOut), hipMemcpyDeviceToHost, st));
+    return placement_report(ks, r->device, st, L, r->d_rtot, q, S, r->d_rsum, r->d_rpos, n - listed);
 }
 
 extern "C" {
@@ -571,111 +550,30 @@ int mf_kmerset_bait_letters(const mf_kmerset *ks, uint8_t *letters, size_t n, si
     return MF_OK;
 }
 
-int mf_pileup(const mf_kmerset *ks_, const mf_reads *reads_, uint32_t threshold, int mode, uint32_t min_depth, uint32_t *out_bits,
+int mf_place(const mf_kmerset *ks, const mf_reads *reads, uint32_t threshold, int mode, uint32_t *out_bits, mf_place_t *place_out,
+             uint32_t *base_depth, mf_place_record_t *records, uint64_t *unplaced, mf_filter_stats_t *stats)
+{
+    PlaceRequest q{"placement", false, false};
+    q.place_out = place_out; q.base_depth = base_depth; q.place_records = records; q.unplaced = unplaced;
+    return placement_resident(ks, reads, threshold, mode, out_bits, stats, q);
+}
+
+int mf_pileup(const mf_kmerset *ks, const mf_reads *reads, uint32_t threshold, int mode, uint32_t min_depth, uint32_t *out_bits,
               mf_pileup_t *pileup, uint8_t *consensus, mf_pileup_record_t *records, uint64_t *unplaced, mf_filter_stats_t *stats)
 {
-    mf_kmerset *ks = const_cast<mf_kmerset *>(ks_);
-    mf_reads *r = const_cast<mf_reads *>(reads_);
-    int rc = pileup_args(ks, min_depth); if (rc) return rc;
-    if (!r) return fail(MF_E_ARG, "NULL handle");
-    rc = filter_common(ks, r, threshold, mode, out_bits, nullptr, 1, stats);
-    if (rc) return rc;
-    DevCtx *ctx; rc = get_ctx(r->device, &ctx, r->lane); if (rc) return rc;
-    hipStream_t st = ctx->stream;
-    const PlaceLayout L(ks, true);
-    const hipError_t e = dev_reserve(r->d_rtot, r->cap_rtot, L.words() * 8, false);
-    if (e == hipErrorOutOfMemory) return pile_nomem(L.words());
-    HIPCHK(e);
-    HIPCHK(dev_reserve(r->d_rsum, r->cap_rsum, PileScratch::sums_bytes(ks), false));
-    HIPCHK(dev_reserve(r->d_rpos, r->cap_rpos, PileScratch::out_bytes(ks) + PileScratch::cons_bytes(ks) + 16, false));
-    HIPCHK(hipMemsetAsync(r->d_rtot, 0, L.words() * 8, st));
-    uint64_t listed = 0;
-    rc = place_after_filter(ks, r, L, r->d_rtot, nullptr, nullptr, &listed); if (rc) return rc;
-    return pileup_report(ks, r->device, st, L, r->d_rtot, min_depth, PileScratch{r->d_rsum, r->rpos_pile(), r->rpos_consensus(ks->positions())}, pileup,
-                         consensus, records, unplaced, r->v.n_reads - listed);
+    PlaceRequest q{"the pile-up", false, true, min_depth};
+    q.pileup = pileup; q.consensus = consensus; q.pileup_records = records; q.unplaced = unplaced;
+    return placement_resident(ks, reads, threshold, mode, out_bits, stats, q);
 }
 
-} // extern "C"
-
-// ------------------------------------------------------------------- verification
-// What verify_report works in: placement's and the pile-up's scratch side by side.  A resident call lays both out in the read set's report
-// buffers (d_rsum: the work words, then the pile-up's sums; d_rpos: the called pile-up, the base depth, the consensus).
-struct VerifyScratch {
-    PlaceScratch place; PileScratch pile;
-    static size_t sums_bytes(const mf_kmerset *ks) { return PlaceScratch::work_bytes(ks) + PileScratch::sums_bytes(ks); }
-    static size_t pos_bytes(const mf_kmerset *ks) { return PileScratch::out_bytes(ks) + PlaceScratch::depth_bytes(ks) + PileScratch::cons_bytes(ks) + 16; }
-    VerifyScratch(const mf_kmerset *ks, unsigned long long *sums, void *pos)
-        : place{sums, reinterpret_cast<uint32_t *>(static_cast<uint8_t *>(pos) + PileScratch::out_bytes(ks))},
-          pile{sums + PlaceScratch::work_bytes(ks) / 8, static_cast<PileOut *>(pos),
-               static_cast<uint8_t *>(pos) + PileScratch::out_bytes(ks) + PlaceScratch::depth_bytes(ks)} {}
-};
-
-// Every report of a verifying placement from the counters t of layout L on `device` (stream st): placement's (place_report), the
-// pile-up's where the layout holds one (pileup_report), the records' scores.  Each optional.
-static int verify_report(mf_kmerset *ks, int device, hipStream_t st, const PlaceLayout &L, unsigned long long *t, uint32_t min_depth, const VerifyScratch &s,
-                         uint32_t *base_depth, mf_place_record_t *place_records, mf_pileup_t *pileup, uint8_t *consensus, mf_pileup_record_t *pileup_records,
-                         mf_score_record_t *score_records, uint64_t *unplaced, uint64_t not_passing)
-{
-    static_assert(sizeof(mf_score_t) == 8 && sizeof(ScoreOut) == 8 && sizeof(mf_score_record_t) == 8 * (4 + MF_SCORE_BINS) && MF_SCORE_BINS == SCORE_BINS, "score records");
-    int rc = place_report(ks, device, st, L, t, s.place, base_depth, place_records, unplaced, not_passing); if (rc) return rc;
-    if (L.n_pile && (pileup || consensus || pileup_records)) {
-        rc = pileup_report(ks, device, st, L, t, min_depth, s.pile, pileup, consensus, pileup_records, nullptr, not_passing); if (rc) return rc;
-    }
-    if (score_records && L.n_rec) {
-        std::vector<unsigned long long> h_cnt(L.n_cnt + L.n_score(), 0);
-        HIPCHK(hipMemcpyAsync(h_cnt.data(), L.cnt(t), h_cnt.size() * 8, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        L.score_records(h_cnt.data(), score_records);
-    }
-    return MF_OK;
-}
-
-static int verify_args(const mf_kmerset *ks, uint32_t min_depth, uint32_t max_permille)
-{
-    if (max_permille > 1000) return fail(MF_E_ARG, "max_permille is %u: the cut is a number from 0 to 1000", max_permille);
-    if (min_depth == 0) return fail(MF_E_ARG, "min_depth is 0: a called position needs at least one base");
-    if (!ks) return fail(MF_E_ARG, "NULL handle");
-    if (ks->kind != MF_KIND_NUCLEOTIDE) return fail(MF_E_ARG, "verification needs a nucleotide bait set");
-    return MF_OK;
-}
-
-extern "C" {
-
-int mf_verify(const mf_kmerset *ks_, const mf_reads *reads_, uint32_t threshold, int mode, uint32_t min_depth, uint32_t max_permille,
+int mf_verify(const mf_kmerset *ks, const mf_reads *reads, uint32_t threshold, int mode, uint32_t min_depth, uint32_t max_permille,
               uint32_t *out_bits, mf_place_t *place_out, mf_score_t *score_out, uint32_t *base_depth, mf_place_record_t *place_records,
               mf_pileup_t *pileup, uint8_t *consensus, mf_pileup_record_t *pileup_records, mf_score_record_t *score_records,
               uint64_t *unplaced, mf_filter_stats_t *stats)
 {
-    mf_kmerset *ks = const_cast<mf_kmerset *>(ks_);
-    mf_reads *r = const_cast<mf_reads *>(reads_);
-    int rc = verify_args(ks, min_depth, max_permille); if (rc) return rc;
-    if (!r) return fail(MF_E_ARG, "NULL handle");
-    rc = filter_common(ks, r, threshold, mode, out_bits, nullptr, 1, stats);
-    if (rc) return rc;
-    DevCtx *ctx; rc = get_ctx(r->device, &ctx, r->lane); if (rc) return rc;
-    hipStream_t st = ctx->stream;
-    const uint64_t n = r->v.n_reads;
-    const PlaceLayout L(ks, pileup || consensus || pileup_records, true, max_permille);
-    const hipError_t e = dev_reserve(r->d_rtot, r->cap_rtot, L.words() * 8, false);
-    if (e == hipErrorOutOfMemory && L.n_pile) return pile_nomem(L.words());
-    HIPCHK(e);
-    HIPCHK(dev_reserve(r->d_rsum, r->cap_rsum, VerifyScratch::sums_bytes(ks), false));
-    HIPCHK(dev_reserve(r->d_rpos, r->cap_rpos, VerifyScratch::pos_bytes(ks), false));
-    HIPCHK(hipMemsetAsync(r->d_rtot, 0, L.words() * 8, st));
-    if (place_out && n) {
-        HIPCHK(dev_reserve(r->d_place, r->cap_place, n * sizeof(PlaceOut), true));
-        HIPCHK(launch_place_init(r->d_place, n, st));
-    }
-    if (score_out && n) {
-        HIPCHK(dev_reserve(r->d_score, r->cap_score, n * sizeof(ScoreOut), true));
-        HIPCHK(hipMemsetAsync(r->d_score, 0, n * sizeof(ScoreOut), st));
-    }
-    uint64_t listed = 0;
-    rc = place_after_filter(ks, r, L, r->d_rtot, place_out ? r->d_place : nullptr, score_out ? r->d_score : nullptr, &listed); if (rc) return rc;
-    if (place_out && n) HIPCHK(hipMemcpyAsync(place_out, r->d_place, n * sizeof(PlaceOut), hipMemcpyDeviceToHost, st));
-    if (score_out && n) HIPCHK(hipMemcpyAsync(score_out, r->d_score, n * sizeof(ScoreOut), hipMemcpyDeviceToHost, st));
-    return verify_report(ks, r->device, st, L, r->d_rtot, min_depth, VerifyScratch(ks, r->d_rsum, r->d_rpos), base_depth, place_records, pileup, consensus,
-                         pileup_records, score_records, unplaced, n - listed);
+    const PlaceRequest q{"verification", true, pileup || consensus || pileup_records, min_depth, max_permille, place_out, score_out, base_depth,
+                         place_records, pileup, consensus, pileup_records, score_records, unplaced};
+    return placement_resident(ks, reads, threshold, mode, out_bits, stats, q);
 }
 
 } // extern "C"
@@ -762,15 +660,14 @@ struct DepthTotals : DeviceTotals {
     int add(mf_reads *R, unsigned long long *t) override { return depth_after_filter(ks, R, t); }
 };
 
-// Placement, and with_pileup the pile-up: the footprints, record counters and bases of every mate that passes (PlaceLayout), and how
-// many mates there were and passed.  verify: the placed reads are scored and cut at max_permille first (mf_verify).
+// The placement family: the footprints, record counters and (with a pile-up) bases of every mate that passes, into the layout of the
+// request q, and how many mates there were and passed.  A verifying request: the placed reads are scored and cut at max_permille first.
 struct PlaceTotals : DeviceTotals {
     const PlaceLayout L;
     std::atomic<uint64_t> mates{0}, passing{0};
-    PlaceTotals(mf_kmerset *ks_, bool with_pileup, bool verify = false, uint32_t max_permille = 1000)
-        : DeviceTotals(ks_, with_pileup ? pile_nomem : nullptr), L(ks_, with_pileup, verify, max_permille) {}
+    PlaceTotals(mf_kmerset *ks_, const PlaceRequest &q) : DeviceTotals(ks_, q.with_pileup ? pile_nomem : nullptr), L(q.layout(ks_)) {}
     void restart() override { release(); mates = 0; passing = 0; }
-    int tables(int device, DevTables *T) override { return L.verify ? pileup_tables(ks, device, T) : place_tables(ks, device, T); }
+    int tables(int device, DevTables *T) override { return placement_tables(ks, device, L, &T); }
     size_t words(const DevTables *) const override { return L.words(); }
     int add(mf_reads *R, unsigned long long *t) override
     {
@@ -800,6 +697,24 @@ static int files_with_totals(mf_kmerset *ks, const char *fq1, const char *fq2, c
     if (rc == MF_OK) rc = dt.fold_into(devices[0], t0);
     if (rc == MF_OK) rc = get_ctx(devices[0], ctx);
     return rc;
+}
+
+// The file-level call of the family: the counters of every mate that passes summed over the devices, then the report once, on the
+// first listed device, in two temporaries of its own.
+static int placement_files(mf_kmerset *ks, const char *fq1, const char *fq2, const char *out1, const char *out2, uint32_t threshold, int pair_mode,
+                           const int *devices, int n_devices, uint64_t *kept, uint64_t *total, const PlaceRequest &q)
+{
+    int rc = q.check(ks); if (rc) return rc;
+    PlaceTotals pt(ks, q);
+    unsigned long long *t0 = nullptr; DevCtx *ctx = nullptr;
+    rc = files_with_totals(ks, fq1, fq2, out1, out2, threshold, pair_mode, devices, n_devices, kept, total, pt, &t0, &ctx);
+    if (rc) return rc;
+    const ReportScratch S = q.scratch(ks);
+    DevScratch tmp;
+    unsigned long long *sums = nullptr; uint8_t *pos = nullptr;
+    if (S.sums_bytes) HIPCHK(tmp.alloc(sums, S.sums_bytes));
+    if (S.pos_bytes) HIPCHK(tmp.alloc(pos, S.pos_bytes));
+    return placement_report(ks, devices[0], ctx->stream, pt.L, t0, q, S, sums, pos, pt.mates - pt.passing);
 }
 
 extern "C" {
@@ -842,17 +757,9 @@ int mf_filter_fastq_files_placed(mf_kmerset *ks, const char *fq1, const char *fq
                                  uint32_t threshold, int pair_mode, const int *devices, int n_devices,
                                  uint32_t *base_depth, mf_place_record_t *records, uint64_t *unplaced, uint64_t *kept, uint64_t *total)
 {
-    if (!ks) return fail(MF_E_ARG, "NULL handle");
-    if (ks->kind != MF_KIND_NUCLEOTIDE) return fail(MF_E_ARG, "placement needs a nucleotide bait set");
-    PlaceTotals pt(ks, false);
-    unsigned long long *t0 = nullptr; DevCtx *ctx = nullptr;
-    const int rc = files_with_totals(ks, fq1, fq2, out1, out2, threshold, pair_mode, devices, n_devices, kept, total, pt, &t0, &ctx);
-    if (rc) return rc;
-    DevScratch tmp;
-    PlaceScratch s{nullptr, nullptr};
-    HIPCHK(tmp.alloc(s.depth, PlaceScratch::depth_bytes(ks)));
-    HIPCHK(tmp.alloc(s.work, PlaceScratch::work_bytes(ks)));
-    return place_report(ks, devices[0], ctx->stream, pt.L, t0, s, base_depth, records, unplaced, pt.mates - pt.passing);
+    PlaceRequest q{"placement", false, false};
+    q.base_depth = base_depth; q.place_records = records; q.unplaced = unplaced;
+    return placement_files(ks, fq1, fq2, out1, out2, threshold, pair_mode, devices, n_devices, kept, total, q);
 }
 
 int mf_filter_fastq_files_pileup(mf_kmerset *ks, const char *fq1, const char *fq2, const char *out1, const char *out2,
@@ -860,17 +767,9 @@ int mf_filter_fastq_files_pileup(mf_kmerset *ks, const char *fq1, const char *fq
                                  mf_pileup_t *pileup, uint8_t *consensus, mf_pileup_record_t *records, uint64_t *unplaced,
                                  uint64_t *kept, uint64_t *total)
 {
-    int rc = pileup_args(ks, min_depth); if (rc) return rc;
-    PlaceTotals pt(ks, true);
-    unsigned long long *t0 = nullptr; DevCtx *ctx = nullptr;
-    rc = files_with_totals(ks, fq1, fq2, out1, out2, threshold, pair_mode, devices, n_devices, kept, total, pt, &t0, &ctx);
-    if (rc) return rc;
-    DevScratch tmp;
-    PileScratch s{nullptr, nullptr, nullptr};
-    HIPCHK(tmp.alloc(s.out, PileScratch::out_bytes(ks)));
-    HIPCHK(tmp.alloc(s.cons, PileScratch::cons_bytes(ks)));
-    HIPCHK(tmp.alloc(s.sums, PileScratch::sums_bytes(ks)));
-    return pileup_report(ks, devices[0], ctx->stream, pt.L, t0, min_depth, s, pileup, consensus, records, unplaced, pt.mates - pt.passing);
+    PlaceRequest q{"the pile-up", false, true, min_depth};
+    q.pileup = pileup; q.consensus = consensus; q.pileup_records = records; q.unplaced = unplaced;
+    return placement_files(ks, fq1, fq2, out1, out2, threshold, pair_mode, devices, n_devices, kept, total, q);
 }
 
 int mf_filter_fastq_files_verified(mf_kmerset *ks, const char *fq1, const char *fq2, const char *out1, const char *out2,
@@ -878,17 +777,9 @@ int mf_filter_fastq_files_verified(mf_kmerset *ks, const char *fq1, const char *
                                    uint32_t *base_depth, mf_place_record_t *place_records, mf_pileup_t *pileup, uint8_t *consensus,
                                    mf_pileup_record_t *pileup_records, mf_score_record_t *score_records, uint64_t *unplaced, uint64_t *kept, uint64_t *total)
 {
-    int rc = verify_args(ks, min_depth, max_permille); if (rc) return rc;
-    PlaceTotals pt(ks, pileup || consensus || pileup_records, true, max_permille);
-    unsigned long long *t0 = nullptr; DevCtx *ctx = nullptr;
-    rc = files_with_totals(ks, fq1, fq2, out1, out2, threshold, pair_mode, devices, n_devices, kept, total, pt, &t0, &ctx);
-    if (rc) return rc;
-    DevScratch tmp;
-    unsigned long long *sums = nullptr; uint8_t *pos = nullptr;
-    HIPCHK(tmp.alloc(sums, VerifyScratch::sums_bytes(ks)));
-    HIPCHK(tmp.alloc(pos, VerifyScratch::pos_bytes(ks)));
-    return verify_report(ks, devices[0], ctx->stream, pt.L, t0, min_depth, VerifyScratch(ks, sums, pos), base_depth, place_records, pileup, consensus,
-                         pileup_records, score_records, unplaced, pt.mates - pt.passing);
+    const PlaceRequest q{"verification", true, pileup || consensus || pileup_records, min_depth, max_permille, nullptr, nullptr, base_depth,
+                         place_records, pileup, consensus, pileup_records, score_records, unplaced};
+    return placement_files(ks, fq1, fq2, out1, out2, threshold, pair_mode, devices, n_devices, kept, total, q);
 }
 
 } // extern "C"

@@ -450,37 +450,49 @@ def record_depth(ks: KmerSet, reads: Reads, threshold: int = 1, mode: int = MODE
     return bits[:(n + 31) // 32], profile[:int(starts[-1])], records[:len(starts) - 1]
 
 
+def _read_outputs(reads: Reads, *dtypes):
+    """the pass bitmap of a resident call and, for each dtype, an array of one entry a read: their pointers in that order, and what
+    gives them trimmed to the read set"""
+    n = reads.info.n_reads
+    a = [np.zeros(max((n + 31) // 32, 1), dtype=np.uint32)] + [np.zeros(max(n, 1), dtype=d) for d in dtypes]
+    return [x.ctypes.data for x in a], lambda: [a[0][:(n + 31) // 32]] + [x[:n] for x in a[1:]]
+
+
+def _report_outputs(ks: KmerSet, fields, leave_out=()):
+    """the per-position and per-record arrays `fields` (named as Verified names them, in the C order of the call) of a placement-family
+    call: their pointers in that order (NULL for those in leave_out), and what gives {field: the array trimmed to the set, or None}"""
+    starts = ks.record_starts
+    P, R = int(starts[-1]), len(starts) - 1
+    shape = {"base_depth": (P, np.uint32), "place_records": (R, PLACE_RECORD), "pileup": (P, PILEUP), "consensus": (P, np.uint8),
+             "pileup_records": (R, PILEUP_RECORD), "score_records": (R, SCORE_RECORD), "unplaced": (2, np.uint64)}
+    a = {f: None if f in leave_out else np.zeros(max(shape[f][0], 1), dtype=shape[f][1]) for f in fields}
+    ptrs = [x.ctypes.data if x is not None else None for x in a.values()]
+    return ptrs, lambda: {f: (x[:shape[f][0]] if x is not None else None) for f, x in a.items()}
+
+
+_PLACE_FIELDS = ("base_depth", "place_records", "unplaced")
+_PILEUP_FIELDS = ("pileup", "consensus", "pileup_records", "unplaced")
+_VERIFY_FIELDS = ("base_depth", "place_records", "pileup", "consensus", "pileup_records", "score_records", "unplaced")
+
+
 def place_reads(ks: KmerSet, reads: Reads, threshold: int = 1, mode: int = MODE_SCREENED):
     """One filter pass, then where every passing read lies on the bait (include/mitofilter.h: mf_place).  -> (bits u32[ceil(n/32)],
     place PLACE[n]: record (or PLACE_AMBIGUOUS / PLACE_NONE), strand, start, end, votes, windows, base_depth u32[positions],
     records PLACE_RECORD[R], unplaced u64[2]: passing reads that are not placed, reads that do not pass)."""
-    n = reads.info.n_reads
-    starts = ks.record_starts
-    bits = np.zeros(max((n + 31) // 32, 1), dtype=np.uint32)
-    place = np.zeros(max(n, 1), dtype=PLACE)
-    base_depth = np.zeros(max(int(starts[-1]), 1), dtype=np.uint32)
-    records = np.zeros(max(len(starts) - 1, 1), dtype=PLACE_RECORD)
-    unplaced = np.zeros(2, dtype=np.uint64)
-    _chk(load().mf_place(ks._h, reads._h, threshold, mode, bits.ctypes.data, place.ctypes.data, base_depth.ctypes.data,
-                         records.ctypes.data, unplaced.ctypes.data, None))
-    return bits[:(n + 31) // 32], place[:n], base_depth[:int(starts[-1])], records[:len(starts) - 1], unplaced
+    per_read, read_results = _read_outputs(reads, PLACE)
+    ptrs, results = _report_outputs(ks, _PLACE_FIELDS)
+    _chk(load().mf_place(ks._h, reads._h, threshold, mode, *per_read, *ptrs, None))
+    return (*read_results(), *results().values())
 
 
 def pileup_reads(ks: KmerSet, reads: Reads, threshold: int = 1, mode: int = MODE_SCREENED, min_depth: int = 1):
     """One filter pass, then the placed reads' bases piled on the bait (include/mitofilter.h: mf_pileup).  -> (bits u32[ceil(n/32)],
     pileup PILEUP[positions]: bases a, c, g, t in the bait's forward letters, consensus u8[positions]: the called letter in upper case,
     N where the most is tied, the bait's letter in lower case below min_depth, records PILEUP_RECORD[R], unplaced u64[2] as place_reads)."""
-    n = reads.info.n_reads
-    starts = ks.record_starts
-    P, R = int(starts[-1]), len(starts) - 1
-    bits = np.zeros(max((n + 31) // 32, 1), dtype=np.uint32)
-    pileup = np.zeros(max(P, 1), dtype=PILEUP)
-    consensus = np.zeros(max(P, 1), dtype=np.uint8)
-    records = np.zeros(max(R, 1), dtype=PILEUP_RECORD)
-    unplaced = np.zeros(2, dtype=np.uint64)
-    _chk(load().mf_pileup(ks._h, reads._h, threshold, mode, min_depth, bits.ctypes.data, pileup.ctypes.data, consensus.ctypes.data,
-                          records.ctypes.data, unplaced.ctypes.data, None))
-    return bits[:(n + 31) // 32], pileup[:P], consensus[:P], records[:R], unplaced
+    per_read, read_results = _read_outputs(reads)
+    ptrs, results = _report_outputs(ks, _PILEUP_FIELDS)
+    _chk(load().mf_pileup(ks._h, reads._h, threshold, mode, min_depth, *per_read, *ptrs, None))
+    return (*read_results(), *results().values())
 
 
 class Verified:
@@ -501,20 +513,6 @@ class Verified:
         return "Verified(%s)" % ", ".join(name for name in self.__slots__ if getattr(self, name) is not None)
 
 
-def _verify_outputs(ks: KmerSet, pileup: bool):
-    """the per-position and per-record arrays of a verifying call, and their pointers in the C order (NULL for what pileup=False leaves out)"""
-    starts = ks.record_starts
-    P, R = int(starts[-1]), len(starts) - 1
-    a = {"base_depth": np.zeros(max(P, 1), dtype=np.uint32), "place_records": np.zeros(max(R, 1), dtype=PLACE_RECORD),
-         "pileup": np.zeros(max(P, 1), dtype=PILEUP) if pileup else None, "consensus": np.zeros(max(P, 1), dtype=np.uint8) if pileup else None,
-         "pileup_records": np.zeros(max(R, 1), dtype=PILEUP_RECORD) if pileup else None,
-         "score_records": np.zeros(max(R, 1), dtype=SCORE_RECORD), "unplaced": np.zeros(2, dtype=np.uint64)}
-    order = ("base_depth", "place_records", "pileup", "consensus", "pileup_records", "score_records", "unplaced")
-    ptrs = [a[f].ctypes.data if a[f] is not None else None for f in order]
-    size = {"base_depth": P, "pileup": P, "consensus": P, "place_records": R, "pileup_records": R, "score_records": R, "unplaced": 2}
-    return a, ptrs, lambda: {f: (a[f][:size[f]] if a[f] is not None else None) for f in order}
-
-
 def _check_cut(min_depth: int, max_permille: int):
     if not 0 <= int(max_permille) <= 1000:
         raise ValueError("max_permille is a number from 0 to 1000")
@@ -528,14 +526,11 @@ def verify_reads(ks: KmerSet, reads: Reads, threshold: int = 1, mode: int = MODE
     thousand compared bases; what is accepted gives base depth and (pileup=True) the pile-up (include/mitofilter.h: mf_verify).
     -> Verified with bits, place, score and the shared fields."""
     _check_cut(min_depth, max_permille)
-    n = reads.info.n_reads
-    bits = np.zeros(max((n + 31) // 32, 1), dtype=np.uint32)
-    place = np.zeros(max(n, 1), dtype=PLACE)
-    score = np.zeros(max(n, 1), dtype=SCORE)
-    _, ptrs, result = _verify_outputs(ks, pileup)
-    _chk(load().mf_verify(ks._h, reads._h, threshold, mode, min_depth, max_permille, bits.ctypes.data, place.ctypes.data, score.ctypes.data,
-                          *ptrs, None))
-    return Verified(bits=bits[:(n + 31) // 32], place=place[:n], score=score[:n], **result())
+    per_read, read_results = _read_outputs(reads, PLACE, SCORE)
+    ptrs, results = _report_outputs(ks, _VERIFY_FIELDS, () if pileup else _PILEUP_FIELDS[:3])
+    _chk(load().mf_verify(ks._h, reads._h, threshold, mode, min_depth, max_permille, *per_read, *ptrs, None))
+    bits, place, score = read_results()
+    return Verified(bits=bits, place=place, score=score, **results())
 
 
 def consensus_fasta(names, starts, consensus, width: int = 60) -> str:
@@ -693,14 +688,9 @@ def filter_fastq_files_placed(ks: KmerSet, fq1: str, fq2: Optional[str], out1: s
     """filter_fastq_files plus the placement on the bait of every mate that passes its own threshold (the pair rule decides only what
     is written).  -> (kept, total, base_depth u32[positions], records PLACE_RECORD[R], unplaced u64[2]: passing mates that are not
     placed, mates that do not pass)."""
-    starts = ks.record_starts
-    P, R = int(starts[-1]), len(starts) - 1
-    base_depth = np.zeros(max(P, 1), dtype=np.uint32)
-    records = np.zeros(max(R, 1), dtype=PLACE_RECORD)
-    unplaced = np.zeros(2, dtype=np.uint64)
-    kept, total = _files_call("mf_filter_fastq_files_placed", ks, fq1, fq2, out1, out2, threshold, pair_mode, devices, n_devices,
-                              base_depth.ctypes.data, records.ctypes.data, unplaced.ctypes.data)
-    return kept, total, base_depth[:P], records[:R], unplaced
+    ptrs, results = _report_outputs(ks, _PLACE_FIELDS)
+    kept, total = _files_call("mf_filter_fastq_files_placed", ks, fq1, fq2, out1, out2, threshold, pair_mode, devices, n_devices, *ptrs)
+    return (kept, total, *results().values())
 
 
 def filter_fastq_files_pileup(ks: KmerSet, fq1: str, fq2: Optional[str], out1: str, out2: Optional[str],
@@ -709,15 +699,10 @@ def filter_fastq_files_pileup(ks: KmerSet, fq1: str, fq2: Optional[str], out1: s
     """filter_fastq_files plus the pile-up on the bait of every mate that passes its own threshold (the pair rule decides only what is
     written).  -> (kept, total, pileup PILEUP[positions], consensus u8[positions], records PILEUP_RECORD[R], unplaced u64[2]: passing
     mates that are not placed, mates that do not pass)."""
-    starts = ks.record_starts
-    P, R = int(starts[-1]), len(starts) - 1
-    pileup = np.zeros(max(P, 1), dtype=PILEUP)
-    consensus = np.zeros(max(P, 1), dtype=np.uint8)
-    records = np.zeros(max(R, 1), dtype=PILEUP_RECORD)
-    unplaced = np.zeros(2, dtype=np.uint64)
+    ptrs, results = _report_outputs(ks, _PILEUP_FIELDS)
     kept, total = _files_call("mf_filter_fastq_files_pileup", ks, fq1, fq2, out1, out2, threshold, pair_mode, devices, n_devices,
-                              min_depth, pileup.ctypes.data, consensus.ctypes.data, records.ctypes.data, unplaced.ctypes.data)
-    return kept, total, pileup[:P], consensus[:P], records[:R], unplaced
+                              min_depth, *ptrs)
+    return (kept, total, *results().values())
 
 
 def filter_fastq_files_verified(ks: KmerSet, fq1: str, fq2: Optional[str], out1: str, out2: Optional[str],
@@ -727,10 +712,10 @@ def filter_fastq_files_verified(ks: KmerSet, fq1: str, fq2: Optional[str], out1:
     mates are scored against the bait and cut at max_permille (the pair rule decides only what is written; a rejected mate is still
     written).  -> Verified with kept, total and the shared fields."""
     _check_cut(min_depth, max_permille)
-    _, ptrs, result = _verify_outputs(ks, pileup)
+    ptrs, results = _report_outputs(ks, _VERIFY_FIELDS, () if pileup else _PILEUP_FIELDS[:3])
     kept, total = _files_call("mf_filter_fastq_files_verified", ks, fq1, fq2, out1, out2, threshold, pair_mode, devices, n_devices,
                               min_depth, max_permille, *ptrs)
-    return Verified(kept=kept, total=total, **result())
+    return Verified(kept=kept, total=total, **results())
 
 
 def set_option(name: str, value) -> None:
