@@ -939,6 +939,18 @@ int mf_filter_packed(const mf_kmerset *ks, int device, const uint32_t *words, co
 // what the calling thread's last file-level call did (mf_last_ingest_stats)
 static thread_local mf_ingest_stats_t t_ingest_stats;
 static thread_local bool t_ingest_stats_valid = false;
+// what a device ingest call that took the input reports through mf_last_ingest_stats
+static void publish_ingest_stats(const IngestStats &is)
+{
+    mf_ingest_stats_t &o = t_ingest_stats;
+    memset(&o, 0, sizeof o);
+    o.path = MF_INGEST_PATH_DEVICE; o.n_devices = is.n_devices; o.consumers = is.consumers;
+    o.input_bytes = is.input_bytes; o.text_bytes = is.text_bytes; o.records = is.records;
+    o.seconds = is.seconds; o.decode_busy_seconds = is.decode_busy_seconds;
+    o.pool_bytes_peak = is.pool_bytes_peak; o.device_bytes_peak = is.device_bytes_peak;
+    o.chunks = is.chunks; o.chunks_linked = is.chunks_linked; o.gaps = is.gaps; o.gap_bytes = is.gap_bytes;
+    t_ingest_stats_valid = true;
+}
 
 // the file-level call on a list of (logical) devices
 // report (optional): what the call reports on the reads that pass (mf_report.cpp), on whichever path takes the input: its after_pass runs
@@ -980,14 +992,7 @@ int filter_fastq_files_on(mf_kmerset *ks, const char *fq1, const char *fq2, cons
             std::string derr; IngestStats is;
             const int drc = run_device_ingest(ks, fq1, fq2, out1, out2, threshold, pair_mode == MF_PAIR_BOTH, devices, n_devices, kept, total, derr, &is, report);
             if (drc == MF_OK) {
-                mf_ingest_stats_t &o = t_ingest_stats;
-                memset(&o, 0, sizeof o);
-                o.path = MF_INGEST_PATH_DEVICE; o.n_devices = is.n_devices; o.consumers = is.consumers;
-                o.input_bytes = is.input_bytes; o.text_bytes = is.text_bytes; o.records = is.records;
-                o.seconds = is.seconds; o.decode_busy_seconds = is.decode_busy_seconds;
-                o.pool_bytes_peak = is.pool_bytes_peak; o.device_bytes_peak = is.device_bytes_peak;
-                o.chunks = is.chunks; o.chunks_linked = is.chunks_linked; o.gaps = is.gaps; o.gap_bytes = is.gap_bytes;
-                t_ingest_stats_valid = true;
+                publish_ingest_stats(is);
                 return MF_OK;
             }
             if (drc != MF_DEVINGEST_DECLINED) return fail(drc, "%s", derr.c_str());
@@ -1126,7 +1131,114 @@ int mf_h2d_bandwidth(int device, size_t bytes, int reps, double *gb_per_s)
     return MF_OK;
 }
 
+} // extern "C"
+
 // ------------------------------------------------------------- quality filter
+// What the host quality path keeps on the device for one call: five scratch buffers that grow with the batches, and the de-duplication
+// set.  The device is set up by the first batch that needs it (the decision thread), while the readers are already parsing: HIP's
+// start-up is a third of a second, as long as the whole pipeline takes for a few million records.  Without a gfx950 device the call
+// fails there with MF_E_NO_DEVICE (no CPU fallback) -- the output files have been created by then.  Everything is freed with the object.
+struct QualDevice {
+    const int device;
+    DevCtx *ctx = nullptr; hipStream_t st = nullptr;
+    struct Scratch { void *p = nullptr; size_t cap = 0; } d_text, d_recs, d_cnt, d_hash, d_flags;
+    // The de-duplication set lives on the device for the whole file: keys + smallest file index per key.  Sized for the first batches
+    // and doubled (rehashed by a kernel) before a batch that could fill it beyond a half.
+    struct Table {
+        unsigned long long *keys = nullptr, *first = nullptr;
+        hipError_t release()
+        {
+            if (!keys && !first) return hipSuccess;
+            const hipError_t a = hipFree(keys), b = hipFree(first);
+            keys = first = nullptr;
+            return a != hipSuccess ? a : b;
+        }
+        ~Table() { (void)release(); }
+    } ds;
+    unsigned long long *small = nullptr;                  // [0] zero_idx, [1] n_keys
+    uint64_t slots = 0, n_keys = 0, base = 0;
+
+    explicit QualDevice(int dev) : device(dev) {}
+    QualDevice(const QualDevice &) = delete;
+    ~QualDevice() { if (ctx) for (Scratch *s : {&d_text, &d_recs, &d_cnt, &d_hash, &d_flags}) (void)hipFree(s->p); if (ctx) (void)hipFree(small); }
+
+#define QCHK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { err = std::string(#call) + ": " + hipGetErrorString(e_); return MF_E_HIP; } } while (0)
+    int ensure_device(std::string &err)
+    {
+        if (ctx) return MF_OK;
+        const int r = get_ctx(device, &ctx);
+        if (r) { ctx = nullptr; err = mf_last_error(); return r; }
+        st = ctx->stream;
+        return MF_OK;
+    }
+    static hipError_t need(Scratch &s, size_t bytes)
+    {
+        if (bytes <= s.cap) return hipSuccess;
+        if (s.p) hipFree(s.p);
+        s.p = nullptr; s.cap = 0;
+        hipError_t e = dev_malloc(&s.p, bytes + bytes / 4 + 4096);
+        if (e == hipSuccess) s.cap = bytes + bytes / 4 + 4096;
+        return e;
+    }
+    // QualScanFn: the counts of a batch's records, and their hashes, which stay on the device for the dedup call
+    int scan(const char *text, size_t len, const QualSpan *recs, uint32_t n, uint32_t q, uint32_t *n_count, uint32_t *bad_count, bool want_hashes, std::string &err)
+    {
+        { const int r = ensure_device(err); if (r) return r; }
+        QCHK(hipSetDevice(phys(device)));
+        QCHK(need(d_text, len + 64)); QCHK(need(d_recs, (size_t)n * sizeof(QualSpan))); QCHK(need(d_cnt, (size_t)n * 8));
+        if (want_hashes) QCHK(need(d_hash, (size_t)n * 8));
+        QCHK(hipMemcpyAsync(d_text.p, text, len, hipMemcpyHostToDevice, st));
+        QCHK(hipMemcpyAsync(d_recs.p, recs, (size_t)n * sizeof(QualSpan), hipMemcpyHostToDevice, st));
+        uint32_t *dn = (uint32_t *)d_cnt.p, *db = dn + n;
+        QCHK(launch_qualscan((const uint8_t *)d_text.p, (const QualRec *)d_recs.p, n, q, dn, db, want_hashes ? (uint64_t *)d_hash.p : nullptr, st));
+        QCHK(hipMemcpyAsync(n_count, dn, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+        QCHK(hipMemcpyAsync(bad_count, db, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+        QCHK(hipStreamSynchronize(st));                   // (the hashes stay on the device for the dedup call)
+        return MF_OK;
+    }
+    int table_alloc(uint64_t n_slots, Table &t, std::string &err)
+    {
+        QCHK(dev_malloc((void **)&t.keys, n_slots * 8)); QCHK(dev_malloc((void **)&t.first, n_slots * 8));
+        QCHK(hipMemsetAsync(t.keys, 0, n_slots * 8, st)); QCHK(hipMemsetAsync(t.first, 0xFF, n_slots * 8, st));
+        return MF_OK;
+    }
+    // QualDedupFn, on the records of the last scan
+    int dedup(const uint8_t *alive, uint32_t n, uint8_t *dup, std::string &err)
+    {
+        QCHK(hipSetDevice(phys(device)));
+        if (!ds.keys) {
+            uint64_t lg = env_u32("MF_DEDUP_LOG2_SLOTS", 24);
+            if (lg < 4) lg = 4; if (lg > 34) lg = 34;
+            slots = (uint64_t)1 << lg;
+            const int rc2 = table_alloc(slots, ds, err); if (rc2) return rc2;
+            QCHK(dev_malloc((void **)&small, 16));
+            QCHK(hipMemsetAsync(small, 0xFF, 8, st)); QCHK(hipMemsetAsync(small + 1, 0, 8, st));
+        }
+        while (2 * (n_keys + n) > slots) {                // (every record of the batch may be a new key)
+            Table t2;                                     // (freed on every way out: it holds the new table until the rehash is done, the old one after)
+            const int rc2 = table_alloc(slots * 2, t2, err); if (rc2) return rc2;
+            QCHK(launch_dedup_rehash(ds.keys, ds.first, slots, t2.keys, t2.first, slots * 2, st));
+            QCHK(hipStreamSynchronize(st));
+            std::swap(ds.keys, t2.keys); std::swap(ds.first, t2.first); slots *= 2;
+            QCHK(t2.release());
+        }
+        QCHK(need(d_flags, (size_t)n * 2));
+        uint8_t *d_alive = (uint8_t *)d_flags.p, *d_dup = d_alive + n;
+        QCHK(hipMemcpyAsync(d_alive, alive, n, hipMemcpyHostToDevice, st));
+        QCHK(launch_dedup((const uint64_t *)d_hash.p, d_alive, n, base, ds.keys, ds.first, slots, small, small + 1, d_dup, st));
+        QCHK(hipMemcpyAsync(dup, d_dup, n, hipMemcpyDeviceToHost, st));
+        unsigned long long nk = 0;
+        QCHK(hipMemcpyAsync(&nk, small + 1, 8, hipMemcpyDeviceToHost, st));
+        QCHK(hipStreamSynchronize(st));
+        n_keys = nk; base += n;
+        return MF_OK;
+    }
+#undef QCHK
+};
+static_assert(sizeof(QualSpan) == sizeof(QualRec), "host and device record layouts must match");
+
+extern "C" {
+
 int mf_qualfilter_files(const char *fq1, const char *fq2, const char *out1, const char *out2,
                         uint64_t start, uint64_t end, uint64_t ns, uint32_t quality, float limit,
                         int dedup, uint64_t trim, int truncate_only, int device,
@@ -1152,14 +1264,7 @@ int mf_qualfilter_files(const char *fq1, const char *fq2, const char *out1, cons
             std::string derr; IngestStats is; bool pan = false;
             const int drc = run_device_qualfilter(fq1, fq2, out1, out2, P, device, kept, total, &pan, derr, &is);
             if (drc == MF_OK) {
-                mf_ingest_stats_t &o = t_ingest_stats;
-                memset(&o, 0, sizeof o);
-                o.path = MF_INGEST_PATH_DEVICE; o.n_devices = is.n_devices; o.consumers = is.consumers;
-                o.input_bytes = is.input_bytes; o.text_bytes = is.text_bytes; o.records = is.records;
-                o.seconds = is.seconds; o.decode_busy_seconds = is.decode_busy_seconds;
-                o.pool_bytes_peak = is.pool_bytes_peak; o.device_bytes_peak = is.device_bytes_peak;
-                o.chunks = is.chunks; o.chunks_linked = is.chunks_linked; o.gaps = is.gaps; o.gap_bytes = is.gap_bytes;
-                t_ingest_stats_valid = true;
+                publish_ingest_stats(is);
                 if (panicked) *panicked = pan ? 1 : 0;
                 return MF_OK;
             }
@@ -1168,85 +1273,13 @@ int mf_qualfilter_files(const char *fq1, const char *fq2, const char *out1, cons
         }
     }
     t_ingest_stats_valid = false;
-    // The device is set up by the first batch that needs it (the decision thread), while the readers are already parsing: HIP's
-    // start-up is a third of a second, as long as the whole pipeline takes for a few million records.  Without a gfx950 device the
-    // call fails there with MF_E_NO_DEVICE (no CPU fallback) -- the output files have been created by then.
-    DevCtx *ctx = nullptr; hipStream_t st = nullptr; int rc = MF_OK;
-    auto ensure_device = [&](std::string &err) -> int {
-        if (ctx) return MF_OK;
-        const int r = get_ctx(device, &ctx);
-        if (r) { ctx = nullptr; err = mf_last_error(); return r; }
-        st = ctx->stream;
-        return MF_OK;
-    };
-    struct Scratch { void *p = nullptr; size_t cap = 0; } d_text, d_recs, d_cnt, d_hash, d_flags;
-    auto need = [&](Scratch &s, size_t bytes) -> hipError_t {
-        if (bytes <= s.cap) return hipSuccess;
-        if (s.p) hipFree(s.p);
-        s.p = nullptr; s.cap = 0;
-        hipError_t e = dev_malloc(&s.p, bytes + bytes / 4 + 4096);
-        if (e == hipSuccess) s.cap = bytes + bytes / 4 + 4096;
-        return e;
-    };
-#define QCHK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { err = std::string(#call) + ": " + hipGetErrorString(e_); return MF_E_HIP; } } while (0)
-    QualScanFn scan = [&](const char *text, size_t len, const QualSpan *recs, uint32_t n, uint32_t q, uint32_t *n_count,
-                          uint32_t *bad_count, bool want_hashes, std::string &err) -> int {
-        { const int r = ensure_device(err); if (r) return r; }
-        QCHK(hipSetDevice(phys(device)));
-        QCHK(need(d_text, len + 64)); QCHK(need(d_recs, (size_t)n * sizeof(QualSpan))); QCHK(need(d_cnt, (size_t)n * 8));
-        if (want_hashes) QCHK(need(d_hash, (size_t)n * 8));
-        QCHK(hipMemcpyAsync(d_text.p, text, len, hipMemcpyHostToDevice, st));
-        QCHK(hipMemcpyAsync(d_recs.p, recs, (size_t)n * sizeof(QualSpan), hipMemcpyHostToDevice, st));
-        uint32_t *dn = (uint32_t *)d_cnt.p, *db = dn + n;
-        QCHK(launch_qualscan((const uint8_t *)d_text.p, (const QualRec *)d_recs.p, n, q, dn, db, want_hashes ? (uint64_t *)d_hash.p : nullptr, st));
-        QCHK(hipMemcpyAsync(n_count, dn, (size_t)n * 4, hipMemcpyDeviceToHost, st));
-        QCHK(hipMemcpyAsync(bad_count, db, (size_t)n * 4, hipMemcpyDeviceToHost, st));
-        QCHK(hipStreamSynchronize(st));                   // (the hashes stay on the device for the dedup call)
-        return MF_OK;
-    };
-    // The de-duplication set lives on the device for the whole file: keys + smallest file index per key.  Sized for the first batches
-    // and doubled (rehashed by a kernel) before a batch that could fill it beyond a half.
-    struct DedupSet { unsigned long long *keys = nullptr, *first = nullptr, *small = nullptr; uint64_t slots = 0, n_keys = 0, base = 0; } ds;     // small: [0] zero_idx, [1] n_keys
-    auto ds_alloc = [&](uint64_t slots, unsigned long long **keys, unsigned long long **first, std::string &err) -> int {
-        QCHK(dev_malloc((void **)keys, slots * 8)); QCHK(dev_malloc((void **)first, slots * 8));
-        QCHK(hipMemsetAsync(*keys, 0, slots * 8, st)); QCHK(hipMemsetAsync(*first, 0xFF, slots * 8, st));
-        return MF_OK;
-    };
-    QualDedupFn dedup_fn = [&](const uint8_t *alive, uint32_t n, uint8_t *dup, std::string &err) -> int {
-        QCHK(hipSetDevice(phys(device)));
-        if (!ds.keys) {
-            uint64_t lg = env_u32("MF_DEDUP_LOG2_SLOTS", 24);
-            if (lg < 4) lg = 4; if (lg > 34) lg = 34;
-            ds.slots = (uint64_t)1 << lg;
-            const int rc2 = ds_alloc(ds.slots, &ds.keys, &ds.first, err); if (rc2) return rc2;
-            QCHK(dev_malloc((void **)&ds.small, 16));
-            QCHK(hipMemsetAsync(ds.small, 0xFF, 8, st)); QCHK(hipMemsetAsync(ds.small + 1, 0, 8, st));
-        }
-        while (2 * (ds.n_keys + n) > ds.slots) {          // (every record of the batch may be a new key)
-            unsigned long long *k2 = nullptr, *f2 = nullptr;
-            const int rc2 = ds_alloc(ds.slots * 2, &k2, &f2, err); if (rc2) return rc2;
-            QCHK(launch_dedup_rehash(ds.keys, ds.first, ds.slots, k2, f2, ds.slots * 2, st));
-            QCHK(hipStreamSynchronize(st));
-            QCHK(hipFree(ds.keys)); QCHK(hipFree(ds.first));
-            ds.keys = k2; ds.first = f2; ds.slots *= 2;
-        }
-        QCHK(need(d_flags, (size_t)n * 2));
-        uint8_t *d_alive = (uint8_t *)d_flags.p, *d_dup = d_alive + n;
-        QCHK(hipMemcpyAsync(d_alive, alive, n, hipMemcpyHostToDevice, st));
-        QCHK(launch_dedup((const uint64_t *)d_hash.p, d_alive, n, ds.base, ds.keys, ds.first, ds.slots, ds.small, ds.small + 1, d_dup, st));
-        QCHK(hipMemcpyAsync(dup, d_dup, n, hipMemcpyDeviceToHost, st));
-        unsigned long long nk = 0;
-        QCHK(hipMemcpyAsync(&nk, ds.small + 1, 8, hipMemcpyDeviceToHost, st));
-        QCHK(hipStreamSynchronize(st));
-        ds.n_keys = nk; ds.base += n;
-        return MF_OK;
-    };
-#undef QCHK
-    static_assert(sizeof(QualSpan) == sizeof(QualRec), "host and device record layouts must match");
+    QualDevice qd(device);
+    QualScanFn scan = [&qd](const char *text, size_t len, const QualSpan *recs, uint32_t n, uint32_t q, uint32_t *n_count, uint32_t *bad_count,
+                            bool want_hashes, std::string &err) { return qd.scan(text, len, recs, n, q, n_count, bad_count, want_hashes, err); };
+    QualDedupFn dedup_fn = [&qd](const uint8_t *alive, uint32_t n, uint8_t *dup, std::string &err) { return qd.dedup(alive, n, dup, err); };
     int threads = (int)std::thread::hardware_concurrency() - 4; if (threads < 2) threads = 2; if (threads > 64) threads = 64;
     QualStats qs; std::string perr;
-    rc = run_qualfilter_pipeline(fq1, fq2, out1, out2, P, threads, env_u32("MF_BATCH_READS", 2000000), scan, dedup_fn, qs, perr);
-    if (ctx) { hipFree(d_text.p); hipFree(d_recs.p); hipFree(d_cnt.p); hipFree(d_hash.p); hipFree(d_flags.p); hipFree(ds.keys); hipFree(ds.first); hipFree(ds.small); }
+    const int rc = run_qualfilter_pipeline(fq1, fq2, out1, out2, P, threads, env_u32("MF_BATCH_READS", 2000000), scan, dedup_fn, qs, perr);
     if (rc != MF_OK) return fail(rc, "%s", perr.c_str());
     if (kept) *kept = qs.kept;
     if (total) *total = qs.total;
