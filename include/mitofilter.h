@@ -456,6 +456,34 @@ int mf_filter_fastq_files_verified(mf_kmerset *ks, const char *fq1, const char *
               uint32_t *base_depth, mf_place_record_t *place_records, mf_pileup_t *pileup, uint8_t *consensus,
               mf_pileup_record_t *pileup_records, mf_score_record_t *score_records, uint64_t *unplaced, uint64_t *kept, uint64_t *total);
 
+/* ---- which mates are written: the keep rule.  The verifying calls above cut the reports only; the two calls below also let the cut
+ * decide what is written.  Every mate has a PASS bit (it passes its own threshold); the keep mode turns it into a KEEP bit:
+ *   MF_KEEP_PASSING   the keep bit is the pass bit: everything is what mf_verify / mf_filter_fastq_files_verified give.
+ *   MF_KEEP_ACCEPTED  a mate that is placed and REJECTED by the cut loses its bit.
+ *   MF_KEEP_PLACED    additionally a passing mate that is NOT PLACED (ambiguous, or no anchor window) loses its bit: only mates that are
+ *                     placed and accepted keep it.
+ * Any other keep is MF_E_ARG.  The keep bit takes the pass bit's place in the pair rule, and the pair rule itself is as it was:
+ * MF_PAIR_EITHER writes a pair when either mate still has its bit, MF_PAIR_BOTH when both have; single-end input writes a read that
+ * keeps its bit.  *kept counts what is written.  What the reports count does NOT depend on the keep mode: base depth, the records,
+ * the pile-up, the scores and unplaced are those of every mate that passes its own threshold, cut at max_permille as above.
+ * Two identities for single-end input, score_records summed over the records:
+ *   MF_KEEP_ACCEPTED:  kept == passing reads - sum(rejected)      (passing reads = total - unplaced[1])
+ *   MF_KEEP_PLACED:    kept == sum(accepted)
+ * Resident: keep_bits (optional, n_reads bits laid out like out_bits, tail bits 0) receives the keep bits; out_bits stays the pass
+ * bits.  With MF_KEEP_PASSING keep_bits equals out_bits.  Scoring still knows no indels: under a tight cut a read with a true indel
+ * against the bait is rejected and, with a keep mode, not written -- read the histogram at max_permille 1000 before picking a cut. */
+enum { MF_KEEP_PASSING = 0, MF_KEEP_ACCEPTED = 1, MF_KEEP_PLACED = 2 };
+/* mf_verify with a keep mode: keep behind max_permille, keep_bits behind out_bits; every output optional */
+int mf_verify_keep(const mf_kmerset *ks, const mf_reads *reads, uint32_t threshold, int mode, uint32_t min_depth, uint32_t max_permille,
+              int keep, uint32_t *out_bits, uint32_t *keep_bits, mf_place_t *place_out, mf_score_t *score_out, uint32_t *base_depth,
+              mf_place_record_t *place_records, mf_pileup_t *pileup, uint8_t *consensus, mf_pileup_record_t *pileup_records,
+              mf_score_record_t *score_records, uint64_t *unplaced, mf_filter_stats_t *stats);
+/* mf_filter_fastq_files_verified with a keep mode (behind max_permille): the output files hold the pairs the keep bits select */
+int mf_filter_fastq_files_verified_keep(mf_kmerset *ks, const char *fq1, const char *fq2, const char *out1, const char *out2,
+              uint32_t threshold, int pair_mode, const int *devices, int n_devices, uint32_t min_depth, uint32_t max_permille, int keep,
+              uint32_t *base_depth, mf_place_record_t *place_records, mf_pileup_t *pileup, uint8_t *consensus,
+              mf_pileup_record_t *pileup_records, mf_score_record_t *score_records, uint64_t *unplaced, uint64_t *kept, uint64_t *total);
+
 /* Options that select which kernels a filter pass runs (process-wide; every variant gives the same bits and is parity-tested):
  *   pass=default|split|serial   adapt=0|1   finish_streams=0|1|2   screen_streams=1|2   split_pipe=0|1   exact_co=0|1
  * and, read when a k-mer set is BUILT (ABI 5; every form gives the same bits -- tests force them on small baits):

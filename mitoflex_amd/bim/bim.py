@@ -137,19 +137,30 @@ def estimate_insert_sizes_device(fasta_file: str, fq1: str, fq2: str, kmer: int 
 
 def kmer_bait_map(threads: int, fasta_file: str, basedir: str, prefix: str,
                   fastq1: str, fastq2: Optional[str], quality: int = 30,
-                  kmer: int = 31, threshold: int = 1, devices: int = 1, anchors: str = "host") -> Tuple[str, str, Optional[str]]:
+                  kmer: int = 31, threshold: int = 1, devices: int = 1, anchors: str = "host",
+                  max_permille: Optional[int] = None, keep: Optional[int] = None) -> Tuple[str, str, Optional[str]]:
     """Drop-in for `bwa_map`: returns (stats, fq1, fq2).  `stats` stands where the BAM path was and is what `cal_insert`
     takes; `threads` and `quality` are accepted for signature compatibility and ignored.  anchors: "host" estimates the insert
     sizes in Python from the first anchor of each mate of a sample of the kept pairs; "device" places every kept mate on the GPU
-    (estimate_insert_sizes_device)."""
+    (estimate_insert_sizes_device).
+    keep: when given (mitofilter.KEEP_ACCEPTED or KEEP_PLACED; KEEP_PASSING writes what the default does), the bait step is a
+    verifying one (mitofilter.filter_fastq_files_verified): every passing mate is placed and scored against the bait, cut at
+    max_permille mismatches per thousand compared bases (1000 when not given), and a mate the keep rule drops loses its vote in the
+    pair rule -- the reads of a diverged copy (a NUMT, a contaminant) do not reach the assembler or the next generation's bait."""
     from mitoflex_amd import mitofilter as mf
     if anchors not in ("host", "device"):
         raise ValueError('anchors is "host" or "device"')
+    if max_permille is not None and not 0 <= int(max_permille) <= 1000:
+        raise ValueError("max_permille is a number from 0 to 1000")
     fq1 = path.join(basedir, prefix + ".1.fq")
     fq2 = path.join(basedir, prefix + ".2.fq") if fastq2 is not None else None
     ks = mf.KmerSet.from_fasta(fasta_file, kmer, 0)          # the device-side set builder, once per generation
     try:
-        mf.filter_fastq_files(ks, fastq1, fastq2, fq1, fq2, threshold, mf.PAIR_EITHER, devices)
+        if keep is None:
+            mf.filter_fastq_files(ks, fastq1, fastq2, fq1, fq2, threshold, mf.PAIR_EITHER, devices)
+        else:
+            mf.filter_fastq_files_verified(ks, fastq1, fastq2, fq1, fq2, threshold, mf.PAIR_EITHER, n_devices=devices, pileup=False,
+                                           max_permille=1000 if max_permille is None else int(max_permille), keep=keep)
     finally:
         ks.close()
     stats = path.join(basedir, prefix + ".bait.stats")

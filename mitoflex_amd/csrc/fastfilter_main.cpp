@@ -16,7 +16,7 @@
 //                     [--report FILE | --group-report FILE [--group-field N] [--group-sep C]
 //                      | --depth-report FILE [--depth-profile FILE] | --place-report FILE [--base-depth FILE]
 //                      | [--pileup FILE] [--consensus FILE] [--variants FILE] [--min-depth N]]
-//                      [--score-report FILE] [--max-mismatch PERMILLE]
+//                      [--score-report FILE] [--max-mismatch PERMILLE] [--write passing|accepted|placed]
 // which loads libmitofilter_hip.so (HIP kernels, gfx950) and prints the kept
 // read/pair count.  --report writes how many kept reads (mates one by one)
 // each bait record attracted as a TSV (record, name, reads; then the
@@ -37,7 +37,11 @@
 // either of those two families) writes per record the placed reads' agreement with the bait along their placement: accepted, rejected,
 // compared, mismatches, mismatches per thousand, and a histogram of mismatches per read; --max-mismatch PERMILLE (with one of the two
 // families or with --score-report, 0 .. 1000) keeps every placed read with more mismatches per thousand compared bases out of the base depth, the placement
-// counts and the pile-up (include/mitofilter.h, mf_verify; the output FASTQ files are not changed by it).  It has no CPU fallback: without the library or a GPU it exits non-zero, which shell_call turns into a RuntimeError
+// counts and the pile-up (include/mitofilter.h, mf_verify; the output FASTQ files are not changed by it).  --write accepted|placed
+// (nucleotide baits; alone or with the placement, pile-up or score reports; default passing) lets that cut decide what is WRITTEN too:
+// `accepted` takes the pass bit from every mate that is placed and rejected before the pair rule looks at it, `placed` also from every
+// passing mate that is not placed; it makes the call a verifying one by itself, cutting at 1000 unless --max-mismatch is given, and the
+// count on stdout is what was written (include/mitofilter.h, the keep rule; the reports do not depend on it).  It has no CPU fallback: without the library or a GPU it exits non-zero, which shell_call turns into a RuntimeError
 // (helper.py:82-86).
 #include "../../include/mitofilter.h"
 #include "mf_coldtrace.h"
@@ -453,11 +457,12 @@ struct BaitArgs {
     std::string bait, fq1, fq2, out1, out2, pair = "either", libpath, report, group_report, group_sep, depth_report, depth_profile, place_report, base_depth_file, pileup_file, consensus_file,
                 variants_file, score_report;
     unsigned min_depth = 1, thr = 1, max_permille = 1000;
+    int keep = MF_KEEP_PASSING;                // --write: which mates the verifying call writes
     int group_field = -1, k = 0, devices = 1, gcode = 5; bool protein = false;
     std::vector<int> device_list;              // --device-list 2,3: these devices instead of 0 .. N - 1
     std::vector<std::pair<std::string, std::string>> options;      // --option pass=serial: how a filter pass is run (mf_set_option)
     bool grouped = false, depth = false, placed = false, piled = false;          // which report (grouped: `report` holds --group-report's file)
-    bool verified = false;                     // --score-report or --max-mismatch: the placed reads are scored (and cut) first
+    bool verified = false;                     // --score-report, --max-mismatch or --write accepted|placed: the placed reads are scored (and cut) first
 };
 
 // what the library's call gave: the arrays the report files are written from
@@ -510,6 +515,11 @@ static int parse_bait_args(int argc, char **argv, BaitArgs &A)
             if (v.empty() || *end || v[0] < '0' || v[0] > '9' || x > 1000) { fprintf(stderr, "error: --max-mismatch wants mismatches per thousand compared bases, from 0 to 1000\n"); return 1; }
             A.max_permille = (unsigned)x; have_max_mismatch = true;
         }
+        else if (o == "--write") {
+            const std::string v = need("--write");
+            if (v == "passing") A.keep = MF_KEEP_PASSING; else if (v == "accepted") A.keep = MF_KEEP_ACCEPTED; else if (v == "placed") A.keep = MF_KEEP_PLACED;
+            else { fprintf(stderr, "error: --write wants passing, accepted or placed\n"); return 1; }
+        }
         else if (o == "--group-field") {
             const std::string v = need("--group-field"); char *end = nullptr; const long x = strtol(v.c_str(), &end, 10);
             if (v.empty() || *end || x < 1 || x > INT_MAX) { fprintf(stderr, "error: --group-field wants a field number from 1\n"); return 1; }
@@ -539,6 +549,7 @@ static int parse_bait_args(int argc, char **argv, BaitArgs &A)
               "       [--report FILE | --group-report FILE [--group-field N] [--group-sep C] | --depth-report FILE [--depth-profile FILE]\n"
               "        | --place-report FILE [--base-depth FILE] | [--pileup FILE] [--consensus FILE] [--variants FILE] [--min-depth N]]\n"
               "       [--score-report FILE] [--max-mismatch PERMILLE]   (with or without the placement or the pile-up reports)\n"
+              "       [--write passing|accepted|placed]   (which mates are written: all that pass, not those the cut rejects, only placed and accepted ones)\n"
               "       fastfilter bait --protein --bait PROTEINS.fa [--code 5] [-k 9] ...   (six-frame peptide k-mers)\n", stderr);
         return 1;
     }
@@ -557,15 +568,20 @@ static int parse_bait_args(int argc, char **argv, BaitArgs &A)
         return 1;
     }
     if (have_min_depth && !piled) { fprintf(stderr, "error: --min-depth needs --pileup, --consensus or --variants\n"); return 1; }
-    if (have_max_mismatch && !placed && !piled && A.score_report.empty()) {
-        fprintf(stderr, "error: --max-mismatch needs --place-report, --base-depth, --pileup, --consensus, --variants or --score-report\n");
+    const bool keeping = A.keep != MF_KEEP_PASSING;
+    if (have_max_mismatch && !placed && !piled && A.score_report.empty() && !keeping) {
+        fprintf(stderr, "error: --max-mismatch needs --place-report, --base-depth, --pileup, --consensus, --variants, --score-report or --write accepted|placed\n");
+        return 1;
+    }
+    if (keeping && (depth || A.protein || !A.report.empty() || !A.group_report.empty())) {
+        fprintf(stderr, "error: --write accepted|placed needs a nucleotide bait and cannot be combined with --report, --group-report, --depth-report, --depth-profile or --protein\n");
         return 1;
     }
     if (!A.score_report.empty() && (depth || A.protein || !A.report.empty() || !A.group_report.empty())) {
         fprintf(stderr, "error: --score-report needs a nucleotide bait and cannot be combined with --report, --group-report, --depth-report, --depth-profile or --protein\n");
         return 1;
     }
-    A.verified = have_max_mismatch || !A.score_report.empty();
+    A.verified = have_max_mismatch || !A.score_report.empty() || keeping;
     if (A.group_report.empty() && (A.group_field >= 0 || have_sep)) { fprintf(stderr, "error: --group-field and --group-sep need --group-report\n"); return 1; }
     if (!have_sep) A.group_sep = "_";
     if (A.k == 0) A.k = A.protein ? 9 : 31;
@@ -646,13 +662,13 @@ static int bait_run(const BaitArgs &A, BaitResult &R, mf_kmerset **ks_out, declt
         if (rc == MF_OK) default_devices(p_mf_device_count, A.devices, device_list);
         const size_t positions = rc == MF_OK ? (size_t)std::max<uint64_t>(R.starts.back(), 1) : 1, n_rec = std::max<size_t>(R.names.size(), 1);
         if (A.verified) {          // the placed reads scored and cut; then what the family asks for, from the accepted ones
-            SYM(mf_kmerset_bait_letters) SYM(mf_filter_fastq_files_verified)
+            SYM(mf_kmerset_bait_letters) SYM(mf_filter_fastq_files_verified_keep)
             R.score_recs.assign(n_rec, mf_score_record_t{});
             if (A.piled) { R.pile.assign(positions, mf_pileup_t{}); R.consensus.assign(positions, 0); R.letters.assign(positions, 0); }
             if (A.placed) { R.profile.assign(positions, 0); R.place_recs.assign(n_rec, mf_place_record_t{}); }
             if (rc == MF_OK && A.piled) rc = p_mf_kmerset_bait_letters(ks, R.letters.data(), R.letters.size(), nullptr);
             if (rc == MF_OK)
-                rc = files(p_mf_filter_fastq_files_verified, A.min_depth, A.max_permille, A.placed ? R.profile.data() : nullptr, A.placed ? R.place_recs.data() : nullptr,
+                rc = files(p_mf_filter_fastq_files_verified_keep, A.min_depth, A.max_permille, A.keep, A.placed ? R.profile.data() : nullptr, A.placed ? R.place_recs.data() : nullptr,
                            A.piled ? R.pile.data() : nullptr, A.piled ? R.consensus.data() : nullptr, (mf_pileup_record_t *)nullptr, R.score_recs.data(), R.unplaced);
         } else if (A.piled) {
             SYM(mf_kmerset_bait_letters) SYM(mf_filter_fastq_files_pileup)

@@ -157,6 +157,7 @@ struct mf_reads {
     uint32_t *rpos_u32() const { return static_cast<uint32_t *>(d_rpos); }
     mf::PlaceOut *d_place = nullptr; size_t cap_place = 0;          // mf_place's per-read results
     mf::ScoreOut *d_score = nullptr; size_t cap_score = 0;          // mf_verify's per-read scores
+    uint32_t *d_keep = nullptr; size_t cap_keep = 0;                // the keep bitmap of a verifying call with a keep mode: laid out like d_bits
     // capacities (bytes), so that a handle can be refilled batch after batch without touching the allocator
     size_t cap_words = 0, cap_offsets = 0, cap_npos = 0, cap_bitmap = 0, cap_recs = 0, cap_rec_counts = 0, cap_hits = 0, cap_npos_blk = 0, cap_off_blk = 0;
 };

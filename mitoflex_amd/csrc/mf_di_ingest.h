@@ -295,6 +295,7 @@ struct Ingest {
         rc = filter_common(ks, R, threshold, MF_MODE_SCREENED, S.h_bits, nullptr, 1, nullptr);
         if (rc) { err = mf_thread_error(); return rc; }
         if (report) { rc = report->after_pass(R, Bt.pairs, err); if (rc) return rc; }
+        if (report) { rc = report->amend_bits(R, S.h_bits, n_rec, err); if (rc) return rc; }
         if (!first_filtered_.exchange(true)) cold_mark("consumer: first piece packed and filtered");
         {
             size_t f = 0, t = 0; const bool got = hipMemGetInfo(&f, &t) == hipSuccess;

@@ -64,6 +64,7 @@ int run_fastq_pipeline(const char *fq1, const char *fq2, const char *out1, const
                     std::string e;
                     int r = filter(d, pb->packed[m], pb->n, bits[m], e);
                     if (r == MF_OK && report) r = report->after_pass(report->held[d], pairs[m], e);      // (the worker's read set still holds this mate)
+                    if (r == MF_OK && report) r = report->amend_bits(report->held[d], bits[m].data(), pb->n, e);
                     if (r != MF_OK) { run.fail(r, e); ok = false; }
                 }
                 if (!ok) break;

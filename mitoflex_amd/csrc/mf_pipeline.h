@@ -28,6 +28,10 @@ struct PassReport {
     explicit PassReport(uint32_t n, bool tallies = true) : n_rec(n), counts(tallies ? (size_t)n + 2 : 0, 0) {}
     virtual ~PassReport() = default;
     virtual int after_pass(mf_reads *reads, std::vector<uint64_t> &pairs, std::string &err) = 0;
+    // Right behind after_pass, on the same thread and read set: the host copy of that mate batch's pass bits (n reads), before the ingest
+    // path stores them or the pair rule reads them.  A report that decides which mates are written clears bits here; the pair rule and
+    // `kept` then work on what is left.  Most reports leave the bits alone.
+    virtual int amend_bits(mf_reads *, uint32_t *, uint64_t, std::string &) { return 0; }
     virtual void restart() { counts.assign(counts.size(), 0); }          // the path that had taken the input declined it: nothing was kept
     // one mate's batch of n reads, n_kept of them kept (keep(i): read i is)
     template <class KeepFn> void add(const std::vector<uint64_t> &pairs, uint64_t n, uint64_t n_kept, KeepFn keep)

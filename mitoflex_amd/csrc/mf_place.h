@@ -18,9 +18,12 @@ struct ScoreOut { uint32_t compared, mismatches; };      // mf_score_t
 // What a verifying launch takes beside a placing one.  bait_words / bait_valid: the bait's packed letters and its validity, one bit a
 // position; *_last: the index of each array's last word (the 16-base compare clamps to it).  score (optional): n_reads entries, zeroed.
 // sums: compared, mismatches of every record, 2 counters each, summed over the ACCEPTED reads.
+// keep_bits (optional): n_reads bits laid out like the pass bitmap and holding a copy of it; a listed read loses its bit there where
+// keep_clears(placed, accepted, keep) of mf_score.h says so (keep: MF_KEEP_ACCEPTED or MF_KEEP_PLACED).  Nothing else is written for it.
 struct PlaceVerify {
     const uint32_t *bait_words; uint64_t bait_words_last; const uint32_t *bait_valid; uint64_t bait_valid_last;
     uint32_t max_permille; ScoreOut *score; unsigned long long *sums;
+    uint32_t *keep_bits = nullptr; int keep = 0;
 };
 
 // Anchor table, indexed by the slot of the key table: anchor[slot] = { the window's position inside its record, record << 1 | b } when

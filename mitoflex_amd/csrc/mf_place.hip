@@ -16,7 +16,8 @@
 //                          clipped footprint sixteen bases at a time -- the read's word funnel-shifted (mirrored and complemented on
 //                          strand 1) against the bait's, masked by length, clip and the bait's validity bits --, one wave reduction,
 //                          then the cut; a rejected read keeps its placement and its score and bumps only `rejected` and its bin,
-//                          and pile_bases does not run for it.
+//                          and pile_bases does not run for it.  Given a keep bitmap (a copy of the pass bitmap), lane 0 also clears
+//                          the read's bit there where the keep rule says so (keep_clears, mf_score.h): one atomicAnd on its word.
 //   place_scan_reduce_kernel, place_scan_partials_kernel, place_profile_kernel
 //                          base depth = inclusive scan of the difference counters (a -1 that lands on the next record's first position
 //                          is right under a global scan: no segmentation): tile sums, their exclusive scan, then per tile the scan, the
@@ -95,11 +96,15 @@ __device__ __forceinline__ void pile_bases(const ReadsView &R, uint64_t b0, bool
 }
 
 // What a verifying launch is given beside a placing one (nothing otherwise: the plain instantiations take no argument more than before).
-template <bool VERIFY> struct VerifyArgs {};
-template <> struct VerifyArgs<true> {
+// KEEP: a verifying launch that is also given a keep bitmap; the verifying launches without one keep their code and their registers.
+template <bool VERIFY, bool KEEP> struct VerifyArgs {};
+template <> struct VerifyArgs<true, false> {
     ScoreBait bait; uint32_t max_permille;
     ScoreOut *__restrict__ score;                  // optional, n_reads entries, zeroed
     unsigned long long *__restrict__ sums;         // compared, mismatches of every record's accepted reads
+};
+template <> struct VerifyArgs<true, true> : VerifyArgs<true, false> {
+    uint32_t *__restrict__ keep_bits; int keep;    // the pass bitmap's copy that loses the bits keep_clears names (mf_score.h)
 };
 
 // The score of the placed read (mf_score.h): lanes take the clipped footprint sixteen bases at a time, a read with an invalid base goes
@@ -124,11 +129,11 @@ __device__ __forceinline__ unsigned long long score_read(const ReadsView &R, uin
     return wave_sum_u64(acc);
 }
 
-template <int KW, bool PILE, bool VERIFY>
+template <int KW, bool PILE, bool VERIFY, bool KEEP>
 __global__ void __launch_bounds__(ASSIGN_BLOCK)
 place_kernel(ReadsView R, KmerSetView S, const Anchor *__restrict__ anchor, const uint64_t *__restrict__ rec_start, const uint32_t *__restrict__ list,
              const unsigned long long *__restrict__ n_list_p, uint32_t n_rec, PlaceOut *__restrict__ place, unsigned long long *__restrict__ diff,
-             unsigned long long *__restrict__ counts, unsigned long long *__restrict__ pile, VerifyArgs<VERIFY> V)
+             unsigned long long *__restrict__ counts, unsigned long long *__restrict__ pile, VerifyArgs<VERIFY, KEEP> V)
 {
     __shared__ uint32_t s_hist[HIST_MAX];
     // forward, reverse, over_begin, over_end of every record; not placed; with VERIFY behind them rejected and the 32 bins of every record
@@ -216,6 +221,9 @@ place_kernel(ReadsView R, KmerSetView S, const Anchor *__restrict__ anchor, cons
                 }
             } else cnt.bump(4 * n_rec);
             if (place) place[r] = out;
+            // the keep rule: the words of the bitmap are shared by the waves of 32 reads, hence the atomic; nothing else is written for it
+            if constexpr (KEEP)
+                if (keep_clears(best_cnt && !tie, accept, V.keep)) atomicAnd(&V.keep_bits[r >> 5], ~(1u << (r & 31u)));
         }
         if (PILE && best_cnt && !tie && accept) {            // (the winner is wave-uniform: into scalar registers)
             const uint32_t rs = __builtin_amdgcn_readfirstlane((uint32_t)(best_key >> 32));
@@ -424,17 +432,22 @@ hipError_t launch_place(const ReadsView &R, const KmerSetView &S, const Anchor *
     // the launch shape of launch_assign: four workgroups (32 waves) a CU at most, never more waves than reads
     const uint64_t waves = std::min<uint64_t>((uint64_t)(n_cu > 0 ? n_cu : 1) * 32, R.n_reads);
     const unsigned grid = grid_of(waves, ASSIGN_BLOCK / 64);
-#define PLACE_LAUNCH(KW, PILE, VERIFY, V) hipLaunchKernelGGL((place_kernel<KW, PILE, VERIFY>), dim3(grid), dim3(ASSIGN_BLOCK), 0, st, R, S, anchor, rec_start, list, n_list, n_rec, place, diff, counts, pile, V)
+#define PLACE_LAUNCH(KW, PILE, VERIFY, KEEP, V) hipLaunchKernelGGL((place_kernel<KW, PILE, VERIFY, KEEP>), dim3(grid), dim3(ASSIGN_BLOCK), 0, st, R, S, anchor, rec_start, list, n_list, n_rec, place, diff, counts, pile, V)
     if (verify) {
-        VerifyArgs<true> V;
+        VerifyArgs<true, true> K;
+        VerifyArgs<true, false> &V = K;
         V.bait = ScoreBait{verify->bait_words, verify->bait_words_last, verify->bait_valid, verify->bait_valid_last};
         V.max_permille = verify->max_permille; V.score = verify->score; V.sums = verify->sums;
-        if (S.kw == 1) { if (pile) PLACE_LAUNCH(1, true, true, V); else PLACE_LAUNCH(1, false, true, V); }
-        else { if (pile) PLACE_LAUNCH(2, true, true, V); else PLACE_LAUNCH(2, false, true, V); }
+        K.keep_bits = verify->keep_bits; K.keep = verify->keep;
+        if (K.keep_bits) {
+            if (S.kw == 1) { if (pile) PLACE_LAUNCH(1, true, true, true, K); else PLACE_LAUNCH(1, false, true, true, K); }
+            else { if (pile) PLACE_LAUNCH(2, true, true, true, K); else PLACE_LAUNCH(2, false, true, true, K); }
+        } else if (S.kw == 1) { if (pile) PLACE_LAUNCH(1, true, true, false, V); else PLACE_LAUNCH(1, false, true, false, V); }
+        else { if (pile) PLACE_LAUNCH(2, true, true, false, V); else PLACE_LAUNCH(2, false, true, false, V); }
     } else {
-        const VerifyArgs<false> V;
-        if (S.kw == 1) { if (pile) PLACE_LAUNCH(1, true, false, V); else PLACE_LAUNCH(1, false, false, V); }
-        else { if (pile) PLACE_LAUNCH(2, true, false, V); else PLACE_LAUNCH(2, false, false, V); }
+        const VerifyArgs<false, false> V;
+        if (S.kw == 1) { if (pile) PLACE_LAUNCH(1, true, false, false, V); else PLACE_LAUNCH(1, false, false, false, V); }
+        else { if (pile) PLACE_LAUNCH(2, true, false, false, V); else PLACE_LAUNCH(2, false, false, false, V); }
     }
 #undef PLACE_LAUNCH
     return hipGetLastError();

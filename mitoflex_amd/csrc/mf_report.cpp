@@ -390,6 +390,7 @@ static int pile_nomem(size_t words) { (void)hipGetLastError(); return fail(MF_E_
 // Everything a call of the placement family is asked for: mf_place, mf_pileup, mf_verify and their file-level calls are each one of
 // these and one call of a driver below.  family: the name the messages use.  with_pileup: the layout holds pile-up counters.  A family
 // that takes no cut leaves min_depth and max_permille as they are here.  Every output is optional; a file-level call has no per-read ones.
+// keep (verifying families): the keep mode, MF_KEEP_*; keep_bits (resident): the pass bits amended by it, n_reads bits.
 struct PlaceRequest {
     const char *family; bool verify, with_pileup;
     uint32_t min_depth = 1, max_permille = 1000;
@@ -397,11 +398,13 @@ struct PlaceRequest {
     uint32_t *base_depth = nullptr; mf_place_record_t *place_records = nullptr;
     mf_pileup_t *pileup = nullptr; uint8_t *consensus = nullptr; mf_pileup_record_t *pileup_records = nullptr;
     mf_score_record_t *score_records = nullptr; uint64_t *unplaced = nullptr;
+    int keep = MF_KEEP_PASSING; uint32_t *keep_bits = nullptr;
     // the one argument check of the family (a resident call checks its read set behind it)
     int check(const mf_kmerset *ks) const
     {
         if (max_permille > 1000) return fail(MF_E_ARG, "max_permille is %u: the cut is a number from 0 to 1000", max_permille);
         if (min_depth == 0) return fail(MF_E_ARG, "min_depth is 0: a called position needs at least one base");
+        if (keep < MF_KEEP_PASSING || keep > MF_KEEP_PLACED) return fail(MF_E_ARG, "keep is %d: the keep mode is MF_KEEP_PASSING (0), MF_KEEP_ACCEPTED (1) or MF_KEEP_PLACED (2)", keep);
         if (!ks) return fail(MF_E_ARG, "NULL handle");
         if (ks->kind != MF_KIND_NUCLEOTIDE) return fail(MF_E_ARG, "%s needs a nucleotide bait set", family);
         return MF_OK;
@@ -424,8 +427,10 @@ static int placement_tables(mf_kmerset *ks, int device, const PlaceLayout &L, De
 // records' counters and (with a pile-up) their bases into the counters t of layout L (on r's device; other read sets there may be adding
 // into them at the same time), their placements into place (optional, initialised, n_reads entries on the device); *listed: how many
 // passed.  A verifying layout: every placed read is scored first and cut at L.max_permille; score (optional, zeroed, n_reads entries on
-// the device) takes the scores.  Ends synchronised.
-static int place_after_filter(mf_kmerset *ks, mf_reads *r, const PlaceLayout &L, unsigned long long *t, PlaceOut *place, ScoreOut *score, uint64_t *listed)
+// the device) takes the scores.  keep_dev (optional, a verifying layout only): the read set's keep bitmap, a copy of the pass bitmap,
+// in which the kernel clears the bits of the reads the keep mode `keep` does not write (keep_clears, mf_score.h).  Ends synchronised.
+static int place_after_filter(mf_kmerset *ks, mf_reads *r, const PlaceLayout &L, unsigned long long *t, PlaceOut *place, ScoreOut *score, uint64_t *listed,
+                              uint32_t *keep_dev = nullptr, int keep = MF_KEEP_PASSING)
 {
     DevTables *T; int rc = placement_tables(ks, r->device, L, &T); if (rc) return rc;
     DevCtx *ctx; rc = get_ctx(r->device, &ctx, r->lane); if (rc) return rc;
@@ -450,12 +455,26 @@ static int place_after_filter(mf_kmerset *ks, mf_reads *r, const PlaceLayout &L,
     HIPCHK(dev_reserve(r->d_alist, r->cap_alist, n * 4, true));
     HIPCHK(launch_pass_list(r->d_bits[r->cur], n, r->d_alist, r->d_acnt, st));
     PlaceVerify pv{};
-    if (L.verify) pv = PlaceVerify{T->pile_words, T->pile_words_n - 1, T->pile_valid, T->pile_valid_n - 1, L.max_permille, score, L.score_sums(t)};
+    if (L.verify) pv = PlaceVerify{T->pile_words, T->pile_words_n - 1, T->pile_valid, T->pile_valid_n - 1, L.max_permille, score, L.score_sums(t), keep_dev, keep};
     HIPCHK(launch_place(r->v, T->view, T->anchor, T->place_starts, r->d_alist, r->d_acnt, (uint32_t)ks->rec_len().size(), place, L.diff(t), L.cnt(t), L.pile(t),
                         L.verify ? &pv : nullptr, ctx->n_cu, st));
     HIPCHK(hipMemcpyAsync(&v, r->d_acnt, 8, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     *listed = v;
+    return MF_OK;
+}
+
+// The keep bitmap of the pass just run on this read set, for a keep mode other than MF_KEEP_PASSING: r->d_keep (reserved once: a warm
+// call allocates nothing) as a device-to-device copy of the pass bitmap, enqueued on st.  *keep_dev stays null for MF_KEEP_PASSING and
+// for an empty read set: no bitmap is handed to the kernel.
+static int keep_bitmap(mf_reads *r, int keep, hipStream_t st, uint32_t **keep_dev)
+{
+    *keep_dev = nullptr;
+    const uint64_t n = r->v.n_reads;
+    if (keep == MF_KEEP_PASSING || !n) return MF_OK;
+    HIPCHK(dev_reserve(r->d_keep, r->cap_keep, r->bitmap_bytes, true));
+    HIPCHK(hipMemcpyAsync(r->d_keep, r->d_bits[r->cur], (size_t)((n + 31) / 32) * 4, hipMemcpyDeviceToDevice, st));
+    *keep_dev = r->d_keep;
     return MF_OK;
 }
 
@@ -530,7 +549,11 @@ static int placement_resident(const mf_kmerset *ks_, const mf_reads *reads_, uin
         HIPCHK(hipMemsetAsync(d_score = r->d_score, 0, n * sizeof(ScoreOut), st));
     }
     uint64_t listed = 0;
-    rc = place_after_filter(ks, r, L, r->d_rtot, d_place, d_score, &listed); if (rc) return rc;
+    uint32_t *d_keep = nullptr;
+    rc = keep_bitmap(r, q.keep, st, &d_keep); if (rc) return rc;
+    rc = place_after_filter(ks, r, L, r->d_rtot, d_place, d_score, &listed, d_keep, q.keep); if (rc) return rc;
+    // (MF_KEEP_PASSING: keep_bits are the pass bits)
+    if (q.keep_bits && n) HIPCHK(hipMemcpyAsync(q.keep_bits, d_keep ? d_keep : r->d_bits[r->cur], (size_t)((n + 31) / 32) * 4, hipMemcpyDeviceToHost, st));
     if (d_place) HIPCHK(hipMemcpyAsync(q.place_out, d_place, n * sizeof(PlaceOut), hipMemcpyDeviceToHost, st));
     if (d_score) HIPCHK(hipMemcpyAsync(q.score_out, d_score, n * sizeof(ScoreOut), hipMemcpyDeviceToHost, st));
     return placement_report(ks, r->device, st, L, r->d_rtot, q, S, r->d_rsum, r->d_rpos, n - listed);
@@ -566,14 +589,23 @@ int mf_pileup(const mf_kmerset *ks, const mf_reads *reads, uint32_t threshold, i
     return placement_resident(ks, reads, threshold, mode, out_bits, stats, q);
 }
 
+int mf_verify_keep(const mf_kmerset *ks, const mf_reads *reads, uint32_t threshold, int mode, uint32_t min_depth, uint32_t max_permille, int keep,
+                   uint32_t *out_bits, uint32_t *keep_bits, mf_place_t *place_out, mf_score_t *score_out, uint32_t *base_depth,
+                   mf_place_record_t *place_records, mf_pileup_t *pileup, uint8_t *consensus, mf_pileup_record_t *pileup_records,
+                   mf_score_record_t *score_records, uint64_t *unplaced, mf_filter_stats_t *stats)
+{
+    const PlaceRequest q{"verification", true, pileup || consensus || pileup_records, min_depth, max_permille, place_out, score_out, base_depth,
+                         place_records, pileup, consensus, pileup_records, score_records, unplaced, keep, keep_bits};
+    return placement_resident(ks, reads, threshold, mode, out_bits, stats, q);
+}
+
 int mf_verify(const mf_kmerset *ks, const mf_reads *reads, uint32_t threshold, int mode, uint32_t min_depth, uint32_t max_permille,
               uint32_t *out_bits, mf_place_t *place_out, mf_score_t *score_out, uint32_t *base_depth, mf_place_record_t *place_records,
               mf_pileup_t *pileup, uint8_t *consensus, mf_pileup_record_t *pileup_records, mf_score_record_t *score_records,
               uint64_t *unplaced, mf_filter_stats_t *stats)
 {
-    const PlaceRequest q{"verification", true, pileup || consensus || pileup_records, min_depth, max_permille, place_out, score_out, base_depth,
-                         place_records, pileup, consensus, pileup_records, score_records, unplaced};
-    return placement_resident(ks, reads, threshold, mode, out_bits, stats, q);
+    return mf_verify_keep(ks, reads, threshold, mode, min_depth, max_permille, MF_KEEP_PASSING, out_bits, nullptr, place_out, score_out, base_depth,
+                          place_records, pileup, consensus, pileup_records, score_records, unplaced, stats);
 }
 
 } // extern "C"
@@ -662,19 +694,38 @@ struct DepthTotals : DeviceTotals {
 
 // The placement family: the footprints, record counters and (with a pile-up) bases of every mate that passes, into the layout of the
 // request q, and how many mates there were and passed.  A verifying request: the placed reads are scored and cut at max_permille first.
+// With a keep mode other than MF_KEEP_PASSING the batch's keep bitmap (the read set's d_keep) replaces the host copy of its pass bits
+// before the ingest path's pair rule sees them (amend_bits): the reports count what they counted, the files take what is left.
 struct PlaceTotals : DeviceTotals {
     const PlaceLayout L;
+    const int keep;
     std::atomic<uint64_t> mates{0}, passing{0};
-    PlaceTotals(mf_kmerset *ks_, const PlaceRequest &q) : DeviceTotals(ks_, q.with_pileup ? pile_nomem : nullptr), L(q.layout(ks_)) {}
+    PlaceTotals(mf_kmerset *ks_, const PlaceRequest &q) : DeviceTotals(ks_, q.with_pileup ? pile_nomem : nullptr), L(q.layout(ks_)), keep(q.keep) {}
     void restart() override { release(); mates = 0; passing = 0; }
     int tables(int device, DevTables *T) override { return placement_tables(ks, device, L, &T); }
     size_t words(const DevTables *) const override { return L.words(); }
     int add(mf_reads *R, unsigned long long *t) override
     {
         uint64_t listed = 0;
-        const int rc = place_after_filter(ks, R, L, t, nullptr, nullptr, &listed);
+        DevCtx *ctx; int rc = get_ctx(R->device, &ctx, R->lane); if (rc) return rc;
+        uint32_t *d_keep = nullptr;
+        rc = keep_bitmap(R, keep, ctx->stream, &d_keep); if (rc) return rc;
+        rc = place_after_filter(ks, R, L, t, nullptr, nullptr, &listed, d_keep, keep);
         if (rc == MF_OK) { mates += R->v.n_reads; passing += listed; }
         return rc;
+    }
+    int amend_bits(mf_reads *R, uint32_t *bits, uint64_t n, std::string &err) override
+    {
+        if (keep == MF_KEEP_PASSING || !R || !n) return MF_OK;
+        return hook_result(copy_keep(R, bits, n), err);
+    }
+    static int copy_keep(mf_reads *R, uint32_t *bits, uint64_t n)
+    {
+        if (n != R->v.n_reads || !R->d_keep) return fail(MF_E_ARG, "the keep bitmap does not belong to this batch");
+        DevCtx *ctx; const int rc = get_ctx(R->device, &ctx, R->lane); if (rc) return rc;
+        HIPCHK(hipMemcpyAsync(bits, R->d_keep, (size_t)((n + 31) / 32) * 4, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(hipStreamSynchronize(ctx->stream));
+        return MF_OK;
     }
 };
 
@@ -772,14 +823,24 @@ int mf_filter_fastq_files_pileup(mf_kmerset *ks, const char *fq1, const char *fq
     return placement_files(ks, fq1, fq2, out1, out2, threshold, pair_mode, devices, n_devices, kept, total, q);
 }
 
+int mf_filter_fastq_files_verified_keep(mf_kmerset *ks, const char *fq1, const char *fq2, const char *out1, const char *out2,
+                                        uint32_t threshold, int pair_mode, const int *devices, int n_devices, uint32_t min_depth, uint32_t max_permille,
+                                        int keep, uint32_t *base_depth, mf_place_record_t *place_records, mf_pileup_t *pileup, uint8_t *consensus,
+                                        mf_pileup_record_t *pileup_records, mf_score_record_t *score_records, uint64_t *unplaced, uint64_t *kept,
+                                        uint64_t *total)
+{
+    const PlaceRequest q{"verification", true, pileup || consensus || pileup_records, min_depth, max_permille, nullptr, nullptr, base_depth,
+                         place_records, pileup, consensus, pileup_records, score_records, unplaced, keep};
+    return placement_files(ks, fq1, fq2, out1, out2, threshold, pair_mode, devices, n_devices, kept, total, q);
+}
+
 int mf_filter_fastq_files_verified(mf_kmerset *ks, const char *fq1, const char *fq2, const char *out1, const char *out2,
                                    uint32_t threshold, int pair_mode, const int *devices, int n_devices, uint32_t min_depth, uint32_t max_permille,
                                    uint32_t *base_depth, mf_place_record_t *place_records, mf_pileup_t *pileup, uint8_t *consensus,
                                    mf_pileup_record_t *pileup_records, mf_score_record_t *score_records, uint64_t *unplaced, uint64_t *kept, uint64_t *total)
 {
-    const PlaceRequest q{"verification", true, pileup || consensus || pileup_records, min_depth, max_permille, nullptr, nullptr, base_depth,
-                         place_records, pileup, consensus, pileup_records, score_records, unplaced};
-    return placement_files(ks, fq1, fq2, out1, out2, threshold, pair_mode, devices, n_devices, kept, total, q);
+    return mf_filter_fastq_files_verified_keep(ks, fq1, fq2, out1, out2, threshold, pair_mode, devices, n_devices, min_depth, max_permille, MF_KEEP_PASSING,
+                                               base_depth, place_records, pileup, consensus, pileup_records, score_records, unplaced, kept, total);
 }
 
 } // extern "C"

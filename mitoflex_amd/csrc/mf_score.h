@@ -132,4 +132,12 @@ MF_SCORE_HD bool score_accepts(uint32_t compared, uint32_t mismatches, uint32_t 
     return (uint64_t)mismatches * 1000u <= (uint64_t)max_permille * compared;
 }
 
+// The keep rule (include/mitofilter.h, "which mates are written"): a PASSING read loses its bit in the keep bitmap when this is true.
+// keep 0 (MF_KEEP_PASSING): never.  1 (MF_KEEP_ACCEPTED): placed and rejected by the cut.  2 (MF_KEEP_PLACED): that, or not placed
+// (ambiguous, no anchor).  `accepted` means nothing for a read that is not placed.
+MF_SCORE_HD bool keep_clears(bool placed, bool accepted, int keep)
+{
+    return keep == 1 ? placed && !accepted : keep == 2 ? !placed || !accepted : false;
+}
+
 } // namespace mf

@@ -21,6 +21,9 @@ MODE_SCREENED = 0
 MODE_EXHAUSTIVE = 1
 PAIR_EITHER = 0
 PAIR_BOTH = 1
+# which mates a verifying call writes (include/mitofilter.h, the keep rule): every passing one, those the cut does not reject, or only
+# those that are placed and accepted
+KEEP_PASSING, KEEP_ACCEPTED, KEEP_PLACED = 0, 1, 2
 # record assignment of a read that passes but that no record wins / of a read that does not pass (mf_assign)
 ASSIGN_AMBIGUOUS = 0xFFFFFFFE
 ASSIGN_NONE = 0xFFFFFFFF
@@ -64,6 +67,7 @@ EXPORTS = (
     "mf_place", "mf_filter_fastq_files_placed",
     "mf_pileup", "mf_filter_fastq_files_pileup", "mf_kmerset_bait_letters",
     "mf_verify", "mf_filter_fastq_files_verified",
+    "mf_verify_keep", "mf_filter_fastq_files_verified_keep",
 )
 
 
@@ -182,6 +186,11 @@ def load(path: Optional[str] = None):
     L.mf_verify.argtypes = [vp, vp, C.c_uint32, C.c_int, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(FilterStats)]
     L.mf_filter_fastq_files_verified.argtypes = [vp, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_uint32, C.c_int,
                                                  C.POINTER(C.c_int), C.c_int, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp, vp, u64p, u64p]
+    L.mf_verify_keep.argtypes = [vp, vp, C.c_uint32, C.c_int, C.c_uint32, C.c_uint32, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
+                                 C.POINTER(FilterStats)]
+    L.mf_filter_fastq_files_verified_keep.argtypes = [vp, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_uint32, C.c_int,
+                                                      C.POINTER(C.c_int), C.c_int, C.c_uint32, C.c_uint32, C.c_int, vp, vp, vp, vp, vp, vp, vp,
+                                                      u64p, u64p]
     if L.mf_abi_version() != 5:
         raise MitoFilterError("libmitofilter_hip ABI version mismatch")
     _lib = L
@@ -499,38 +508,61 @@ class Verified:
     """What a verifying call gives (include/mitofilter.h, verification).  verify_reads fills bits, place PLACE[n] and score SCORE[n];
     filter_fastq_files_verified fills kept and total; the fields a call does not fill are None.  Both give base_depth u32[positions],
     place_records PLACE_RECORD[R], score_records SCORE_RECORD[R], unplaced u64[2] and, unless the call ran with pileup=False (then
-    None), pileup PILEUP[positions], consensus u8[positions] and pileup_records PILEUP_RECORD[R]."""
+    None), pileup PILEUP[positions], consensus u8[positions] and pileup_records PILEUP_RECORD[R].  keep_bits is None here: verify_reads
+    with a keep mode other than KEEP_PASSING gives a VerifiedKeep, which holds them."""
     __slots__ = ("bits", "kept", "total", "place", "score", "base_depth", "place_records", "pileup", "consensus", "pileup_records",
                  "score_records", "unplaced")
 
+    keep_bits = None          # (no slot: a call without a keep mode returns the object it always returned)
+
+    @classmethod
+    def _names(cls):
+        return [name for c in reversed(cls.__mro__) for name in getattr(c, "__slots__", ())]
+
     def __init__(self, **fields):
-        for name in self.__slots__:
+        for name in self._names():
             setattr(self, name, fields.pop(name, None))
         if fields:
             raise TypeError("unknown field(s): %s" % ", ".join(sorted(fields)))
 
     def __repr__(self):
-        return "Verified(%s)" % ", ".join(name for name in self.__slots__ if getattr(self, name) is not None)
+        return "%s(%s)" % (type(self).__name__, ", ".join(name for name in self._names() if getattr(self, name) is not None))
 
 
-def _check_cut(min_depth: int, max_permille: int):
+class VerifiedKeep(Verified):
+    """Verified plus the keep_bits slot: u32[ceil(n/32)], the pass bits amended by the keep rule (include/mitofilter.h, "which mates are
+    written"), laid out like bits.  What verify_reads gives for keep = KEEP_ACCEPTED or KEEP_PLACED."""
+    __slots__ = ("keep_bits",)
+
+
+def _check_cut(min_depth: int, max_permille: int, keep: int = KEEP_PASSING):
     if not 0 <= int(max_permille) <= 1000:
         raise ValueError("max_permille is a number from 0 to 1000")
     if int(min_depth) < 1:
         raise ValueError("min_depth is at least 1")
+    if int(keep) not in (KEEP_PASSING, KEEP_ACCEPTED, KEEP_PLACED):
+        raise ValueError("keep is KEEP_PASSING, KEEP_ACCEPTED or KEEP_PLACED")
 
 
 def verify_reads(ks: KmerSet, reads: Reads, threshold: int = 1, mode: int = MODE_SCREENED, min_depth: int = 1, max_permille: int = 1000,
-                 pileup: bool = True) -> Verified:
+                 pileup: bool = True, keep: int = KEEP_PASSING) -> Verified:
     """One filter pass, then every placed read scored against the bait along its placement and cut at max_permille mismatches per
     thousand compared bases; what is accepted gives base depth and (pileup=True) the pile-up (include/mitofilter.h: mf_verify).
-    -> Verified with bits, place, score and the shared fields."""
-    _check_cut(min_depth, max_permille)
+    keep = KEEP_ACCEPTED / KEEP_PLACED: keep_bits are the pass bits without the reads the keep rule does not write (mf_verify_keep);
+    nothing else depends on it.  -> Verified (VerifiedKeep with a keep mode) with bits, place, score and the shared fields."""
+    _check_cut(min_depth, max_permille, keep)
     per_read, read_results = _read_outputs(reads, PLACE, SCORE)
     ptrs, results = _report_outputs(ks, _VERIFY_FIELDS, () if pileup else _PILEUP_FIELDS[:3])
-    _chk(load().mf_verify(ks._h, reads._h, threshold, mode, min_depth, max_permille, *per_read, *ptrs, None))
+    if int(keep) == KEEP_PASSING:
+        _chk(load().mf_verify(ks._h, reads._h, threshold, mode, min_depth, max_permille, *per_read, *ptrs, None))
+        bits, place, score = read_results()
+        return Verified(bits=bits, place=place, score=score, **results())
+    n = reads.info.n_reads
+    keep_bits = np.zeros(max((n + 31) // 32, 1), dtype=np.uint32)
+    _chk(load().mf_verify_keep(ks._h, reads._h, threshold, mode, min_depth, max_permille, int(keep), per_read[0], keep_bits.ctypes.data,
+                               *per_read[1:], *ptrs, None))
     bits, place, score = read_results()
-    return Verified(bits=bits, place=place, score=score, **results())
+    return VerifiedKeep(bits=bits, keep_bits=keep_bits[:(n + 31) // 32], place=place, score=score, **results())
 
 
 def consensus_fasta(names, starts, consensus, width: int = 60) -> str:
@@ -707,14 +739,21 @@ def filter_fastq_files_pileup(ks: KmerSet, fq1: str, fq2: Optional[str], out1: s
 
 def filter_fastq_files_verified(ks: KmerSet, fq1: str, fq2: Optional[str], out1: str, out2: Optional[str],
                                 threshold: int = 1, pair_mode: int = PAIR_EITHER, devices: Optional[Sequence[int]] = None,
-                                n_devices: int = 1, min_depth: int = 1, max_permille: int = 1000, pileup: bool = True) -> Verified:
+                                n_devices: int = 1, min_depth: int = 1, max_permille: int = 1000, pileup: bool = True,
+                                keep: int = KEEP_PASSING) -> Verified:
     """filter_fastq_files plus verified placement and (pileup=True) pile-up of every mate that passes its own threshold: the placed
-    mates are scored against the bait and cut at max_permille (the pair rule decides only what is written; a rejected mate is still
-    written).  -> Verified with kept, total and the shared fields."""
-    _check_cut(min_depth, max_permille)
+    mates are scored against the bait and cut at max_permille.  keep = KEEP_PASSING: the pair rule decides only what is written and
+    a rejected mate is still written.  KEEP_ACCEPTED: a rejected mate loses its bit before the pair rule; KEEP_PLACED: so does a passing
+    mate that is not placed (mf_filter_fastq_files_verified_keep); the reports are the same under every keep mode.
+    -> Verified with kept (what was written), total and the shared fields."""
+    _check_cut(min_depth, max_permille, keep)
     ptrs, results = _report_outputs(ks, _VERIFY_FIELDS, () if pileup else _PILEUP_FIELDS[:3])
-    kept, total = _files_call("mf_filter_fastq_files_verified", ks, fq1, fq2, out1, out2, threshold, pair_mode, devices, n_devices,
-                              min_depth, max_permille, *ptrs)
+    if int(keep) == KEEP_PASSING:
+        kept, total = _files_call("mf_filter_fastq_files_verified", ks, fq1, fq2, out1, out2, threshold, pair_mode, devices, n_devices,
+                                  min_depth, max_permille, *ptrs)
+    else:
+        kept, total = _files_call("mf_filter_fastq_files_verified_keep", ks, fq1, fq2, out1, out2, threshold, pair_mode, devices,
+                                  n_devices, min_depth, max_permille, int(keep), *ptrs)
     return Verified(kept=kept, total=total, **results())
 
 

@@ -12,6 +12,11 @@ DIR/mitoflex_amd/libmitofilter_hip.so).  Each builds its own k-mer set and its o
                runs a side, ms a pass.  `inside_parent_range`: the change's median lies inside the parent's own min .. max.
                Also mf_verify without the pile (`ms_verify_no_pile`) and this tree's own mf_pileup (`ms_pileup_here`: the untouched
                instantiation, a control).
+               Where the parent's library has mf_verify itself: this tree's mf_verify against the parent's, with and without the pile
+               (`verify_vs_parent_verify_ms`, `verify_no_pile_vs_parent_verify_ms`) -- what a change to the verifying kernel is held
+               to.  Where this tree's library has mf_verify_keep: a pass at MF_KEEP_ACCEPTED and a cut of 30 (no keep_bits copied
+               back) against mf_verify at the same cut, both of THIS build (`keep_accepted_vs_verify_cut30_ms`; its "parent" side is
+               mf_verify).
   eight        the same against the 8-record, ~132 kbp bait of tools/bench_assign.py
   files        filter_fastq_files_pileup of the parent against filter_fastq_files_verified at 1000 permille, wall seconds, alternately,
                5 warm calls a side, on a ~2 M-pair PE set from tools/make_fastq.py compressed with tools/pgzip.py
@@ -96,6 +101,24 @@ def passes(mf, ks, reads, pf, pks, preads, reps, min_depth=3):
     out["verify_no_pile_vs_parent_pileup_ms"] = compared(tp, tn)
     tp, th = alternately(pu, u, reps)
     out["pileup_here_vs_parent_pileup_ms"] = compared(tp, th)
+    if hasattr(PL, "mf_verify"):
+        pprecs, psrecs = np.zeros(max(R, 1), pf.PLACE_RECORD), np.zeros(max(R, 1), pf.SCORE_RECORD)
+
+        def pverify(pile):
+            return lambda: pf._chk(PL.mf_verify(pks._h, preads._h, 1, pf.MODE_SCREENED, min_depth, 1000, None, None, None, None, pprecs.ctypes.data, None, None,
+                                                purecs.ctypes.data if pile else None, psrecs.ctypes.data, punplaced.ctypes.data, None))
+        for pile, name in ((True, "verify_vs_parent_verify_ms"), (False, "verify_no_pile_vs_parent_verify_ms")):
+            tp, tv = alternately(pverify(pile), verify(pile), reps)
+            out[name] = compared(tp, tv)
+        out["same_score_records_as_parent"] = bool(all(np.array_equal(srecs[f], psrecs[f]) for f in pf.SCORE_RECORD.names))
+    if hasattr(L, "mf_verify_keep"):
+        cut30 = lambda: mf._chk(L.mf_verify(ks._h, reads._h, 1, mf.MODE_SCREENED, min_depth, 30, None, None, None, None, precs.ctypes.data, None, None,
+                                            urecs.ctypes.data, srecs.ctypes.data, unplaced.ctypes.data, None))
+        keep30 = lambda: mf._chk(L.mf_verify_keep(ks._h, reads._h, 1, mf.MODE_SCREENED, min_depth, 30, mf.KEEP_ACCEPTED, None, None, None, None, None,
+                                                  precs.ctypes.data, None, None, urecs.ctypes.data, srecs.ctypes.data, unplaced.ctypes.data, None))
+        tv, tk = alternately(cut30, keep30, reps)
+        out["keep_accepted_vs_verify_cut30_ms"] = compared(tv, tk)
+        out["rejected_at_30"] = int(srecs["rejected"].sum())
     return out
 
 
