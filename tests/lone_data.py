@@ -24,6 +24,13 @@ CHUNK_BASES = 2 * BORDER
 MIN_CHUNKS = 526                  # more than twice the largest screen grid (256 workgroups): some workgroups take three chunks
 UNIFORM_READS, UNIFORM_LEN = 460_000, 150
 LAYOUTS = ("uniform", "ragged")
+# the length axis: a third layout, ("uniform", L), of LENGTH_CHUNKS chunks.  The read arithmetic of the kernels (the division by L, the
+# straddle test, the run start handed to the lane on the left) depends on a chunk's first base, not on how many chunks a workgroup takes,
+# and the MIN_CHUNKS streams at L = 150 hold that other axis.
+LENGTH_CHUNKS = 40
+LENGTHS = (36, 64, 75, 100, 101, 125, 151, 250, 4095, 4096, 4097)
+LENGTH_KS = (19, 21, 27, 28, 31, 32, 33, 41, 48, 63)      # the stride-8 geometries, the 32 | 33 key-word switch, 47 | 48 (the exact kernel behind finish)
+LONG_READ = 70001                 # longer than a lane piece
 
 # how a window came to its place
 AT_RANDOM, AT_START, AT_END, AT_BORDER, AT_STREAM_START, AT_STREAM_END = range(6)
@@ -59,6 +66,17 @@ def layout_lens(layout: str, k: int, seed: int) -> np.ndarray:
     return lens
 
 
+def uniform_lens(L: int, chunks: int = LENGTH_CHUNKS) -> np.ndarray:
+    """read lengths of the layout ("uniform", L): the fewest reads of L bases that fill `chunks` chunks and 4096 bases more"""
+    return np.full(-(-(chunks * CHUNK_BASES + 4096) // L), L, dtype=np.int64)
+
+
+def lengths_for(k: int) -> list:
+    """the uniform lengths run at k: both ends of "a read holds one window", lengths of every gcd with 16 and 64, the real ones (PE100,
+    125, 151, 250), both sides of the 4096 limit of the 32-bit division, and for two k a read longer than a lane piece"""
+    return sorted({L for L in (k, k + 1) + LENGTHS if L >= k}) + ([LONG_READ] if k in (31, 63) else [])
+
+
 def pack_codes(codes: np.ndarray) -> np.ndarray:
     """codes 0..3 -> u32 words of sixteen bases, base g in bits 2 (g & 15) of word g >> 4, plus eight zero words of slack"""
     n_words = (codes.size + 15) // 16
@@ -69,8 +87,8 @@ def pack_codes(codes: np.ndarray) -> np.ndarray:
     return np.ascontiguousarray(b).view("<u4").astype(np.uint32, copy=False)
 
 
-def lone_set(bait_text: str, k: int, lens, seed: int) -> SimpleNamespace:
-    """A stream of len(lens) reads of random bases with one window of k bait bases planted into about one read in four.
+def lone_set(bait_text: str, k: int, lens, seed: int, share: float = 0.25) -> SimpleNamespace:
+    """A stream of len(lens) reads of random bases with one window of k bait bases planted into about one read in four (`share` of them).
 
     -> words, offsets, npos (as Reads.from_packed / OracleReads.from_arrays take them) and, one entry a planted window in stream order:
     read (index of the read the window starts in), g0 (its first base in the stream), strand (0 the bait's, 1 its reverse complement), kind (PLAIN ..
@@ -86,7 +104,7 @@ def lone_set(bait_text: str, k: int, lens, seed: int) -> SimpleNamespace:
     codes = rng.integers(0, 4, size=total, dtype=np.uint8)
 
     # ---- which reads, which kind, where in the read
-    chosen = np.nonzero((rng.random(n) < 0.25) & (lens >= k))[0]
+    chosen = np.nonzero((rng.random(n) < share) & (lens >= k))[0]
     m = chosen.size
     kind = np.searchsorted(_KIND_EDGES, rng.random(m), side="right").astype(np.int8)
     L = lens[chosen]
@@ -187,12 +205,13 @@ def border_distance(g0: np.ndarray, k: int) -> np.ndarray:
 SEED = 20261019
 
 
-@functools.lru_cache(maxsize=16)
-def cached_set(k: int, layout: str, bait_text: str) -> SimpleNamespace:
-    """the set of (k, layout) with the oracle's answers: obits / ohits at threshold 1, obits2 at threshold 2 (one generation and two
-    oracle runs a set, shared by every test of a module that asks for it; nothing writes to it)"""
+# (k, L) of the length axis whose set under SEED breaks a condition of tests/test_lone_data.py -> the seed it takes instead
+LENGTH_SEEDS = {}
+
+
+def _with_oracle(k: int, layout, lens, seed: int, bait_text: str, share: float = 0.25) -> SimpleNamespace:
     from oracle import oracle_lib as ol
-    s = lone_set(bait_text, k, layout_lens(layout, k, SEED), SEED)
+    s = lone_set(bait_text, k, lens, seed, share)
     s.layout = layout
     s.oreads = ol.OracleReads.from_arrays(s.words, s.offsets, s.npos)
     t = ol.OracleTable(bait_text, k)
@@ -201,3 +220,26 @@ def cached_set(k: int, layout: str, bait_text: str) -> SimpleNamespace:
     for a in (s.words, s.offsets, s.npos, s.obits, s.ohits, s.obits2, s.read, s.g0, s.strand, s.kind):
         a.flags.writeable = False
     return s
+
+
+@functools.lru_cache(maxsize=16)
+def _cached_layout(k: int, layout: str, bait_text: str) -> SimpleNamespace:
+    return _with_oracle(k, layout, layout_lens(layout, k, SEED), SEED, bait_text)
+
+
+@functools.lru_cache(maxsize=16)
+def _cached_length(k: int, L: int, bait_text: str) -> SimpleNamespace:           # (a cache of their own: these small sets push no large one out)
+    # 4095 .. 4097: 1281 reads in all.  One in four planted leaves some thirty plain windows at a read's first base, too few to start on all
+    # sixteen places of a stream word, so every read of these sets is drawn
+    share = 1.0 if 250 < L < LONG_READ else 0.25
+    return _with_oracle(k, ("uniform", L), uniform_lens(L), LENGTH_SEEDS.get((k, L), SEED), bait_text, share)
+
+
+def cached_set(k: int, layout, bait_text: str) -> SimpleNamespace:
+    """the set of (k, layout) with the oracle's answers: obits / ohits at threshold 1, obits2 at threshold 2 (one generation and two
+    oracle runs a set, shared by every test of a module that asks for it; nothing writes to it).  layout: "uniform", "ragged", or
+    ("uniform", L) for the LENGTH_CHUNKS stream of reads of L bases."""
+    if isinstance(layout, tuple):
+        assert layout[0] == "uniform" and len(layout) == 2
+        return _cached_length(k, int(layout[1]), bait_text)
+    return _cached_layout(k, layout, bait_text)

@@ -65,7 +65,7 @@ class Case:
         self.want2 = int(bits_to_bool(s.obits2, s.n_reads).sum())
 
     def ctx(self, call):
-        return dict(k=self.s.k, layout=self.s.layout, call=call, options=dict(self.option.now))
+        return dict(k=self.s.k, layout=self.s.layout, L=int(self.reads.info.uniform_len), call=call, options=dict(self.option.now))
 
     def diagnose(self, differ):
         """the first ten planted reads among the differing ones: kind, g0 mod 64, strand, in-read position, distance to the nearest

@@ -110,6 +110,76 @@ def test_synth_uniform_matches_oracle(mf, ol, bait_text):
     assert 0.003 * n < n_pass < 0.008 * n            # ~0.5 % bait reads
 
 
+# --------------------------------------------------------------------------- uniform lengths other than 150, bait-rich
+# Every length takes the uniform code of the kernels: L = 1 read_holding's own case (len_magic == 0); 2 .. 4096 the 32-bit division by
+# multiplication of the mark and finish kernels, with 4096 its last length; 4097 their ragged-style branch over read_holding's start /
+# end; reads shorter than k, of k bases (one window) and of k + 1; lengths of every gcd with 16; PE75 / 100 / 101 / 125 / 151 / 250 / 300.
+UNIFORM_KS = (21, 31, 41, 63)
+UNIFORM_KL = sorted({(k, L) for k in UNIFORM_KS for L in (1, 2, 15, 16, 17, k - 1, k, k + 1, 75, 100, 101, 125, 151, 250, 300, 4095, 4096, 4097)},
+                    key=lambda kl: (kl[1], kl[0]))          # (by length: a length's reads are generated once)
+_uniform_reads = {}
+
+
+def uniform_reads(ol, bait_text, L):
+    """n = max(6000, ceil(3 * 131072 / L)) reads of L bases, at most 400 000: even the shortest span more than one 131 072-base chunk.
+    One set a length, shared by every k (kept for the next k only: the cases run length by length).  make_reads draws from the bait
+    records longer than L + 10: make_bait()'s first one has 16 569 bases, enough for 4097."""
+    if L not in _uniform_reads:
+        _uniform_reads.clear()
+        n = min(400_000, max(6000, -(-3 * 131072 // L)))
+        seqs = make_reads(bait_text, n, seed=500 + L, read_len=L, uniform=True)
+        assert len(seqs) == n and all(len(s) == L for s in seqs)
+        _uniform_reads[L] = ol.OracleReads.from_seqs(seqs)
+    return _uniform_reads[L]
+
+
+@pytest.mark.parametrize("k,L", UNIFORM_KL)
+def test_filter_matches_oracle_uniform_lengths(mf, ol, bait_text, k, L):
+    R = uniform_reads(ol, bait_text, L)
+    n = R.n_reads
+    assert n * L > 2 * 131072
+    t = ol.OracleTable(bait_text, k)
+    ks = mf.KmerSet.from_text(bait_text, k)
+    reads = mf.Reads.from_packed(R.words, R.offsets, R.npos)
+    assert reads.info.uniform_len == L and reads.info.n_reads == n
+    for thr in (1, 2, 7):
+        obits, ohits = ol.filter_reads(t, R, thr, threads=4)
+        for mode in (mf.MODE_SCREENED, mf.MODE_EXHAUSTIVE):
+            bits, hits, st = mf.filter_reads(ks, reads, thr, mode, want_hits=True)
+            assert np.array_equal(hits, ohits), (k, L, thr, mode)
+            assert np.array_equal(bits, obits), (k, L, thr, mode)
+            bits2, _, st2 = mf.filter_reads(ks, reads, thr, mode)          # early-exit variant
+            assert np.array_equal(bits2, obits), (k, L, thr, mode)
+            assert st2.n_pass == int(bits_to_bool(obits, n).sum())
+    if L >= k + 7:
+        assert int(ohits.max()) >= 8                                       # (bait-rich: a read from the bait has L - k + 1 hits)
+    # one-shot host-buffer entry point
+    assert np.array_equal(mf.filter_packed(ks, R.words, R.offsets, R.npos, 1), ol.filter_reads(t, R, 1)[0])
+    reads.close()
+    ks.close()
+
+
+@pytest.mark.parametrize("L", [100, 151, 250])
+def test_synth_other_lengths_match_oracle(mf, ol, bait_text, L):
+    """test_synth_uniform_matches_oracle at other lengths: the library's own generator (mf_synth.cpp) is not bound to 150"""
+    n = 50_000
+    ks = mf.KmerSet.from_text(bait_text, 31)
+    reads = mf.Reads.synth(n, L, seed=7, bait_text=bait_text, keep_host=True)
+    assert reads.info.uniform_len == L and reads.info.n_reads == n
+    off = np.arange(n + 1, dtype=np.uint64) * L
+    R = ol.OracleReads.from_arrays(reads.host_words, off, reads.host_npos)
+    t = ol.OracleTable(bait_text, 31)
+    obits, ohits = ol.filter_reads(t, R, 1, threads=4)
+    for mode in (mf.MODE_SCREENED, mf.MODE_EXHAUSTIVE):
+        bits, hits, st = mf.filter_reads(ks, reads, 1, mode, want_hits=True)
+        assert np.array_equal(hits, ohits), (L, mode)
+        assert np.array_equal(bits, obits), (L, mode)
+    n_pass = int(bits_to_bool(obits, n).sum())
+    assert 0.003 * n < n_pass < 0.008 * n            # ~0.5 % bait reads
+    reads.close()
+    ks.close()
+
+
 @pytest.mark.parametrize("batch", [None, 700, 1])
 @pytest.mark.parametrize("gz", [False, True])
 @pytest.mark.parametrize("ingest", ["host", "default"])
@@ -160,6 +230,76 @@ def test_fastq_files_match_oracle(mf, ol, bait_text, tmp_path, gz, batch, ingest
     reads = mf.Reads.from_fastq(fq1)
     R = ol.OracleReads.from_fastq(fq1)
     assert reads.info.n_reads == R.n_reads == n1
+    t = ol.OracleTable(bait_text, 31)
+    assert np.array_equal(mf.filter_reads(ks, reads, 1)[0], ol.filter_reads(t, R, 1)[0])
+
+
+def _uniform_files(bait_text, name):
+    """-> (reads of file 1, reads of file 2, uniform length of file 1 or 0); 3000 records a file"""
+    u = lambda seed, L: make_reads(bait_text, 3000, seed=seed, read_len=L, uniform=True)
+    if name == "100+100":
+        return u(31, 100), u(32, 100), 100
+    if name == "151+100":                                 # the mates differ: each file's batches are uniform at their own length
+        return u(33, 151), u(34, 100), 151
+    if name == "125+ragged":
+        return u(35, 125), make_reads(bait_text, 3000, seed=36), 125
+    if name == "101-last-37":                             # the last complete record is shorter: exactly one batch or slab falls back to offsets
+        s1 = u(37, 101)
+        s1[-1] = s1[-1][:37]
+        return s1, u(38, 101), 0
+    raise ValueError(name)
+
+
+@pytest.mark.parametrize("files", ["100+100", "151+100", "125+ragged", "101-last-37"])
+@pytest.mark.parametrize("batch", [None, 700])
+@pytest.mark.parametrize("gz", [False, True])
+@pytest.mark.parametrize("ingest", ["host", "default"])
+def test_uniform_fastq_files_match_oracle(mf, ol, bait_text, tmp_path, gz, batch, ingest, files, monkeypatch):
+    """test_fastq_files_match_oracle on files whose reads share one length: a batch of the host pipeline, and a slab of the device ingest
+    path, then carries no offsets array (launch_pack and reads_finish with a uniform length).  The files of that test are ragged, so its
+    one-record slabs (`batch` 1) were the only uniform ones."""
+    if ingest == "host":
+        monkeypatch.setenv("MF_INGEST", "host")
+    if batch is not None:
+        monkeypatch.setenv("MF_BATCH_READS", str(batch))
+        monkeypatch.setenv("MF_PARSE_SEG", "997")
+        if ingest == "default":
+            monkeypatch.setenv("MF_GZDEV_CHUNK_BYTES", "4096")
+            monkeypatch.setenv("MF_GZDEV_SLAB_CHUNKS", "3")
+            monkeypatch.setenv("MF_INGEST_SLAB_BYTES", "70001")
+    ext = ".fq.gz" if gz else ".fq"
+    s1, s2, L1 = _uniform_files(bait_text, files)
+    n1 = len(s1)
+    fq1, fq2 = str(tmp_path / ("a_1" + ext)), str(tmp_path / ("a_2" + ext))
+    write_fastq(fq1, s1, "a", crlf=False, trailing_partial=True, gz=gz)
+    write_fastq(fq2, s2, "b", crlf=True, gz=gz)
+    bait = str(tmp_path / "bait.fa")
+    open(bait, "w").write(bait_text)
+    ks = mf.KmerSet.from_fasta(bait, 31)
+    import gzip
+    rd = (lambda p: gzip.open(p, "rb").read()) if gz else (lambda p: open(p, "rb").read())
+    for pair_mode in (mf.PAIR_EITHER, mf.PAIR_BOTH):
+        o1, o2 = str(tmp_path / "o1.fq"), str(tmp_path / "o2.fq")
+        g1, g2 = str(tmp_path / ("g1" + ext)), str(tmp_path / ("g2" + ext))
+        ok, ot = ol.filter_fastq_files(bait, 31, 1, pair_mode, fq1, fq2, o1, o2, threads=2)
+        gk, gt = mf.filter_fastq_files(ks, fq1, fq2, g1, g2, 1, pair_mode)
+        if ingest == "default":
+            assert mf.last_ingest_stats()["path"] == 1          # the device ingest path ran
+        assert (gk, gt) == (ok, ot) and ot == n1 and ok > 0
+        assert rd(g1) == open(o1, "rb").read()
+        assert rd(g2) == open(o2, "rb").read()
+    # single end
+    o1, g1 = str(tmp_path / "se_o.fq"), str(tmp_path / "se_g.fq")
+    ok, ot = ol.filter_fastq_files(bait, 31, 2, 0, fq1, None, o1, None)
+    gk, gt = mf.filter_fastq_files(ks, fq1, None, g1, None, 2)
+    if ingest == "default":
+        assert mf.last_ingest_stats()["path"] == 1
+    assert (gk, gt) == (ok, ot) and ok > 0
+    assert open(g1, "rb").read() == open(o1, "rb").read()
+    # reads straight from a FASTQ file: the whole file as one uniform set
+    reads = mf.Reads.from_fastq(fq1)
+    R = ol.OracleReads.from_fastq(fq1)
+    assert reads.info.n_reads == R.n_reads == n1 and reads.info.uniform_len == L1
     t = ol.OracleTable(bait_text, 31)
     assert np.array_equal(mf.filter_reads(ks, reads, 1)[0], ol.filter_reads(t, R, 1)[0])
 
@@ -499,7 +639,8 @@ def test_other_pass_kinds_match_oracle(kind):
              "two-finish-streams": dict(MF_FINISH_STREAMS="2")}[kind]
     env = dict(os.environ, MF_ENV_KNOBS="1", **extra)          # (without MF_ENV_KNOBS=1 the library ignores these variables: test_options_are_not_read_from_a_stray_environment)
     p = subprocess.run([sys.executable, "-m", "pytest", os.path.join(ROOT, "tests", "test_gpu_parity.py"), os.path.join(ROOT, "tests", "test_kmer_golden.py"),
-                        "-m", "gpu", "-q", "-x", "-k", "test_filter_matches_oracle or test_edge_cases or test_gpu_matches_golden or test_synth_uniform or test_multi_pass_calls"],
+                        "-m", "gpu", "-q", "-x", "-k", "(test_filter_matches_oracle or test_edge_cases or test_gpu_matches_golden or test_synth_uniform or test_multi_pass_calls)"
+                        " and not uniform_lengths"],          # (the selection it always was: the length grid below runs once, under the default pass)
                        capture_output=True, env=env, cwd=ROOT, timeout=900)
     assert p.returncode == 0, p.stdout.decode()[-3000:]
 

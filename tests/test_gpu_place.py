@@ -82,8 +82,8 @@ def special_reads(parts, k):
     return list(seqs), list(seqs.values())
 
 
-def place_reads(text, parts, k, n, seed, uniform):
-    seqs = make_reads(text, n, seed=seed, uniform=uniform, mito_frac=0.5)
+def place_reads(text, parts, k, n, seed, uniform, read_len=150):
+    seqs = make_reads(text, n, seed=seed, read_len=read_len, uniform=uniform, mito_frac=0.5)
     if uniform:
         return [], seqs
     names, special = special_reads(parts, k)

@@ -63,6 +63,30 @@ def test_six_frame_filter_matches_oracle(mf, ol, kp, code, uniform):
     assert int(ohits.max()) > 20                                         # planted reads light up a whole frame
 
 
+@pytest.mark.parametrize("kp,code", [(7, 5), (9, 2)])
+@pytest.mark.parametrize("dl", ["3kp-1", "3kp", "3kp+1", "3kp+2", "100", "151"])
+def test_six_frame_filter_uniform_lengths(mf, ol, kp, code, dl):
+    """uniform reads at lengths other than 150 (pfilter_kernel's b0 = r * L): one base short of a peptide k-mer, exactly one in one frame
+    of a strand, in two, in all three, and PE100 / PE151"""
+    L = {"3kp-1": 3 * kp - 1, "3kp": 3 * kp, "3kp+1": 3 * kp + 1, "3kp+2": 3 * kp + 2}.get(dl) or int(dl)
+    prot_fa, gene_fa = make_protein_bait(code=code)
+    seqs = make_reads(gene_fa, 4000, seed=kp * 31 + code + L, read_len=L, uniform=True, mito_frac=0.4)
+    R = ol.OracleReads.from_seqs(seqs)
+    t = ol.OracleTable(prot_fa, kp, protein=True)
+    ks = mf.KmerSet.protein_from_text(prot_fa, kp, code)
+    reads = mf.Reads.from_packed(R.words, R.offsets, R.npos)
+    assert reads.info.uniform_len == L and reads.info.n_reads == 4000
+    for thr in (1, 2, 9):
+        obits, ohits = ol.pfilter_reads(t, R, code, thr, threads=4)
+        bits, hits, st = mf.filter_reads(ks, reads, thr, want_hits=True)
+        assert np.array_equal(hits, ohits), (kp, code, L, thr)
+        assert np.array_equal(bits, obits), (kp, code, L, thr)
+        bits2, _, st2 = mf.filter_reads(ks, reads, thr)                  # early-exit variant
+        assert np.array_equal(bits2, obits), (kp, code, L, thr)
+        assert st2.n_pass == int(bits_to_bool(obits, len(seqs)).sum())
+    assert int(ohits.max()) == 0 if L < 3 * kp else int(ohits.max()) >= 1
+
+
 def test_edge_cases(mf, ol, db):
     ks = mf.KmerSet.protein_from_text(db[0], 7, 5)
     t = ol.OracleTable(db[0], 7, protein=True)

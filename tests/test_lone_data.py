@@ -101,6 +101,109 @@ def test_windows_cover_every_alignment_and_border(lone, k, layout):
     assert s.g0[-1] + k == s.total and s.kind[-1] == ld.PLAIN and s.read[-1] == s.n_reads - 1
 
 
+# --------------------------------------------------------------------------- the length axis: ("uniform", L), LENGTH_CHUNKS chunks
+MAX_STRAY_READS_SHORT = 3       # (the stream is 13 times shorter than the one MAX_STRAY_READS was set for)
+KL = [(k, L) for k in ld.LENGTH_KS for L in ld.lengths_for(k)]
+
+
+def reachable_alignments(k, L):
+    """How many (g0 mod 64, strand) a window inside a read of L bases can take.  A read starts at a multiple of g = gcd(L, 64) and the
+    window at one of the L - k + 1 places in it, so g0 mod g takes min(g, L - k + 1) values and g0 mod 64 takes 64 / g times as many.
+    All 128 for most (k, L); measured and explained at (21, 64): every read starts at g0 mod 64 = 0, the window at 0 .. 43 in it, which is
+    44 residues on two strands = 88.  ((31, 32): reads start at 0 or 32 and the window at 0 or 1: 4 residues, 8.)"""
+    g = int(np.gcd(L, 64))
+    return 2 * (64 // g) * min(g, L - k + 1)
+
+
+def test_reachable_alignments():
+    assert reachable_alignments(21, 64) == 88 and reachable_alignments(31, 32) == 8 and reachable_alignments(63, 64) == 4
+    assert all(reachable_alignments(31, L) == 128 for L in (31, 36, 75, 100, 101, 125, 151, 250))
+    assert reachable_alignments(19, 20) == 64 and reachable_alignments(48, 48) == 8 and reachable_alignments(33, 36) == 128
+
+
+@pytest.mark.parametrize("k,L", KL)
+def test_uniform_length_set(lone, k, L):
+    """the conditions of a ("uniform", L) set: the layout, the hit counts of the kinds, the alignments and the borders the windows reach"""
+    s = lone(k, ("uniform", L))
+    n = -(-(ld.LENGTH_CHUNKS * ld.CHUNK_BASES + 4096) // L)
+    assert s.n_reads == n and s.total == n * L and s.total >= ld.LENGTH_CHUNKS * ld.CHUNK_BASES + 4096
+    assert s.offsets[0] == 0 and s.offsets.size == n + 1 and np.all(np.diff(s.offsets.astype(np.int64)) == L)
+    assert s.words.size == (s.total + 15) // 16 + 8 and not s.words[-8:].any()
+    assert np.all(np.diff(s.npos.astype(np.int64)) > 0)
+    w = s.words[(s.npos >> np.uint64(4)).astype(np.int64)] >> (2 * (s.npos & np.uint64(15))).astype(np.uint32)
+    assert not (w & 3).any(), "an invalid base is stored as 0"
+    assert np.all(np.diff(s.g0) > 2 * k + 4 + k)
+    assert s.g0[0] == 0 and s.kind[0] == ld.PLAIN and s.read[0] == 0
+    assert s.g0[-1] + k == s.total and s.kind[-1] == ld.PLAIN and s.read[-1] == n - 1
+    at = s.how == ld.AT_BORDER
+    d = s.border[at] - s.g0[at]
+    assert np.all((d >= 0) & (d < k)) and np.all(s.kind[at] == ld.PLAIN)
+    assert (s.total - 1) // ld.BORDER == 2 * ld.LENGTH_CHUNKS
+    if L == ld.LONG_READ:
+        # several forced border windows fall in one read: the hit counts of the kinds do not apply
+        assert n == 75 and int(at.sum()) >= 78, (k, L, int(at.sum()))
+        return
+    assert int(at.sum()) >= 2 * ld.LENGTH_CHUNKS - 1, (k, L, int(at.sum()))          # (L = 4096: the last border is the last read's first base)
+
+    if L <= 250:
+        assert s.read.size >= 0.08 * n, (k, L, s.read.size, n)
+    else:
+        assert s.read.size >= 250, (k, L, s.read.size)
+    hits = s.ohits.astype(np.int64)
+    good = 0
+    shares = {}
+    for kind, name in enumerate(ld.KINDS):
+        sel = s.kind == kind
+        ok = hits[s.read[sel]] == ld.KIND_HITS[kind]
+        if kind == ld.STRADDLE:
+            ok &= hits[s.read[sel] + 1] == 0
+        good += int(ok.sum())
+        shares[name] = (float(ok.mean()) if sel.any() else 1.0, int(sel.sum()))       # (n_outside: none when the window and its flanks fill the read)
+    print(k, L, {name: "%.4f of %d" % v for name, v in shares.items()})
+    for name, (share, count) in shares.items():
+        if count >= 400:
+            assert share >= MIN_KIND_SHARE, (k, L, name, shares)
+    assert good >= 0.99 * s.read.size, (k, L, shares)
+    planted = np.zeros(n, dtype=bool)
+    planted[s.read] = True
+    planted[s.read[s.kind == ld.STRADDLE] + 1] = True
+    stray = int((hits[~planted] > 0).sum())
+    assert stray <= MAX_STRAY_READS_SHORT, (k, L, stray)                               # (should a set break this: its seed changes, lone_data.LENGTH_SEEDS)
+    from tests.util_data import bits_to_bool
+    assert np.array_equal(bits_to_bool(s.obits, n), hits >= 1)
+    assert np.array_equal(bits_to_bool(s.obits2, n), hits >= 2)
+
+    plain = s.kind == ld.PLAIN
+    if L <= 250:
+        got = np.unique((s.g0[plain] % 64) * 2 + s.strand[plain]).size
+        assert got == reachable_alignments(k, L), (k, L, got)
+    # a read's first and last window on every place of a stream word that reads of L bases start on: 16 // gcd(L, 16) of them.  The reads that
+    # hold a multiple of 65 536 carry their window across it, not at an end; at L = 4095 and 4097 these are the reads 16 j and 16 j + 15, all
+    # the reads of one place, which leaves 15 of 16 at one end of the read (measured, every k: L = 4095 16 at the start -- the stream's first
+    # window is the sixteenth -- and 15 at the end; L = 4097 15 at the start and 16 at the end, with the stream's last window).  Required:
+    # every place that a read without a border starts on.
+    starts = s.offsets.astype(np.int64)[:-1]
+    free = np.ones(n, dtype=bool)
+    free[np.arange(ld.BORDER, s.total, ld.BORDER) // L] = False
+    free[[0, n - 1]] = False                                                           # (the stream's first and last window: `own` below)
+    for name, at_pos, shift, own in (("first", 0, 0, 0), ("last", L - k, L - k, s.total - k)):
+        got = set((s.g0[plain & (s.pos == at_pos)] % 16).tolist())
+        want = set(((starts[free] + shift) % 16).tolist()) | {own % 16}
+        assert want <= got and len(got) <= 16 // int(np.gcd(L, 16)), (k, L, name, sorted(want - got))
+        if L <= 250:
+            assert len(got) == 16 // int(np.gcd(L, 16)), (k, L, name, sorted(got))
+
+
+def test_existing_layouts_are_what_they_were(bait_text):
+    """the length axis left the two MIN_CHUNKS layouts byte for byte as they were (md5 of words, offsets, npos at k = 31)"""
+    import hashlib
+    want = {"uniform": ("b9f5974ccdd17a8ccebf780895713845", "de215e6ec3883f26368546e76d601053", "9e93ea9d2e4135adb4029c680c562100"),
+            "ragged": ("b50538feacdb8b418a4c47bf0ef804a1", "6c2f5bbb092d115fa0f65824a24f52fa", "1d131aec448ba6bc2609ba228b874788")}
+    for layout in ld.LAYOUTS:
+        s = ld.lone_set(bait_text, 31, ld.layout_lens(layout, 31, ld.SEED), ld.SEED)
+        assert tuple(hashlib.md5(a.tobytes()).hexdigest() for a in (s.words, s.offsets, s.npos)) == want[layout], layout
+
+
 def test_border_distance():
     g0 = np.array([0, 1, 65536 - 31, 65536 - 30, 65536, 65537, 131072 - 100, 65536 + 40000], dtype=np.int64)
     assert ld.border_distance(g0, 31).tolist() == [0, 1, -1, 0, 0, 1, -70, -(65536 - 40000 - 30)]
