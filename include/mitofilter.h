@@ -421,8 +421,8 @@ int mf_filter_fastq_files_pileup(mf_kmerset *ks, const char *fq1, const char *fq
  * COMPARED when 0 <= c < len_j, the read base is a valid letter and the bait letter at c is valid.  A compared base is a MISMATCH when
  * the oriented read letter differs from the bait letter.  compared and mismatches are the two counts.  The winning anchor's window lies
  * inside both the read and the record and matches exactly, so compared >= k and mismatches <= compared - k: nothing ever divides by
- * zero.  Overhangs, read Ns and invalid bait letters are not compared.  There is still no handling of indels: behind an insertion the
- * shifted bases are mismatches, which is what the score is there to show.
+ * zero.  Overhangs, read Ns and invalid bait letters are not compared.  This score handles no indels: behind an insertion the
+ * shifted bases are mismatches, which is what the score is there to show (the banded alignment below handles them).
  * Cut: max_permille in 0 .. 1000 (more is MF_E_ARG).  A placed read is ACCEPTED iff
  * (uint64_t)mismatches * 1000 <= (uint64_t)max_permille * compared, otherwise REJECTED.  A rejected read contributes NOTHING to base
  * depth, to forward / reverse / over_begin / over_end, or to the pile-up counters.  It is not "unplaced": its mf_place_t keeps the real
@@ -470,8 +470,9 @@ int mf_filter_fastq_files_verified(mf_kmerset *ks, const char *fq1, const char *
  *   MF_KEEP_ACCEPTED:  kept == passing reads - sum(rejected)      (passing reads = total - unplaced[1])
  *   MF_KEEP_PLACED:    kept == sum(accepted)
  * Resident: keep_bits (optional, n_reads bits laid out like out_bits, tail bits 0) receives the keep bits; out_bits stays the pass
- * bits.  With MF_KEEP_PASSING keep_bits equals out_bits.  Scoring still knows no indels: under a tight cut a read with a true indel
- * against the bait is rejected and, with a keep mode, not written -- read the histogram at max_permille 1000 before picking a cut. */
+ * bits.  With MF_KEEP_PASSING keep_bits equals out_bits.  This scoring knows no indels: under a tight cut a read with a true indel
+ * against the bait is rejected and, with a keep mode, not written -- read the histogram at max_permille 1000 before picking a cut, or
+ * use the aligning calls below. */
 enum { MF_KEEP_PASSING = 0, MF_KEEP_ACCEPTED = 1, MF_KEEP_PLACED = 2 };
 /* mf_verify with a keep mode: keep behind max_permille, keep_bits behind out_bits; every output optional */
 int mf_verify_keep(const mf_kmerset *ks, const mf_reads *reads, uint32_t threshold, int mode, uint32_t min_depth, uint32_t max_permille,
@@ -483,6 +484,58 @@ int mf_filter_fastq_files_verified_keep(mf_kmerset *ks, const char *fq1, const c
               uint32_t threshold, int pair_mode, const int *devices, int n_devices, uint32_t min_depth, uint32_t max_permille, int keep,
               uint32_t *base_depth, mf_place_record_t *place_records, mf_pileup_t *pileup, uint8_t *consensus,
               mf_pileup_record_t *pileup_records, mf_score_record_t *score_records, uint64_t *unplaced, uint64_t *kept, uint64_t *total);
+
+/* ---- banded alignment: the verifying calls with indels.  mf_align is mf_verify_keep with one more parameter, band (W); placement --
+ * the anchor vote, the strict winner, mf_place_t -- is exactly as above.  Every placed read is then aligned to its record inside the
+ * band of 2 W + 1 diagonals around the winning one, and the cut, the histogram, the keep rule, the base-depth footprint, over_begin /
+ * over_end and the pile-up coordinates follow the alignment; a per-position indel table is new.  Nucleotide sets only.
+ * The rule.  A read of L bases is placed at (record j of len positions, strand, start).  x[0 .. L) is the read oriented to the bait's
+ * forward strand (on strand 1 its reverse complement); i indexes x; c is a record coordinate.  Cells D(i, c), 0 <= i <= L,
+ * |c - (start + i)| <= W; everything outside the band is +inf.
+ *   D(0, c) = 0 for every c of the band (the begin on the bait is free; row 0 has no step inside the row).
+ *   D(i, c), i >= 1, is the least of   diagonal   D(i-1, c-1) + sub(i-1, c-1)
+ *                                      insertion  D(i-1, c) + 1      (read base i-1 against nothing)
+ *                                      deletion   D(i, c-1) + 1      (bait position c-1 against nothing)
+ *   sub(i, c) = 0 and the column is NOT COMPARED when c < 0, c >= len, x[i] is an N or the bait letter at c is invalid; otherwise the
+ *   column is COMPARED and sub is 1 iff the letters differ (mf_verify's compared and mismatch).  A coordinate outside [0, len) is a
+ *   wildcard even where a neighbouring record lies there.
+ *   End cell: the c of row L with the least D(L, c); ties go to the least |c - (start + L)|, then to the smaller c.  That c is ref_end.
+ *   Traceback from (L, ref_end): at a cell the first move that reproduces its value, in the order diagonal, deletion, insertion; it
+ *   stops at i == 0, and the c there is ref_begin.
+ *   compared and mismatches are counted over the diagonal steps; insertions = insertion steps (read bases), deletions = deletion steps
+ *   (bait positions); edits = mismatches + insertions + deletions.
+ *   Cut: accepted iff (uint64_t)edits * 1000 <= (uint64_t)max_permille * (compared + insertions + deletions).
+ * band is 0 .. min(31, k - 1); anything else is MF_E_ARG.  With band < k the footprint clipped to the record is never empty.  At
+ * band == 0 the rule is mf_verify_keep's, and every output equals that call's bit for bit (mf_align_t's compared / mismatches are
+ * mf_score_t's, its ref_begin / ref_end are start / end).
+ * What an ACCEPTED read adds: base depth over [max(ref_begin, 0), min(ref_end, len)) -- deleted positions inside count as covered --;
+ * forward or reverse; over_begin iff ref_begin < 0, over_end iff ref_end > len; to the pile-up, for every diagonal step whose read base
+ * is valid and whose c lies in [0, len), 1 at [c][oriented letter] (inserted bases add nowhere); to the indel table (mf_indel_t, one
+ * entry a bait position, clamped like the depth): a deletion step over c in [0, len) adds 1 to del[c]; a maximal run of n insertion
+ * steps at column c (between positions c-1 and c) adds 1 to ins[c-1] and n to ins_bases[c-1] when 0 <= c-1 < len.  A REJECTED read adds
+ * to `rejected` and its histogram bin only.
+ * Per read (mf_align_t): all zero for a read that is not placed.  Per record (mf_align_record_t): sums over the accepted reads; gapped =
+ * accepted reads with at least one gap; hist[min(edits, 31)] over all placed reads.
+ * accepted == forward + reverse; sum(hist) == accepted + rejected; base_sum == the sum of the clipped footprints of the accepted reads;
+ * sum(del) over a record <= deletions; mismatches of the pile-up record == mismatches of the align record.
+ * The consensus rule is unchanged and calls substitutions only: the indel table is the report on indels.
+ * Device memory: the traceback's direction bits and per-base columns live in a slice per resident wave (24 bytes a base of the longest
+ * read), bounded whatever the number of reads; there is no read-length limit below placement's. */
+typedef struct { uint32_t compared, mismatches, insertions, deletions; int32_t ref_begin, ref_end; } mf_align_t;
+typedef struct { uint32_t del, ins, ins_bases; } mf_indel_t;
+typedef struct { uint64_t accepted, rejected, compared, mismatches, insertions, deletions, gapped, hist[MF_SCORE_BINS]; } mf_align_record_t;
+/* mf_verify_keep with band behind keep, align_out for score_out, indels (starts[R] entries) behind pileup_records and align_records for
+ * score_records; every output optional */
+int mf_align(const mf_kmerset *ks, const mf_reads *reads, uint32_t threshold, int mode, uint32_t min_depth, uint32_t max_permille,
+              int keep, uint32_t band, uint32_t *out_bits, uint32_t *keep_bits, mf_place_t *place_out, mf_align_t *align_out, uint32_t *base_depth,
+              mf_place_record_t *place_records, mf_pileup_t *pileup, uint8_t *consensus, mf_pileup_record_t *pileup_records,
+              mf_indel_t *indels, mf_align_record_t *align_records, uint64_t *unplaced, mf_filter_stats_t *stats);
+/* mf_filter_fastq_files_verified_keep likewise: the output files hold the pairs the keep bits of the aligned cut select */
+int mf_filter_fastq_files_aligned(mf_kmerset *ks, const char *fq1, const char *fq2, const char *out1, const char *out2,
+              uint32_t threshold, int pair_mode, const int *devices, int n_devices, uint32_t min_depth, uint32_t max_permille, int keep,
+              uint32_t band, uint32_t *base_depth, mf_place_record_t *place_records, mf_pileup_t *pileup, uint8_t *consensus,
+              mf_pileup_record_t *pileup_records, mf_indel_t *indels, mf_align_record_t *align_records, uint64_t *unplaced,
+              uint64_t *kept, uint64_t *total);
 
 /* Options that select which kernels a filter pass runs (process-wide; every variant gives the same bits and is parity-tested):
  *   pass=default|split|serial   adapt=0|1   finish_streams=0|1|2   screen_streams=1|2   split_pipe=0|1   exact_co=0|1

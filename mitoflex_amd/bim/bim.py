@@ -138,7 +138,7 @@ def estimate_insert_sizes_device(fasta_file: str, fq1: str, fq2: str, kmer: int 
 def kmer_bait_map(threads: int, fasta_file: str, basedir: str, prefix: str,
                   fastq1: str, fastq2: Optional[str], quality: int = 30,
                   kmer: int = 31, threshold: int = 1, devices: int = 1, anchors: str = "host",
-                  max_permille: Optional[int] = None, keep: Optional[int] = None) -> Tuple[str, str, Optional[str]]:
+                  max_permille: Optional[int] = None, keep: Optional[int] = None, band: Optional[int] = None) -> Tuple[str, str, Optional[str]]:
     """Drop-in for `bwa_map`: returns (stats, fq1, fq2).  `stats` stands where the BAM path was and is what `cal_insert`
     takes; `threads` and `quality` are accepted for signature compatibility and ignored.  anchors: "host" estimates the insert
     sizes in Python from the first anchor of each mate of a sample of the kept pairs; "device" places every kept mate on the GPU
@@ -146,21 +146,30 @@ def kmer_bait_map(threads: int, fasta_file: str, basedir: str, prefix: str,
     keep: when given (mitofilter.KEEP_ACCEPTED or KEEP_PLACED; KEEP_PASSING writes what the default does), the bait step is a
     verifying one (mitofilter.filter_fastq_files_verified): every passing mate is placed and scored against the bait, cut at
     max_permille mismatches per thousand compared bases (1000 when not given), and a mate the keep rule drops loses its vote in the
-    pair rule -- the reads of a diverged copy (a NUMT, a contaminant) do not reach the assembler or the next generation's bait."""
+    pair rule -- the reads of a diverged copy (a NUMT, a contaminant) do not reach the assembler or the next generation's bait.
+    band: when given with keep (0 .. 31, below kmer), the placed mates are aligned inside that band before the cut
+    (mitofilter.filter_fastq_files_aligned): a mate with a true indel against the bait costs its indel's bases, not the mismatches
+    behind it, and is kept under a tight cut.  None keeps today's calls."""
     from mitoflex_amd import mitofilter as mf
     if anchors not in ("host", "device"):
         raise ValueError('anchors is "host" or "device"')
     if max_permille is not None and not 0 <= int(max_permille) <= 1000:
         raise ValueError("max_permille is a number from 0 to 1000")
+    _check_band(band, kmer)
+    if band is not None and keep is None:
+        raise ValueError("band needs a keep mode: without one no mate is placed")
     fq1 = path.join(basedir, prefix + ".1.fq")
     fq2 = path.join(basedir, prefix + ".2.fq") if fastq2 is not None else None
     ks = mf.KmerSet.from_fasta(fasta_file, kmer, 0)          # the device-side set builder, once per generation
     try:
         if keep is None:
             mf.filter_fastq_files(ks, fastq1, fastq2, fq1, fq2, threshold, mf.PAIR_EITHER, devices)
-        else:
+        elif band is None:
             mf.filter_fastq_files_verified(ks, fastq1, fastq2, fq1, fq2, threshold, mf.PAIR_EITHER, n_devices=devices, pileup=False,
                                            max_permille=1000 if max_permille is None else int(max_permille), keep=keep)
+        else:
+            mf.filter_fastq_files_aligned(ks, fastq1, fastq2, fq1, fq2, int(band), threshold, mf.PAIR_EITHER, n_devices=devices, pileup=False,
+                                          max_permille=1000 if max_permille is None else int(max_permille), keep=keep)
     finally:
         ks.close()
     stats = path.join(basedir, prefix + ".bait.stats")
@@ -173,8 +182,13 @@ def kmer_bait_map(threads: int, fasta_file: str, basedir: str, prefix: str,
     return stats, fq1, fq2
 
 
+def _check_band(band: Optional[int], kmer: int):
+    if band is not None and not 0 <= int(band) <= min(31, kmer - 1):
+        raise ValueError("band is a number from 0 to 31 and below kmer")
+
+
 def consensus_bait(fasta_file: str, fq1: str, fq2: Optional[str], out_fasta: str, kmer: int = 31, min_depth: int = 3,
-                   max_permille: Optional[int] = None):
+                   max_permille: Optional[int] = None, band: Optional[int] = None):
     """A polished bait for the next generation: the reads of (fq1, fq2) -- the kept reads of a bait step -- are placed on the bait
     `fasta_file` and piled up on the device (mitofilter.filter_fastq_files_pileup), and the consensus is written to `out_fasta` under the
     bait's record names: the reads' letter where at least `min_depth` bases agree on one, N where the most is tied, the bait's own
@@ -182,12 +196,17 @@ def consensus_bait(fasta_file: str, fq1: str, fq2: Optional[str], out_fasta: str
     ambiguous, variants).
     max_permille: when given (0 .. 1000), every placed read is first scored against the bait along its placement and piled only when
     its mismatches are at most that many per thousand compared bases (mitofilter.filter_fastq_files_verified): reads of a diverged
-    copy -- a NUMT, a paralogue, a contaminant -- then stay out of the polished bait.  None: no read is scored."""
+    copy -- a NUMT, a paralogue, a contaminant -- then stay out of the polished bait.  None: no read is scored.
+    band: when given (0 .. 31, below kmer), every placed read is aligned inside that band first (mitofilter.filter_fastq_files_aligned;
+    the cut is max_permille edits per thousand alignment columns, 1000 when not given) and its bases pile where the alignment puts
+    them: the bases behind an indel no longer pile up as false mismatches.  The consensus still calls substitutions only.  None keeps
+    today's calls."""
     from mitoflex_amd import mitofilter as mf
     if min_depth < 1:
         raise ValueError("min_depth is at least 1")
     if max_permille is not None and not 0 <= int(max_permille) <= 1000:
         raise ValueError("max_permille is a number from 0 to 1000")
+    _check_band(band, kmer)
     if kmer < 1:
         raise ValueError("kmer is at least 1")
     if path.abspath(out_fasta) == path.abspath(fasta_file):
@@ -197,7 +216,11 @@ def consensus_bait(fasta_file: str, fq1: str, fq2: Optional[str], out_fasta: str
         names, starts = ks.record_names, ks.record_starts
         with tempfile.TemporaryDirectory(prefix="consensus_bait_") as tmp:          # (the call writes its kept reads; they are not wanted)
             out1, out2 = path.join(tmp, "k.1.fq"), path.join(tmp, "k.2.fq") if fq2 is not None else None
-            if max_permille is None:
+            if band is not None:
+                v = mf.filter_fastq_files_aligned(ks, fq1, fq2, out1, out2, int(band), 1, mf.PAIR_EITHER, min_depth=min_depth,
+                                                  max_permille=1000 if max_permille is None else int(max_permille))
+                consensus, records = v.consensus, v.pileup_records
+            elif max_permille is None:
                 _, _, _, consensus, records, _ = mf.filter_fastq_files_pileup(ks, fq1, fq2, out1, out2, 1, mf.PAIR_EITHER, min_depth=min_depth)
             else:
                 v = mf.filter_fastq_files_verified(ks, fq1, fq2, out1, out2, 1, mf.PAIR_EITHER, min_depth=min_depth, max_permille=int(max_permille))

@@ -455,8 +455,9 @@ static std::string exe_dir()
 // what the command line asks for (checked: one kind of report at most)
 struct BaitArgs {
     std::string bait, fq1, fq2, out1, out2, pair = "either", libpath, report, group_report, group_sep, depth_report, depth_profile, place_report, base_depth_file, pileup_file, consensus_file,
-                variants_file, score_report;
-    unsigned min_depth = 1, thr = 1, max_permille = 1000;
+                variants_file, score_report, indels_file;
+    unsigned min_depth = 1, thr = 1, max_permille = 1000, band = 0;
+    bool aligned = false;                      // --band: the placed reads are aligned inside the band before they are scored and cut
     int keep = MF_KEEP_PASSING;                // --write: which mates the verifying call writes
     int group_field = -1, k = 0, devices = 1, gcode = 5; bool protein = false;
     std::vector<int> device_list;              // --device-list 2,3: these devices instead of 0 .. N - 1
@@ -476,12 +477,14 @@ struct BaitResult {
     std::vector<mf_pileup_t> pile;
     std::vector<uint8_t> consensus, letters;
     std::vector<mf_score_record_t> score_recs;
+    std::vector<mf_align_record_t> align_recs;          // with --band, in place of score_recs
+    std::vector<mf_indel_t> indels;
 };
 
 // 0, or the exit code of a command line that cannot be run
 static int parse_bait_args(int argc, char **argv, BaitArgs &A)
 {
-    bool have_min_depth = false, have_sep = false, have_max_mismatch = false;
+    bool have_min_depth = false, have_sep = false, have_max_mismatch = false, have_band = false;
     for (int a = 2; a < argc; a++) {
         std::string o = argv[a];
         auto need = [&](const char *name) -> std::string {
@@ -515,6 +518,12 @@ static int parse_bait_args(int argc, char **argv, BaitArgs &A)
             if (v.empty() || *end || v[0] < '0' || v[0] > '9' || x > 1000) { fprintf(stderr, "error: --max-mismatch wants mismatches per thousand compared bases, from 0 to 1000\n"); return 1; }
             A.max_permille = (unsigned)x; have_max_mismatch = true;
         }
+        else if (o == "--band") {
+            const std::string v = need("--band"); char *end = nullptr; const unsigned long x = strtoul(v.c_str(), &end, 10);
+            if (v.empty() || *end || v[0] < '0' || v[0] > '9' || x > 31) { fprintf(stderr, "error: --band wants a number of diagonals on either side of the placement's, from 0 to 31 (and below k)\n"); return 1; }
+            A.band = (unsigned)x; have_band = true;
+        }
+        else if (o == "--indels") A.indels_file = need("--indels");
         else if (o == "--write") {
             const std::string v = need("--write");
             if (v == "passing") A.keep = MF_KEEP_PASSING; else if (v == "accepted") A.keep = MF_KEEP_ACCEPTED; else if (v == "placed") A.keep = MF_KEEP_PLACED;
@@ -549,6 +558,7 @@ static int parse_bait_args(int argc, char **argv, BaitArgs &A)
               "       [--report FILE | --group-report FILE [--group-field N] [--group-sep C] | --depth-report FILE [--depth-profile FILE]\n"
               "        | --place-report FILE [--base-depth FILE] | [--pileup FILE] [--consensus FILE] [--variants FILE] [--min-depth N]]\n"
               "       [--score-report FILE] [--max-mismatch PERMILLE]   (with or without the placement or the pile-up reports)\n"
+              "       [--band W [--indels FILE]]   (wherever --max-mismatch may go: the placed reads are aligned inside 2 W + 1 diagonals, indels cost one edit a base)\n"
               "       [--write passing|accepted|placed]   (which mates are written: all that pass, not those the cut rejects, only placed and accepted ones)\n"
               "       fastfilter bait --protein --bait PROTEINS.fa [--code 5] [-k 9] ...   (six-frame peptide k-mers)\n", stderr);
         return 1;
@@ -573,6 +583,15 @@ static int parse_bait_args(int argc, char **argv, BaitArgs &A)
         fprintf(stderr, "error: --max-mismatch needs --place-report, --base-depth, --pileup, --consensus, --variants, --score-report or --write accepted|placed\n");
         return 1;
     }
+    if (have_band && !placed && !piled && A.score_report.empty() && !keeping && A.indels_file.empty()) {
+        fprintf(stderr, "error: --band needs --place-report, --base-depth, --pileup, --consensus, --variants, --score-report, --indels or --write accepted|placed\n");
+        return 1;
+    }
+    if (!A.indels_file.empty() && !have_band) { fprintf(stderr, "error: --indels needs --band\n"); return 1; }
+    if (have_band && (depth || A.protein || !A.report.empty() || !A.group_report.empty())) {
+        fprintf(stderr, "error: --band needs a nucleotide bait and cannot be combined with --report, --group-report, --depth-report, --depth-profile or --protein\n");
+        return 1;
+    }
     if (keeping && (depth || A.protein || !A.report.empty() || !A.group_report.empty())) {
         fprintf(stderr, "error: --write accepted|placed needs a nucleotide bait and cannot be combined with --report, --group-report, --depth-report, --depth-profile or --protein\n");
         return 1;
@@ -581,10 +600,12 @@ static int parse_bait_args(int argc, char **argv, BaitArgs &A)
         fprintf(stderr, "error: --score-report needs a nucleotide bait and cannot be combined with --report, --group-report, --depth-report, --depth-profile or --protein\n");
         return 1;
     }
-    A.verified = have_max_mismatch || !A.score_report.empty() || keeping;
+    A.verified = have_max_mismatch || !A.score_report.empty() || keeping || have_band;
+    A.aligned = have_band;
     if (A.group_report.empty() && (A.group_field >= 0 || have_sep)) { fprintf(stderr, "error: --group-field and --group-sep need --group-report\n"); return 1; }
     if (!have_sep) A.group_sep = "_";
     if (A.k == 0) A.k = A.protein ? 9 : 31;
+    if (have_band && (int)A.band >= A.k) { fprintf(stderr, "error: --band stays below k (%d)\n", A.k); return 1; }
     if (A.libpath.empty()) { const char *e = getenv("MITOFILTER_LIB"); if (e && *e) A.libpath = e; }          // (as the Python wrapper and filter_v2 do)
     if (A.libpath.empty()) A.libpath = exe_dir() + "/../libmitofilter_hip.so";
     A.grouped = !A.group_report.empty();
@@ -663,11 +684,17 @@ static int bait_run(const BaitArgs &A, BaitResult &R, mf_kmerset **ks_out, declt
         const size_t positions = rc == MF_OK ? (size_t)std::max<uint64_t>(R.starts.back(), 1) : 1, n_rec = std::max<size_t>(R.names.size(), 1);
         if (A.verified) {          // the placed reads scored and cut; then what the family asks for, from the accepted ones
             SYM(mf_kmerset_bait_letters) SYM(mf_filter_fastq_files_verified_keep)
+            const bool with_depth = A.placed || !A.indels_file.empty();          // (the indel table is written beside the base depth)
             R.score_recs.assign(n_rec, mf_score_record_t{});
             if (A.piled) { R.pile.assign(positions, mf_pileup_t{}); R.consensus.assign(positions, 0); R.letters.assign(positions, 0); }
-            if (A.placed) { R.profile.assign(positions, 0); R.place_recs.assign(n_rec, mf_place_record_t{}); }
+            if (with_depth) { R.profile.assign(positions, 0); R.place_recs.assign(n_rec, mf_place_record_t{}); }
             if (rc == MF_OK && A.piled) rc = p_mf_kmerset_bait_letters(ks, R.letters.data(), R.letters.size(), nullptr);
-            if (rc == MF_OK)
+            if (rc == MF_OK && A.aligned) {          // the same behind the banded alignment
+                SYM(mf_filter_fastq_files_aligned)
+                R.align_recs.assign(n_rec, mf_align_record_t{}); R.indels.assign(positions, mf_indel_t{});
+                rc = files(p_mf_filter_fastq_files_aligned, A.min_depth, A.max_permille, A.keep, A.band, with_depth ? R.profile.data() : nullptr, with_depth ? R.place_recs.data() : nullptr,
+                           A.piled ? R.pile.data() : nullptr, A.piled ? R.consensus.data() : nullptr, (mf_pileup_record_t *)nullptr, R.indels.data(), R.align_recs.data(), R.unplaced);
+            } else if (rc == MF_OK)
                 rc = files(p_mf_filter_fastq_files_verified_keep, A.min_depth, A.max_permille, A.keep, A.placed ? R.profile.data() : nullptr, A.placed ? R.place_recs.data() : nullptr,
                            A.piled ? R.pile.data() : nullptr, A.piled ? R.consensus.data() : nullptr, (mf_pileup_record_t *)nullptr, R.score_recs.data(), R.unplaced);
         } else if (A.piled) {
@@ -725,7 +752,9 @@ static bool write_reports(const BaitArgs &A, const BaitResult &R)
         && write_file(A.pileup_file, "pile-up", [&](FILE *f) { return write_pileup(f, R.names, R.starts, R.letters.data(), R.pile.data()); })
         && write_file(A.consensus_file, "consensus", [&](FILE *f) { return write_consensus(f, R.names, R.starts, R.consensus.data()); })
         && write_file(A.variants_file, "variants", [&](FILE *f) { return write_variants(f, R.names, R.starts, R.letters.data(), R.pile.data(), R.consensus.data()); })
-        && write_file(A.score_report, "score report", [&](FILE *f) { return write_score_report(f, R.names, R.starts, R.score_recs.data()); });
+        && write_file(A.score_report, "score report", [&](FILE *f) { return A.aligned ? write_align_report(f, R.names, R.starts, R.align_recs.data())
+                                                                                      : write_score_report(f, R.names, R.starts, R.score_recs.data()); })
+        && write_file(A.indels_file, "indel table", [&](FILE *f) { return write_indels(f, R.names, R.starts, R.profile.data(), R.indels.data()); });
 }
 
 static int bait_main(int argc, char **argv)

@@ -1,0 +1,253 @@
+// Banded alignment of the placed reads (gfx950, 64-wide waves): the verifying placement with indels.
+//
+//   align_kernel   one wave per listed read, grid-stride.  The vote is place_kernel's (place_vote, mf_vote_dev.h: the anchor vote, the
+//                  strict winner).  A placed read is then aligned to its record inside the band of
+//                  2 W + 1 diagonals around the winning one (align_read, the rule of mf_align.h):
+//                    rows      lane l <= 2 W owns diagonal d = l - W and holds D(i, start + i + d) of the row in one register.  Per row
+//                              t[d] = min(prev[d] + sub, prev[d + 1] + 1) -- prev[d + 1] is the lane above's --, then the deletions
+//                              inside the row: D[d] = min over e <= d of t[e] + (d - e), an inclusive prefix minimum over the lanes of
+//                              t[e] + (63 - lane) in log2 steps that stop at the band's width (none at W == 0).  Every cell of the band
+//                              is finite (D <= i), so only the two lanes at the band's edges need a predicate in place of infinity.
+//                              The read's oriented letters are fetched 64 rows at a time, one a lane (an N through the npos index),
+//                              and handed round by a shuffle; a lane reads the bait letter of its own column.
+//                    moves     two bits a cell (align_move), 32 rows to a 64-bit word a lane, stored [row block][lane] -- 512 bytes a
+//                              block, coalesced -- into the wave's slice of work memory.
+//                    end       wave minimum of align_end_key over the last row.
+//                    traceback wave-uniform, a row block at a time: the block's words are loaded once, a lane each, and the move of the
+//                              current cell is picked out of the owning lane's register.  For read base b it leaves one word: the column
+//                              the path enters row b + 1 at, whether base b was inserted, and how many bait positions row b + 1 deletes
+//                              behind it -- 32 a block, stored coalesced behind the direction bits.
+//                    counts    lanes take the read bases 64 at a time: compared and mismatches of the diagonal steps, one reduction.
+//                  Lane 0 then does what place_kernel's lane 0 does, with the alignment's coordinates and the cut over edits; for an
+//                  accepted read the wave walks the base words once more (align_adds): the pile-up of the diagonal steps, the deleted
+//                  positions, the insertion runs.
+// Work memory: align_work_words(max_len) words a wave, as many waves as the launch has: bounded whatever the number of reads.
+#include "mf_align_launch.h"
+#include "mf_vote_dev.h"
+#include "mf_align.h"
+#include <algorithm>
+
+namespace mf {
+
+constexpr uint64_t ALIGN_WORK_BYTES = 256ull << 20;
+constexpr uint64_t ALIGN_WAVES_PER_BLOCK = ASSIGN_BLOCK / 64;
+
+__device__ __forceinline__ unsigned long long wave_min_u64(unsigned long long v) { return ~wave_max_u64(~v); }
+
+// base i of the read oriented to the bait's forward strand: 0 .. 3, or ALIGN_X_NONE for an N
+__device__ __forceinline__ uint32_t oriented_base(const ReadsView &R, uint64_t b0, bool hasn, uint64_t L, uint32_t strand, uint64_t i)
+{
+    const uint64_t g = b0 + (strand ? L - 1 - i : i);
+    if (hasn) { const uint64_t ni = npos_lower_bound(R, g); if (ni < R.n_npos && R.npos[ni] == g) return ALIGN_X_NONE; }
+    const uint32_t letter = (R.words[g >> 4] >> (2 * ((uint32_t)g & 15u))) & 3u;
+    return strand ? letter ^ 3u : letter;
+}
+
+struct AlignResult { uint32_t compared, mismatches, insertions, deletions; int64_t ref_begin, ref_end; };
+
+// what the traceback leaves for a read base: the column (low word), inserted (bit 32), deleted positions behind it (from bit 33)
+__device__ __forceinline__ int64_t ent_column(unsigned long long e) { return (int64_t)(int32_t)(uint32_t)e; }
+__device__ __forceinline__ bool ent_inserted(unsigned long long e) { return (e >> 32) & 1u; }
+__device__ __forceinline__ uint32_t ent_deleted(unsigned long long e) { return (uint32_t)(e >> 33); }
+
+// The whole wave aligns one placed read; every lane returns the same result.  dirs, ent: the wave's work memory.
+__device__ __forceinline__ AlignResult align_read(const ReadsView &R, uint64_t b0, bool hasn, uint64_t L, uint32_t strand, int64_t start, uint64_t s0,
+                                                  int64_t len, const ScoreBait &B, int W, unsigned long long *dirs, unsigned long long *ent, int lane)
+{
+    const int d = lane - W;
+    const bool active = lane <= 2 * W;
+    uint32_t prev = 0, xv = ALIGN_X_NONE;
+    unsigned long long bits = 0;
+    for (uint64_t i = 1; i <= L; i++) {
+        const uint64_t b = i - 1;                                   // the read base this row consumes
+        if ((b & 63) == 0) xv = b + (uint64_t)lane < L ? oriented_base(R, b0, hasn, L, strand, b + (uint64_t)lane) : ALIGN_X_NONE;
+        const uint32_t x = __shfl(xv, (int)(b & 63));
+        bool cmp;
+        const uint32_t diag = prev + (active ? align_sub(x, start + (int64_t)b + d, len, B, s0, cmp) : 0u);
+        const uint32_t up = __shfl_down(prev, 1);                   // D(i - 1, c): the lane above's
+        uint32_t t = diag;
+        if (lane < 2 * W && up + 1u < t) t = up + 1u;
+        uint32_t key = t + (uint32_t)(63 - lane);
+        for (int o = 1; o <= 2 * W; o <<= 1) { const uint32_t v = __shfl_up(key, o); if (lane >= o && v < key) key = v; }
+        const uint32_t D = key - (uint32_t)(63 - lane);
+        const uint32_t left = __shfl_up(D, 1);                      // D(i, c - 1)
+        bits |= (unsigned long long)align_move(D, diag, lane > 0, left) << (2 * ((uint32_t)b & 31u));
+        if (((uint32_t)b & 31u) == 31u || i == L) { dirs[(b >> 5) * 64 + (uint64_t)lane] = bits; bits = 0; }
+        prev = D;
+    }
+    int dd = align_end_diagonal(wave_min_u64(active ? align_end_key(prev, d) : ~0ull));
+    AlignResult a{0, 0, 0, 0, 0, start + (int64_t)L + dd};
+    __threadfence_block();                                          // (the wave's own stores, read back below)
+    uint64_t i = L;
+    uint32_t pend = 0;                                              // deletions of the current row seen so far
+    for (uint64_t blk = (L - 1) >> 5;; blk--) {
+        const unsigned long long w = dirs[blk * 64 + (uint64_t)lane];
+        unsigned long long mine = 0;
+        while (i > blk * 32) {
+            const uint32_t bi = (uint32_t)(i - 1) & 31u;
+            const unsigned long long wd = __shfl(w, dd + W);
+            const uint32_t mv = __builtin_amdgcn_readfirstlane((uint32_t)(wd >> (2 * bi)) & 3u);
+            if (mv == ALIGN_DEL && dd > -W) { a.deletions++; pend++; dd--; continue; }
+            const bool ins = mv == ALIGN_INS && dd < W;
+            if ((uint32_t)lane == bi)
+                mine = ((unsigned long long)pend << 33) | ((unsigned long long)ins << 32) | (uint32_t)(int32_t)(start + (int64_t)i + dd);
+            pend = 0;
+            if (ins) { a.insertions++; dd++; }
+            i--;
+        }
+        if (lane < 32 && blk * 32 + (uint64_t)lane < L) ent[blk * 32 + (uint64_t)lane] = mine;
+        if (blk == 0) break;
+    }
+    a.ref_begin = start + dd;
+    __threadfence_block();
+    unsigned long long acc = 0;
+    for (uint64_t b = (uint64_t)lane; b < L; b += 64) {
+        const unsigned long long e = ent[b];
+        if (ent_inserted(e)) continue;
+        bool cmp;
+        const uint32_t s = align_sub(oriented_base(R, b0, hasn, L, strand, b), ent_column(e) - 1, len, B, s0, cmp);
+        acc += ((unsigned long long)s << 32) | (cmp ? 1u : 0u);
+    }
+    acc = wave_sum_u64(acc);
+    a.compared = __builtin_amdgcn_readfirstlane((uint32_t)acc); a.mismatches = __builtin_amdgcn_readfirstlane((uint32_t)(acc >> 32));
+    return a;
+}
+
+// What an accepted read adds per position, lane l taking bases l, l + 64, ..: the base of a diagonal step into pile (optional), the
+// positions its row deletes into indel[.][0], an inserted base into indel[.][2] and, where it begins a run, indel[.][1].
+__device__ __forceinline__ void align_adds(const ReadsView &R, uint64_t b0, bool hasn, uint64_t L, uint32_t strand, uint64_t s0, int64_t len,
+                                           const unsigned long long *ent, unsigned long long *__restrict__ pile, unsigned long long *__restrict__ indel, int lane)
+{
+    for (uint64_t b = (uint64_t)lane; b < L; b += 64) {
+        const unsigned long long e = ent[b];
+        const int64_t c = ent_column(e);
+        for (uint32_t q = 0; q < ent_deleted(e); q++) {
+            const int64_t p = c + (int64_t)q;
+            if (p >= 0 && p < len) atomicAdd(&indel[ALIGN_INDEL * (s0 + (uint64_t)p)], 1ull);
+        }
+        const int64_t p = c - 1;
+        if (p < 0 || p >= len) continue;
+        if (!ent_inserted(e)) {
+            if (!pile) continue;
+            const uint32_t x = oriented_base(R, b0, hasn, L, strand, b);
+            if (x < ALIGN_X_NONE) atomicAdd(&pile[4 * (s0 + (uint64_t)p) + x], 1ull);
+        } else {
+            atomicAdd(&indel[ALIGN_INDEL * (s0 + (uint64_t)p) + 2], 1ull);
+            // the base before it is of the same run when it was inserted too and its row deleted nothing
+            if (!(b > 0 && (ent[b - 1] >> 32) == 1ull)) atomicAdd(&indel[ALIGN_INDEL * (s0 + (uint64_t)p) + 1], 1ull);
+        }
+    }
+}
+
+struct AlignArgs {
+    ScoreBait bait; uint32_t max_permille; int band;
+    AlignOut *__restrict__ align; unsigned long long *__restrict__ sums, *__restrict__ indel;
+    uint32_t *__restrict__ keep_bits; int keep;
+    unsigned long long *work; uint64_t max_len, dir_words, work_words;
+};
+
+template <int KW>
+__global__ void __launch_bounds__(ASSIGN_BLOCK)
+align_kernel(ReadsView R, KmerSetView S, const Anchor *__restrict__ anchor, const uint64_t *__restrict__ rec_start, const uint32_t *__restrict__ list,
+             const unsigned long long *__restrict__ n_list_p, uint32_t n_rec, PlaceOut *__restrict__ place, unsigned long long *__restrict__ diff,
+             unsigned long long *__restrict__ counts, unsigned long long *__restrict__ pile, AlignArgs A)
+{
+    __shared__ uint32_t s_hist[HIST_MAX];
+    // forward, reverse, over_begin, over_end of every record; not placed; behind them rejected and the 32 bins of every record
+    GatheredCounts cnt(s_hist, counts, 4 * n_rec + 1 + SCORE_GATHERED * n_rec);
+    cnt.hist_begin();
+    NucWindows<KW> src(R, S, nullptr);
+    const int lane = threadIdx.x & 63;
+    const uint64_t n_list = *n_list_p;
+    const uint64_t n_waves = (uint64_t)gridDim.x * (ASSIGN_BLOCK / 64);
+    const uint64_t wave = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    unsigned long long *const dirs = A.work + wave * A.work_words, *const ent = dirs + A.dir_words;
+    uint32_t sum_j = 0; bool sum_any = false;                // (lane 0) the sums of a run of accepted reads on one record
+    unsigned long long sum_v[ALIGN_SUMS] = {0, 0, 0, 0, 0};
+    auto flush = [&]() {
+#pragma unroll
+        for (uint32_t q = 0; q < ALIGN_SUMS; q++) { if (sum_v[q]) atomicAdd(&A.sums[ALIGN_SUMS * sum_j + q], sum_v[q]); sum_v[q] = 0; }
+        sum_any = false;
+    };
+    for (uint64_t i = wave; i < n_list; i += n_waves) {
+        const uint32_t r = list[i];
+        const uint64_t np = src.begin(r);                    // windows; the read has np + k - 1 bases when np > 0
+        uint32_t best_cnt, windows; uint64_t best_key; bool tie;
+        place_vote<KW>(R, S, anchor, src, np, lane, best_cnt, best_key, tie, windows);
+        const uint64_t L = np + (uint64_t)S.k - 1;
+        const bool placed = best_cnt && !tie && L <= A.max_len;          // (no listed read is longer than max_len: the work memory's bound)
+        AlignResult a{0, 0, 0, 0, 0, 0};
+        bool accept = true;
+        uint32_t rs = 0; uint64_t s0 = 0; int64_t start = 0, len = 0;
+        if (placed) {                                        // (the winner is wave-uniform: into scalar registers)
+            rs = __builtin_amdgcn_readfirstlane((uint32_t)(best_key >> 32));
+            start = (int32_t)__builtin_amdgcn_readfirstlane((uint32_t)best_key);
+            s0 = rec_start[rs >> 1];
+            len = (int64_t)(rec_start[(rs >> 1) + 1] - s0);
+            a = align_read(R, src.b0, src.hasn, L, rs & 1u, start, s0, len, A.bait, A.band, dirs, ent, lane);
+            accept = align_accepts(a.compared, a.mismatches, a.insertions, a.deletions, A.max_permille);
+        }
+        if (lane == 0) {
+            PlaceOut out{PLACE_AMBIGUOUS, 0u, 0, 0, 0u, windows};
+            if (placed) {
+                const uint32_t j = rs >> 1;
+                out = PlaceOut{j, rs & 1u, (int32_t)start, (int32_t)(start + (int64_t)L), best_cnt, windows};
+                if (accept) {
+                    // band < k: the winning anchor's window lies inside the record on diagonal 0, the clipped footprint is not empty
+                    const int64_t lo = a.ref_begin < 0 ? 0 : a.ref_begin < len ? a.ref_begin : len;
+                    const int64_t hi = a.ref_end < 0 ? 0 : a.ref_end < len ? a.ref_end : len;
+                    atomicAdd(&diff[s0 + (uint64_t)lo], 1ull);
+                    atomicAdd(&diff[s0 + (uint64_t)hi], ~0ull);
+                    cnt.bump(4 * j + (rs & 1u));
+                    if (a.ref_begin < 0) cnt.add(4 * j + 2, 1);
+                    if (a.ref_end > len) cnt.add(4 * j + 3, 1);
+                }
+                const uint32_t g0 = 4 * n_rec + 1 + SCORE_GATHERED * j;
+                const uint32_t edits = a.mismatches + a.insertions + a.deletions;
+                if (!accept) cnt.add(g0, 1);
+                cnt.add(g0 + 1 + (edits < SCORE_BINS - 1 ? edits : SCORE_BINS - 1), 1);
+                if (accept) {
+                    if (sum_any && sum_j != j) flush();
+                    sum_j = j; sum_any = true;
+                    sum_v[0] += a.compared; sum_v[1] += a.mismatches; sum_v[2] += a.insertions; sum_v[3] += a.deletions;
+                    sum_v[4] += (a.insertions | a.deletions) != 0;
+                }
+                if (A.align) A.align[r] = AlignOut{a.compared, a.mismatches, a.insertions, a.deletions, (int32_t)a.ref_begin, (int32_t)a.ref_end};
+            } else cnt.bump(4 * n_rec);
+            if (place) place[r] = out;
+            if (A.keep_bits && keep_clears(placed, accept, A.keep)) atomicAnd(&A.keep_bits[r >> 5], ~(1u << (r & 31u)));
+        }
+        if (placed && accept) align_adds(R, src.b0, src.hasn, L, rs & 1u, s0, len, ent, pile, A.indel, lane);
+    }
+    if (lane == 0 && sum_any) flush();
+    cnt.hist_end(lane);
+}
+
+uint64_t align_work_words(uint64_t max_len)
+{
+    const uint64_t n = std::max<uint64_t>(max_len, 1);
+    return 64 * ((n + 31) / 32) + n;
+}
+
+uint64_t align_waves(uint64_t n_reads, uint64_t max_len, int n_cu)
+{
+    uint64_t waves = std::min<uint64_t>((uint64_t)(n_cu > 0 ? n_cu : 1) * 32, std::max<uint64_t>(n_reads, 1));
+    waves = std::min(waves, ALIGN_WORK_BYTES / (align_work_words(max_len) * 8));
+    return std::max<uint64_t>((waves + ALIGN_WAVES_PER_BLOCK - 1) / ALIGN_WAVES_PER_BLOCK, 1) * ALIGN_WAVES_PER_BLOCK;
+}
+
+hipError_t launch_align(const ReadsView &R, const KmerSetView &S, const Anchor *anchor, const uint64_t *rec_start, const uint32_t *list,
+                        const unsigned long long *n_list, uint32_t n_rec, PlaceOut *place, unsigned long long *diff, unsigned long long *counts,
+                        unsigned long long *pile, const PlaceAlign &P, int n_cu, hipStream_t st)
+{
+    if (!R.n_reads) return hipSuccess;
+    const unsigned grid = (unsigned)(align_waves(R.n_reads, P.max_len, n_cu) / ALIGN_WAVES_PER_BLOCK);
+    const uint64_t n = std::max<uint64_t>(P.max_len, 1);
+    const AlignArgs A{ScoreBait{P.bait_words, P.bait_words_last, P.bait_valid, P.bait_valid_last}, P.max_permille, (int)P.band, P.align, P.sums, P.indel,
+                      P.keep_bits, P.keep, P.work, P.max_len, 64 * ((n + 31) / 32), align_work_words(P.max_len)};
+    if (S.kw == 1) hipLaunchKernelGGL(align_kernel<1>, dim3(grid), dim3(ASSIGN_BLOCK), 0, st, R, S, anchor, rec_start, list, n_list, n_rec, place, diff, counts, pile, A);
+    else hipLaunchKernelGGL(align_kernel<2>, dim3(grid), dim3(ASSIGN_BLOCK), 0, st, R, S, anchor, rec_start, list, n_list, n_rec, place, diff, counts, pile, A);
+    return hipGetLastError();
+}
+
+} // namespace mf

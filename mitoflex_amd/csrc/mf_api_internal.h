@@ -7,6 +7,7 @@
 #include "mf_kernels.h"
 #include "mf_assign.h"
 #include "mf_place.h"
+#include "mf_align_launch.h"
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <map>
@@ -158,6 +159,8 @@ struct mf_reads {
     mf::PlaceOut *d_place = nullptr; size_t cap_place = 0;          // mf_place's per-read results
     mf::ScoreOut *d_score = nullptr; size_t cap_score = 0;          // mf_verify's per-read scores
     uint32_t *d_keep = nullptr; size_t cap_keep = 0;                // the keep bitmap of a verifying call with a keep mode: laid out like d_bits
+    mf::AlignOut *d_align = nullptr; size_t cap_align = 0;          // mf_align's per-read alignments
+    unsigned long long *d_awork = nullptr; size_t cap_awork = 0;    // ... and its kernel's work memory, a slice a wave (mf_align_launch.h)
     // capacities (bytes), so that a handle can be refilled batch after batch without touching the allocator
     size_t cap_words = 0, cap_offsets = 0, cap_npos = 0, cap_bitmap = 0, cap_recs = 0, cap_rec_counts = 0, cap_hits = 0, cap_npos_blk = 0, cap_off_blk = 0;
 };

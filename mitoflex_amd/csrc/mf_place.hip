@@ -4,7 +4,8 @@
 //   anchor_finish_kernel   one thread per slot keeps the key as an anchor where both agree (exactly one window holds it, whatever order the
 //                          windows came in) and that window is not its own reverse complement: its position inside its record, its
 //                          record (binary search over the record starts) and the bait's orientation go into one 8-byte entry.
-//   place_kernel           one wave per listed read, grid-stride.  Lanes take the read's windows 64 at a time: canonical key and the
+//   place_kernel           one wave per listed read, grid-stride.  The vote is place_vote (mf_vote_dev.h, shared with align_kernel of
+//                          mf_align.hip).  Lanes take the read's windows 64 at a time: canonical key and the
 //                          read's orientation together, slot, anchor entry -- one 8-byte gather --, candidate (record, strand, start)
 //                          as a 64-bit key.  The votes are tallied by mf_tally_dev.h's WaveTally (the leader loop and the repeated
 //                          sweeps of assign_kernel, over a wider key).  Lane 0 writes the read's placement, bumps the record's counters
@@ -25,7 +26,7 @@
 //   pileup_call_kernel     per position, tiled like place_profile_kernel: the four counters clamped, the consensus byte, the records' six
 //                          sums through the same record walk (RecordWalk).
 #include "mf_place.h"
-#include "mf_tally_dev.h"
+#include "mf_vote_dev.h"
 #include "mf_score.h"
 #include <algorithm>
 
@@ -147,35 +148,8 @@ place_kernel(ReadsView R, KmerSetView S, const Anchor *__restrict__ anchor, cons
     for (uint64_t i = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6; i < n_list; i += n_waves) {
         const uint32_t r = list[i];
         const uint64_t np = src.begin(r);                    // windows; the read has np + k - 1 bases when np > 0
-        uint32_t best_cnt = 0, windows = 0; uint64_t best_key = 0; bool tie = false;
-        uint64_t lo_bound = 0;                               // the candidates this sweep counts: lo_bound and above
-        for (;;) {
-            WaveTally<uint64_t> tally;
-            for (uint64_t p0 = 0; p0 < np; p0 += 64) {
-                const uint64_t p = p0 + (uint64_t)lane;
-                uint64_t id = WaveTally<uint64_t>::NONE;
-                bool voted = false;
-                if (p < np && src.valid_at(p)) {
-                    uint32_t rev;
-                    const uint64_t slot = table_find(S, oriented_at<KW>(R.words, src.b0 + p, S.k, rev));
-                    if (slot != ~0ULL) {
-                        const Anchor a = anchor[slot];
-                        if (a.pos != ANCHOR_NONE) {            // (a window that is its own reverse complement finds no anchor: the build drops them)
-                            const uint32_t rs = a.rb ^ (rev & 1u);   // record << 1 | strand
-                            const uint32_t off = (uint32_t)((rs & 1u) ? np - 1 - p : p);
-                            const uint64_t cand = ((uint64_t)rs << 32) | (uint32_t)((int32_t)a.pos - (int32_t)off);
-                            voted = true;
-                            if (cand >= lo_bound) id = cand;
-                        }
-                    }
-                }
-                if (lo_bound == 0) windows += (uint32_t)__popcll(__ballot(voted));
-                tally.add(id, lane);
-            }
-            tally.fold(best_cnt, best_key, tie);
-            if (!tally.overflow) break;
-            lo_bound = tally.next_bound();
-        }
+        uint32_t best_cnt, windows; uint64_t best_key; bool tie;
+        place_vote<KW>(R, S, anchor, src, np, lane, best_cnt, best_key, tie, windows);
         // VERIFY: the read is scored before anything of it is counted; a rejected read then counts nowhere but in rejected and its bin
         uint32_t compared = 0, mismatches = 0; bool accept = true;
         if constexpr (VERIFY) {

@@ -9,6 +9,8 @@ namespace mf {
 constexpr uint32_t SCORE_BINS = 32;                      // MF_SCORE_BINS
 constexpr uint32_t SCORE_GATHERED = 1 + SCORE_BINS;      // counters a record that a verifying launch gathers behind placement's: rejected, the bins
 constexpr uint32_t PILE_SUMS = 6;                        // counters a record of the call kernel's sums: the fields of mf_pileup_record_t
+constexpr uint32_t ALIGN_RECORD_SUMS = 5;                // an aligning placement's sums a record: compared, mismatches, insertions, deletions, gapped
+constexpr uint32_t ALIGN_POSITION_COUNTERS = 3;          // ... and its counters a position: del, ins, ins_bases (mf_indel_t)
 
 // The counters of a placement, one array of 64-bit words: [pile-up counters | difference counters | record counters].  The four pile-up
 // counters a position (only with a pile-up) come FIRST because the call kernel reads them 16 bytes at a time: at the front of an
@@ -16,13 +18,18 @@ constexpr uint32_t PILE_SUMS = 6;                        // counters a record of
 // array).  Then the difference counters (positions + 1), then forward / reverse / over_begin / over_end of every record and the passing
 // reads that are not placed (4 R + 1).  A verifying placement keeps a fourth section behind them: rejected and the MF_SCORE_BINS bins of
 // every record (what the kernel gathers with the record counters, SCORE_GATHERED R), then compared and mismatches of every record (2 R).
+// An ALIGNING placement (mf_align; it is a verifying one) keeps the wider sums there -- compared, mismatches, insertions, deletions, gapped
+// of every record (ALIGN_RECORD_SUMS R) -- and a fifth section behind them: del, ins, ins_bases of every position.
 // Every offset into the array is computed here.
 struct PlaceLayout {
-    size_t n_pile, n_diff, n_cnt, n_rec; bool verify; uint32_t max_permille;
-    PlaceLayout(uint64_t positions, size_t n_rec_, bool pileup, bool verify_, uint32_t max_permille_)
-        : n_pile(pileup ? 4 * (size_t)positions : 0), n_diff((size_t)positions + 1), n_cnt(4 * n_rec_ + 1), n_rec(n_rec_), verify(verify_), max_permille(max_permille_) {}
-    size_t n_score() const { return verify ? ((size_t)SCORE_GATHERED + 2) * n_rec : 0; }
-    size_t words() const { return n_pile + n_diff + n_cnt + n_score(); }
+    size_t n_pile, n_diff, n_cnt, n_rec; bool verify; uint32_t max_permille; bool align; uint32_t band; size_t n_indel;
+    PlaceLayout(uint64_t positions, size_t n_rec_, bool pileup, bool verify_, uint32_t max_permille_, bool align_ = false, uint32_t band_ = 0)
+        : n_pile(pileup ? 4 * (size_t)positions : 0), n_diff((size_t)positions + 1), n_cnt(4 * n_rec_ + 1), n_rec(n_rec_), verify(verify_), max_permille(max_permille_),
+          align(align_), band(band_), n_indel(align_ ? ALIGN_POSITION_COUNTERS * (size_t)positions : 0) {}
+    size_t n_sums() const { return align ? ALIGN_RECORD_SUMS : 2; }
+    size_t n_score() const { return verify ? ((size_t)SCORE_GATHERED + n_sums()) * n_rec : 0; }
+    size_t words() const { return n_pile + n_diff + n_cnt + n_score() + n_indel; }
+    unsigned long long *indel(unsigned long long *base) const { return n_indel ? cnt(base) + n_cnt + n_score() : nullptr; }
     unsigned long long *pile(unsigned long long *base) const { return n_pile ? base : nullptr; }
     unsigned long long *diff(unsigned long long *base) const { return base + n_pile; }
     unsigned long long *cnt(unsigned long long *base) const { return base + n_pile + n_diff; }
@@ -34,6 +41,17 @@ struct PlaceLayout {
         for (size_t j = 0; j < n_rec; j++) {
             out[j].accepted = h_cnt[4 * j] + h_cnt[4 * j + 1]; out[j].rejected = g[SCORE_GATHERED * j];
             out[j].compared = sums[2 * j]; out[j].mismatches = sums[2 * j + 1];
+            for (uint32_t b = 0; b < SCORE_BINS; b++) out[j].hist[b] = g[SCORE_GATHERED * j + 1 + b];
+        }
+    }
+    // the same section of an aligning placement into its records
+    void align_records(const unsigned long long *h_cnt, mf_align_record_t *out) const
+    {
+        const unsigned long long *g = h_cnt + n_cnt, *sums = g + (size_t)SCORE_GATHERED * n_rec;
+        for (size_t j = 0; j < n_rec; j++) {
+            const unsigned long long *s = sums + ALIGN_RECORD_SUMS * j;
+            out[j].accepted = h_cnt[4 * j] + h_cnt[4 * j + 1]; out[j].rejected = g[SCORE_GATHERED * j];
+            out[j].compared = s[0]; out[j].mismatches = s[1]; out[j].insertions = s[2]; out[j].deletions = s[3]; out[j].gapped = s[4];
             for (uint32_t b = 0; b < SCORE_BINS; b++) out[j].hist[b] = g[SCORE_GATHERED * j + 1 + b];
         }
     }

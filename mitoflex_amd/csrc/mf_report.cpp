@@ -5,6 +5,7 @@
 // mf_place.hip's.
 #include "mf_api_internal.h"
 #include "mf_pipeline.h"
+#include "mf_align.h"
 
 #include <atomic>
 #include <string.h>
@@ -399,17 +400,22 @@ struct PlaceRequest {
     mf_pileup_t *pileup = nullptr; uint8_t *consensus = nullptr; mf_pileup_record_t *pileup_records = nullptr;
     mf_score_record_t *score_records = nullptr; uint64_t *unplaced = nullptr;
     int keep = MF_KEEP_PASSING; uint32_t *keep_bits = nullptr;
+    // an aligning family (a verifying one): the band, and what it gives in place of the scores
+    bool align = false; uint32_t band = 0;
+    mf_align_t *align_out = nullptr; mf_indel_t *indels = nullptr; mf_align_record_t *align_records = nullptr;
     // the one argument check of the family (a resident call checks its read set behind it)
     int check(const mf_kmerset *ks) const
     {
         if (max_permille > 1000) return fail(MF_E_ARG, "max_permille is %u: the cut is a number from 0 to 1000", max_permille);
         if (min_depth == 0) return fail(MF_E_ARG, "min_depth is 0: a called position needs at least one base");
         if (keep < MF_KEEP_PASSING || keep > MF_KEEP_PLACED) return fail(MF_E_ARG, "keep is %d: the keep mode is MF_KEEP_PASSING (0), MF_KEEP_ACCEPTED (1) or MF_KEEP_PLACED (2)", keep);
+        if (align && band > ALIGN_MAX_BAND) return fail(MF_E_ARG, "band is %u: the band is a number from 0 to %u and below k", band, ALIGN_MAX_BAND);
         if (!ks) return fail(MF_E_ARG, "NULL handle");
         if (ks->kind != MF_KIND_NUCLEOTIDE) return fail(MF_E_ARG, "%s needs a nucleotide bait set", family);
+        if (align && !align_band_ok(band, ks->k)) return fail(MF_E_ARG, "band is %u: the band stays below k = %d", band, ks->k);
         return MF_OK;
     }
-    PlaceLayout layout(const mf_kmerset *ks) const { return PlaceLayout(ks->positions(), ks->rec_len().size(), with_pileup, verify, max_permille); }
+    PlaceLayout layout(const mf_kmerset *ks) const { return PlaceLayout(ks->positions(), ks->rec_len().size(), with_pileup, verify, max_permille, align, band); }
     ReportScratch scratch(const mf_kmerset *ks) const
     {
         return ReportScratch(ks->positions(), ks->rec_len().size(), place_scan_tiles(ks->positions()), base_depth || place_records, with_pileup);
@@ -428,9 +434,11 @@ static int placement_tables(mf_kmerset *ks, int device, const PlaceLayout &L, De
 // into them at the same time), their placements into place (optional, initialised, n_reads entries on the device); *listed: how many
 // passed.  A verifying layout: every placed read is scored first and cut at L.max_permille; score (optional, zeroed, n_reads entries on
 // the device) takes the scores.  keep_dev (optional, a verifying layout only): the read set's keep bitmap, a copy of the pass bitmap,
-// in which the kernel clears the bits of the reads the keep mode `keep` does not write (keep_clears, mf_score.h).  Ends synchronised.
+// in which the kernel clears the bits of the reads the keep mode `keep` does not write (keep_clears, mf_score.h).  An aligning layout:
+// the placed reads are aligned inside L.band instead (launch_align, in the read set's work memory d_awork); align (optional, zeroed,
+// n_reads entries on the device) takes the alignments and score stays null.  Ends synchronised.
 static int place_after_filter(mf_kmerset *ks, mf_reads *r, const PlaceLayout &L, unsigned long long *t, PlaceOut *place, ScoreOut *score, uint64_t *listed,
-                              uint32_t *keep_dev = nullptr, int keep = MF_KEEP_PASSING)
+                              uint32_t *keep_dev = nullptr, int keep = MF_KEEP_PASSING, AlignOut *align = nullptr)
 {
     DevTables *T; int rc = placement_tables(ks, r->device, L, &T); if (rc) return rc;
     DevCtx *ctx; rc = get_ctx(r->device, &ctx, r->lane); if (rc) return rc;
@@ -443,7 +451,7 @@ static int place_after_filter(mf_kmerset *ks, mf_reads *r, const PlaceLayout &L,
     const uint64_t room = 0x80000000ull - ks->positions();
     unsigned long long v = 0;
     bool too_long = r->v.uniform_len >= room;
-    if (!r->v.uniform_len && r->v.total_bases >= room) {          // only then can a ragged set hold such a read
+    if (!r->v.uniform_len && (r->v.total_bases >= room || L.align)) {          // only then can a ragged set hold such a read; the alignment's work memory goes by the longest
         HIPCHK(hipMemsetAsync(r->d_acnt, 0, 8, st));
         HIPCHK(launch_max_read_len(r->v.offsets, n, r->d_acnt, st));
         HIPCHK(hipMemcpyAsync(&v, r->d_acnt, 8, hipMemcpyDeviceToHost, st));
@@ -454,6 +462,21 @@ static int place_after_filter(mf_kmerset *ks, mf_reads *r, const PlaceLayout &L,
     HIPCHK(hipMemsetAsync(r->d_acnt, 0, 8, st));
     HIPCHK(dev_reserve(r->d_alist, r->cap_alist, n * 4, true));
     HIPCHK(launch_pass_list(r->d_bits[r->cur], n, r->d_alist, r->d_acnt, st));
+    if (L.align) {
+        const uint64_t max_len = r->v.uniform_len ? r->v.uniform_len : v;
+        const size_t bytes = (size_t)(align_waves(n, max_len, ctx->n_cu) * align_work_words(max_len)) * 8;
+        const hipError_t e = dev_reserve(r->d_awork, r->cap_awork, bytes, false);
+        if (e == hipErrorOutOfMemory) { (void)hipGetLastError(); return fail(MF_E_NOMEM, "the alignment of reads of up to %llu bases needs %llu bytes on the device", (unsigned long long)max_len, (unsigned long long)bytes); }
+        HIPCHK(e);
+        const PlaceAlign pa{T->pile_words, T->pile_words_n - 1, T->pile_valid, T->pile_valid_n - 1, L.max_permille, L.band, align, L.score_sums(t), L.indel(t),
+                            keep_dev, keep, r->d_awork, max_len};
+        HIPCHK(launch_align(r->v, T->view, T->anchor, T->place_starts, r->d_alist, r->d_acnt, (uint32_t)ks->rec_len().size(), place, L.diff(t), L.cnt(t), L.pile(t),
+                            pa, ctx->n_cu, st));
+        HIPCHK(hipMemcpyAsync(&v, r->d_acnt, 8, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        *listed = v;
+        return MF_OK;
+    }
     PlaceVerify pv{};
     if (L.verify) pv = PlaceVerify{T->pile_words, T->pile_words_n - 1, T->pile_valid, T->pile_valid_n - 1, L.max_permille, score, L.score_sums(t), keep_dev, keep};
     HIPCHK(launch_place(r->v, T->view, T->anchor, T->place_starts, r->d_alist, r->d_acnt, (uint32_t)ks->rec_len().size(), place, L.diff(t), L.cnt(t), L.pile(t),
@@ -488,9 +511,11 @@ static int placement_report(mf_kmerset *ks, int device, hipStream_t st, const Pl
     static_assert(sizeof(mf_place_t) == 24 && sizeof(PlaceOut) == 24 && sizeof(mf_place_record_t) == 48, "placement records");
     static_assert(sizeof(mf_pileup_t) == 16 && sizeof(PileOut) == 16 && sizeof(mf_pileup_record_t) == 8 * PILE_SUMS, "pile-up records");
     static_assert(sizeof(mf_score_t) == 8 && sizeof(ScoreOut) == 8 && sizeof(mf_score_record_t) == 8 * (4 + MF_SCORE_BINS) && MF_SCORE_BINS == SCORE_BINS, "score records");
+    static_assert(sizeof(mf_align_t) == 24 && sizeof(AlignOut) == 24 && sizeof(mf_indel_t) == 12 && sizeof(mf_align_record_t) == 8 * (7 + MF_SCORE_BINS), "align records");
+    static_assert(ALIGN_SUMS == ALIGN_RECORD_SUMS && ALIGN_INDEL == ALIGN_POSITION_COUNTERS, "the kernel's counters are the layout's");
     DevTables *T; int rc = placement_tables(ks, device, L, &T); if (rc) return rc;
     const uint64_t total = ks->positions(), n_rec = L.n_rec;
-    std::vector<unsigned long long> h_cnt(L.n_cnt + (q.score_records ? L.n_score() : 0), 0), h_sum(2 * n_rec + 1, 0);
+    std::vector<unsigned long long> h_cnt(L.n_cnt + (q.score_records || q.align_records ? L.n_score() : 0), 0), h_sum(2 * n_rec + 1, 0), h_indel(q.indels ? L.n_indel : 0, 0);
     if (q.base_depth || q.place_records) {
         unsigned long long *work = S.work.in<unsigned long long>(sums); uint32_t *depth = S.depth.in<uint32_t>(pos);
         if (q.place_records && n_rec) HIPCHK(hipMemsetAsync(work, 0, 2 * n_rec * 8, st));
@@ -508,8 +533,14 @@ static int placement_report(mf_kmerset *ks, int device, hipStream_t st, const Pl
         if (q.consensus && total) HIPCHK(hipMemcpyAsync(q.consensus, cons, total, hipMemcpyDeviceToHost, st));
         if (q.pileup_records && n_rec) HIPCHK(hipMemcpyAsync(q.pileup_records, psums, PILE_SUMS * n_rec * 8, hipMemcpyDeviceToHost, st));
     }
+    if (!h_indel.empty()) HIPCHK(hipMemcpyAsync(h_indel.data(), L.indel(t), h_indel.size() * 8, hipMemcpyDeviceToHost, st));
     HIPCHK(hipMemcpyAsync(h_cnt.data(), L.cnt(t), h_cnt.size() * 8, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
+    for (size_t p = 0; p < h_indel.size() / ALIGN_INDEL; p++) {          // (clamped like the depth)
+        const auto clamp = [](unsigned long long c) { return c < PLACE_CLAMP ? (uint32_t)c : PLACE_CLAMP; };
+        q.indels[p] = mf_indel_t{clamp(h_indel[ALIGN_INDEL * p]), clamp(h_indel[ALIGN_INDEL * p + 1]), clamp(h_indel[ALIGN_INDEL * p + 2])};
+    }
+    if (q.align_records) L.align_records(h_cnt.data(), q.align_records);
     if (q.place_records)
         for (uint64_t j = 0; j < n_rec; j++)
             q.place_records[j] = mf_place_record_t{h_cnt[4 * j], h_cnt[4 * j + 1], h_cnt[4 * j + 2], h_cnt[4 * j + 3], h_sum[2 * j], h_sum[2 * j + 1]};
@@ -548,14 +579,20 @@ static int placement_resident(const mf_kmerset *ks_, const mf_reads *reads_, uin
         HIPCHK(dev_reserve(r->d_score, r->cap_score, n * sizeof(ScoreOut), true));
         HIPCHK(hipMemsetAsync(d_score = r->d_score, 0, n * sizeof(ScoreOut), st));
     }
+    AlignOut *d_align = nullptr;
+    if (q.align_out && n) {
+        HIPCHK(dev_reserve(r->d_align, r->cap_align, n * sizeof(AlignOut), true));
+        HIPCHK(hipMemsetAsync(d_align = r->d_align, 0, n * sizeof(AlignOut), st));
+    }
     uint64_t listed = 0;
     uint32_t *d_keep = nullptr;
     rc = keep_bitmap(r, q.keep, st, &d_keep); if (rc) return rc;
-    rc = place_after_filter(ks, r, L, r->d_rtot, d_place, d_score, &listed, d_keep, q.keep); if (rc) return rc;
+    rc = place_after_filter(ks, r, L, r->d_rtot, d_place, d_score, &listed, d_keep, q.keep, d_align); if (rc) return rc;
     // (MF_KEEP_PASSING: keep_bits are the pass bits)
     if (q.keep_bits && n) HIPCHK(hipMemcpyAsync(q.keep_bits, d_keep ? d_keep : r->d_bits[r->cur], (size_t)((n + 31) / 32) * 4, hipMemcpyDeviceToHost, st));
     if (d_place) HIPCHK(hipMemcpyAsync(q.place_out, d_place, n * sizeof(PlaceOut), hipMemcpyDeviceToHost, st));
     if (d_score) HIPCHK(hipMemcpyAsync(q.score_out, d_score, n * sizeof(ScoreOut), hipMemcpyDeviceToHost, st));
+    if (d_align) HIPCHK(hipMemcpyAsync(q.align_out, d_align, n * sizeof(AlignOut), hipMemcpyDeviceToHost, st));
     return placement_report(ks, r->device, st, L, r->d_rtot, q, S, r->d_rsum, r->d_rpos, n - listed);
 }
 
@@ -596,6 +633,16 @@ int mf_verify_keep(const mf_kmerset *ks, const mf_reads *reads, uint32_t thresho
 {
     const PlaceRequest q{"verification", true, pileup || consensus || pileup_records, min_depth, max_permille, place_out, score_out, base_depth,
                          place_records, pileup, consensus, pileup_records, score_records, unplaced, keep, keep_bits};
+    return placement_resident(ks, reads, threshold, mode, out_bits, stats, q);
+}
+
+int mf_align(const mf_kmerset *ks, const mf_reads *reads, uint32_t threshold, int mode, uint32_t min_depth, uint32_t max_permille, int keep, uint32_t band,
+             uint32_t *out_bits, uint32_t *keep_bits, mf_place_t *place_out, mf_align_t *align_out, uint32_t *base_depth, mf_place_record_t *place_records,
+             mf_pileup_t *pileup, uint8_t *consensus, mf_pileup_record_t *pileup_records, mf_indel_t *indels, mf_align_record_t *align_records,
+             uint64_t *unplaced, mf_filter_stats_t *stats)
+{
+    const PlaceRequest q{"alignment", true, pileup || consensus || pileup_records, min_depth, max_permille, place_out, nullptr, base_depth,
+                         place_records, pileup, consensus, pileup_records, nullptr, unplaced, keep, keep_bits, true, band, align_out, indels, align_records};
     return placement_resident(ks, reads, threshold, mode, out_bits, stats, q);
 }
 
@@ -831,6 +878,17 @@ int mf_filter_fastq_files_verified_keep(mf_kmerset *ks, const char *fq1, const c
 {
     const PlaceRequest q{"verification", true, pileup || consensus || pileup_records, min_depth, max_permille, nullptr, nullptr, base_depth,
                          place_records, pileup, consensus, pileup_records, score_records, unplaced, keep};
+    return placement_files(ks, fq1, fq2, out1, out2, threshold, pair_mode, devices, n_devices, kept, total, q);
+}
+
+int mf_filter_fastq_files_aligned(mf_kmerset *ks, const char *fq1, const char *fq2, const char *out1, const char *out2,
+                                  uint32_t threshold, int pair_mode, const int *devices, int n_devices, uint32_t min_depth, uint32_t max_permille, int keep,
+                                  uint32_t band, uint32_t *base_depth, mf_place_record_t *place_records, mf_pileup_t *pileup, uint8_t *consensus,
+                                  mf_pileup_record_t *pileup_records, mf_indel_t *indels, mf_align_record_t *align_records, uint64_t *unplaced,
+                                  uint64_t *kept, uint64_t *total)
+{
+    const PlaceRequest q{"alignment", true, pileup || consensus || pileup_records, min_depth, max_permille, nullptr, nullptr, base_depth,
+                         place_records, pileup, consensus, pileup_records, nullptr, unplaced, keep, nullptr, true, band, nullptr, indels, align_records};
     return placement_files(ks, fq1, fq2, out1, out2, threshold, pair_mode, devices, n_devices, kept, total, q);
 }
 

@@ -133,4 +133,36 @@ inline bool write_score_report(FILE *f, const Names &names, const Starts &starts
     return written(f);
 }
 
+// --score-report with --band: the same behind a banded alignment -- insertions, deletions and gapped behind mismatches, edits (mismatches
+// + insertions + deletions) per thousand alignment columns (compared + insertions + deletions), the bins of min(edits, 31)
+inline bool write_align_report(FILE *f, const Names &names, const Starts &starts, const mf_align_record_t *recs)
+{
+    if (!f) return false;
+    fputs("record\tname\tlength\taccepted\trejected\tcompared\tmismatches\tinsertions\tdeletions\tgapped\tpermille", f);
+    for (int b = 0; b < MF_SCORE_BINS; b++) fprintf(f, b == MF_SCORE_BINS - 1 ? "\ted%d+" : "\ted%d", b);
+    fputc('\n', f);
+    for (size_t i = 0; i < names.size(); i++) {
+        const mf_align_record_t &d = recs[i];
+        const uint64_t gaps = d.insertions + d.deletions, columns = d.compared + gaps;
+        fprintf(f, "%zu\t%s\t%llu\t%llu\t%llu\t%llu\t%llu\t%llu\t%llu\t%llu\t%.3f", i, names[i].c_str(), (ull)(starts[i + 1] - starts[i]), (ull)d.accepted, (ull)d.rejected,
+                (ull)d.compared, (ull)d.mismatches, (ull)d.insertions, (ull)d.deletions, (ull)d.gapped, columns ? 1000.0 * (double)(d.mismatches + gaps) / (double)columns : 0.0);
+        for (int b = 0; b < MF_SCORE_BINS; b++) fprintf(f, "\t%llu", (ull)d.hist[b]);
+        fputc('\n', f);
+    }
+    return written(f);
+}
+
+// --indels: name, 1-based position, base depth, del, ins, ins_bases of the positions where any of the three is not zero (an insertion lies
+// behind its position)
+inline bool write_indels(FILE *f, const Names &names, const Starts &starts, const uint32_t *base_depth, const mf_indel_t *indels)
+{
+    if (!f) return false;
+    fputs("name\tpos\tdepth\tdel\tins\tins_bases\n", f);
+    for (size_t i = 0; i < names.size(); i++)
+        for (uint64_t p = starts[i]; p < starts[i + 1]; p++)
+            if (indels[p].del || indels[p].ins || indels[p].ins_bases)
+                fprintf(f, "%s\t%llu\t%u\t%u\t%u\t%u\n", names[i].c_str(), (ull)(p - starts[i] + 1), base_depth[p], indels[p].del, indels[p].ins, indels[p].ins_bases);
+    return written(f);
+}
+
 } // namespace mf_text

@@ -48,6 +48,16 @@ SCORE_BINS = 32
 SCORE = np.dtype([("compared", np.uint32), ("mismatches", np.uint32)])
 SCORE_RECORD = np.dtype([("accepted", np.uint64), ("rejected", np.uint64), ("compared", np.uint64), ("mismatches", np.uint64),
                          ("hist", np.uint64, (SCORE_BINS,))])
+# banded alignment of a placed read (mf_align_t), the indel counters of a bait position (mf_indel_t), the per-record summary
+# (mf_align_record_t), and an indel position (indel_variants): pos is 0-based inside the record
+ALIGN_MAX_BAND = 31
+ALIGN = np.dtype([("compared", np.uint32), ("mismatches", np.uint32), ("insertions", np.uint32), ("deletions", np.uint32),
+                  ("ref_begin", np.int32), ("ref_end", np.int32)])
+INDEL = np.dtype([("del", np.uint32), ("ins", np.uint32), ("ins_bases", np.uint32)])
+ALIGN_RECORD = np.dtype([("accepted", np.uint64), ("rejected", np.uint64), ("compared", np.uint64), ("mismatches", np.uint64),
+                         ("insertions", np.uint64), ("deletions", np.uint64), ("gapped", np.uint64), ("hist", np.uint64, (SCORE_BINS,))])
+INDEL_VARIANT = np.dtype([("record", np.uint32), ("pos", np.uint64), ("depth", np.uint64), ("del", np.uint64), ("ins", np.uint64),
+                          ("ins_bases", np.uint64)])
 # a variant position (pileup_variants): pos is 0-based inside the record, ref / alt are letters
 VARIANT = np.dtype([("record", np.uint32), ("pos", np.uint64), ("ref", "S1"), ("alt", "S1"), ("depth", np.uint64), ("alt_count", np.uint64)])
 # the largest insert size pair_inserts keeps (bim.estimate_insert_sizes' rule)
@@ -68,6 +78,7 @@ EXPORTS = (
     "mf_pileup", "mf_filter_fastq_files_pileup", "mf_kmerset_bait_letters",
     "mf_verify", "mf_filter_fastq_files_verified",
     "mf_verify_keep", "mf_filter_fastq_files_verified_keep",
+    "mf_align", "mf_filter_fastq_files_aligned",
 )
 
 
@@ -191,6 +202,11 @@ def load(path: Optional[str] = None):
     L.mf_filter_fastq_files_verified_keep.argtypes = [vp, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_uint32, C.c_int,
                                                       C.POINTER(C.c_int), C.c_int, C.c_uint32, C.c_uint32, C.c_int, vp, vp, vp, vp, vp, vp, vp,
                                                       u64p, u64p]
+    L.mf_align.argtypes = [vp, vp, C.c_uint32, C.c_int, C.c_uint32, C.c_uint32, C.c_int, C.c_uint32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
+                           C.POINTER(FilterStats)]
+    L.mf_filter_fastq_files_aligned.argtypes = [vp, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_uint32, C.c_int,
+                                                C.POINTER(C.c_int), C.c_int, C.c_uint32, C.c_uint32, C.c_int, C.c_uint32, vp, vp, vp, vp, vp, vp,
+                                                vp, vp, u64p, u64p]
     if L.mf_abi_version() != 5:
         raise MitoFilterError("libmitofilter_hip ABI version mismatch")
     _lib = L
@@ -473,7 +489,8 @@ def _report_outputs(ks: KmerSet, fields, leave_out=()):
     starts = ks.record_starts
     P, R = int(starts[-1]), len(starts) - 1
     shape = {"base_depth": (P, np.uint32), "place_records": (R, PLACE_RECORD), "pileup": (P, PILEUP), "consensus": (P, np.uint8),
-             "pileup_records": (R, PILEUP_RECORD), "score_records": (R, SCORE_RECORD), "unplaced": (2, np.uint64)}
+             "pileup_records": (R, PILEUP_RECORD), "score_records": (R, SCORE_RECORD), "unplaced": (2, np.uint64),
+             "indels": (P, INDEL), "align_records": (R, ALIGN_RECORD)}
     a = {f: None if f in leave_out else np.zeros(max(shape[f][0], 1), dtype=shape[f][1]) for f in fields}
     ptrs = [x.ctypes.data if x is not None else None for x in a.values()]
     return ptrs, lambda: {f: (x[:shape[f][0]] if x is not None else None) for f, x in a.items()}
@@ -482,6 +499,7 @@ def _report_outputs(ks: KmerSet, fields, leave_out=()):
 _PLACE_FIELDS = ("base_depth", "place_records", "unplaced")
 _PILEUP_FIELDS = ("pileup", "consensus", "pileup_records", "unplaced")
 _VERIFY_FIELDS = ("base_depth", "place_records", "pileup", "consensus", "pileup_records", "score_records", "unplaced")
+_ALIGN_FIELDS = ("base_depth", "place_records", "pileup", "consensus", "pileup_records", "indels", "align_records", "unplaced")
 
 
 def place_reads(ks: KmerSet, reads: Reads, threshold: int = 1, mode: int = MODE_SCREENED):
@@ -563,6 +581,62 @@ def verify_reads(ks: KmerSet, reads: Reads, threshold: int = 1, mode: int = MODE
                                *per_read[1:], *ptrs, None))
     bits, place, score = read_results()
     return VerifiedKeep(bits=bits, keep_bits=keep_bits[:(n + 31) // 32], place=place, score=score, **results())
+
+
+class Aligned(Verified):
+    """What an aligning call gives (include/mitofilter.h, banded alignment): Verified's fields with score and score_records None, and
+    align ALIGN[n] (align_reads only), indels INDEL[positions], align_records ALIGN_RECORD[R] and keep_bits u32[ceil(n/32)] (align_reads
+    only; the pass bits under KEEP_PASSING)."""
+    __slots__ = ("keep_bits", "align", "indels", "align_records")
+
+
+def _check_band(band: int):
+    if not 0 <= int(band) <= ALIGN_MAX_BAND:
+        raise ValueError("band is a number from 0 to %d (and below k)" % ALIGN_MAX_BAND)
+
+
+def align_reads(ks: KmerSet, reads: Reads, band: int = 8, min_depth: int = 1, max_permille: int = 1000, keep: int = KEEP_PASSING,
+                pileup: bool = True, threshold: int = 1, mode: int = MODE_SCREENED) -> Aligned:
+    """One filter pass, then every placed read aligned to its record inside the band of 2 * band + 1 diagonals around its placement and
+    cut at max_permille edits per thousand alignment columns; base depth, the records, the keep bits and (pileup=True) the pile-up
+    follow the alignment, and indels counts deletions and insertions per bait position (include/mitofilter.h: mf_align).  band = 0 is
+    verify_reads.  -> Aligned with bits, keep_bits, place, align and the shared fields."""
+    _check_cut(min_depth, max_permille, keep)
+    _check_band(band)
+    per_read, read_results = _read_outputs(reads, PLACE, ALIGN)
+    ptrs, results = _report_outputs(ks, _ALIGN_FIELDS, () if pileup else _PILEUP_FIELDS[:3])
+    n = reads.info.n_reads
+    keep_bits = np.zeros(max((n + 31) // 32, 1), dtype=np.uint32)
+    _chk(load().mf_align(ks._h, reads._h, threshold, mode, min_depth, max_permille, int(keep), int(band), per_read[0], keep_bits.ctypes.data,
+                         *per_read[1:], *ptrs, None))
+    bits, place, align = read_results()
+    return Aligned(bits=bits, keep_bits=keep_bits[:(n + 31) // 32], place=place, align=align, **results())
+
+
+def indel_variants(record_starts, base_depth, indels, min_depth: int = 1, min_permille: int = 500) -> np.ndarray:
+    """The indel positions of an aligning call: positions of at least min_depth base depth whose del or ins, per thousand of that depth,
+    reaches min_permille.  -> INDEL_VARIANT[n]: record, pos (0-based inside the record; an insertion lies behind it), depth, del, ins,
+    ins_bases.  Needs no device."""
+    if int(min_depth) < 1:
+        raise ValueError("min_depth is at least 1")
+    if not 0 <= int(min_permille) <= 1000:
+        raise ValueError("min_permille is a number from 0 to 1000")
+    starts = np.asarray(record_starts, dtype=np.uint64)
+    P = int(starts[-1])
+    depth = np.asarray(base_depth)[:P].astype(np.uint64)
+    indels = np.asarray(indels)[:P]
+    if not (len(depth) == len(indels) == P):
+        raise ValueError("base_depth and indels hold one entry per position")
+    most = np.maximum(indels["del"], indels["ins"]).astype(np.uint64)
+    at = np.nonzero((depth >= np.uint64(min_depth)) & (most > 0) & (most * np.uint64(1000) >= np.uint64(min_permille) * depth))[0]
+    out = np.zeros(at.size, dtype=INDEL_VARIANT)
+    rec = np.searchsorted(starts, at, side="right") - 1
+    out["record"] = rec
+    out["pos"] = at - starts[rec].astype(np.int64) if at.size else at
+    out["depth"] = depth[at]
+    for f in ("del", "ins", "ins_bases"):
+        out[f] = indels[f][at]
+    return out
 
 
 def consensus_fasta(names, starts, consensus, width: int = 60) -> str:
@@ -755,6 +829,20 @@ def filter_fastq_files_verified(ks: KmerSet, fq1: str, fq2: Optional[str], out1:
         kept, total = _files_call("mf_filter_fastq_files_verified_keep", ks, fq1, fq2, out1, out2, threshold, pair_mode, devices,
                                   n_devices, min_depth, max_permille, int(keep), *ptrs)
     return Verified(kept=kept, total=total, **results())
+
+
+def filter_fastq_files_aligned(ks: KmerSet, fq1: str, fq2: Optional[str], out1: str, out2: Optional[str], band: int = 8,
+                               threshold: int = 1, pair_mode: int = PAIR_EITHER, devices: Optional[Sequence[int]] = None,
+                               n_devices: int = 1, min_depth: int = 1, max_permille: int = 1000, pileup: bool = True,
+                               keep: int = KEEP_PASSING) -> Aligned:
+    """filter_fastq_files_verified behind the banded alignment (mf_filter_fastq_files_aligned): the cut, the keep rule and the reports
+    are those of align_reads, added over the mates.  -> Aligned with kept, total and the shared fields."""
+    _check_cut(min_depth, max_permille, keep)
+    _check_band(band)
+    ptrs, results = _report_outputs(ks, _ALIGN_FIELDS, () if pileup else _PILEUP_FIELDS[:3])
+    kept, total = _files_call("mf_filter_fastq_files_aligned", ks, fq1, fq2, out1, out2, threshold, pair_mode, devices, n_devices,
+                              min_depth, max_permille, int(keep), int(band), *ptrs)
+    return Aligned(kept=kept, total=total, **results())
 
 
 def set_option(name: str, value) -> None:
