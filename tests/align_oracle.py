@@ -206,3 +206,14 @@ class AlignOracle:
             prec[j, 4], prec[j, 5] = int((d > 0).sum()), int(d.sum())
         return {"passes": passes, "rows": rows, "aligns": aligns, "accepted": accepted, "depth": depth, "place_rec": prec.astype(np.uint64),
                 "align_rec": arec.astype(np.uint64), "unplaced": unplaced, "counts": counts, "indels": indels, "footprints": foot}
+
+
+def keep_bits(want, keep):
+    """the keep bits of every read from what AlignOracle.run gave: 0 the passing reads, 1 (accepted) without the placed reads the cut
+    rejects, 2 (placed) the accepted reads alone"""
+    placed = want["rows"][:, 0] < po.AMBIGUOUS
+    if keep == 1:
+        return want["passes"] & ~(placed & ~want["accepted"])
+    if keep == 2:
+        return want["passes"] & placed & want["accepted"]
+    return want["passes"].copy()
