@@ -518,7 +518,8 @@ int mf_filter_fastq_files_verified_keep(mf_kmerset *ks, const char *fq1, const c
  * accepted reads with at least one gap; hist[min(edits, 31)] over all placed reads.
  * accepted == forward + reverse; sum(hist) == accepted + rejected; base_sum == the sum of the clipped footprints of the accepted reads;
  * sum(del) over a record <= deletions; mismatches of the pile-up record == mismatches of the align record.
- * The consensus rule is unchanged and calls substitutions only: the indel table is the report on indels.
+ * The consensus rule is unchanged and calls substitutions only: the indel table is the report on indels (the gapped consensus below
+ * calls them).
  * Device memory: the traceback's direction bits and per-base columns live in a slice per resident wave (24 bytes a base of the longest
  * read), bounded whatever the number of reads; there is no read-length limit below placement's. */
 typedef struct { uint32_t compared, mismatches, insertions, deletions; int32_t ref_begin, ref_end; } mf_align_t;
@@ -536,6 +537,46 @@ int mf_filter_fastq_files_aligned(mf_kmerset *ks, const char *fq1, const char *f
               uint32_t band, uint32_t *base_depth, mf_place_record_t *place_records, mf_pileup_t *pileup, uint8_t *consensus,
               mf_pileup_record_t *pileup_records, mf_indel_t *indels, mf_align_record_t *align_records, uint64_t *unplaced,
               uint64_t *kept, uint64_t *total);
+
+/* ---- gapped consensus: the aligning calls with the letters of the inserted bases, and a consensus that calls indels.  mf_align_gapped
+ * and mf_filter_fastq_files_gapped are mf_align and mf_filter_fastq_files_aligned with four outputs behind align_records, each optional.
+ * With all four NULL they ARE the older calls: nothing more is allocated, the same kernels run, the same bits come back.  Asking for any
+ * of them implies the pile-up counters.  Nucleotide sets only; band as above.  ABI 5 still.
+ * The rule.  span = 2 * band: a run of insertion steps stays in one column and moves one diagonal a step, so no run is longer.
+ *   Insertion pile.  An accepted read's maximal run of n insertion steps at column c (between record positions c-1 and c; the run that
+ *   adds 1 to ins[c-1] and n to ins_bases[c-1]), when 0 <= c-1 < len: the t-th base of the run, t from 0 in the order of the oriented read
+ *   x (so in the bait's forward letters), adds 1 at ins_pile[(s0 + c-1) * span + t][letter].  An inserted N adds nowhere and still takes
+ *   its offset t.  Rejected, ambiguous, unplaced and non-passing reads add nothing.  For every position the sum over t and the four
+ *   letters is <= ins_bases, equal when no inserted base is an N.  Output: mf_pileup_t[positions * span], clamped at 0xFFFFFFFE like the
+ *   pile-up.  The call below goes by the unclamped sums.
+ *   Call.  For each position p of a record, in order.  D: the unclamped base depth of the aligning call (deleted positions count as
+ *   covered).  min_depth: the pile-up's (0 is MF_E_ARG).
+ *     p is DELETED iff D >= min_depth and 2 * del[p] > D; a deleted position emits no byte.  Otherwise it emits the byte the unchanged
+ *     consensus rule gives for p.
+ *     Then the insertion columns behind p, q = 0, 1, .., span - 1, n_q being the sum of the four counts at (p, q): column q is emitted iff
+ *     D >= min_depth and 2 * n_q > D, and emission stops at the first q that is not.  An emitted column's byte is the letter with
+ *     strictly the largest count, in upper case; a tie gives 'N'.
+ *     Both majorities are strict: support from exactly half of the covering reads calls nothing.
+ *   Result.  gapped: the emitted bytes of all records, concatenated; the caller's buffer holds positions * (1 + span) bytes, which is
+ *   always enough.  gapped_starts: R + 1 offsets into gapped.  mf_gapped_record_t per record: insertions counts the positions with at
+ *   least one emitted column.
+ *   length == len_j - deleted + inserted_bases.  At band == 0 the span is 0 and nothing is deleted: gapped is consensus byte for byte and
+ *   gapped_starts is the record starts.
+ * File level: the insertion counters add over mates, batches and devices before they are clamped, like the pile-up's; the call is made
+ * once, from the sums.
+ * Device memory: 4 * span 64-bit counters a position behind the indel counters (512 bytes a position at band 8, about 2 KB at band 31);
+ * where they cannot be allocated the call returns MF_E_NOMEM and names the size. */
+typedef struct { uint64_t length, deleted, insertions, inserted_bases; } mf_gapped_record_t;
+int mf_align_gapped(const mf_kmerset *ks, const mf_reads *reads, uint32_t threshold, int mode, uint32_t min_depth, uint32_t max_permille,
+              int keep, uint32_t band, uint32_t *out_bits, uint32_t *keep_bits, mf_place_t *place_out, mf_align_t *align_out, uint32_t *base_depth,
+              mf_place_record_t *place_records, mf_pileup_t *pileup, uint8_t *consensus, mf_pileup_record_t *pileup_records,
+              mf_indel_t *indels, mf_align_record_t *align_records, mf_pileup_t *ins_pile, uint8_t *gapped, uint64_t *gapped_starts,
+              mf_gapped_record_t *gapped_records, uint64_t *unplaced, mf_filter_stats_t *stats);
+int mf_filter_fastq_files_gapped(mf_kmerset *ks, const char *fq1, const char *fq2, const char *out1, const char *out2,
+              uint32_t threshold, int pair_mode, const int *devices, int n_devices, uint32_t min_depth, uint32_t max_permille, int keep,
+              uint32_t band, uint32_t *base_depth, mf_place_record_t *place_records, mf_pileup_t *pileup, uint8_t *consensus,
+              mf_pileup_record_t *pileup_records, mf_indel_t *indels, mf_align_record_t *align_records, mf_pileup_t *ins_pile, uint8_t *gapped,
+              uint64_t *gapped_starts, mf_gapped_record_t *gapped_records, uint64_t *unplaced, uint64_t *kept, uint64_t *total);
 
 /* Options that select which kernels a filter pass runs (process-wide; every variant gives the same bits and is parity-tested):
  *   pass=default|split|serial   adapt=0|1   finish_streams=0|1|2   screen_streams=1|2   split_pipe=0|1   exact_co=0|1

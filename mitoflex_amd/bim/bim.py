@@ -138,7 +138,8 @@ def estimate_insert_sizes_device(fasta_file: str, fq1: str, fq2: str, kmer: int 
 def kmer_bait_map(threads: int, fasta_file: str, basedir: str, prefix: str,
                   fastq1: str, fastq2: Optional[str], quality: int = 30,
                   kmer: int = 31, threshold: int = 1, devices: int = 1, anchors: str = "host",
-                  max_permille: Optional[int] = None, keep: Optional[int] = None, band: Optional[int] = None) -> Tuple[str, str, Optional[str]]:
+                  max_permille: Optional[int] = None, keep: Optional[int] = None, band: Optional[int] = None,
+                  gapped: bool = False) -> Tuple[str, str, Optional[str]]:
     """Drop-in for `bwa_map`: returns (stats, fq1, fq2).  `stats` stands where the BAM path was and is what `cal_insert`
     takes; `threads` and `quality` are accepted for signature compatibility and ignored.  anchors: "host" estimates the insert
     sizes in Python from the first anchor of each mate of a sample of the kept pairs; "device" places every kept mate on the GPU
@@ -149,8 +150,12 @@ def kmer_bait_map(threads: int, fasta_file: str, basedir: str, prefix: str,
     pair rule -- the reads of a diverged copy (a NUMT, a contaminant) do not reach the assembler or the next generation's bait.
     band: when given with keep (0 .. 31, below kmer), the placed mates are aligned inside that band before the cut
     (mitofilter.filter_fastq_files_aligned): a mate with a true indel against the bait costs its indel's bases, not the mismatches
-    behind it, and is kept under a tight cut.  None keeps today's calls."""
+    behind it, and is kept under a tight cut.  None keeps today's calls.
+    gapped: with band, the aligning call is the gapped one (mitofilter.filter_fastq_files_aligned(gapped=True)); the files it writes are
+    the same.  Without band it is a ValueError."""
     from mitoflex_amd import mitofilter as mf
+    if gapped and band is None:
+        raise ValueError("gapped needs a band: the gapped consensus comes from the banded alignment")
     if anchors not in ("host", "device"):
         raise ValueError('anchors is "host" or "device"')
     if max_permille is not None and not 0 <= int(max_permille) <= 1000:
@@ -169,7 +174,7 @@ def kmer_bait_map(threads: int, fasta_file: str, basedir: str, prefix: str,
                                            max_permille=1000 if max_permille is None else int(max_permille), keep=keep)
         else:
             mf.filter_fastq_files_aligned(ks, fastq1, fastq2, fq1, fq2, int(band), threshold, mf.PAIR_EITHER, n_devices=devices, pileup=False,
-                                          max_permille=1000 if max_permille is None else int(max_permille), keep=keep)
+                                          max_permille=1000 if max_permille is None else int(max_permille), keep=keep, gapped=bool(gapped))
     finally:
         ks.close()
     stats = path.join(basedir, prefix + ".bait.stats")
@@ -188,7 +193,7 @@ def _check_band(band: Optional[int], kmer: int):
 
 
 def consensus_bait(fasta_file: str, fq1: str, fq2: Optional[str], out_fasta: str, kmer: int = 31, min_depth: int = 3,
-                   max_permille: Optional[int] = None, band: Optional[int] = None):
+                   max_permille: Optional[int] = None, band: Optional[int] = None, gapped: bool = False):
     """A polished bait for the next generation: the reads of (fq1, fq2) -- the kept reads of a bait step -- are placed on the bait
     `fasta_file` and piled up on the device (mitofilter.filter_fastq_files_pileup), and the consensus is written to `out_fasta` under the
     bait's record names: the reads' letter where at least `min_depth` bases agree on one, N where the most is tied, the bait's own
@@ -200,8 +205,13 @@ def consensus_bait(fasta_file: str, fq1: str, fq2: Optional[str], out_fasta: str
     band: when given (0 .. 31, below kmer), every placed read is aligned inside that band first (mitofilter.filter_fastq_files_aligned;
     the cut is max_permille edits per thousand alignment columns, 1000 when not given) and its bases pile where the alignment puts
     them: the bases behind an indel no longer pile up as false mismatches.  The consensus still calls substitutions only.  None keeps
-    today's calls."""
+    today's calls.
+    gapped: with band, the GAPPED consensus is written instead (include/mitofilter.h, gapped consensus): a position that more than half
+    of its covering reads delete is left out, the bases that more than half of them insert behind a position are written behind it, and
+    the polished bait has the sample's length and coordinates.  Without band it is a ValueError."""
     from mitoflex_amd import mitofilter as mf
+    if gapped and band is None:
+        raise ValueError("gapped needs a band: the gapped consensus comes from the banded alignment")
     if min_depth < 1:
         raise ValueError("min_depth is at least 1")
     if max_permille is not None and not 0 <= int(max_permille) <= 1000:
@@ -218,8 +228,10 @@ def consensus_bait(fasta_file: str, fq1: str, fq2: Optional[str], out_fasta: str
             out1, out2 = path.join(tmp, "k.1.fq"), path.join(tmp, "k.2.fq") if fq2 is not None else None
             if band is not None:
                 v = mf.filter_fastq_files_aligned(ks, fq1, fq2, out1, out2, int(band), 1, mf.PAIR_EITHER, min_depth=min_depth,
-                                                  max_permille=1000 if max_permille is None else int(max_permille))
+                                                  max_permille=1000 if max_permille is None else int(max_permille), gapped=bool(gapped))
                 consensus, records = v.consensus, v.pileup_records
+                if gapped:
+                    consensus, starts = v.gapped, v.gapped_starts
             elif max_permille is None:
                 _, _, _, consensus, records, _ = mf.filter_fastq_files_pileup(ks, fq1, fq2, out1, out2, 1, mf.PAIR_EITHER, min_depth=min_depth)
             else:

@@ -41,7 +41,10 @@
 // (nucleotide baits; alone or with the placement, pile-up or score reports; default passing) lets that cut decide what is WRITTEN too:
 // `accepted` takes the pass bit from every mate that is placed and rejected before the pair rule looks at it, `placed` also from every
 // passing mate that is not placed; it makes the call a verifying one by itself, cutting at 1000 unless --max-mismatch is given, and the
-// count on stdout is what was written (include/mitofilter.h, the keep rule; the reports do not depend on it).  It has no CPU fallback: without the library or a GPU it exits non-zero, which shell_call turns into a RuntimeError
+// count on stdout is what was written (include/mitofilter.h, the keep rule; the reports do not depend on it).  With --band W,
+// --gapped-consensus writes the consensus that calls deletions and insertions too, as FASTA under the bait's record names, and --insertions
+// the letters of the inserted bases (name, 1-based position, offset inside the insertion behind it, base depth, A, C, G, T; include/mitofilter.h,
+// gapped consensus); without either no call changes.  It has no CPU fallback: without the library or a GPU it exits non-zero, which shell_call turns into a RuntimeError
 // (helper.py:82-86).
 #include "../../include/mitofilter.h"
 #include "mf_coldtrace.h"
@@ -455,7 +458,7 @@ static std::string exe_dir()
 // what the command line asks for (checked: one kind of report at most)
 struct BaitArgs {
     std::string bait, fq1, fq2, out1, out2, pair = "either", libpath, report, group_report, group_sep, depth_report, depth_profile, place_report, base_depth_file, pileup_file, consensus_file,
-                variants_file, score_report, indels_file;
+                variants_file, score_report, indels_file, gapped_file, insertions_file;
     unsigned min_depth = 1, thr = 1, max_permille = 1000, band = 0;
     bool aligned = false;                      // --band: the placed reads are aligned inside the band before they are scored and cut
     int keep = MF_KEEP_PASSING;                // --write: which mates the verifying call writes
@@ -479,6 +482,8 @@ struct BaitResult {
     std::vector<mf_score_record_t> score_recs;
     std::vector<mf_align_record_t> align_recs;          // with --band, in place of score_recs
     std::vector<mf_indel_t> indels;
+    std::vector<mf_pileup_t> ins_pile;          // with --gapped-consensus or --insertions: 2 * band entries a position
+    std::vector<uint8_t> gapped; std::vector<uint64_t> gapped_starts;
 };
 
 // 0, or the exit code of a command line that cannot be run
@@ -524,6 +529,8 @@ static int parse_bait_args(int argc, char **argv, BaitArgs &A)
             A.band = (unsigned)x; have_band = true;
         }
         else if (o == "--indels") A.indels_file = need("--indels");
+        else if (o == "--gapped-consensus") A.gapped_file = need("--gapped-consensus");
+        else if (o == "--insertions") A.insertions_file = need("--insertions");
         else if (o == "--write") {
             const std::string v = need("--write");
             if (v == "passing") A.keep = MF_KEEP_PASSING; else if (v == "accepted") A.keep = MF_KEEP_ACCEPTED; else if (v == "placed") A.keep = MF_KEEP_PLACED;
@@ -558,7 +565,7 @@ static int parse_bait_args(int argc, char **argv, BaitArgs &A)
               "       [--report FILE | --group-report FILE [--group-field N] [--group-sep C] | --depth-report FILE [--depth-profile FILE]\n"
               "        | --place-report FILE [--base-depth FILE] | [--pileup FILE] [--consensus FILE] [--variants FILE] [--min-depth N]]\n"
               "       [--score-report FILE] [--max-mismatch PERMILLE]   (with or without the placement or the pile-up reports)\n"
-              "       [--band W [--indels FILE]]   (wherever --max-mismatch may go: the placed reads are aligned inside 2 W + 1 diagonals, indels cost one edit a base)\n"
+              "       [--band W [--indels FILE] [--gapped-consensus FILE] [--insertions FILE]]   (wherever --max-mismatch may go: the placed reads are aligned inside 2 W + 1 diagonals, indels cost one edit a base)\n"
               "       [--write passing|accepted|placed]   (which mates are written: all that pass, not those the cut rejects, only placed and accepted ones)\n"
               "       fastfilter bait --protein --bait PROTEINS.fa [--code 5] [-k 9] ...   (six-frame peptide k-mers)\n", stderr);
         return 1;
@@ -577,13 +584,15 @@ static int parse_bait_args(int argc, char **argv, BaitArgs &A)
         fprintf(stderr, "error: --pileup / --consensus / --variants need a nucleotide bait and cannot be combined with --report, --group-report, --depth-report, --depth-profile, --place-report, --base-depth or --protein\n");
         return 1;
     }
-    if (have_min_depth && !piled) { fprintf(stderr, "error: --min-depth needs --pileup, --consensus or --variants\n"); return 1; }
+    const bool gapped = !A.gapped_file.empty() || !A.insertions_file.empty();
+    if (gapped && !have_band) { fprintf(stderr, "error: --gapped-consensus and --insertions need --band\n"); return 1; }
+    if (have_min_depth && !piled && A.gapped_file.empty()) { fprintf(stderr, "error: --min-depth needs --pileup, --consensus or --variants\n"); return 1; }
     const bool keeping = A.keep != MF_KEEP_PASSING;
     if (have_max_mismatch && !placed && !piled && A.score_report.empty() && !keeping) {
         fprintf(stderr, "error: --max-mismatch needs --place-report, --base-depth, --pileup, --consensus, --variants, --score-report or --write accepted|placed\n");
         return 1;
     }
-    if (have_band && !placed && !piled && A.score_report.empty() && !keeping && A.indels_file.empty()) {
+    if (have_band && !placed && !piled && A.score_report.empty() && !keeping && A.indels_file.empty() && !gapped) {
         fprintf(stderr, "error: --band needs --place-report, --base-depth, --pileup, --consensus, --variants, --score-report, --indels or --write accepted|placed\n");
         return 1;
     }
@@ -684,12 +693,20 @@ static int bait_run(const BaitArgs &A, BaitResult &R, mf_kmerset **ks_out, declt
         const size_t positions = rc == MF_OK ? (size_t)std::max<uint64_t>(R.starts.back(), 1) : 1, n_rec = std::max<size_t>(R.names.size(), 1);
         if (A.verified) {          // the placed reads scored and cut; then what the family asks for, from the accepted ones
             SYM(mf_kmerset_bait_letters) SYM(mf_filter_fastq_files_verified_keep)
-            const bool with_depth = A.placed || !A.indels_file.empty();          // (the indel table is written beside the base depth)
+            const bool with_depth = A.placed || !A.indels_file.empty() || !A.insertions_file.empty();          // (the indel tables are written beside the base depth)
             R.score_recs.assign(n_rec, mf_score_record_t{});
             if (A.piled) { R.pile.assign(positions, mf_pileup_t{}); R.consensus.assign(positions, 0); R.letters.assign(positions, 0); }
             if (with_depth) { R.profile.assign(positions, 0); R.place_recs.assign(n_rec, mf_place_record_t{}); }
             if (rc == MF_OK && A.piled) rc = p_mf_kmerset_bait_letters(ks, R.letters.data(), R.letters.size(), nullptr);
-            if (rc == MF_OK && A.aligned) {          // the same behind the banded alignment
+            if (rc == MF_OK && A.aligned && (!A.gapped_file.empty() || !A.insertions_file.empty())) {          // ... and with the gapped consensus
+                SYM(mf_filter_fastq_files_gapped)
+                const size_t span = 2 * (size_t)A.band;
+                R.align_recs.assign(n_rec, mf_align_record_t{}); R.indels.assign(positions, mf_indel_t{});
+                R.ins_pile.assign(std::max<size_t>(positions * span, 1), mf_pileup_t{}); R.gapped.assign(positions * (1 + span), 0); R.gapped_starts.assign(n_rec + 1, 0);
+                rc = files(p_mf_filter_fastq_files_gapped, A.min_depth, A.max_permille, A.keep, A.band, with_depth ? R.profile.data() : nullptr, with_depth ? R.place_recs.data() : nullptr,
+                           A.piled ? R.pile.data() : nullptr, A.piled ? R.consensus.data() : nullptr, (mf_pileup_record_t *)nullptr, R.indels.data(), R.align_recs.data(),
+                           span ? R.ins_pile.data() : nullptr, R.gapped.data(), R.gapped_starts.data(), (mf_gapped_record_t *)nullptr, R.unplaced);
+            } else if (rc == MF_OK && A.aligned) {          // the same behind the banded alignment
                 SYM(mf_filter_fastq_files_aligned)
                 R.align_recs.assign(n_rec, mf_align_record_t{}); R.indels.assign(positions, mf_indel_t{});
                 rc = files(p_mf_filter_fastq_files_aligned, A.min_depth, A.max_permille, A.keep, A.band, with_depth ? R.profile.data() : nullptr, with_depth ? R.place_recs.data() : nullptr,
@@ -754,7 +771,9 @@ static bool write_reports(const BaitArgs &A, const BaitResult &R)
         && write_file(A.variants_file, "variants", [&](FILE *f) { return write_variants(f, R.names, R.starts, R.letters.data(), R.pile.data(), R.consensus.data()); })
         && write_file(A.score_report, "score report", [&](FILE *f) { return A.aligned ? write_align_report(f, R.names, R.starts, R.align_recs.data())
                                                                                       : write_score_report(f, R.names, R.starts, R.score_recs.data()); })
-        && write_file(A.indels_file, "indel table", [&](FILE *f) { return write_indels(f, R.names, R.starts, R.profile.data(), R.indels.data()); });
+        && write_file(A.indels_file, "indel table", [&](FILE *f) { return write_indels(f, R.names, R.starts, R.profile.data(), R.indels.data()); })
+        && write_file(A.gapped_file, "gapped consensus", [&](FILE *f) { return write_gapped_consensus(f, R.names, R.gapped_starts.data(), R.gapped.data()); })
+        && write_file(A.insertions_file, "insertion table", [&](FILE *f) { return write_insertions(f, R.names, R.starts, R.profile.data(), R.ins_pile.data(), 2 * A.band); });
 }
 
 static int bait_main(int argc, char **argv)

@@ -20,7 +20,9 @@
 //                    counts    lanes take the read bases 64 at a time: compared and mismatches of the diagonal steps, one reduction.
 //                  Lane 0 then does what place_kernel's lane 0 does, with the alignment's coordinates and the cut over edits; for an
 //                  accepted read the wave walks the base words once more (align_adds): the pile-up of the diagonal steps, the deleted
-//                  positions, the insertion runs.
+//                  positions, the insertion runs.  The GAPPED instantiations (the gapped consensus, include/mitofilter.h) also add the
+//                  letter of every inserted base into the insertion pile, at its offset inside its run (align_run_offset, mf_align.h);
+//                  the plain ones take an empty argument more and are otherwise the code they were.
 // Work memory: align_work_words(max_len) words a wave, as many waves as the launch has: bounded whatever the number of reads.
 #include "mf_align_launch.h"
 #include "mf_vote_dev.h"
@@ -115,8 +117,12 @@ __device__ __forceinline__ AlignResult align_read(const ReadsView &R, uint64_t b
 
 // What an accepted read adds per position, lane l taking bases l, l + 64, ..: the base of a diagonal step into pile (optional), the
 // positions its row deletes into indel[.][0], an inserted base into indel[.][2] and, where it begins a run, indel[.][1].
+// GAPPED: the t-th base of an insertion run also into ins_pile[(position) * span + t][letter], span = 2 W; t < span holds the store
+// inside the position's own entries whatever the walk counted.
+template <bool GAPPED>
 __device__ __forceinline__ void align_adds(const ReadsView &R, uint64_t b0, bool hasn, uint64_t L, uint32_t strand, uint64_t s0, int64_t len,
-                                           const unsigned long long *ent, unsigned long long *__restrict__ pile, unsigned long long *__restrict__ indel, int lane)
+                                           const unsigned long long *ent, unsigned long long *__restrict__ pile, unsigned long long *__restrict__ indel,
+                                           unsigned long long *__restrict__ ins_pile, uint32_t span, int lane)
 {
     for (uint64_t b = (uint64_t)lane; b < L; b += 64) {
         const unsigned long long e = ent[b];
@@ -135,6 +141,11 @@ __device__ __forceinline__ void align_adds(const ReadsView &R, uint64_t b0, bool
             atomicAdd(&indel[ALIGN_INDEL * (s0 + (uint64_t)p) + 2], 1ull);
             // the base before it is of the same run when it was inserted too and its row deleted nothing
             if (!(b > 0 && (ent[b - 1] >> 32) == 1ull)) atomicAdd(&indel[ALIGN_INDEL * (s0 + (uint64_t)p) + 1], 1ull);
+            if (GAPPED) {
+                const uint32_t t = align_run_offset(ent, b, span);
+                const uint32_t x = oriented_base(R, b0, hasn, L, strand, b);
+                if (t < span && x < ALIGN_X_NONE) atomicAdd(&ins_pile[4 * ((s0 + (uint64_t)p) * span + t) + x], 1ull);
+            }
         }
     }
 }
@@ -146,11 +157,15 @@ struct AlignArgs {
     unsigned long long *work; uint64_t max_len, dir_words, work_words;
 };
 
-template <int KW>
+// What the gapped launch takes beside the plain one (nothing otherwise: the plain instantiations take no argument they would read).
+template <bool GAPPED> struct GapArgs {};
+template <> struct GapArgs<true> { unsigned long long *__restrict__ ins_pile; };
+
+template <int KW, bool GAPPED>
 __global__ void __launch_bounds__(ASSIGN_BLOCK)
 align_kernel(ReadsView R, KmerSetView S, const Anchor *__restrict__ anchor, const uint64_t *__restrict__ rec_start, const uint32_t *__restrict__ list,
              const unsigned long long *__restrict__ n_list_p, uint32_t n_rec, PlaceOut *__restrict__ place, unsigned long long *__restrict__ diff,
-             unsigned long long *__restrict__ counts, unsigned long long *__restrict__ pile, AlignArgs A)
+             unsigned long long *__restrict__ counts, unsigned long long *__restrict__ pile, AlignArgs A, GapArgs<GAPPED> G)
 {
     __shared__ uint32_t s_hist[HIST_MAX];
     // forward, reverse, over_begin, over_end of every record; not placed; behind them rejected and the 32 bins of every record
@@ -217,7 +232,11 @@ align_kernel(ReadsView R, KmerSetView S, const Anchor *__restrict__ anchor, cons
             if (place) place[r] = out;
             if (A.keep_bits && keep_clears(placed, accept, A.keep)) atomicAnd(&A.keep_bits[r >> 5], ~(1u << (r & 31u)));
         }
-        if (placed && accept) align_adds(R, src.b0, src.hasn, L, rs & 1u, s0, len, ent, pile, A.indel, lane);
+        if (placed && accept) {
+            unsigned long long *ins_pile = nullptr;
+            if constexpr (GAPPED) ins_pile = G.ins_pile;
+            align_adds<GAPPED>(R, src.b0, src.hasn, L, rs & 1u, s0, len, ent, pile, A.indel, ins_pile, 2u * (uint32_t)A.band, lane);
+        }
     }
     if (lane == 0 && sum_any) flush();
     cnt.hist_end(lane);
@@ -245,8 +264,11 @@ hipError_t launch_align(const ReadsView &R, const KmerSetView &S, const Anchor *
     const uint64_t n = std::max<uint64_t>(P.max_len, 1);
     const AlignArgs A{ScoreBait{P.bait_words, P.bait_words_last, P.bait_valid, P.bait_valid_last}, P.max_permille, (int)P.band, P.align, P.sums, P.indel,
                       P.keep_bits, P.keep, P.work, P.max_len, 64 * ((n + 31) / 32), align_work_words(P.max_len)};
-    if (S.kw == 1) hipLaunchKernelGGL(align_kernel<1>, dim3(grid), dim3(ASSIGN_BLOCK), 0, st, R, S, anchor, rec_start, list, n_list, n_rec, place, diff, counts, pile, A);
-    else hipLaunchKernelGGL(align_kernel<2>, dim3(grid), dim3(ASSIGN_BLOCK), 0, st, R, S, anchor, rec_start, list, n_list, n_rec, place, diff, counts, pile, A);
+    if (P.ins_pile && P.band) {          // (band 0: the table has no entry)
+        if (S.kw == 1) hipLaunchKernelGGL((align_kernel<1, true>), dim3(grid), dim3(ASSIGN_BLOCK), 0, st, R, S, anchor, rec_start, list, n_list, n_rec, place, diff, counts, pile, A, GapArgs<true>{P.ins_pile});
+        else hipLaunchKernelGGL((align_kernel<2, true>), dim3(grid), dim3(ASSIGN_BLOCK), 0, st, R, S, anchor, rec_start, list, n_list, n_rec, place, diff, counts, pile, A, GapArgs<true>{P.ins_pile});
+    } else if (S.kw == 1) hipLaunchKernelGGL((align_kernel<1, false>), dim3(grid), dim3(ASSIGN_BLOCK), 0, st, R, S, anchor, rec_start, list, n_list, n_rec, place, diff, counts, pile, A, GapArgs<false>{});
+    else hipLaunchKernelGGL((align_kernel<2, false>), dim3(grid), dim3(ASSIGN_BLOCK), 0, st, R, S, anchor, rec_start, list, n_list, n_rec, place, diff, counts, pile, A, GapArgs<false>{});
     return hipGetLastError();
 }
 

@@ -64,4 +64,13 @@ struct PileOut { uint32_t a, c, g, t; };                 // mf_pileup_t
 hipError_t launch_pileup_call(const unsigned long long *pile, const BaitView &B, const uint64_t *rec_start, uint32_t n_rec, uint32_t min_depth,
                               PileOut *out, uint8_t *consensus, unsigned long long *rec_sums, hipStream_t st);
 
+// The gapped consensus called (include/mitofilter.h, "gapped consensus") from the counters of an aligning placement: diff (total + 1, as
+// launch_place_profile takes them; partial: place_scan_tiles(total) + 1 words, the scan is made here), indel (ALIGN_POSITION_COUNTERS a
+// position), ins_pile (4 * span counters a position; null only when span is 0) and the called consensus bytes.  Per position p: ins_out
+// (optional) = its span entries of ins_pile clamped at PLACE_CLAMP; count[p] = the bytes it emits, 0 .. 1 + span; bytes[p * (1 + span) ..]
+// = those bytes.  rec_sums (optional, zeroed by the caller): length, deleted, insertions, inserted_bases of every record (GAPPED_SUMS).
+hipError_t launch_gapped_call(const unsigned long long *diff, uint64_t total, const unsigned long long *indel, const unsigned long long *ins_pile, uint32_t span,
+                              const uint8_t *consensus, const uint64_t *rec_start, uint32_t n_rec, uint32_t min_depth, unsigned long long *partial,
+                              PileOut *ins_out, uint8_t *count, uint8_t *bytes, unsigned long long *rec_sums, hipStream_t st);
+
 } // namespace mf

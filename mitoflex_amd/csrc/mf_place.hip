@@ -25,9 +25,12 @@
 //                          clamp and the records' covered / base_sum (reduced over the wave where a wave lies inside one record).
 //   pileup_call_kernel     per position, tiled like place_profile_kernel: the four counters clamped, the consensus byte, the records' six
 //                          sums through the same record walk (RecordWalk).
+//   gapped_call_kernel     per position, tiled the same way and behind the same scan: the gapped consensus of an aligning placement --
+//                          the insertion pile clamped, the bytes the position emits and how many, the records' four sums.
 #include "mf_place.h"
 #include "mf_vote_dev.h"
 #include "mf_score.h"
+#include "mf_align.h"          // gapped_call_position
 #include <algorithm>
 
 namespace mf {
@@ -368,6 +371,48 @@ pileup_call_kernel(const unsigned long long *__restrict__ pile, BaitView B, cons
     if (rec_sums) walk.finish();
 }
 
+// The gapped consensus called (include/mitofilter.h, "gapped consensus"), tiled like place_profile_kernel, whose scan of the difference
+// counters it repeats: the call goes by the UNCLAMPED base depth D, position by position (gapped_call_position, mf_align.h, which the
+// CPU model check compiles too).  Per position: the clamped counters into ins_out (optional), the
+// number of emitted bytes into count[p] (0 .. 1 + span) and the bytes into bytes[p * (1 + span) ..]; per record (rec_sums, optional,
+// zeroed): length, deleted, insertions, inserted_bases.
+__global__ void __launch_bounds__(PS_BLOCK)
+gapped_call_kernel(const unsigned long long *__restrict__ diff, uint64_t n, const unsigned long long *__restrict__ partial,
+                   const unsigned long long *__restrict__ indel, const unsigned long long *__restrict__ ins_pile, uint32_t span,
+                   const uint8_t *__restrict__ consensus, const uint64_t *__restrict__ rec_start, uint32_t n_rec, uint32_t min_depth,
+                   PileOut *__restrict__ ins_out, uint8_t *__restrict__ count, uint8_t *__restrict__ bytes, unsigned long long *__restrict__ rec_sums)
+{
+    __shared__ unsigned long long lds[PS_BLOCK / 64];
+    const uint64_t i0 = (uint64_t)blockIdx.x * PS_TILE + (uint64_t)threadIdx.x * PS_ITEMS;
+    unsigned long long v[PS_ITEMS], s = 0;
+#pragma unroll
+    for (uint32_t k = 0; k < PS_ITEMS; k++) { v[k] = i0 + k < n ? diff[i0 + k] : 0; s += v[k]; }
+    unsigned long long run = partial[blockIdx.x] + block_exclusive_u64(s, lds, nullptr);
+    RecordWalk<(int)GAPPED_SUMS> walk(rec_start, rec_sums);          // length, deleted, insertions, inserted_bases
+    if (rec_sums && i0 < n) walk.begin(n_rec, i0);
+    for (uint32_t k = 0; k < PS_ITEMS; k++) {
+        const uint64_t p = i0 + k;
+        run += v[k];
+        if (p >= n) break;
+        const unsigned long long *const ins = span ? ins_pile + 4 * p * (uint64_t)span : nullptr;
+        if (ins_out)
+            for (uint32_t q = 0; q < span; q++) {
+                const unsigned long long c0 = ins[4 * q], c1 = ins[4 * q + 1], c2 = ins[4 * q + 2], c3 = ins[4 * q + 3];
+                ins_out[p * (uint64_t)span + q] = PileOut{c0 < PLACE_CLAMP ? (uint32_t)c0 : PLACE_CLAMP, c1 < PLACE_CLAMP ? (uint32_t)c1 : PLACE_CLAMP,
+                                                          c2 < PLACE_CLAMP ? (uint32_t)c2 : PLACE_CLAMP, c3 < PLACE_CLAMP ? (uint32_t)c3 : PLACE_CLAMP};
+            }
+        bool deleted;
+        const uint32_t m = gapped_call_position(run, span ? indel[ALIGN_POSITION_COUNTERS * p] : 0ull, ins, span, min_depth, consensus[p],
+                                                bytes + p * (uint64_t)(1 + span), deleted);
+        count[p] = (uint8_t)m;
+        if (!rec_sums) continue;
+        walk.next(p);
+        const uint32_t inserted = m - (deleted ? 0u : 1u);
+        walk.v[0] += m; walk.v[1] += deleted; walk.v[2] += inserted != 0; walk.v[3] += inserted;
+    }
+    if (rec_sums) walk.finish();
+}
+
 hipError_t launch_build_anchor(const BaitView &B, const uint64_t *rec_start, uint32_t n_rec, const KmerSetView &S, Anchor *anchor, uint32_t *lo,
                                uint32_t *hi, hipStream_t st)
 {
@@ -446,6 +491,19 @@ hipError_t launch_pileup_call(const unsigned long long *pile, const BaitView &B,
     const uint64_t nb = place_scan_tiles(B.total);
     if (!nb || !n_rec) return hipSuccess;
     hipLaunchKernelGGL(pileup_call_kernel, dim3((unsigned)nb), dim3(PS_BLOCK), 0, st, pile, B, rec_start, n_rec, min_depth, out, consensus, rec_sums);
+    return hipGetLastError();
+}
+
+hipError_t launch_gapped_call(const unsigned long long *diff, uint64_t total, const unsigned long long *indel, const unsigned long long *ins_pile, uint32_t span,
+                              const uint8_t *consensus, const uint64_t *rec_start, uint32_t n_rec, uint32_t min_depth, unsigned long long *partial,
+                              PileOut *ins_out, uint8_t *count, uint8_t *bytes, unsigned long long *rec_sums, hipStream_t st)
+{
+    const uint64_t nb = place_scan_tiles(total);
+    if (!nb || !n_rec) return hipSuccess;
+    hipLaunchKernelGGL(place_scan_reduce_kernel, dim3((unsigned)nb), dim3(PS_BLOCK), 0, st, diff, total, partial);
+    hipLaunchKernelGGL(place_scan_partials_kernel, dim3(1), dim3(PS_BLOCK), 0, st, partial, nb);
+    hipLaunchKernelGGL(gapped_call_kernel, dim3((unsigned)nb), dim3(PS_BLOCK), 0, st, diff, total, partial, indel, ins_pile, span, consensus, rec_start, n_rec,
+                       min_depth, ins_out, count, bytes, rec_sums);
     return hipGetLastError();
 }
 

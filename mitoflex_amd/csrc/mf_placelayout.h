@@ -20,15 +20,20 @@ constexpr uint32_t ALIGN_POSITION_COUNTERS = 3;          // ... and its counters
 // every record (what the kernel gathers with the record counters, SCORE_GATHERED R), then compared and mismatches of every record (2 R).
 // An ALIGNING placement (mf_align; it is a verifying one) keeps the wider sums there -- compared, mismatches, insertions, deletions, gapped
 // of every record (ALIGN_RECORD_SUMS R) -- and a fifth section behind them: del, ins, ins_bases of every position.
+// A GAPPED aligning placement (mf_align_gapped with the insertion pile or the gapped consensus asked for) keeps a sixth section behind
+// the indel counters: the insertion pile, 4 * span words a position (span = 2 * band), [position][run offset][A, C, G, T].
 // Every offset into the array is computed here.
 struct PlaceLayout {
-    size_t n_pile, n_diff, n_cnt, n_rec; bool verify; uint32_t max_permille; bool align; uint32_t band; size_t n_indel;
-    PlaceLayout(uint64_t positions, size_t n_rec_, bool pileup, bool verify_, uint32_t max_permille_, bool align_ = false, uint32_t band_ = 0)
+    size_t n_pile, n_diff, n_cnt, n_rec; bool verify; uint32_t max_permille; bool align; uint32_t band; size_t n_indel, n_ins;
+    PlaceLayout(uint64_t positions, size_t n_rec_, bool pileup, bool verify_, uint32_t max_permille_, bool align_ = false, uint32_t band_ = 0, bool gapped = false)
         : n_pile(pileup ? 4 * (size_t)positions : 0), n_diff((size_t)positions + 1), n_cnt(4 * n_rec_ + 1), n_rec(n_rec_), verify(verify_), max_permille(max_permille_),
-          align(align_), band(band_), n_indel(align_ ? ALIGN_POSITION_COUNTERS * (size_t)positions : 0) {}
+          align(align_), band(band_), n_indel(align_ ? ALIGN_POSITION_COUNTERS * (size_t)positions : 0),
+          n_ins(align_ && gapped ? 4 * (size_t)(2 * band_) * (size_t)positions : 0) {}
     size_t n_sums() const { return align ? ALIGN_RECORD_SUMS : 2; }
     size_t n_score() const { return verify ? ((size_t)SCORE_GATHERED + n_sums()) * n_rec : 0; }
-    size_t words() const { return n_pile + n_diff + n_cnt + n_score() + n_indel; }
+    size_t words() const { return n_pile + n_diff + n_cnt + n_score() + n_indel + n_ins; }
+    uint32_t span() const { return 2 * band; }
+    unsigned long long *ins(unsigned long long *base) const { return n_ins ? cnt(base) + n_cnt + n_score() + n_indel : nullptr; }
     unsigned long long *indel(unsigned long long *base) const { return n_indel ? cnt(base) + n_cnt + n_score() : nullptr; }
     unsigned long long *pile(unsigned long long *base) const { return n_pile ? base : nullptr; }
     unsigned long long *diff(unsigned long long *base) const { return base + n_pile; }
@@ -63,7 +68,11 @@ struct PlaceLayout {
 // "positions" buffer: the called pile-up FIRST, because the call kernel writes it 16 bytes an entry, then the base depth (u32), then the
 // consensus (bytes), then 16 spare bytes behind it.  place: base depth or placement records are asked for; pile: the layout holds a
 // pile-up.  A resident call cuts the sections out of the read set's cached buffers (d_rsum, d_rpos), a file-level call out of two
-// temporaries of its own.  Every offset is computed here.
+// temporaries of its own.  A gapped call (gapped_span >= 0, the span of its insertion pile) has three sections more behind the spare
+// bytes of the positions buffer, the first at a multiple of 16 -- the clamped insertion pile (span entries a position), the number of
+// bytes every position emits, those bytes (1 + span a position) -- and its record sums (GAPPED_SUMS a record) at the end of the sums
+// buffer.  Every offset is computed here.
+constexpr uint32_t GAPPED_SUMS = 4;                      // counters a record of the gapped call: the fields of mf_gapped_record_t
 struct ReportScratch {
     struct Section {
         size_t off = 0, bytes = 0;
@@ -71,19 +80,29 @@ struct ReportScratch {
     };
     Section work, pile_sums;                           // of the sums buffer
     Section pile_out, depth, consensus, spare;         // of the positions buffer
+    Section gap_sums;                                  // of the sums buffer, a gapped call
+    Section ins_out, gap_count, gap_bytes;             // of the positions buffer, a gapped call
     size_t sums_bytes, pos_bytes;
-    ReportScratch(uint64_t positions, size_t n_rec, uint64_t scan_tiles, bool place, bool pile)
+    ReportScratch(uint64_t positions, size_t n_rec, uint64_t scan_tiles, bool place, bool pile, int gapped_span = -1)
     {
         const size_t P = (size_t)std::max<uint64_t>(positions, 1), R = std::max<size_t>(n_rec, 1);
         size_t at = 0;
         auto put = [&at](Section &s, size_t bytes) { s.off = at; s.bytes = bytes; at += bytes; };
         put(work, place ? (2 * n_rec + (size_t)scan_tiles + 1) * 8 : 0);
         put(pile_sums, pile ? PILE_SUMS * R * 8 : 0);
+        put(gap_sums, gapped_span >= 0 ? GAPPED_SUMS * R * 8 : 0);
         sums_bytes = at; at = 0;
         put(pile_out, pile ? P * sizeof(mf_pileup_t) : 0);
         put(depth, place ? P * 4 : 0);
         put(consensus, pile ? P : 0);
         put(spare, pile ? 16 : 0);
+        if (gapped_span >= 0) {
+            const size_t span = (size_t)gapped_span;
+            at = (at + 15) / 16 * 16;
+            put(ins_out, P * span * sizeof(mf_pileup_t));
+            put(gap_count, P);
+            put(gap_bytes, P * (1 + span));
+        }
         pos_bytes = at;
     }
 };

@@ -387,6 +387,7 @@ static int pileup_tables(mf_kmerset *ks, int device, DevTables *T)
 }
 
 static int pile_nomem(size_t words) { (void)hipGetLastError(); return fail(MF_E_NOMEM, "the pile-up counters need %llu bytes on the device", (unsigned long long)(words * 8)); }
+static int gap_nomem(size_t words) { (void)hipGetLastError(); return fail(MF_E_NOMEM, "the pile-up counters and the insertion pile need %llu bytes on the device", (unsigned long long)(words * 8)); }
 
 // Everything a call of the placement family is asked for: mf_place, mf_pileup, mf_verify and their file-level calls are each one of
 // these and one call of a driver below.  family: the name the messages use.  with_pileup: the layout holds pile-up counters.  A family
@@ -403,6 +404,11 @@ struct PlaceRequest {
     // an aligning family (a verifying one): the band, and what it gives in place of the scores
     bool align = false; uint32_t band = 0;
     mf_align_t *align_out = nullptr; mf_indel_t *indels = nullptr; mf_align_record_t *align_records = nullptr;
+    // a gapped aligning family: the insertion pile (positions * 2 * band entries), the gapped consensus (room for positions * (1 + 2 * band)
+    // bytes), its R + 1 record offsets and its record summaries.  All null: the aligning family as it was.
+    mf_pileup_t *ins_pile = nullptr; uint8_t *gapped = nullptr; uint64_t *gapped_starts = nullptr; mf_gapped_record_t *gapped_records = nullptr;
+    bool gap() const { return align && (ins_pile || gapped || gapped_starts || gapped_records); }
+    int (*nomem() const)(size_t) { return gap() ? gap_nomem : with_pileup ? pile_nomem : nullptr; }
     // the one argument check of the family (a resident call checks its read set behind it)
     int check(const mf_kmerset *ks) const
     {
@@ -415,10 +421,11 @@ struct PlaceRequest {
         if (align && !align_band_ok(band, ks->k)) return fail(MF_E_ARG, "band is %u: the band stays below k = %d", band, ks->k);
         return MF_OK;
     }
-    PlaceLayout layout(const mf_kmerset *ks) const { return PlaceLayout(ks->positions(), ks->rec_len().size(), with_pileup, verify, max_permille, align, band); }
+    PlaceLayout layout(const mf_kmerset *ks) const { return PlaceLayout(ks->positions(), ks->rec_len().size(), with_pileup, verify, max_permille, align, band, gap()); }
     ReportScratch scratch(const mf_kmerset *ks) const
     {
-        return ReportScratch(ks->positions(), ks->rec_len().size(), place_scan_tiles(ks->positions()), base_depth || place_records, with_pileup);
+        return ReportScratch(ks->positions(), ks->rec_len().size(), place_scan_tiles(ks->positions()), base_depth || place_records || gap(), with_pileup,
+                             gap() ? (int)(2 * band) : -1);
     }
 };
 
@@ -469,7 +476,7 @@ static int place_after_filter(mf_kmerset *ks, mf_reads *r, const PlaceLayout &L,
         if (e == hipErrorOutOfMemory) { (void)hipGetLastError(); return fail(MF_E_NOMEM, "the alignment of reads of up to %llu bases needs %llu bytes on the device", (unsigned long long)max_len, (unsigned long long)bytes); }
         HIPCHK(e);
         const PlaceAlign pa{T->pile_words, T->pile_words_n - 1, T->pile_valid, T->pile_valid_n - 1, L.max_permille, L.band, align, L.score_sums(t), L.indel(t),
-                            keep_dev, keep, r->d_awork, max_len};
+                            keep_dev, keep, r->d_awork, max_len, L.ins(t)};
         HIPCHK(launch_align(r->v, T->view, T->anchor, T->place_starts, r->d_alist, r->d_acnt, (uint32_t)ks->rec_len().size(), place, L.diff(t), L.cnt(t), L.pile(t),
                             pa, ctx->n_cu, st));
         HIPCHK(hipMemcpyAsync(&v, r->d_acnt, 8, hipMemcpyDeviceToHost, st));
@@ -512,6 +519,7 @@ static int placement_report(mf_kmerset *ks, int device, hipStream_t st, const Pl
     static_assert(sizeof(mf_pileup_t) == 16 && sizeof(PileOut) == 16 && sizeof(mf_pileup_record_t) == 8 * PILE_SUMS, "pile-up records");
     static_assert(sizeof(mf_score_t) == 8 && sizeof(ScoreOut) == 8 && sizeof(mf_score_record_t) == 8 * (4 + MF_SCORE_BINS) && MF_SCORE_BINS == SCORE_BINS, "score records");
     static_assert(sizeof(mf_align_t) == 24 && sizeof(AlignOut) == 24 && sizeof(mf_indel_t) == 12 && sizeof(mf_align_record_t) == 8 * (7 + MF_SCORE_BINS), "align records");
+    static_assert(sizeof(mf_gapped_record_t) == 8 * GAPPED_SUMS, "gapped records");
     static_assert(ALIGN_SUMS == ALIGN_RECORD_SUMS && ALIGN_INDEL == ALIGN_POSITION_COUNTERS, "the kernel's counters are the layout's");
     DevTables *T; int rc = placement_tables(ks, device, L, &T); if (rc) return rc;
     const uint64_t total = ks->positions(), n_rec = L.n_rec;
@@ -524,14 +532,32 @@ static int placement_report(mf_kmerset *ks, int device, hipStream_t st, const Pl
         if (q.base_depth && total) HIPCHK(hipMemcpyAsync(q.base_depth, depth, total * 4, hipMemcpyDeviceToHost, st));
         if (q.place_records && n_rec) HIPCHK(hipMemcpyAsync(h_sum.data(), work, 2 * n_rec * 8, hipMemcpyDeviceToHost, st));
     }
-    if (q.with_pileup && (q.pileup || q.consensus || q.pileup_records)) {
+    const bool gap = q.gap();          // (the gapped call reads the consensus bytes on the device, asked for or not)
+    std::vector<uint8_t> h_gcount, h_gbytes; std::vector<unsigned long long> h_gsum;
+    if (q.with_pileup && (q.pileup || q.consensus || q.pileup_records || gap)) {
         unsigned long long *psums = S.pile_sums.in<unsigned long long>(sums); PileOut *out = S.pile_out.in<PileOut>(pos); uint8_t *cons = S.consensus.in<uint8_t>(pos);
         if (q.pileup_records && n_rec) HIPCHK(hipMemsetAsync(psums, 0, PILE_SUMS * n_rec * 8, st));
         HIPCHK(launch_pileup_call(L.pile(t), BaitView{T->pile_words, total, T->pile_runlen}, T->place_starts, (uint32_t)n_rec, q.min_depth,
-                                  q.pileup ? out : nullptr, q.consensus ? cons : nullptr, q.pileup_records ? psums : nullptr, st));
+                                  q.pileup ? out : nullptr, q.consensus || gap ? cons : nullptr, q.pileup_records ? psums : nullptr, st));
         if (q.pileup && total) HIPCHK(hipMemcpyAsync(q.pileup, out, total * sizeof(PileOut), hipMemcpyDeviceToHost, st));
         if (q.consensus && total) HIPCHK(hipMemcpyAsync(q.consensus, cons, total, hipMemcpyDeviceToHost, st));
         if (q.pileup_records && n_rec) HIPCHK(hipMemcpyAsync(q.pileup_records, psums, PILE_SUMS * n_rec * 8, hipMemcpyDeviceToHost, st));
+    }
+    const size_t span = L.span();
+    if (gap) {
+        unsigned long long *work = S.work.in<unsigned long long>(sums), *gsums = S.gap_sums.in<unsigned long long>(sums);
+        PileOut *ins_out = S.ins_out.in<PileOut>(pos); uint8_t *gcount = S.gap_count.in<uint8_t>(pos), *gbytes = S.gap_bytes.in<uint8_t>(pos);
+        const bool call = q.gapped || q.gapped_starts;          // (the record summaries come from the kernel's sums)
+        if (n_rec) HIPCHK(hipMemsetAsync(gsums, 0, GAPPED_SUMS * n_rec * 8, st));
+        HIPCHK(launch_gapped_call(L.diff(t), total, L.indel(t), L.ins(t), (uint32_t)span, S.consensus.in<uint8_t>(pos), T->place_starts, (uint32_t)n_rec, q.min_depth,
+                                  work + 2 * n_rec, q.ins_pile ? ins_out : nullptr, gcount, gbytes, gsums, st));
+        if (q.ins_pile && total && span) HIPCHK(hipMemcpyAsync(q.ins_pile, ins_out, total * span * sizeof(PileOut), hipMemcpyDeviceToHost, st));
+        if (call && total) {
+            h_gcount.resize(total); h_gbytes.resize(total * (1 + span));
+            HIPCHK(hipMemcpyAsync(h_gcount.data(), gcount, total, hipMemcpyDeviceToHost, st));
+            HIPCHK(hipMemcpyAsync(h_gbytes.data(), gbytes, h_gbytes.size(), hipMemcpyDeviceToHost, st));
+        }
+        if (q.gapped_records && n_rec) { h_gsum.resize(GAPPED_SUMS * n_rec); HIPCHK(hipMemcpyAsync(h_gsum.data(), gsums, h_gsum.size() * 8, hipMemcpyDeviceToHost, st)); }
     }
     if (!h_indel.empty()) HIPCHK(hipMemcpyAsync(h_indel.data(), L.indel(t), h_indel.size() * 8, hipMemcpyDeviceToHost, st));
     HIPCHK(hipMemcpyAsync(h_cnt.data(), L.cnt(t), h_cnt.size() * 8, hipMemcpyDeviceToHost, st));
@@ -540,6 +566,21 @@ static int placement_report(mf_kmerset *ks, int device, hipStream_t st, const Pl
         const auto clamp = [](unsigned long long c) { return c < PLACE_CLAMP ? (uint32_t)c : PLACE_CLAMP; };
         q.indels[p] = mf_indel_t{clamp(h_indel[ALIGN_INDEL * p]), clamp(h_indel[ALIGN_INDEL * p + 1]), clamp(h_indel[ALIGN_INDEL * p + 2])};
     }
+    if (gap && (q.gapped || q.gapped_starts)) {          // the positions' bytes, concatenated record by record
+        const std::vector<uint64_t> starts = record_starts(ks);
+        uint64_t at = 0;
+        for (uint64_t j = 0; j < n_rec; j++) {
+            if (q.gapped_starts) q.gapped_starts[j] = at;
+            for (uint64_t p = starts[j]; p < starts[j + 1]; p++) {
+                const size_t m = std::min<size_t>(h_gcount[p], 1 + span);
+                if (q.gapped) memcpy(q.gapped + at, h_gbytes.data() + p * (1 + span), m);
+                at += m;
+            }
+        }
+        if (q.gapped_starts) q.gapped_starts[n_rec] = at;
+    }
+    for (size_t j = 0; j < h_gsum.size() / GAPPED_SUMS; j++)
+        q.gapped_records[j] = mf_gapped_record_t{h_gsum[GAPPED_SUMS * j], h_gsum[GAPPED_SUMS * j + 1], h_gsum[GAPPED_SUMS * j + 2], h_gsum[GAPPED_SUMS * j + 3]};
     if (q.align_records) L.align_records(h_cnt.data(), q.align_records);
     if (q.place_records)
         for (uint64_t j = 0; j < n_rec; j++)
@@ -565,10 +606,12 @@ static int placement_resident(const mf_kmerset *ks_, const mf_reads *reads_, uin
     const PlaceLayout L = q.layout(ks);
     const ReportScratch S = q.scratch(ks);
     const hipError_t e = dev_reserve(r->d_rtot, r->cap_rtot, L.words() * 8, false);
-    if (e == hipErrorOutOfMemory && q.with_pileup) return pile_nomem(L.words());
+    if (e == hipErrorOutOfMemory && q.nomem()) return q.nomem()(L.words());
     HIPCHK(e);
     HIPCHK(dev_reserve(r->d_rsum, r->cap_rsum, S.sums_bytes, false));
-    HIPCHK(dev_reserve(r->d_rpos, r->cap_rpos, S.pos_bytes, false));
+    const hipError_t e2 = dev_reserve(r->d_rpos, r->cap_rpos, S.pos_bytes, false);
+    if (e2 == hipErrorOutOfMemory && q.gap()) { (void)hipGetLastError(); return fail(MF_E_NOMEM, "the gapped consensus needs %llu bytes on the device", (unsigned long long)S.pos_bytes); }
+    HIPCHK(e2);
     HIPCHK(hipMemsetAsync(r->d_rtot, 0, L.words() * 8, st));
     PlaceOut *d_place = nullptr; ScoreOut *d_score = nullptr;
     if (q.place_out && n) {
@@ -643,6 +686,18 @@ int mf_align(const mf_kmerset *ks, const mf_reads *reads, uint32_t threshold, in
 {
     const PlaceRequest q{"alignment", true, pileup || consensus || pileup_records, min_depth, max_permille, place_out, nullptr, base_depth,
                          place_records, pileup, consensus, pileup_records, nullptr, unplaced, keep, keep_bits, true, band, align_out, indels, align_records};
+    return placement_resident(ks, reads, threshold, mode, out_bits, stats, q);
+}
+
+int mf_align_gapped(const mf_kmerset *ks, const mf_reads *reads, uint32_t threshold, int mode, uint32_t min_depth, uint32_t max_permille, int keep, uint32_t band,
+                    uint32_t *out_bits, uint32_t *keep_bits, mf_place_t *place_out, mf_align_t *align_out, uint32_t *base_depth, mf_place_record_t *place_records,
+                    mf_pileup_t *pileup, uint8_t *consensus, mf_pileup_record_t *pileup_records, mf_indel_t *indels, mf_align_record_t *align_records,
+                    mf_pileup_t *ins_pile, uint8_t *gapped, uint64_t *gapped_starts, mf_gapped_record_t *gapped_records, uint64_t *unplaced, mf_filter_stats_t *stats)
+{
+    const bool gap = ins_pile || gapped || gapped_starts || gapped_records;
+    const PlaceRequest q{"alignment", true, pileup || consensus || pileup_records || gap, min_depth, max_permille, place_out, nullptr, base_depth,
+                         place_records, pileup, consensus, pileup_records, nullptr, unplaced, keep, keep_bits, true, band, align_out, indels, align_records,
+                         ins_pile, gapped, gapped_starts, gapped_records};
     return placement_resident(ks, reads, threshold, mode, out_bits, stats, q);
 }
 
@@ -747,7 +802,7 @@ struct PlaceTotals : DeviceTotals {
     const PlaceLayout L;
     const int keep;
     std::atomic<uint64_t> mates{0}, passing{0};
-    PlaceTotals(mf_kmerset *ks_, const PlaceRequest &q) : DeviceTotals(ks_, q.with_pileup ? pile_nomem : nullptr), L(q.layout(ks_)), keep(q.keep) {}
+    PlaceTotals(mf_kmerset *ks_, const PlaceRequest &q) : DeviceTotals(ks_, q.nomem()), L(q.layout(ks_)), keep(q.keep) {}
     void restart() override { release(); mates = 0; passing = 0; }
     int tables(int device, DevTables *T) override { return placement_tables(ks, device, L, &T); }
     size_t words(const DevTables *) const override { return L.words(); }
@@ -811,7 +866,11 @@ static int placement_files(mf_kmerset *ks, const char *fq1, const char *fq2, con
     DevScratch tmp;
     unsigned long long *sums = nullptr; uint8_t *pos = nullptr;
     if (S.sums_bytes) HIPCHK(tmp.alloc(sums, S.sums_bytes));
-    if (S.pos_bytes) HIPCHK(tmp.alloc(pos, S.pos_bytes));
+    if (S.pos_bytes) {
+        const hipError_t e = tmp.alloc(pos, S.pos_bytes);
+        if (e == hipErrorOutOfMemory && q.gap()) { (void)hipGetLastError(); return fail(MF_E_NOMEM, "the gapped consensus needs %llu bytes on the device", (unsigned long long)S.pos_bytes); }
+        HIPCHK(e);
+    }
     return placement_report(ks, devices[0], ctx->stream, pt.L, t0, q, S, sums, pos, pt.mates - pt.passing);
 }
 
@@ -889,6 +948,19 @@ int mf_filter_fastq_files_aligned(mf_kmerset *ks, const char *fq1, const char *f
 {
     const PlaceRequest q{"alignment", true, pileup || consensus || pileup_records, min_depth, max_permille, nullptr, nullptr, base_depth,
                          place_records, pileup, consensus, pileup_records, nullptr, unplaced, keep, nullptr, true, band, nullptr, indels, align_records};
+    return placement_files(ks, fq1, fq2, out1, out2, threshold, pair_mode, devices, n_devices, kept, total, q);
+}
+
+int mf_filter_fastq_files_gapped(mf_kmerset *ks, const char *fq1, const char *fq2, const char *out1, const char *out2,
+                                 uint32_t threshold, int pair_mode, const int *devices, int n_devices, uint32_t min_depth, uint32_t max_permille, int keep,
+                                 uint32_t band, uint32_t *base_depth, mf_place_record_t *place_records, mf_pileup_t *pileup, uint8_t *consensus,
+                                 mf_pileup_record_t *pileup_records, mf_indel_t *indels, mf_align_record_t *align_records, mf_pileup_t *ins_pile, uint8_t *gapped,
+                                 uint64_t *gapped_starts, mf_gapped_record_t *gapped_records, uint64_t *unplaced, uint64_t *kept, uint64_t *total)
+{
+    const bool gap = ins_pile || gapped || gapped_starts || gapped_records;
+    const PlaceRequest q{"alignment", true, pileup || consensus || pileup_records || gap, min_depth, max_permille, nullptr, nullptr, base_depth,
+                         place_records, pileup, consensus, pileup_records, nullptr, unplaced, keep, nullptr, true, band, nullptr, indels, align_records,
+                         ins_pile, gapped, gapped_starts, gapped_records};
     return placement_files(ks, fq1, fq2, out1, out2, threshold, pair_mode, devices, n_devices, kept, total, q);
 }
 

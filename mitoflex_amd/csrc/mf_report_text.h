@@ -165,4 +165,26 @@ inline bool write_indels(FILE *f, const Names &names, const Starts &starts, cons
     return written(f);
 }
 
+// --gapped-consensus: FASTA like --consensus, the records cut out of the gapped consensus by its own R + 1 offsets
+inline bool write_gapped_consensus(FILE *f, const Names &names, const uint64_t *gapped_starts, const uint8_t *gapped)
+{
+    return write_consensus(f, names, Starts(gapped_starts, gapped_starts + names.size() + 1), gapped);
+}
+
+// --insertions: name, 1-based position, 0-based offset inside the insertion behind it, base depth, A, C, G, T of every (position, offset)
+// of the insertion pile (span entries a position) with a count that is not zero
+inline bool write_insertions(FILE *f, const Names &names, const Starts &starts, const uint32_t *base_depth, const mf_pileup_t *ins_pile, uint32_t span)
+{
+    if (!f) return false;
+    fputs("name\tpos\toffset\tdepth\tA\tC\tG\tT\n", f);
+    for (size_t i = 0; i < names.size(); i++)
+        for (uint64_t p = starts[i]; p < starts[i + 1]; p++)
+            for (uint32_t q = 0; q < span; q++) {
+                const mf_pileup_t &c = ins_pile[p * span + q];
+                if (c.a || c.c || c.g || c.t)
+                    fprintf(f, "%s\t%llu\t%u\t%u\t%u\t%u\t%u\t%u\n", names[i].c_str(), (ull)(p - starts[i] + 1), q, base_depth[p], c.a, c.c, c.g, c.t);
+            }
+    return written(f);
+}
+
 } // namespace mf_text

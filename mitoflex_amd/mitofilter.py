@@ -56,6 +56,8 @@ ALIGN = np.dtype([("compared", np.uint32), ("mismatches", np.uint32), ("insertio
 INDEL = np.dtype([("del", np.uint32), ("ins", np.uint32), ("ins_bases", np.uint32)])
 ALIGN_RECORD = np.dtype([("accepted", np.uint64), ("rejected", np.uint64), ("compared", np.uint64), ("mismatches", np.uint64),
                          ("insertions", np.uint64), ("deletions", np.uint64), ("gapped", np.uint64), ("hist", np.uint64, (SCORE_BINS,))])
+# the per-record summary of the gapped consensus (mf_gapped_record_t)
+GAPPED_RECORD = np.dtype([("length", np.uint64), ("deleted", np.uint64), ("insertions", np.uint64), ("inserted_bases", np.uint64)])
 INDEL_VARIANT = np.dtype([("record", np.uint32), ("pos", np.uint64), ("depth", np.uint64), ("del", np.uint64), ("ins", np.uint64),
                           ("ins_bases", np.uint64)])
 # a variant position (pileup_variants): pos is 0-based inside the record, ref / alt are letters
@@ -79,6 +81,7 @@ EXPORTS = (
     "mf_verify", "mf_filter_fastq_files_verified",
     "mf_verify_keep", "mf_filter_fastq_files_verified_keep",
     "mf_align", "mf_filter_fastq_files_aligned",
+    "mf_align_gapped", "mf_filter_fastq_files_gapped",
 )
 
 
@@ -207,6 +210,11 @@ def load(path: Optional[str] = None):
     L.mf_filter_fastq_files_aligned.argtypes = [vp, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_uint32, C.c_int,
                                                 C.POINTER(C.c_int), C.c_int, C.c_uint32, C.c_uint32, C.c_int, C.c_uint32, vp, vp, vp, vp, vp, vp,
                                                 vp, vp, u64p, u64p]
+    L.mf_align_gapped.argtypes = [vp, vp, C.c_uint32, C.c_int, C.c_uint32, C.c_uint32, C.c_int, C.c_uint32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
+                                  vp, vp, vp, vp, vp, C.POINTER(FilterStats)]
+    L.mf_filter_fastq_files_gapped.argtypes = [vp, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_uint32, C.c_int,
+                                               C.POINTER(C.c_int), C.c_int, C.c_uint32, C.c_uint32, C.c_int, C.c_uint32, vp, vp, vp, vp, vp, vp,
+                                               vp, vp, vp, vp, vp, vp, u64p, u64p]
     if L.mf_abi_version() != 5:
         raise MitoFilterError("libmitofilter_hip ABI version mismatch")
     _lib = L
@@ -586,8 +594,21 @@ def verify_reads(ks: KmerSet, reads: Reads, threshold: int = 1, mode: int = MODE
 class Aligned(Verified):
     """What an aligning call gives (include/mitofilter.h, banded alignment): Verified's fields with score and score_records None, and
     align ALIGN[n] (align_reads only), indels INDEL[positions], align_records ALIGN_RECORD[R] and keep_bits u32[ceil(n/32)] (align_reads
-    only; the pass bits under KEEP_PASSING)."""
-    __slots__ = ("keep_bits", "align", "indels", "align_records")
+    only; the pass bits under KEEP_PASSING).  A call with gapped=True (include/mitofilter.h, gapped consensus) also gives ins_pile
+    PILEUP[positions, 2 * band], gapped u8[its length], gapped_starts u64[R + 1] and gapped_records GAPPED_RECORD[R]; None otherwise."""
+    __slots__ = ("keep_bits", "align", "indels", "align_records", "ins_pile", "gapped", "gapped_starts", "gapped_records")
+
+
+def _gapped_outputs(ks: KmerSet, band: int):
+    """the four outputs of a gapped call: their pointers in the C order, and what gives them as Aligned names them"""
+    starts = ks.record_starts
+    P, R, span = int(starts[-1]), len(starts) - 1, 2 * int(band)
+    ins = np.zeros((max(P, 1), max(span, 1)), dtype=PILEUP)
+    gapped = np.zeros(max(P * (1 + span), 1), dtype=np.uint8)
+    gstarts = np.zeros(R + 1, dtype=np.uint64)
+    grec = np.zeros(max(R, 1), dtype=GAPPED_RECORD)
+    ptrs = [ins.ctypes.data if span else None, gapped.ctypes.data, gstarts.ctypes.data, grec.ctypes.data]
+    return ptrs, lambda: {"ins_pile": ins[:P, :span], "gapped": gapped[:int(gstarts[-1])], "gapped_starts": gstarts, "gapped_records": grec[:R]}
 
 
 def _check_band(band: int):
@@ -596,21 +617,70 @@ def _check_band(band: int):
 
 
 def align_reads(ks: KmerSet, reads: Reads, band: int = 8, min_depth: int = 1, max_permille: int = 1000, keep: int = KEEP_PASSING,
-                pileup: bool = True, threshold: int = 1, mode: int = MODE_SCREENED) -> Aligned:
+                pileup: bool = True, threshold: int = 1, mode: int = MODE_SCREENED, gapped: bool = False) -> Aligned:
     """One filter pass, then every placed read aligned to its record inside the band of 2 * band + 1 diagonals around its placement and
     cut at max_permille edits per thousand alignment columns; base depth, the records, the keep bits and (pileup=True) the pile-up
     follow the alignment, and indels counts deletions and insertions per bait position (include/mitofilter.h: mf_align).  band = 0 is
-    verify_reads.  -> Aligned with bits, keep_bits, place, align and the shared fields."""
+    verify_reads.  gapped=True: the letters of the inserted bases and the consensus that calls deletions and insertions too
+    (mf_align_gapped).  -> Aligned with bits, keep_bits, place, align and the shared fields."""
     _check_cut(min_depth, max_permille, keep)
     _check_band(band)
     per_read, read_results = _read_outputs(reads, PLACE, ALIGN)
     ptrs, results = _report_outputs(ks, _ALIGN_FIELDS, () if pileup else _PILEUP_FIELDS[:3])
     n = reads.info.n_reads
     keep_bits = np.zeros(max((n + 31) // 32, 1), dtype=np.uint32)
-    _chk(load().mf_align(ks._h, reads._h, threshold, mode, min_depth, max_permille, int(keep), int(band), per_read[0], keep_bits.ctypes.data,
-                         *per_read[1:], *ptrs, None))
+    more = {}
+    if gapped:
+        gptrs, gresults = _gapped_outputs(ks, band)
+        _chk(load().mf_align_gapped(ks._h, reads._h, threshold, mode, min_depth, max_permille, int(keep), int(band), per_read[0],
+                                    keep_bits.ctypes.data, *per_read[1:], *ptrs[:-1], *gptrs, ptrs[-1], None))
+        more = gresults()
+    else:
+        _chk(load().mf_align(ks._h, reads._h, threshold, mode, min_depth, max_permille, int(keep), int(band), per_read[0], keep_bits.ctypes.data,
+                             *per_read[1:], *ptrs, None))
     bits, place, align = read_results()
-    return Aligned(bits=bits, keep_bits=keep_bits[:(n + 31) // 32], place=place, align=align, **results())
+    return Aligned(bits=bits, keep_bits=keep_bits[:(n + 31) // 32], place=place, align=align, **results(), **more)
+
+
+def gapped_consensus(record_starts, base_depth, indels, ins_pile, consensus, min_depth: int = 1):
+    """The call rule of the gapped consensus (include/mitofilter.h) over the downloaded outputs of an aligning call, valid where no
+    counter is clamped: a position is deleted where more than half of its base depth deletes it (and the depth reaches min_depth, the
+    call's), else it keeps its consensus byte; behind it the insertion columns that more than half of the depth carries, up to the first
+    that fewer do, each the letter with strictly the most bases or N.  ins_pile: PILEUP[positions, span].
+    -> (gapped u8, gapped_starts u64[R + 1], gapped_records GAPPED_RECORD[R]).  Needs no device."""
+    if int(min_depth) < 1:
+        raise ValueError("min_depth is at least 1")
+    starts = np.asarray(record_starts, dtype=np.uint64)
+    P, R = int(starts[-1]), len(starts) - 1
+    depth = np.asarray(base_depth)[:P].astype(np.int64)
+    cons = np.asarray(consensus, dtype=np.uint8)[:P]
+    ins = np.asarray(ins_pile)
+    if ins.dtype != PILEUP or ins.ndim != 2:
+        raise ValueError("ins_pile is PILEUP[positions, span]")
+    span = ins.shape[1]
+    ins = ins[:P]
+    dels = np.asarray(indels)[:P]["del"].astype(np.int64) if span else np.zeros(P, np.int64)
+    if not (len(depth) == len(cons) == len(ins) == len(dels) == P):
+        raise ValueError("base_depth, indels, ins_pile and consensus hold one entry per position")
+    counts = np.stack([ins[f].astype(np.int64) for f in ("a", "c", "g", "t")], axis=2) if span else np.zeros((P, 0, 4), np.int64)
+    deep = depth >= int(min_depth)
+    deleted = deep & (2 * dels > depth)
+    carried = deep[:, None] & (2 * counts.sum(axis=2) > depth[:, None])
+    n_cols = np.minimum.accumulate(carried, axis=1).sum(axis=1) if span else np.zeros(P, np.int64)          # up to the first that is not
+    most = counts.max(axis=2) if span else counts.sum(axis=2)
+    alone = (counts == most[:, :, None]).sum(axis=2) == 1
+    letters = np.where(alone, np.frombuffer(b"ACGT", np.uint8)[counts.argmax(axis=2)] if span else 0, ord("N")).astype(np.uint8)
+    out, gstarts, rec = bytearray(), np.zeros(R + 1, np.uint64), np.zeros(R, dtype=GAPPED_RECORD)
+    for j in range(R):
+        gstarts[j] = len(out)
+        for p in range(int(starts[j]), int(starts[j + 1])):
+            if not deleted[p]:
+                out.append(int(cons[p]))
+            out += letters[p, :n_cols[p]].tobytes()
+        lo, hi = int(starts[j]), int(starts[j + 1])
+        rec[j] = (len(out) - int(gstarts[j]), int(deleted[lo:hi].sum()), int((n_cols[lo:hi] > 0).sum()), int(n_cols[lo:hi].sum()))
+    gstarts[R] = len(out)
+    return np.frombuffer(bytes(out), np.uint8), gstarts, rec
 
 
 def indel_variants(record_starts, base_depth, indels, min_depth: int = 1, min_permille: int = 500) -> np.ndarray:
@@ -834,15 +904,21 @@ def filter_fastq_files_verified(ks: KmerSet, fq1: str, fq2: Optional[str], out1:
 def filter_fastq_files_aligned(ks: KmerSet, fq1: str, fq2: Optional[str], out1: str, out2: Optional[str], band: int = 8,
                                threshold: int = 1, pair_mode: int = PAIR_EITHER, devices: Optional[Sequence[int]] = None,
                                n_devices: int = 1, min_depth: int = 1, max_permille: int = 1000, pileup: bool = True,
-                               keep: int = KEEP_PASSING) -> Aligned:
+                               keep: int = KEEP_PASSING, gapped: bool = False) -> Aligned:
     """filter_fastq_files_verified behind the banded alignment (mf_filter_fastq_files_aligned): the cut, the keep rule and the reports
-    are those of align_reads, added over the mates.  -> Aligned with kept, total and the shared fields."""
+    are those of align_reads, added over the mates.  gapped=True: the insertion pile added over the mates and the gapped consensus
+    called from the sums (mf_filter_fastq_files_gapped).  -> Aligned with kept, total and the shared fields."""
     _check_cut(min_depth, max_permille, keep)
     _check_band(band)
     ptrs, results = _report_outputs(ks, _ALIGN_FIELDS, () if pileup else _PILEUP_FIELDS[:3])
-    kept, total = _files_call("mf_filter_fastq_files_aligned", ks, fq1, fq2, out1, out2, threshold, pair_mode, devices, n_devices,
-                              min_depth, max_permille, int(keep), int(band), *ptrs)
-    return Aligned(kept=kept, total=total, **results())
+    if not gapped:
+        kept, total = _files_call("mf_filter_fastq_files_aligned", ks, fq1, fq2, out1, out2, threshold, pair_mode, devices, n_devices,
+                                  min_depth, max_permille, int(keep), int(band), *ptrs)
+        return Aligned(kept=kept, total=total, **results())
+    gptrs, gresults = _gapped_outputs(ks, band)
+    kept, total = _files_call("mf_filter_fastq_files_gapped", ks, fq1, fq2, out1, out2, threshold, pair_mode, devices, n_devices,
+                              min_depth, max_permille, int(keep), int(band), *ptrs[:-1], *gptrs, ptrs[-1])
+    return Aligned(kept=kept, total=total, **results(), **gresults())
 
 
 def set_option(name: str, value) -> None:
