@@ -8,6 +8,7 @@
 // Every cell of the band is reached by its own diagonal, so D(i, c) <= i: only the neighbours outside the band are infinite.
 #pragma once
 #include "mf_score.h"
+#include "mf_call.h"          // gapped_call_position: the gapped consensus' other scalar piece, beside align_run_offset here
 
 namespace mf {
 
@@ -47,30 +48,6 @@ MF_SCORE_HD uint32_t align_run_offset(const unsigned long long *ent, uint64_t b,
     uint32_t t = 0;
     while (t < span && (uint64_t)t < b && (ent[b - 1 - t] >> 32) == 1ull) t++;
     return t;
-}
-
-// The call of the gapped consensus at one position (include/mitofilter.h, "gapped consensus"), from unclamped sums: D the base depth,
-// del the position's deletion counter, ins its 4 * span insertion counters [offset][A, C, G, T] (not read when span is 0), cons its
-// consensus byte.  Writes the emitted bytes to out (room for 1 + span) and returns how many; deleted: the position emits no byte of
-// its own.  Both majorities are strict.
-MF_SCORE_HD uint32_t gapped_call_position(unsigned long long D, unsigned long long del, const unsigned long long *ins, uint32_t span, uint32_t min_depth,
-                                          uint8_t cons, uint8_t *out, bool &deleted)
-{
-    const bool deep = D >= (unsigned long long)min_depth;
-    deleted = span != 0 && deep && 2 * del > D;          // (band 0: nothing is deleted)
-    uint32_t m = 0;
-    if (!deleted) out[m++] = cons;
-    for (uint32_t q = 0; deep && q < span; q++) {          // the columns are emitted up to the first that is not
-        const unsigned long long c0 = ins[4 * q], c1 = ins[4 * q + 1], c2 = ins[4 * q + 2], c3 = ins[4 * q + 3];
-        if (!(2 * (c0 + c1 + c2 + c3) > D)) break;
-        // the letter with strictly the most bases
-        unsigned long long most = c0; uint32_t best = 0; bool tied = false;
-        if (c1 > most) { most = c1; best = 1; tied = false; } else if (c1 == most) tied = true;
-        if (c2 > most) { most = c2; best = 2; tied = false; } else if (c2 == most) tied = true;
-        if (c3 > most) { most = c3; best = 3; tied = false; } else if (c3 == most) tied = true;
-        out[m++] = (uint8_t)(tied ? 'N' : (0x54474341u >> (8 * best)) & 255u);          // "ACGT", letter l in byte l
-    }
-    return m;
 }
 
 // The end cell is the cell of row L with the least key: least D, then least |d| (d = c - (start + L)), then the smaller c.

@@ -1,8 +1,8 @@
 // Banded alignment of the placed reads (gfx950, 64-wide waves): the verifying placement with indels.
 //
-//   align_kernel   one wave per listed read, grid-stride.  The vote is place_kernel's (place_vote, mf_vote_dev.h: the anchor vote, the
-//                  strict winner).  A placed read is then aligned to its record inside the band of
-//                  2 W + 1 diagonals around the winning one (align_read, the rule of mf_align.h):
+//   align_kernel   one wave per listed read, grid-stride.  The vote, its winner and lane 0's commit are place_kernel's (place_vote, Winner,
+//                  commit_read: mf_vote_dev.h).  A placed read is aligned to its record inside the band of 2 W + 1 diagonals around
+//                  the winning one (align_read, the rule of mf_align.h):
 //                    rows      lane l <= 2 W owns diagonal d = l - W and holds D(i, start + i + d) of the row in one register.  Per row
 //                              t[d] = min(prev[d] + sub, prev[d + 1] + 1) -- prev[d + 1] is the lane above's --, then the deletions
 //                              inside the row: D[d] = min over e <= d of t[e] + (d - e), an inclusive prefix minimum over the lanes of
@@ -18,11 +18,12 @@
 //                              the path enters row b + 1 at, whether base b was inserted, and how many bait positions row b + 1 deletes
 //                              behind it -- 32 a block, stored coalesced behind the direction bits.
 //                    counts    lanes take the read bases 64 at a time: compared and mismatches of the diagonal steps, one reduction.
-//                  Lane 0 then does what place_kernel's lane 0 does, with the alignment's coordinates and the cut over edits; for an
-//                  accepted read the wave walks the base words once more (align_adds): the pile-up of the diagonal steps, the deleted
-//                  positions, the insertion runs.  The GAPPED instantiations (the gapped consensus, include/mitofilter.h) also add the
-//                  letter of every inserted base into the insertion pile, at its offset inside its run (align_run_offset, mf_align.h);
-//                  the plain ones take an empty argument more and are otherwise the code they were.
+//                  Lane 0 then commits the read with the alignment's footprint and its edits as the bin value, and keeps the five
+//                  sums of a run of accepted reads on one record; for an accepted read the wave walks the base words once more
+//                  (align_adds): the pile-up of the diagonal steps, the deleted positions, the insertion runs.  The GAPPED
+//                  instantiations (the gapped consensus, include/mitofilter.h) also add the letter of every inserted base into the
+//                  insertion pile, at its offset inside its run (align_run_offset, mf_align.h); the plain ones take an empty
+//                  argument more and are otherwise the code they were.
 // Work memory: align_work_words(max_len) words a wave, as many waves as the launch has: bounded whatever the number of reads.
 #include "mf_align_launch.h"
 #include "mf_vote_dev.h"
@@ -37,12 +38,11 @@ constexpr uint64_t ALIGN_WAVES_PER_BLOCK = ASSIGN_BLOCK / 64;
 __device__ __forceinline__ unsigned long long wave_min_u64(unsigned long long v) { return ~wave_max_u64(~v); }
 
 // base i of the read oriented to the bait's forward strand: 0 .. 3, or ALIGN_X_NONE for an N
+static_assert(ALIGN_X_NONE == READ_LETTER_NONE, "an N is the same value in both");
 __device__ __forceinline__ uint32_t oriented_base(const ReadsView &R, uint64_t b0, bool hasn, uint64_t L, uint32_t strand, uint64_t i)
 {
-    const uint64_t g = b0 + (strand ? L - 1 - i : i);
-    if (hasn) { const uint64_t ni = npos_lower_bound(R, g); if (ni < R.n_npos && R.npos[ni] == g) return ALIGN_X_NONE; }
-    const uint32_t letter = (R.words[g >> 4] >> (2 * ((uint32_t)g & 15u))) & 3u;
-    return strand ? letter ^ 3u : letter;
+    const uint32_t letter = read_letter(R, b0 + (strand ? L - 1 - i : i), hasn);
+    return strand && letter != READ_LETTER_NONE ? letter ^ 3u : letter;
 }
 
 struct AlignResult { uint32_t compared, mismatches, insertions, deletions; int64_t ref_begin, ref_end; };
@@ -193,49 +193,28 @@ align_kernel(ReadsView R, KmerSetView S, const Anchor *__restrict__ anchor, cons
         const bool placed = best_cnt && !tie && L <= A.max_len;          // (no listed read is longer than max_len: the work memory's bound)
         AlignResult a{0, 0, 0, 0, 0, 0};
         bool accept = true;
-        uint32_t rs = 0; uint64_t s0 = 0; int64_t start = 0, len = 0;
-        if (placed) {                                        // (the winner is wave-uniform: into scalar registers)
-            rs = __builtin_amdgcn_readfirstlane((uint32_t)(best_key >> 32));
-            start = (int32_t)__builtin_amdgcn_readfirstlane((uint32_t)best_key);
-            s0 = rec_start[rs >> 1];
-            len = (int64_t)(rec_start[(rs >> 1) + 1] - s0);
-            a = align_read(R, src.b0, src.hasn, L, rs & 1u, start, s0, len, A.bait, A.band, dirs, ent, lane);
+        Winner W{};
+        if (placed) {
+            W = winner_of(best_key, rec_start);
+            a = align_read(R, src.b0, src.hasn, L, W.strand(), W.start, W.s0, W.len, A.bait, A.band, dirs, ent, lane);
             accept = align_accepts(a.compared, a.mismatches, a.insertions, a.deletions, A.max_permille);
         }
         if (lane == 0) {
-            PlaceOut out{PLACE_AMBIGUOUS, 0u, 0, 0, 0u, windows};
-            if (placed) {
-                const uint32_t j = rs >> 1;
-                out = PlaceOut{j, rs & 1u, (int32_t)start, (int32_t)(start + (int64_t)L), best_cnt, windows};
-                if (accept) {
-                    // band < k: the winning anchor's window lies inside the record on diagonal 0, the clipped footprint is not empty
-                    const int64_t lo = a.ref_begin < 0 ? 0 : a.ref_begin < len ? a.ref_begin : len;
-                    const int64_t hi = a.ref_end < 0 ? 0 : a.ref_end < len ? a.ref_end : len;
-                    atomicAdd(&diff[s0 + (uint64_t)lo], 1ull);
-                    atomicAdd(&diff[s0 + (uint64_t)hi], ~0ull);
-                    cnt.bump(4 * j + (rs & 1u));
-                    if (a.ref_begin < 0) cnt.add(4 * j + 2, 1);
-                    if (a.ref_end > len) cnt.add(4 * j + 3, 1);
-                }
-                const uint32_t g0 = 4 * n_rec + 1 + SCORE_GATHERED * j;
-                const uint32_t edits = a.mismatches + a.insertions + a.deletions;
-                if (!accept) cnt.add(g0, 1);
-                cnt.add(g0 + 1 + (edits < SCORE_BINS - 1 ? edits : SCORE_BINS - 1), 1);
-                if (accept) {
-                    if (sum_any && sum_j != j) flush();
-                    sum_j = j; sum_any = true;
-                    sum_v[0] += a.compared; sum_v[1] += a.mismatches; sum_v[2] += a.insertions; sum_v[3] += a.deletions;
-                    sum_v[4] += (a.insertions | a.deletions) != 0;
-                }
-                if (A.align) A.align[r] = AlignOut{a.compared, a.mismatches, a.insertions, a.deletions, (int32_t)a.ref_begin, (int32_t)a.ref_end};
-            } else cnt.bump(4 * n_rec);
-            if (place) place[r] = out;
-            if (A.keep_bits && keep_clears(placed, accept, A.keep)) atomicAnd(&A.keep_bits[r >> 5], ~(1u << (r & 31u)));
+            // (the alignment is written before the commit: in this order the kernel has the registers it had with its own block)
+            if (placed && A.align) A.align[r] = AlignOut{a.compared, a.mismatches, a.insertions, a.deletions, (int32_t)a.ref_begin, (int32_t)a.ref_end};
+            commit_read(placed, accept, W, L, a.ref_begin, a.ref_end, true, a.mismatches + a.insertions + a.deletions, best_cnt, windows, r, n_rec, place, diff, cnt,
+                        A.keep_bits, A.keep);
+            if (placed && accept) {
+                if (sum_any && sum_j != W.record()) flush();
+                sum_j = W.record(); sum_any = true;
+                sum_v[0] += a.compared; sum_v[1] += a.mismatches; sum_v[2] += a.insertions; sum_v[3] += a.deletions;
+                sum_v[4] += (a.insertions | a.deletions) != 0;
+            }
         }
         if (placed && accept) {
             unsigned long long *ins_pile = nullptr;
             if constexpr (GAPPED) ins_pile = G.ins_pile;
-            align_adds<GAPPED>(R, src.b0, src.hasn, L, rs & 1u, s0, len, ent, pile, A.indel, ins_pile, 2u * (uint32_t)A.band, lane);
+            align_adds<GAPPED>(R, src.b0, src.hasn, L, W.strand(), W.s0, W.len, ent, pile, A.indel, ins_pile, 2u * (uint32_t)A.band, lane);
         }
     }
     if (lane == 0 && sum_any) flush();
@@ -262,13 +241,14 @@ hipError_t launch_align(const ReadsView &R, const KmerSetView &S, const Anchor *
     if (!R.n_reads) return hipSuccess;
     const unsigned grid = (unsigned)(align_waves(R.n_reads, P.max_len, n_cu) / ALIGN_WAVES_PER_BLOCK);
     const uint64_t n = std::max<uint64_t>(P.max_len, 1);
-    const AlignArgs A{ScoreBait{P.bait_words, P.bait_words_last, P.bait_valid, P.bait_valid_last}, P.max_permille, (int)P.band, P.align, P.sums, P.indel,
-                      P.keep_bits, P.keep, P.work, P.max_len, 64 * ((n + 31) / 32), align_work_words(P.max_len)};
-    if (P.ins_pile && P.band) {          // (band 0: the table has no entry)
-        if (S.kw == 1) hipLaunchKernelGGL((align_kernel<1, true>), dim3(grid), dim3(ASSIGN_BLOCK), 0, st, R, S, anchor, rec_start, list, n_list, n_rec, place, diff, counts, pile, A, GapArgs<true>{P.ins_pile});
-        else hipLaunchKernelGGL((align_kernel<2, true>), dim3(grid), dim3(ASSIGN_BLOCK), 0, st, R, S, anchor, rec_start, list, n_list, n_rec, place, diff, counts, pile, A, GapArgs<true>{P.ins_pile});
-    } else if (S.kw == 1) hipLaunchKernelGGL((align_kernel<1, false>), dim3(grid), dim3(ASSIGN_BLOCK), 0, st, R, S, anchor, rec_start, list, n_list, n_rec, place, diff, counts, pile, A, GapArgs<false>{});
-    else hipLaunchKernelGGL((align_kernel<2, false>), dim3(grid), dim3(ASSIGN_BLOCK), 0, st, R, S, anchor, rec_start, list, n_list, n_rec, place, diff, counts, pile, A, GapArgs<false>{});
+    const AlignArgs A{P.cut.bait, P.cut.max_permille, (int)P.band, P.align, P.cut.sums, P.indel, P.cut.keep_bits, P.cut.keep, P.work, P.max_len, 64 * ((n + 31) / 32),
+                      align_work_words(P.max_len)};
+    dispatch_kw_flag(S.kw, P.ins_pile && P.band, [&](auto KW, auto GAPPED) {          // (band 0: the insertion pile has no entry)
+        GapArgs<decltype(GAPPED)::value> G;
+        if constexpr (decltype(GAPPED)::value) G.ins_pile = P.ins_pile;
+        hipLaunchKernelGGL((align_kernel<decltype(KW)::value, decltype(GAPPED)::value>), dim3(grid), dim3(ASSIGN_BLOCK), 0, st, R, S, anchor, rec_start, list, n_list,
+                           n_rec, place, diff, counts, pile, A, G);
+    });
     return hipGetLastError();
 }
 

@@ -9,18 +9,15 @@ struct AlignOut { uint32_t compared, mismatches, insertions, deletions; int32_t 
 constexpr uint32_t ALIGN_SUMS = 5;             // counters a record: compared, mismatches, insertions, deletions, gapped of its accepted reads
 constexpr uint32_t ALIGN_INDEL = 3;            // counters a position: del, ins, ins_bases
 
-// What the aligning launch takes beside a placing one.  The bait as PlaceVerify has it.  band: 0 .. 31.  align (optional): n_reads
-// entries, zeroed.  sums: ALIGN_SUMS counters a record.  indel: ALIGN_INDEL counters a position, [position][del, ins, ins_bases].
-// keep_bits, keep: as PlaceVerify's.  work: align_work_words(max_len) words for each of align_waves(..) waves -- the direction bits
-// of a read's band and what the traceback leaves per read base; max_len: no listed read is longer.
-// ins_pile (optional; the gapped launch): 4 * 2 * band counters a position, [position][run offset][A, C, G, T], zeroed -- the letters of
-// the inserted bases of the accepted reads; everything else is the plain launch's.
+// The aligning launch: a cutting launch (PlaceCut; cut.sums: ALIGN_SUMS counters a record) and  band: 0 .. 31.  align (optional): n_reads
+// entries, zeroed.  indel: ALIGN_INDEL counters a position, [position][del, ins, ins_bases].  work: align_work_words(max_len) words for
+// each of align_waves(..) waves -- the direction bits of a read's band and what the traceback leaves per read base; max_len: no listed
+// read is longer.  ins_pile (optional; the gapped launch): 4 * 2 * band counters a position, [position][run offset][A, C, G, T], zeroed --
+// the letters of the inserted bases of the accepted reads; everything else is the plain launch's.
 struct PlaceAlign {
-    const uint32_t *bait_words; uint64_t bait_words_last; const uint32_t *bait_valid; uint64_t bait_valid_last;
-    uint32_t max_permille, band; AlignOut *align; unsigned long long *sums, *indel;
-    uint32_t *keep_bits; int keep;
+    PlaceCut cut; uint32_t band; AlignOut *align; unsigned long long *indel;
     unsigned long long *work; uint64_t max_len;
-    unsigned long long *ins_pile = nullptr;
+    unsigned long long *ins_pile;
 };
 // 64-bit words of work memory a wave needs for reads of up to max_len bases: two direction bits a cell (64 lanes x 32 rows a block of
 // 64 words), then one word a read base

@@ -5,26 +5,25 @@
 #include "mf_common.h"
 #include "mf_kernels.h"
 #include "mf_placelayout.h"          // SCORE_BINS, SCORE_GATHERED, PILE_SUMS: what the kernels share with the host's layout
+#include "mf_score.h"                // ScoreBait, keep_clears
+#include "mf_call.h"                 // PLACE_CLAMP and the call rules
 
 namespace mf {
 
 constexpr uint32_t ANCHOR_NONE = 0xFFFFFFFFu;        // position of a slot whose key is no anchor
 constexpr uint32_t PLACE_AMBIGUOUS = 0xFFFFFFFEu;    // MF_PLACE_AMBIGUOUS
 constexpr uint32_t PLACE_NONE = 0xFFFFFFFFu;         // MF_PLACE_NONE
-constexpr uint32_t PLACE_CLAMP = 0xFFFFFFFEu;        // the largest base depth reported
 struct alignas(8) Anchor { uint32_t pos, rb; };          // position inside the record (ANCHOR_NONE: no anchor), record << 1 | b
 struct PlaceOut { uint32_t record, strand; int32_t start, end; uint32_t votes, windows; };       // mf_place_t
 struct ScoreOut { uint32_t compared, mismatches; };      // mf_score_t
-// What a verifying launch takes beside a placing one.  bait_words / bait_valid: the bait's packed letters and its validity, one bit a
-// position; *_last: the index of each array's last word (the 16-base compare clamps to it).  score (optional): n_reads entries, zeroed.
-// sums: compared, mismatches of every record, 2 counters each, summed over the ACCEPTED reads.
-// keep_bits (optional): n_reads bits laid out like the pass bitmap and holding a copy of it; a listed read loses its bit there where
-// keep_clears(placed, accepted, keep) of mf_score.h says so (keep: MF_KEEP_ACCEPTED or MF_KEEP_PLACED).  Nothing else is written for it.
-struct PlaceVerify {
-    const uint32_t *bait_words; uint64_t bait_words_last; const uint32_t *bait_valid; uint64_t bait_valid_last;
-    uint32_t max_permille; ScoreOut *score; unsigned long long *sums;
-    uint32_t *keep_bits = nullptr; int keep = 0;
-};
+// What a cutting launch (a verifying or an aligning one) takes beside a placing one.  bait: the bait's packed letters and its validity,
+// one bit a position, with the index of each array's last word (the 16-base compare clamps to it).  sums: counters of every record,
+// summed over the ACCEPTED reads.  keep_bits (optional): n_reads bits laid out like the pass bitmap and holding a copy of it; a listed
+// read loses its bit there where keep_clears(placed, accepted, keep) of mf_score.h says so (keep: MF_KEEP_ACCEPTED or MF_KEEP_PLACED).
+// Nothing else is written for it.
+struct PlaceCut { ScoreBait bait; uint32_t max_permille; unsigned long long *sums; uint32_t *keep_bits; int keep; };
+// The verifying launch.  score (optional): n_reads entries, zeroed.  cut.sums: compared, mismatches, 2 counters a record.
+struct PlaceVerify { PlaceCut cut; ScoreOut *score; };
 
 // Anchor table, indexed by the slot of the key table: anchor[slot] = { the window's position inside its record, record << 1 | b } when
 // exactly one valid bait window holds the key and that window is not its own reverse complement (b: 1 when the bait's reverse

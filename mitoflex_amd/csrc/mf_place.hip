@@ -1,36 +1,36 @@
 // Placement of baited reads on the bait (gfx950, 64-wide waves): position, strand and base depth; the pile-up of their bases.
+// What place_kernel shares with align_kernel (mf_align.hip) is stated once in mf_vote_dev.h -- the vote, the winner, a read's letter,
+// lane 0's commit --, the call rules once in mf_call.h.
 //
 //   anchor_span_kernel     one thread per bait window: atomicMin / atomicMax of its position into two slot-indexed arrays;
 //   anchor_finish_kernel   one thread per slot keeps the key as an anchor where both agree (exactly one window holds it, whatever order the
 //                          windows came in) and that window is not its own reverse complement: its position inside its record, its
-//                          record (binary search over the record starts) and the bait's orientation go into one 8-byte entry.
-//   place_kernel           one wave per listed read, grid-stride.  The vote is place_vote (mf_vote_dev.h, shared with align_kernel of
-//                          mf_align.hip).  Lanes take the read's windows 64 at a time: canonical key and the
-//                          read's orientation together, slot, anchor entry -- one 8-byte gather --, candidate (record, strand, start)
-//                          as a 64-bit key.  The votes are tallied by mf_tally_dev.h's WaveTally (the leader loop and the repeated
-//                          sweeps of assign_kernel, over a wider key).  Lane 0 writes the read's placement, bumps the record's counters
-//                          through the per-wave run and the workgroup's LDS histogram, and adds +1 / -1 into the difference counters at
-//                          the clipped ends of the read's footprint.  With PILE the wave then walks the placed read's bases 64 at a time
-//                          (pile_bases): letter from the packed words, N through the read's has_n bit and the invalid-position index,
-//                          complement on strand 1, clip to the record, one 64-bit add into [position][letter].
-//                          With VERIFY the wave first scores the winner against the bait (score_read, mf_score.h): lanes take the
-//                          clipped footprint sixteen bases at a time -- the read's word funnel-shifted (mirrored and complemented on
-//                          strand 1) against the bait's, masked by length, clip and the bait's validity bits --, one wave reduction,
-//                          then the cut; a rejected read keeps its placement and its score and bumps only `rejected` and its bin,
-//                          and pile_bases does not run for it.  Given a keep bitmap (a copy of the pass bitmap), lane 0 also clears
-//                          the read's bit there where the keep rule says so (keep_clears, mf_score.h): one atomicAnd on its word.
+//                          record (record_of) and the bait's orientation go into one 8-byte entry.
+//   place_kernel           one wave per listed read, grid-stride.  place_vote: every window whose key is an anchor votes for (record,
+//                          strand, start); a strict winner places the read (Winner: decoded wave-uniform once for score_read and once
+//                          more for pile_bases, and by lane 0 for its own block).  With VERIFY the wave then scores the winner against the bait (score_read, mf_score.h): lanes take the clipped footprint
+//                          sixteen bases at a time -- the read's word funnel-shifted (mirrored and complemented on strand 1) against the
+//                          bait's, masked by length, clip and the bait's validity bits --, a read with an N base by base (read_letter);
+//                          one wave reduction, then the cut.  Lane 0 commits the read (commit_read): its placement, +1 / -1 into the
+//                          difference counters at the clipped ends of its footprint, its record's counters through the per-wave run and
+//                          the workgroup's LDS histogram; a rejected read keeps its placement and its score and bumps only `rejected`
+//                          and its bin.  Given a keep bitmap (KEEP) the read's bit there is cleared where the keep rule says so; those
+//                          instantiations keep a commit block of their own, which holds their registers.  Lane 0 also keeps the
+//                          packed sums of a run of accepted reads on one record (VERIFY, run_add).  With PILE the wave last walks an
+//                          accepted read's bases 64 at a time (pile_bases): read_letter, complement on strand 1, clip to the record, one
+//                          64-bit add into [position][letter].
 //   place_scan_reduce_kernel, place_scan_partials_kernel, place_profile_kernel
 //                          base depth = inclusive scan of the difference counters (a -1 that lands on the next record's first position
-//                          is right under a global scan: no segmentation): tile sums, their exclusive scan, then per tile the scan, the
-//                          clamp and the records' covered / base_sum (reduced over the wave where a wave lies inside one record).
-//   pileup_call_kernel     per position, tiled like place_profile_kernel: the four counters clamped, the consensus byte, the records' six
-//                          sums through the same record walk (RecordWalk).
+//                          is right under a global scan: no segmentation): tile sums, their exclusive scan (launch_tile_partials), then
+//                          per tile the scan (tile_scan_begin), the clamp and the records' covered / base_sum through RecordWalk
+//                          (reduced over the wave where a wave lies inside one record).
+//   pileup_call_kernel     per position, tiled like place_profile_kernel: the four counters clamped, pileup_call_position (mf_call.h) for
+//                          the consensus byte and what the records' six sums add, through the same record walk.
 //   gapped_call_kernel     per position, tiled the same way and behind the same scan: the gapped consensus of an aligning placement --
-//                          the insertion pile clamped, the bytes the position emits and how many, the records' four sums.
+//                          the insertion pile clamped, gapped_call_position (mf_call.h) for the bytes the position emits and how many,
+//                          the records' four sums.
 #include "mf_place.h"
 #include "mf_vote_dev.h"
-#include "mf_score.h"
-#include "mf_align.h"          // gapped_call_position
 #include <algorithm>
 
 namespace mf {
@@ -60,8 +60,7 @@ anchor_finish_kernel(BaitView B, const uint64_t *__restrict__ rec_start, uint32_
         uint32_t rev;
         (void)oriented_at<KW>(B.words, p, k, rev);
         if (rev != 2u) {
-            uint32_t a = 0, b = n_rec;                                  // last record that starts at or before p
-            while (b - a > 1) { const uint32_t m = (a + b) >> 1; if (rec_start[m] <= p) a = m; else b = m; }
+            const uint32_t a = record_of(rec_start, n_rec, p);
             out = Anchor{p - (uint32_t)rec_start[a], (a << 1) | rev};
         }
     }
@@ -82,52 +81,49 @@ __global__ void __launch_bounds__(256) max_read_len_kernel(const uint64_t *__res
     if ((threadIdx.x & 63) == 0 && len) atomicMax(max_len, len);
 }
 
-// The bases of a read of L bases at b0, placed on strand `strand` with its leftmost base at record coordinate `start` of the record
-// at s0 (len positions), into pile: [position][letter].  The whole wave calls it; lane l takes bases l, l + 64, ..  Consecutive lanes
-// add to consecutive positions: no two lanes of an instruction share a counter.
-__device__ __forceinline__ void pile_bases(const ReadsView &R, uint64_t b0, bool hasn, uint64_t L, uint32_t strand, int64_t start, uint64_t s0,
-                                           int64_t len, unsigned long long *__restrict__ pile, int lane)
+// The bases of a read of L bases at b0, placed as W says, into pile: [position][letter].  The whole wave calls it; lane l takes bases
+// l, l + 64, ..  Consecutive lanes add to consecutive positions: no two lanes of an instruction share a counter.
+__device__ __forceinline__ void pile_bases(const ReadsView &R, uint64_t b0, bool hasn, uint64_t L, const Winner &W, unsigned long long *__restrict__ pile, int lane)
 {
     for (uint64_t i = (uint64_t)lane; i < L; i += 64) {
-        const uint64_t g = b0 + i;
-        if (hasn) { const uint64_t ni = npos_lower_bound(R, g); if (ni < R.n_npos && R.npos[ni] == g) continue; }     // an N counts nowhere
-        uint32_t letter = (R.words[g >> 4] >> (2 * ((uint32_t)g & 15u))) & 3u;
-        int64_t c = start + (int64_t)i;
-        if (strand) { c = start + (int64_t)(L - 1 - i); letter ^= 3u; }
-        if (c < 0 || c >= len) continue;                                                                                // an overhang counts nowhere
-        atomicAdd(&pile[4 * (s0 + (uint64_t)c) + letter], 1ull);
+        uint32_t letter = read_letter(R, b0 + i, hasn);
+        if (letter == READ_LETTER_NONE) continue;                                                                       // an N counts nowhere
+        int64_t c = W.start + (int64_t)i;
+        if (W.strand()) { c = W.start + (int64_t)(L - 1 - i); letter ^= 3u; }
+        if (c < 0 || c >= W.len) continue;                                                                              // an overhang counts nowhere
+        atomicAdd(&pile[4 * (W.s0 + (uint64_t)c) + letter], 1ull);
     }
 }
 
 // What a verifying launch is given beside a placing one (nothing otherwise: the plain instantiations take no argument more than before).
 // KEEP: a verifying launch that is also given a keep bitmap; the verifying launches without one keep their code and their registers.
-template <bool VERIFY, bool KEEP> struct VerifyArgs {};
+template <bool VERIFY, bool KEEP> struct VerifyArgs { static constexpr bool verify = false, keep_rule = false; };
 template <> struct VerifyArgs<true, false> {
+    static constexpr bool verify = true, keep_rule = false;
     ScoreBait bait; uint32_t max_permille;
     ScoreOut *__restrict__ score;                  // optional, n_reads entries, zeroed
     unsigned long long *__restrict__ sums;         // compared, mismatches of every record's accepted reads
 };
 template <> struct VerifyArgs<true, true> : VerifyArgs<true, false> {
+    static constexpr bool keep_rule = true;
     uint32_t *__restrict__ keep_bits; int keep;    // the pass bitmap's copy that loses the bits keep_clears names (mf_score.h)
 };
 
 // The score of the placed read (mf_score.h): lanes take the clipped footprint sixteen bases at a time, a read with an invalid base goes
 // base by base; one wave reduction of the packed pair.  Every lane returns the read's (mismatches << 32) | compared.
-__device__ __forceinline__ unsigned long long score_read(const ReadsView &R, uint64_t b0, bool hasn, uint64_t L, uint32_t strand, int64_t start, uint64_t s0,
-                                                         int64_t len, const ScoreBait &B, int lane)
+__device__ __forceinline__ unsigned long long score_read(const ReadsView &R, uint64_t b0, bool hasn, uint64_t L, const Winner &W, const ScoreBait &B, int lane)
 {
     unsigned long long acc = 0;
     if (!hasn) {
         int64_t lo, hi;
-        score_footprint(L, start, len, lo, hi);
+        score_footprint(L, W.start, W.len, lo, hi);
         const uint64_t chunks = (uint64_t)(hi - lo + 15) >> 4;
         const uint64_t r_last = R.n_words ? R.n_words - 1 : 0;
-        for (uint64_t t = (uint64_t)lane; t < chunks; t += 64) acc += score_chunk16(R.words, r_last, b0, L, strand, start, B, s0, lo, hi, t);
+        for (uint64_t t = (uint64_t)lane; t < chunks; t += 64) acc += score_chunk16(R.words, r_last, b0, L, W.strand(), W.start, B, W.s0, lo, hi, t);
     } else {
         for (uint64_t i = (uint64_t)lane; i < L; i += 64) {
-            const uint64_t g = b0 + i, ni = npos_lower_bound(R, g);
-            if (ni < R.n_npos && R.npos[ni] == g) continue;                                                             // an N is not compared
-            acc += score_base(R.words, b0, L, strand, start, B, s0, len, i);
+            if (read_letter(R, b0 + i, true) == READ_LETTER_NONE) continue;                                             // an N is not compared
+            acc += score_base(R.words, b0, L, W.strand(), W.start, B, W.s0, W.len, i);
         }
     }
     return wave_sum_u64(acc);
@@ -153,61 +149,67 @@ place_kernel(ReadsView R, KmerSetView S, const Anchor *__restrict__ anchor, cons
         const uint64_t np = src.begin(r);                    // windows; the read has np + k - 1 bases when np > 0
         uint32_t best_cnt, windows; uint64_t best_key; bool tie;
         place_vote<KW>(R, S, anchor, src, np, lane, best_cnt, best_key, tie, windows);
+        const uint64_t L = np + S.k - 1;
+        const bool placed = best_cnt && !tie;
         // VERIFY: the read is scored before anything of it is counted; a rejected read then counts nowhere but in rejected and its bin
         uint32_t compared = 0, mismatches = 0; bool accept = true;
         if constexpr (VERIFY) {
-            if (best_cnt && !tie) {                          // (the winner is wave-uniform: into scalar registers)
-                const uint32_t rs = __builtin_amdgcn_readfirstlane((uint32_t)(best_key >> 32));
-                const int32_t start = (int32_t)__builtin_amdgcn_readfirstlane((uint32_t)best_key);
-                const uint64_t s0 = rec_start[rs >> 1];
-                const unsigned long long sc = score_read(R, src.b0, src.hasn, np + S.k - 1, rs & 1u, (int64_t)start, s0, (int64_t)(rec_start[(rs >> 1) + 1] - s0),
-                                                         V.bait, lane);
+            if (placed) {
+                const unsigned long long sc = score_read(R, src.b0, src.hasn, L, winner_of(best_key, rec_start), V.bait, lane);
                 compared = __builtin_amdgcn_readfirstlane((uint32_t)sc); mismatches = __builtin_amdgcn_readfirstlane((uint32_t)(sc >> 32));
                 accept = score_accepts(compared, mismatches, V.max_permille);
             }
         }
-        if (lane == 0) {
-            PlaceOut out{PLACE_AMBIGUOUS, 0u, 0, 0, 0u, windows};
-            if (best_cnt && !tie) {
-                const uint32_t rs = (uint32_t)(best_key >> 32), j = rs >> 1;
-                const int64_t start = (int32_t)(uint32_t)best_key, end = start + (int64_t)(np + S.k - 1);
-                const uint64_t s0 = rec_start[j];
-                const int64_t len = (int64_t)(rec_start[j + 1] - s0);
-                out = PlaceOut{j, rs & 1u, (int32_t)start, (int32_t)end, best_cnt, windows};
-                if (accept) {
-                    // the winning anchor's window lies inside the record and inside the read: 0 <= begin < last <= len
-                    atomicAdd(&diff[s0 + (uint64_t)(start > 0 ? start : 0)], 1ull);
-                    atomicAdd(&diff[s0 + (uint64_t)(end < len ? end : len)], ~0ull);
-                    cnt.bump(4 * j + (rs & 1u));
-                    if (start < 0) cnt.add(4 * j + 2, 1);
-                    if (end > len) cnt.add(4 * j + 3, 1);
+        // (lane 0, VERIFY) an accepted read on record j into the run of packed sums
+        auto run_add = [&](uint32_t j) {
+            if constexpr (VERIFY) {
+                if (sum_v && sum_j != j) { atomicAdd(&V.sums[2 * sum_j], sum_v & 0xFFFFFFFFull); atomicAdd(&V.sums[2 * sum_j + 1], sum_v >> 32); sum_v = 0; }
+                // (a run's packed halves stay below 2^32: flushed before either could carry)
+                if ((sum_v & 0xFFFFFFFFull) + compared > 0xFFFFFFFFull || (sum_v >> 32) + mismatches > 0xFFFFFFFFull) {
+                    atomicAdd(&V.sums[2 * sum_j], sum_v & 0xFFFFFFFFull); atomicAdd(&V.sums[2 * sum_j + 1], sum_v >> 32); sum_v = 0;
                 }
-                if constexpr (VERIFY) {
+                sum_j = j; sum_v += ((unsigned long long)mismatches << 32) | compared;
+            }
+        };
+        if (lane == 0) {
+            // lane 0 decodes the winner for itself, as it always did: behind one wave-uniform decode in front of this block a pass over
+            // reads stacked on one start took 0.5 % longer; align_kernel shares its one decode
+            Winner W{};
+            if (placed) W = winner_at((uint32_t)(best_key >> 32), (int32_t)(uint32_t)best_key, rec_start);
+            if constexpr (KEEP) {
+                // the keep-rule instantiations keep their own block: through commit_read the one without the pile lost a register, went from
+                // five to six waves a SIMD and took 1.3 to 4.9 % longer
+                PlaceOut out{PLACE_AMBIGUOUS, 0u, 0, 0, 0u, windows};
+                if (placed) {
+                    const uint32_t j = W.record();
+                    const int64_t start = W.start, end = start + (int64_t)L;
+                    out = PlaceOut{j, W.strand(), (int32_t)start, (int32_t)end, best_cnt, windows};
+                    if (accept) {
+                        // the winning anchor's window lies inside the record and inside the read: 0 <= begin < last <= len
+                        atomicAdd(&diff[W.s0 + (uint64_t)(start > 0 ? start : 0)], 1ull);
+                        atomicAdd(&diff[W.s0 + (uint64_t)(end < W.len ? end : W.len)], ~0ull);
+                        cnt.bump(4 * j + W.strand());
+                        if (start < 0) cnt.add(4 * j + 2, 1);
+                        if (end > W.len) cnt.add(4 * j + 3, 1);
+                    }
                     const uint32_t g0 = 4 * n_rec + 1 + SCORE_GATHERED * j;
                     if (!accept) cnt.add(g0, 1);
                     cnt.add(g0 + 1 + (mismatches < SCORE_BINS - 1 ? mismatches : SCORE_BINS - 1), 1);
-                    if (accept) {
-                        if (sum_v && sum_j != j) { atomicAdd(&V.sums[2 * sum_j], sum_v & 0xFFFFFFFFull); atomicAdd(&V.sums[2 * sum_j + 1], sum_v >> 32); sum_v = 0; }
-                        // (a run's packed halves stay below 2^32: flushed before either could carry)
-                        if ((sum_v & 0xFFFFFFFFull) + compared > 0xFFFFFFFFull || (sum_v >> 32) + mismatches > 0xFFFFFFFFull) {
-                            atomicAdd(&V.sums[2 * sum_j], sum_v & 0xFFFFFFFFull); atomicAdd(&V.sums[2 * sum_j + 1], sum_v >> 32); sum_v = 0;
-                        }
-                        sum_j = j; sum_v += ((unsigned long long)mismatches << 32) | compared;
-                    }
+                    if (accept) run_add(j);
                     if (V.score) V.score[r] = ScoreOut{compared, mismatches};
+                } else cnt.bump(4 * n_rec);
+                if (place) place[r] = out;
+                // the keep rule: the words of the bitmap are shared by the waves of 32 reads, hence the atomic; nothing else is written for it
+                if (keep_clears(placed, accept, V.keep)) atomicAnd(&V.keep_bits[r >> 5], ~(1u << (r & 31u)));
+            } else {
+                commit_read(placed, accept, W, L, W.start, W.start + (int64_t)L, VERIFY, mismatches, best_cnt, windows, r, n_rec, place, diff, cnt, nullptr, 0);
+                if constexpr (VERIFY) {
+                    if (placed && accept) run_add(W.record());
+                    if (placed && V.score) V.score[r] = ScoreOut{compared, mismatches};
                 }
-            } else cnt.bump(4 * n_rec);
-            if (place) place[r] = out;
-            // the keep rule: the words of the bitmap are shared by the waves of 32 reads, hence the atomic; nothing else is written for it
-            if constexpr (KEEP)
-                if (keep_clears(best_cnt && !tie, accept, V.keep)) atomicAnd(&V.keep_bits[r >> 5], ~(1u << (r & 31u)));
+            }
         }
-        if (PILE && best_cnt && !tie && accept) {            // (the winner is wave-uniform: into scalar registers)
-            const uint32_t rs = __builtin_amdgcn_readfirstlane((uint32_t)(best_key >> 32));
-            const int32_t start = (int32_t)__builtin_amdgcn_readfirstlane((uint32_t)best_key);
-            const uint64_t s0 = rec_start[rs >> 1];
-            pile_bases(R, src.b0, src.hasn, np + S.k - 1, rs & 1u, (int64_t)start, s0, (int64_t)(rec_start[(rs >> 1) + 1] - s0), pile, lane);
-        }
+        if (PILE && placed && accept) pile_bases(R, src.b0, src.hasn, L, winner_of(best_key, rec_start), pile, lane);
     }
     if constexpr (VERIFY)
         if (lane == 0 && sum_v) { atomicAdd(&V.sums[2 * sum_j], sum_v & 0xFFFFFFFFull); atomicAdd(&V.sums[2 * sum_j + 1], sum_v >> 32); }
@@ -273,12 +275,7 @@ struct RecordWalk {
 #pragma unroll
         for (int k = 0; k < N; k++) v[k] = 0;
     }
-    __device__ __forceinline__ void begin(uint32_t n_rec, uint64_t i0)
-    {
-        uint32_t a = 0, b = n_rec;                                      // last record that starts at or before i0
-        while (b - a > 1) { const uint32_t m = (a + b) >> 1; if (rec_start[m] <= i0) a = m; else b = m; }
-        j = a; j_end = rec_start[a + 1];
-    }
+    __device__ __forceinline__ void begin(uint32_t n_rec, uint64_t i0) { j = record_of(rec_start, n_rec, i0); j_end = rec_start[j + 1]; }
     __device__ __forceinline__ void flush()
     {
 #pragma unroll
@@ -301,16 +298,31 @@ struct RecordWalk {
     }
 };
 
+// The scan of the difference counters inside a tile: v = the thread's PS_ITEMS counters from position i0 on (0 behind n); returns the sum
+// of every counter before i0 -- the tile's partial and the workgroup's exclusive prefix.  The whole workgroup calls it.
+__device__ __forceinline__ unsigned long long tile_scan_begin(const unsigned long long *__restrict__ diff, uint64_t n, const unsigned long long *__restrict__ partial,
+                                                              uint64_t i0, unsigned long long *lds, unsigned long long (&v)[PS_ITEMS])
+{
+    unsigned long long s = 0;
+#pragma unroll
+    for (uint32_t k = 0; k < PS_ITEMS; k++) { v[k] = i0 + k < n ? diff[i0 + k] : 0; s += v[k]; }
+    return partial[blockIdx.x] + block_exclusive_u64(s, lds, nullptr);
+}
+
+// the four counters of a position as they are reported
+__device__ __forceinline__ PileOut pile_clamped(unsigned long long c0, unsigned long long c1, unsigned long long c2, unsigned long long c3)
+{
+    return PileOut{clamp_count(c0), clamp_count(c1), clamp_count(c2), clamp_count(c3)};
+}
+
 __global__ void __launch_bounds__(PS_BLOCK)
 place_profile_kernel(const unsigned long long *__restrict__ diff, uint64_t n, const unsigned long long *__restrict__ partial,
                      const uint64_t *__restrict__ rec_start, uint32_t n_rec, uint32_t *__restrict__ depth, unsigned long long *__restrict__ rec_sums)
 {
     __shared__ unsigned long long lds[PS_BLOCK / 64];
     const uint64_t i0 = (uint64_t)blockIdx.x * PS_TILE + (uint64_t)threadIdx.x * PS_ITEMS;
-    unsigned long long v[PS_ITEMS], s = 0;
-#pragma unroll
-    for (uint32_t k = 0; k < PS_ITEMS; k++) { v[k] = i0 + k < n ? diff[i0 + k] : 0; s += v[k]; }
-    unsigned long long run = partial[blockIdx.x] + block_exclusive_u64(s, lds, nullptr);
+    unsigned long long v[PS_ITEMS];
+    unsigned long long run = tile_scan_begin(diff, n, partial, i0, lds, v);
     // the thread's positions lie in one record and the records behind it: covered and base_sum per record, added when the record changes
     RecordWalk<2> walk(rec_start, rec_sums);
     if (rec_sums && i0 < n) walk.begin(n_rec, i0);
@@ -319,7 +331,7 @@ place_profile_kernel(const unsigned long long *__restrict__ diff, uint64_t n, co
         const uint64_t p = i0 + k;
         run += v[k];
         if (p >= n) continue;
-        if (depth) depth[p] = run < PLACE_CLAMP ? (uint32_t)run : PLACE_CLAMP;
+        if (depth) depth[p] = clamp_count(run);
         if (!rec_sums) continue;
         walk.next(p);
         walk.v[0] += run != 0; walk.v[1] += run;
@@ -338,42 +350,29 @@ pileup_call_kernel(const unsigned long long *__restrict__ pile, BaitView B, cons
     RecordWalk<(int)PILE_SUMS> walk(rec_start, rec_sums);          // bases, matches, mismatches, called, ambiguous, variants
     if (rec_sums && i0 < n) walk.begin(n_rec, i0);
     const uint32_t word = i0 < n ? B.words[i0 >> 4] : 0u;
-    constexpr uint32_t LETTERS = 0x54474341u;                       // "ACGT", letter l in byte l
 #pragma unroll 4
     for (uint32_t k = 0; k < PS_ITEMS; k++) {
         const uint64_t p = i0 + k;
         if (p >= n) break;
         const ulonglong2 lo = reinterpret_cast<const ulonglong2 *>(pile)[2 * p], hi = reinterpret_cast<const ulonglong2 *>(pile)[2 * p + 1];
-        const unsigned long long c0 = lo.x, c1 = lo.y, c2 = hi.x, c3 = hi.y;
-        const unsigned long long d = c0 + c1 + c2 + c3;
-        // the letter with strictly the most bases
-        unsigned long long m = c0; uint32_t best = 0; bool tied = false;
-        if (c1 > m) { m = c1; best = 1; tied = false; } else if (c1 == m) tied = true;
-        if (c2 > m) { m = c2; best = 2; tied = false; } else if (c2 == m) tied = true;
-        if (c3 > m) { m = c3; best = 3; tied = false; } else if (c3 == m) tied = true;
         const bool valid = B.runlen[p] != 0;
-        const uint32_t b = (word >> (2 * k)) & 3u;
-        const bool deep = d >= (unsigned long long)min_depth;
-        if (out) out[p] = PileOut{c0 < PLACE_CLAMP ? (uint32_t)c0 : PLACE_CLAMP, c1 < PLACE_CLAMP ? (uint32_t)c1 : PLACE_CLAMP,
-                                  c2 < PLACE_CLAMP ? (uint32_t)c2 : PLACE_CLAMP, c3 < PLACE_CLAMP ? (uint32_t)c3 : PLACE_CLAMP};
-        if (consensus)
-            consensus[p] = (uint8_t)(deep ? (tied ? (uint32_t)'N' : (LETTERS >> (8 * best)) & 255u)
-                                          : (valid ? ((LETTERS >> (8 * b)) & 255u) | 0x20u : (uint32_t)'n'));
+        const PileCall c = pileup_call_position(lo.x, lo.y, hi.x, hi.y, (word >> (2 * k)) & 3u, valid, min_depth);          // (mf_call.h)
+        if (out) out[p] = pile_clamped(lo.x, lo.y, hi.x, hi.y);
+        if (consensus) consensus[p] = c.consensus;
         if (!rec_sums) continue;
         walk.next(p);
-        const unsigned long long own = b == 0 ? c0 : b == 1 ? c1 : b == 2 ? c2 : c3;
-        walk.v[0] += d;
-        if (valid) { walk.v[1] += own; walk.v[2] += d - own; }
-        walk.v[3] += deep && !tied;
-        walk.v[4] += deep && tied;
-        walk.v[5] += deep && !tied && valid && best != b;
+        walk.v[0] += c.depth;
+        if (valid) { walk.v[1] += c.own; walk.v[2] += c.depth - c.own; }
+        walk.v[3] += c.called;
+        walk.v[4] += c.ambiguous;
+        walk.v[5] += c.variant;
     }
     if (rec_sums) walk.finish();
 }
 
 // The gapped consensus called (include/mitofilter.h, "gapped consensus"), tiled like place_profile_kernel, whose scan of the difference
-// counters it repeats: the call goes by the UNCLAMPED base depth D, position by position (gapped_call_position, mf_align.h, which the
-// CPU model check compiles too).  Per position: the clamped counters into ins_out (optional), the
+// counters it shares (tile_scan_begin): the call goes by the UNCLAMPED base depth D, position by position (gapped_call_position,
+// mf_call.h, which the CPU model check compiles too).  Per position: the clamped counters into ins_out (optional), the
 // number of emitted bytes into count[p] (0 .. 1 + span) and the bytes into bytes[p * (1 + span) ..]; per record (rec_sums, optional,
 // zeroed): length, deleted, insertions, inserted_bases.
 __global__ void __launch_bounds__(PS_BLOCK)
@@ -384,10 +383,8 @@ gapped_call_kernel(const unsigned long long *__restrict__ diff, uint64_t n, cons
 {
     __shared__ unsigned long long lds[PS_BLOCK / 64];
     const uint64_t i0 = (uint64_t)blockIdx.x * PS_TILE + (uint64_t)threadIdx.x * PS_ITEMS;
-    unsigned long long v[PS_ITEMS], s = 0;
-#pragma unroll
-    for (uint32_t k = 0; k < PS_ITEMS; k++) { v[k] = i0 + k < n ? diff[i0 + k] : 0; s += v[k]; }
-    unsigned long long run = partial[blockIdx.x] + block_exclusive_u64(s, lds, nullptr);
+    unsigned long long v[PS_ITEMS];
+    unsigned long long run = tile_scan_begin(diff, n, partial, i0, lds, v);
     RecordWalk<(int)GAPPED_SUMS> walk(rec_start, rec_sums);          // length, deleted, insertions, inserted_bases
     if (rec_sums && i0 < n) walk.begin(n_rec, i0);
     for (uint32_t k = 0; k < PS_ITEMS; k++) {
@@ -396,11 +393,7 @@ gapped_call_kernel(const unsigned long long *__restrict__ diff, uint64_t n, cons
         if (p >= n) break;
         const unsigned long long *const ins = span ? ins_pile + 4 * p * (uint64_t)span : nullptr;
         if (ins_out)
-            for (uint32_t q = 0; q < span; q++) {
-                const unsigned long long c0 = ins[4 * q], c1 = ins[4 * q + 1], c2 = ins[4 * q + 2], c3 = ins[4 * q + 3];
-                ins_out[p * (uint64_t)span + q] = PileOut{c0 < PLACE_CLAMP ? (uint32_t)c0 : PLACE_CLAMP, c1 < PLACE_CLAMP ? (uint32_t)c1 : PLACE_CLAMP,
-                                                          c2 < PLACE_CLAMP ? (uint32_t)c2 : PLACE_CLAMP, c3 < PLACE_CLAMP ? (uint32_t)c3 : PLACE_CLAMP};
-            }
+            for (uint32_t q = 0; q < span; q++) ins_out[p * (uint64_t)span + q] = pile_clamped(ins[4 * q], ins[4 * q + 1], ins[4 * q + 2], ins[4 * q + 3]);
         bool deleted;
         const uint32_t m = gapped_call_position(run, span ? indel[ALIGN_POSITION_COUNTERS * p] : 0ull, ins, span, min_depth, consensus[p],
                                                 bytes + p * (uint64_t)(1 + span), deleted);
@@ -451,36 +444,37 @@ hipError_t launch_place(const ReadsView &R, const KmerSetView &S, const Anchor *
     // the launch shape of launch_assign: four workgroups (32 waves) a CU at most, never more waves than reads
     const uint64_t waves = std::min<uint64_t>((uint64_t)(n_cu > 0 ? n_cu : 1) * 32, R.n_reads);
     const unsigned grid = grid_of(waves, ASSIGN_BLOCK / 64);
-#define PLACE_LAUNCH(KW, PILE, VERIFY, KEEP, V) hipLaunchKernelGGL((place_kernel<KW, PILE, VERIFY, KEEP>), dim3(grid), dim3(ASSIGN_BLOCK), 0, st, R, S, anchor, rec_start, list, n_list, n_rec, place, diff, counts, pile, V)
+    const auto launch = [&](auto V) {                        // the instantiation that V's type, the key width and the pile-up name
+        dispatch_kw_flag(S.kw, pile != nullptr, [&](auto KW, auto PILE) {
+            hipLaunchKernelGGL((place_kernel<decltype(KW)::value, decltype(PILE)::value, decltype(V)::verify, decltype(V)::keep_rule>), dim3(grid),
+                               dim3(ASSIGN_BLOCK), 0, st, R, S, anchor, rec_start, list, n_list, n_rec, place, diff, counts, pile, V);
+        });
+    };
     if (verify) {
+        const PlaceCut &C = verify->cut;
         VerifyArgs<true, true> K;
-        VerifyArgs<true, false> &V = K;
-        V.bait = ScoreBait{verify->bait_words, verify->bait_words_last, verify->bait_valid, verify->bait_valid_last};
-        V.max_permille = verify->max_permille; V.score = verify->score; V.sums = verify->sums;
-        K.keep_bits = verify->keep_bits; K.keep = verify->keep;
-        if (K.keep_bits) {
-            if (S.kw == 1) { if (pile) PLACE_LAUNCH(1, true, true, true, K); else PLACE_LAUNCH(1, false, true, true, K); }
-            else { if (pile) PLACE_LAUNCH(2, true, true, true, K); else PLACE_LAUNCH(2, false, true, true, K); }
-        } else if (S.kw == 1) { if (pile) PLACE_LAUNCH(1, true, true, false, V); else PLACE_LAUNCH(1, false, true, false, V); }
-        else { if (pile) PLACE_LAUNCH(2, true, true, false, V); else PLACE_LAUNCH(2, false, true, false, V); }
-    } else {
-        const VerifyArgs<false, false> V;
-        if (S.kw == 1) { if (pile) PLACE_LAUNCH(1, true, false, false, V); else PLACE_LAUNCH(1, false, false, false, V); }
-        else { if (pile) PLACE_LAUNCH(2, true, false, false, V); else PLACE_LAUNCH(2, false, false, false, V); }
-    }
-#undef PLACE_LAUNCH
+        K.bait = C.bait; K.max_permille = C.max_permille; K.score = verify->score; K.sums = C.sums;
+        K.keep_bits = C.keep_bits; K.keep = C.keep;
+        if (K.keep_bits) launch(K); else launch(static_cast<const VerifyArgs<true, false> &>(K));
+    } else launch(VerifyArgs<false, false>{});
     return hipGetLastError();
 }
 
 uint64_t place_scan_tiles(uint64_t total) { return (total + PS_TILE - 1) / PS_TILE; }
+
+// the tiles' exclusive prefixes of the difference counters into partial: what tile_scan_begin starts from
+static void launch_tile_partials(const unsigned long long *diff, uint64_t total, unsigned long long *partial, uint64_t nb, hipStream_t st)
+{
+    hipLaunchKernelGGL(place_scan_reduce_kernel, dim3((unsigned)nb), dim3(PS_BLOCK), 0, st, diff, total, partial);
+    hipLaunchKernelGGL(place_scan_partials_kernel, dim3(1), dim3(PS_BLOCK), 0, st, partial, nb);
+}
 
 hipError_t launch_place_profile(const unsigned long long *diff, uint64_t total, const uint64_t *rec_start, uint32_t n_rec, unsigned long long *partial,
                                 uint32_t *depth, unsigned long long *rec_sums, hipStream_t st)
 {
     const uint64_t nb = place_scan_tiles(total);
     if (!nb || !n_rec) return hipSuccess;
-    hipLaunchKernelGGL(place_scan_reduce_kernel, dim3((unsigned)nb), dim3(PS_BLOCK), 0, st, diff, total, partial);
-    hipLaunchKernelGGL(place_scan_partials_kernel, dim3(1), dim3(PS_BLOCK), 0, st, partial, nb);
+    launch_tile_partials(diff, total, partial, nb, st);
     hipLaunchKernelGGL(place_profile_kernel, dim3((unsigned)nb), dim3(PS_BLOCK), 0, st, diff, total, partial, rec_start, n_rec, depth, rec_sums);
     return hipGetLastError();
 }
@@ -500,8 +494,7 @@ hipError_t launch_gapped_call(const unsigned long long *diff, uint64_t total, co
 {
     const uint64_t nb = place_scan_tiles(total);
     if (!nb || !n_rec) return hipSuccess;
-    hipLaunchKernelGGL(place_scan_reduce_kernel, dim3((unsigned)nb), dim3(PS_BLOCK), 0, st, diff, total, partial);
-    hipLaunchKernelGGL(place_scan_partials_kernel, dim3(1), dim3(PS_BLOCK), 0, st, partial, nb);
+    launch_tile_partials(diff, total, partial, nb, st);
     hipLaunchKernelGGL(gapped_call_kernel, dim3((unsigned)nb), dim3(PS_BLOCK), 0, st, diff, total, partial, indel, ins_pile, span, consensus, rec_start, n_rec,
                        min_depth, ins_out, count, bytes, rec_sums);
     return hipGetLastError();

@@ -469,25 +469,22 @@ static int place_after_filter(mf_kmerset *ks, mf_reads *r, const PlaceLayout &L,
     HIPCHK(hipMemsetAsync(r->d_acnt, 0, 8, st));
     HIPCHK(dev_reserve(r->d_alist, r->cap_alist, n * 4, true));
     HIPCHK(launch_pass_list(r->d_bits[r->cur], n, r->d_alist, r->d_acnt, st));
+    PlaceCut cut{};
+    if (L.verify || L.align) cut = PlaceCut{ScoreBait{T->pile_words, T->pile_words_n - 1, T->pile_valid, T->pile_valid_n - 1}, L.max_permille, L.score_sums(t), keep_dev, keep};
     if (L.align) {
         const uint64_t max_len = r->v.uniform_len ? r->v.uniform_len : v;
         const size_t bytes = (size_t)(align_waves(n, max_len, ctx->n_cu) * align_work_words(max_len)) * 8;
         const hipError_t e = dev_reserve(r->d_awork, r->cap_awork, bytes, false);
         if (e == hipErrorOutOfMemory) { (void)hipGetLastError(); return fail(MF_E_NOMEM, "the alignment of reads of up to %llu bases needs %llu bytes on the device", (unsigned long long)max_len, (unsigned long long)bytes); }
         HIPCHK(e);
-        const PlaceAlign pa{T->pile_words, T->pile_words_n - 1, T->pile_valid, T->pile_valid_n - 1, L.max_permille, L.band, align, L.score_sums(t), L.indel(t),
-                            keep_dev, keep, r->d_awork, max_len, L.ins(t)};
+        const PlaceAlign pa{cut, L.band, align, L.indel(t), r->d_awork, max_len, L.ins(t)};
         HIPCHK(launch_align(r->v, T->view, T->anchor, T->place_starts, r->d_alist, r->d_acnt, (uint32_t)ks->rec_len().size(), place, L.diff(t), L.cnt(t), L.pile(t),
                             pa, ctx->n_cu, st));
-        HIPCHK(hipMemcpyAsync(&v, r->d_acnt, 8, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        *listed = v;
-        return MF_OK;
+    } else {
+        const PlaceVerify pv{cut, score};
+        HIPCHK(launch_place(r->v, T->view, T->anchor, T->place_starts, r->d_alist, r->d_acnt, (uint32_t)ks->rec_len().size(), place, L.diff(t), L.cnt(t), L.pile(t),
+                            L.verify ? &pv : nullptr, ctx->n_cu, st));
     }
-    PlaceVerify pv{};
-    if (L.verify) pv = PlaceVerify{T->pile_words, T->pile_words_n - 1, T->pile_valid, T->pile_valid_n - 1, L.max_permille, score, L.score_sums(t), keep_dev, keep};
-    HIPCHK(launch_place(r->v, T->view, T->anchor, T->place_starts, r->d_alist, r->d_acnt, (uint32_t)ks->rec_len().size(), place, L.diff(t), L.cnt(t), L.pile(t),
-                        L.verify ? &pv : nullptr, ctx->n_cu, st));
     HIPCHK(hipMemcpyAsync(&v, r->d_acnt, 8, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     *listed = v;
@@ -562,10 +559,8 @@ static int placement_report(mf_kmerset *ks, int device, hipStream_t st, const Pl
     if (!h_indel.empty()) HIPCHK(hipMemcpyAsync(h_indel.data(), L.indel(t), h_indel.size() * 8, hipMemcpyDeviceToHost, st));
     HIPCHK(hipMemcpyAsync(h_cnt.data(), L.cnt(t), h_cnt.size() * 8, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
-    for (size_t p = 0; p < h_indel.size() / ALIGN_INDEL; p++) {          // (clamped like the depth)
-        const auto clamp = [](unsigned long long c) { return c < PLACE_CLAMP ? (uint32_t)c : PLACE_CLAMP; };
-        q.indels[p] = mf_indel_t{clamp(h_indel[ALIGN_INDEL * p]), clamp(h_indel[ALIGN_INDEL * p + 1]), clamp(h_indel[ALIGN_INDEL * p + 2])};
-    }
+    for (size_t p = 0; p < h_indel.size() / ALIGN_INDEL; p++)          // (clamped like the depth)
+        q.indels[p] = mf_indel_t{clamp_count(h_indel[ALIGN_INDEL * p]), clamp_count(h_indel[ALIGN_INDEL * p + 1]), clamp_count(h_indel[ALIGN_INDEL * p + 2])};
     if (gap && (q.gapped || q.gapped_starts)) {          // the positions' bytes, concatenated record by record
         const std::vector<uint64_t> starts = record_starts(ks);
         uint64_t at = 0;
@@ -664,8 +659,8 @@ int mf_place(const mf_kmerset *ks, const mf_reads *reads, uint32_t threshold, in
 int mf_pileup(const mf_kmerset *ks, const mf_reads *reads, uint32_t threshold, int mode, uint32_t min_depth, uint32_t *out_bits,
               mf_pileup_t *pileup, uint8_t *consensus, mf_pileup_record_t *records, uint64_t *unplaced, mf_filter_stats_t *stats)
 {
-    PlaceRequest q{"the pile-up", false, true, min_depth};
-    q.pileup = pileup; q.consensus = consensus; q.pileup_records = records; q.unplaced = unplaced;
+    PlaceRequest q{"the pile-up", false, true};
+    q.min_depth = min_depth; q.pileup = pileup; q.consensus = consensus; q.pileup_records = records; q.unplaced = unplaced;
     return placement_resident(ks, reads, threshold, mode, out_bits, stats, q);
 }
 
@@ -674,8 +669,10 @@ int mf_verify_keep(const mf_kmerset *ks, const mf_reads *reads, uint32_t thresho
                    mf_place_record_t *place_records, mf_pileup_t *pileup, uint8_t *consensus, mf_pileup_record_t *pileup_records,
                    mf_score_record_t *score_records, uint64_t *unplaced, mf_filter_stats_t *stats)
 {
-    const PlaceRequest q{"verification", true, pileup || consensus || pileup_records, min_depth, max_permille, place_out, score_out, base_depth,
-                         place_records, pileup, consensus, pileup_records, score_records, unplaced, keep, keep_bits};
+    PlaceRequest q{"verification", true, pileup || consensus || pileup_records};
+    q.min_depth = min_depth; q.max_permille = max_permille; q.keep = keep; q.keep_bits = keep_bits;
+    q.place_out = place_out; q.score_out = score_out; q.base_depth = base_depth; q.place_records = place_records;
+    q.pileup = pileup; q.consensus = consensus; q.pileup_records = pileup_records; q.score_records = score_records; q.unplaced = unplaced;
     return placement_resident(ks, reads, threshold, mode, out_bits, stats, q);
 }
 
@@ -684,9 +681,8 @@ int mf_align(const mf_kmerset *ks, const mf_reads *reads, uint32_t threshold, in
              mf_pileup_t *pileup, uint8_t *consensus, mf_pileup_record_t *pileup_records, mf_indel_t *indels, mf_align_record_t *align_records,
              uint64_t *unplaced, mf_filter_stats_t *stats)
 {
-    const PlaceRequest q{"alignment", true, pileup || consensus || pileup_records, min_depth, max_permille, place_out, nullptr, base_depth,
-                         place_records, pileup, consensus, pileup_records, nullptr, unplaced, keep, keep_bits, true, band, align_out, indels, align_records};
-    return placement_resident(ks, reads, threshold, mode, out_bits, stats, q);
+    return mf_align_gapped(ks, reads, threshold, mode, min_depth, max_permille, keep, band, out_bits, keep_bits, place_out, align_out, base_depth, place_records,
+                           pileup, consensus, pileup_records, indels, align_records, nullptr, nullptr, nullptr, nullptr, unplaced, stats);
 }
 
 int mf_align_gapped(const mf_kmerset *ks, const mf_reads *reads, uint32_t threshold, int mode, uint32_t min_depth, uint32_t max_permille, int keep, uint32_t band,
@@ -694,10 +690,11 @@ int mf_align_gapped(const mf_kmerset *ks, const mf_reads *reads, uint32_t thresh
                     mf_pileup_t *pileup, uint8_t *consensus, mf_pileup_record_t *pileup_records, mf_indel_t *indels, mf_align_record_t *align_records,
                     mf_pileup_t *ins_pile, uint8_t *gapped, uint64_t *gapped_starts, mf_gapped_record_t *gapped_records, uint64_t *unplaced, mf_filter_stats_t *stats)
 {
-    const bool gap = ins_pile || gapped || gapped_starts || gapped_records;
-    const PlaceRequest q{"alignment", true, pileup || consensus || pileup_records || gap, min_depth, max_permille, place_out, nullptr, base_depth,
-                         place_records, pileup, consensus, pileup_records, nullptr, unplaced, keep, keep_bits, true, band, align_out, indels, align_records,
-                         ins_pile, gapped, gapped_starts, gapped_records};
+    PlaceRequest q{"alignment", true, pileup || consensus || pileup_records || ins_pile || gapped || gapped_starts || gapped_records};
+    q.min_depth = min_depth; q.max_permille = max_permille; q.keep = keep; q.keep_bits = keep_bits; q.align = true; q.band = band;
+    q.place_out = place_out; q.align_out = align_out; q.base_depth = base_depth; q.place_records = place_records;
+    q.pileup = pileup; q.consensus = consensus; q.pileup_records = pileup_records; q.indels = indels; q.align_records = align_records;
+    q.ins_pile = ins_pile; q.gapped = gapped; q.gapped_starts = gapped_starts; q.gapped_records = gapped_records; q.unplaced = unplaced;
     return placement_resident(ks, reads, threshold, mode, out_bits, stats, q);
 }
 
@@ -924,8 +921,8 @@ int mf_filter_fastq_files_pileup(mf_kmerset *ks, const char *fq1, const char *fq
                                  mf_pileup_t *pileup, uint8_t *consensus, mf_pileup_record_t *records, uint64_t *unplaced,
                                  uint64_t *kept, uint64_t *total)
 {
-    PlaceRequest q{"the pile-up", false, true, min_depth};
-    q.pileup = pileup; q.consensus = consensus; q.pileup_records = records; q.unplaced = unplaced;
+    PlaceRequest q{"the pile-up", false, true};
+    q.min_depth = min_depth; q.pileup = pileup; q.consensus = consensus; q.pileup_records = records; q.unplaced = unplaced;
     return placement_files(ks, fq1, fq2, out1, out2, threshold, pair_mode, devices, n_devices, kept, total, q);
 }
 
@@ -935,8 +932,9 @@ int mf_filter_fastq_files_verified_keep(mf_kmerset *ks, const char *fq1, const c
                                         mf_pileup_record_t *pileup_records, mf_score_record_t *score_records, uint64_t *unplaced, uint64_t *kept,
                                         uint64_t *total)
 {
-    const PlaceRequest q{"verification", true, pileup || consensus || pileup_records, min_depth, max_permille, nullptr, nullptr, base_depth,
-                         place_records, pileup, consensus, pileup_records, score_records, unplaced, keep};
+    PlaceRequest q{"verification", true, pileup || consensus || pileup_records};
+    q.min_depth = min_depth; q.max_permille = max_permille; q.keep = keep; q.base_depth = base_depth; q.place_records = place_records;
+    q.pileup = pileup; q.consensus = consensus; q.pileup_records = pileup_records; q.score_records = score_records; q.unplaced = unplaced;
     return placement_files(ks, fq1, fq2, out1, out2, threshold, pair_mode, devices, n_devices, kept, total, q);
 }
 
@@ -946,9 +944,9 @@ int mf_filter_fastq_files_aligned(mf_kmerset *ks, const char *fq1, const char *f
                                   mf_pileup_record_t *pileup_records, mf_indel_t *indels, mf_align_record_t *align_records, uint64_t *unplaced,
                                   uint64_t *kept, uint64_t *total)
 {
-    const PlaceRequest q{"alignment", true, pileup || consensus || pileup_records, min_depth, max_permille, nullptr, nullptr, base_depth,
-                         place_records, pileup, consensus, pileup_records, nullptr, unplaced, keep, nullptr, true, band, nullptr, indels, align_records};
-    return placement_files(ks, fq1, fq2, out1, out2, threshold, pair_mode, devices, n_devices, kept, total, q);
+    return mf_filter_fastq_files_gapped(ks, fq1, fq2, out1, out2, threshold, pair_mode, devices, n_devices, min_depth, max_permille, keep, band, base_depth,
+                                        place_records, pileup, consensus, pileup_records, indels, align_records, nullptr, nullptr, nullptr, nullptr, unplaced,
+                                        kept, total);
 }
 
 int mf_filter_fastq_files_gapped(mf_kmerset *ks, const char *fq1, const char *fq2, const char *out1, const char *out2,
@@ -957,10 +955,10 @@ int mf_filter_fastq_files_gapped(mf_kmerset *ks, const char *fq1, const char *fq
                                  mf_pileup_record_t *pileup_records, mf_indel_t *indels, mf_align_record_t *align_records, mf_pileup_t *ins_pile, uint8_t *gapped,
                                  uint64_t *gapped_starts, mf_gapped_record_t *gapped_records, uint64_t *unplaced, uint64_t *kept, uint64_t *total)
 {
-    const bool gap = ins_pile || gapped || gapped_starts || gapped_records;
-    const PlaceRequest q{"alignment", true, pileup || consensus || pileup_records || gap, min_depth, max_permille, nullptr, nullptr, base_depth,
-                         place_records, pileup, consensus, pileup_records, nullptr, unplaced, keep, nullptr, true, band, nullptr, indels, align_records,
-                         ins_pile, gapped, gapped_starts, gapped_records};
+    PlaceRequest q{"alignment", true, pileup || consensus || pileup_records || ins_pile || gapped || gapped_starts || gapped_records};
+    q.min_depth = min_depth; q.max_permille = max_permille; q.keep = keep; q.align = true; q.band = band; q.base_depth = base_depth; q.place_records = place_records;
+    q.pileup = pileup; q.consensus = consensus; q.pileup_records = pileup_records; q.indels = indels; q.align_records = align_records;
+    q.ins_pile = ins_pile; q.gapped = gapped; q.gapped_starts = gapped_starts; q.gapped_records = gapped_records; q.unplaced = unplaced;
     return placement_files(ks, fq1, fq2, out1, out2, threshold, pair_mode, devices, n_devices, kept, total, q);
 }
 

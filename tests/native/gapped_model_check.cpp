@@ -1,4 +1,4 @@
-// The gapped consensus' scalar pieces (mitoflex_amd/csrc/mf_align.h) on the CPU, against cases that the plain-Python oracle
+// The gapped consensus' scalar pieces (mitoflex_amd/csrc/mf_align.h, mf_call.h) on the CPU, against cases that the plain-Python oracle
 // (tests/gapped_oracle.py) dumps.  Built by tests/test_gapped_model.py, once plain and once with -fsanitize=address,undefined: the
 // insertion pile is an exactly-sized heap array, so a store behind a position's own entries at the end of the bait stops the program.
 //

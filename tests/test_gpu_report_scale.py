@@ -33,7 +33,7 @@ pytestmark = pytest.mark.gpu
 
 K = 31
 HIST_MAX = 8192                  # mf_tally_dev.h: counters up to this gather in LDS
-SCORE_GATHERED = 33              # mf_score.h: rejected and the 32 bins of every record
+SCORE_GATHERED = 33              # mf_placelayout.h: rejected and the 32 bins of every record
 MAX_WAVES = 8192                 # 32 waves a CU on 256 CUs
 EDGE = 256 * TILE                # the first position of the scan's second turn over the tile sums
 
