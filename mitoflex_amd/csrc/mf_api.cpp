@@ -778,7 +778,7 @@ static int enqueue_pass(mf_reads *r, const KmerSetView &S, uint32_t thr, int mod
     const PassKnobs knobs{g_opt.pass, g_opt.finish_streams, g_opt.screen_streams, g_opt.split_pipe, g_opt.exact_co, g_opt.s8_finish};
     const PassInputs in{(int)S.prot, (int)S.s, (int)S.stride, (int)S.kw, (int)S.k, (int)S.s8_finish, thr, mode, count_all, overlap, more, r->fb, r->flip, r->cur, NSETS};
     const PassPlan P = plan_pass(knobs, in);
-    const int n_cu = ctx->n_cu, q = P.q; const bool finish = P.kind == PassKind::FINISH;
+    const int n_cu = ctx->n_cu, q = P.q; const bool finish = P.kind == PassKind::FINISH, quad = quad_records_for(P.kind, S);
     hipStream_t const streams[] = {ctx->stream, ctx->stream2, ctx->stream3, ctx->stream4}, ss = streams[(int)P.screen_on], sf = streams[(int)P.later_on];          // (PassStream's order)
     const hipEvent_t done = P.two_streams ? r->ev_finish[q] : nullptr;          // completes with the pass's last kernel
     KernelTiming tm[3]; const KernelTiming *t0 = nullptr, *t1 = nullptr, *t2 = nullptr;
@@ -792,7 +792,7 @@ static int enqueue_pass(mf_reads *r, const KmerSetView &S, uint32_t thr, int mod
         // (hipExtLaunchKernelGGL completion events); a separately recorded event costs the next dispatch ~5 us
         KernelTiming scr_done{nullptr, r->ev_screen[q]};
         HIPCHK(launch_screen(r->v, S, r->d_recs[q], r->d_rec_counts[q], n_cu, ss, t0 ? t0 : (P.two_streams ? &scr_done : nullptr),
-                             P.screen_clears_bits ? r->d_bits[q] : nullptr, P.screen_clears_bits ? ((r->v.n_reads + 31) / 32 + 3) / 4 : 0));
+                             P.screen_clears_bits ? r->d_bits[q] : nullptr, P.screen_clears_bits ? ((r->v.n_reads + 31) / 32 + 3) / 4 : 0, quad));
         if (P.two_streams) { if (t0) HIPCHK(hipEventRecord(r->ev_screen[q], ss)); HIPCHK(hipStreamWaitEvent(sf, r->ev_screen[q], 0)); }
     }
 #ifdef MF_DEBUG_KNOBS              // timing experiment: the pass without its finish kernels (WRONG result bits)
@@ -803,7 +803,7 @@ static int enqueue_pass(mf_reads *r, const KmerSetView &S, uint32_t thr, int mod
     else if (finish) {
         if (P.exact_behind_finish) { const int rc = clean_cand(r, q, sf); if (rc) return rc; }
         uint32_t *const cand = P.exact_behind_finish ? r->d_cand[q] : nullptr;
-        HIPCHK(launch_finish(r->v, S, r->d_recs[q], r->d_rec_counts[q], r->d_bits[q], tally_of(r, q), n_cu, sf, t2, cand ? nullptr : done, cand));
+        HIPCHK(launch_finish(r->v, S, r->d_recs[q], r->d_rec_counts[q], r->d_bits[q], tally_of(r, q), n_cu, sf, t2, cand ? nullptr : done, cand, quad));
         if (cand) HIPCHK(launch_exact(r->v, S, cand, 1, false, r->d_bits[q], nullptr, tally_of(r, q) + TallyLayout::region(2), n_cu, sf, nullptr, P.exact_coresident, done, true));
     } else {          // (hit counts come from the one-stream pass alone)
         uint32_t *const cand = P.needs_cand ? r->d_cand[q] : nullptr;

@@ -21,16 +21,21 @@ struct KernelTiming { hipEvent_t start, stop; };
 // screen = screen_kernel (records stage-1 positives) + mark_kernel (finishes them, sets candidate bits)
 uint64_t screen_grid_for(const ReadsView &R, int n_cu, int stride);
 uint64_t screen_rec_cap_for(const ReadsView &R, int n_cu, int stride);          // 16-byte records per screen workgroup
+// quad records (one record per four lanes of the screen): the plain LDS-table screen at stride 16 can emit them and only the finish
+// kernels read them, so a pass uses them when it is a FINISH pass of such a set.  The screen and the finish launch of a pass take the same choice.
+inline bool quad_records_fit(const KmerSetView &S) { return S.stride == 16 && S.front_mode == 0; }
+inline bool quad_records_for(PassKind kind, const KmerSetView &S) { return kind == PassKind::FINISH && quad_records_fit(S); }
 // clear (optional): a result bitmap of clear_vec4 uint4 that the screen zeroes on the side (for the pass after this one)
 hipError_t launch_screen(const ReadsView &R, const KmerSetView &S, void *recs, uint32_t *rec_counts, int n_cu, hipStream_t st,
-                         const KernelTiming *tm = nullptr, uint32_t *clear = nullptr, uint64_t clear_vec4 = 0);
+                         const KernelTiming *tm = nullptr, uint32_t *clear = nullptr, uint64_t clear_vec4 = 0, bool quad = false);
 // threshold 1, no hit counts: two launches of finish_kernel (runs, then the rest) settle every stage-1 record and set the pass
 // bits (bits must be clean).  partials: a pass's tally block (TallyLayout: phase 0, phase 1, the exact kernel behind them).
 // done (optional): an event that completes with the last finish kernel
 // cand (optional): a clean candidate bitmap -- phase 1 then marks the reads that hold a bait s-mer outside any run instead of counting their windows itself, and
 // the caller runs launch_exact(cand, thr = 1, merge = true) behind it (third tally region)
 hipError_t launch_finish(const ReadsView &R, const KmerSetView &S, const void *recs, const uint32_t *rec_counts, uint32_t *bits,
-                         unsigned long long *partials, int n_cu, hipStream_t st, const KernelTiming *tm = nullptr, hipEvent_t done = nullptr, uint32_t *cand = nullptr);
+                         unsigned long long *partials, int n_cu, hipStream_t st, const KernelTiming *tm = nullptr, hipEvent_t done = nullptr, uint32_t *cand = nullptr,
+                         bool quad = false);
 hipError_t launch_mark(const ReadsView &R, const KmerSetView &S, const void *recs, const uint32_t *rec_counts, uint32_t *cand, int n_cu,
                        hipStream_t st, const KernelTiming *tm = nullptr);
 hipError_t launch_exact(const ReadsView &R, const KmerSetView &S, uint32_t *cand, uint32_t thr, bool count_all,

@@ -5,6 +5,11 @@
 //                   positive only RECORDS it (16 bytes: chunk, lane, hit mask) -- no dependent load, no returning
 //                   atomic, no division in the streaming loop.  Pure integer/indexing work, HBM-bound by design: persistent
 //                   workgroups on seven CUs out of eight (stride 16; every CU for the VALU-bound stride-8 geometries).
+//                   QUAD RECORDS (a threshold-1 pass of a stride-16 set behind this plain LDS-table screen -- quad_records_for,
+//                   mf_kernels.h): lanes 4j .. 4j+3 hold 64 contiguous bytes of a row, so the quad ORs its four hit masks into
+//                   one word with two DPP moves and its first lane writes ONE record: about half as many records for a bait
+//                   read, 27 % fewer finish round trips at the benchmark's mix.  Every other pass kind and screen keeps one
+//                   record per lane.
 //   finish_kernel   threshold 1, no hit counts (the default pass): one thread per record, two launches.  Phase 0 tries the
 //                   first run of neighbouring positives of every record -- one canonical k-mer, one probe of the
 //                   open-address bait table; phase 1 settles what is left (exact s-mer table, then the sixteen windows a
@@ -131,10 +136,25 @@ __device__ __forceinline__ uint32_t canon_key(uint32_t x, uint32_t smask, uint32
 // One per (lane, chunk) that saw at least one positive.  Sample i of the lane's chunk slice
 // (i = (u*4+q)*SPW+j) is bit NS-1-i of hitmask, NS = U*4*SPW.
 struct __attribute__((aligned(16))) ScreenRec { uint32_t chunk, tid, hitmask, pad; };
+// A QUAD record (screen_kernel<.., QUAD = true>; stride 16) stands for the four lanes tid .. tid+3 of a wave, whose pieces are 64 contiguous
+// bytes of each row u: lane tid+l's eight bits, as above, are byte 3-l of hitmask.
+constexpr int QUAD_LANES = 4;
+// the same samples row by row, as they lie in the stream: sample i of row u (256 bases; i = 4l + q) is bit 31 - 16u - i
+__host__ __device__ __forceinline__ uint32_t quad_rows(uint32_t h)
+{
+    return (h & 0xF000000Fu) | ((h & 0x00F00000u) << 4) | ((h & 0x0000F000u) << 8) | ((h & 0x000000F0u) << 12)
+         | ((h & 0x0F000000u) >> 12) | ((h & 0x000F0000u) >> 8) | ((h & 0x00000F00u) >> 4);
+}
 
 // SPW: samples per word (stride 16 -> 1, stride 8 -> 2).  For s < 16 a sample is the low 2s bits of what is hashed; the bits
 // above them ride along (stage1_index_lo in mf_common.h).
-template <int SPW, int U, int CANON = 0>
+//
+// QUAD (stride 16, threshold-1 passes through the finish kernels): one record per FOUR lanes.  Lanes 4j .. 4j+3 of a wave hold 64 contiguous
+// bytes of each row u (v = c*chunk + u*blockDim.x + tid), 256 bases, so a 150-base bait read that used to show in 3.3 lane records shows in
+// about half as many quad records -- and every record is a thread in both finish launches.  The loads are untouched: each lane shifts its eight
+// bits into its byte of a word, two DPP quad_perm moves OR the word across the quad, and the quad's first lane records it (tid = that lane).
+// No LDS traffic for the exchange: the LDS pipe is the busier unit of this loop.
+template <int SPW, int U, int CANON = 0, bool QUAD = false>
 __global__ void __launch_bounds__(1024)
 screen_kernel(ReadsView R, KmerSetView S, ScreenRec *__restrict__ recs, uint32_t rec_cap, uint32_t *__restrict__ rec_counts,
               uint4 *__restrict__ clear, uint64_t clear_vec4)
@@ -182,6 +202,14 @@ screen_kernel(ReadsView R, KmerSetView S, ScreenRec *__restrict__ recs, uint32_t
                     hitmask = alignbit(hitmask, t, 31);             // (hitmask << 1) | sign(t)
                 }
             }
+        }
+        if (QUAD) {
+            static_assert(!QUAD || (SPW == 1 && QUAD_LANES * U * 4 * SPW <= 32), "a quad's samples fill one 32-bit mask");
+            // (unconditional: every lane of the quad takes part in the DPP reads; stage1 is called in block-uniform control flow)
+            hitmask <<= 8u * (~threadIdx.x & 3u);
+            hitmask |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)hitmask, 0xB1, 0xF, 0xF, true);          // quad_perm:[1,0,3,2]
+            hitmask |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)hitmask, 0x4E, 0xF, 0xF, true);          // quad_perm:[2,3,0,1]
+            if ((threadIdx.x & 3u) != 0) hitmask = 0;
         }
         if (hitmask) {
             const uint32_t slot = atomicAdd(&s_nrec, 1u);
@@ -1194,11 +1222,20 @@ __device__ __forceinline__ bool sample_item(const ReadsView &R, const KmerSetVie
 //  PHASE 1, THE REST  every read a run has passed is known now (kernel boundary), so a record's remaining positives mostly
 //                     end at one look at their read's bit.  What is left (mostly stage-1 false positives) is looked up in the
 //                     exact s-mer table, and a true bait s-mer outside any run gets its sixteen windows counted (sample_item).
+#ifndef MF_QUAD_LEFT
+#define MF_QUAD_LEFT 1              // (an experiment build turns the rule off for quad records: profiles/r07/quad_records_ab.txt)
+#endif
 constexpr int FINISH_BLOCK = 256;
 constexpr int FINISH_GRID = 1024;            // one tally pair per workgroup in the first half of the tally buffer (MF_FINISH_GRID: up to EXACT_MAX_GRID; 2048 measured the same)
 static_assert(FINISH_GRID <= EXACT_MAX_GRID, "tally buffer");          // phase 1's pairs go to the second half
 
-template <int SPW, int U, int KW, int PHASE>
+//
+// QUAD: the records are the screen's quad records.  A record row is the sixteen consecutive samples (256 bases) of four lanes, so the same
+// shift-and-AND finds the runs across the lane borders inside a quad, and a 150-base bait read costs about half the finish threads.  Two rules
+// above are optimisations whose reach changes: "a run start is left to the record on the left" now looks at the quad on the left (tid - 4), and
+// the k > 32 continuation into the next record is dropped (a row holds sixteen samples, a run three or four: the few reads whose every run
+// crosses a quad border go to phase 1).  Exactness depends on neither: phase 1 examines every positive of a read that has not passed.
+template <int SPW, int U, int KW, int PHASE, bool QUAD = false>
 __global__ void __launch_bounds__(FINISH_BLOCK)
 finish_kernel(ReadsView R, KmerSetView S, const ScreenRec *__restrict__ recs, uint32_t rec_cap, const uint32_t *__restrict__ rec_counts,
               uint32_t n_lists, uint32_t screen_block, uint32_t *__restrict__ bits, unsigned long long *__restrict__ partials, uint32_t *__restrict__ cand)
@@ -1223,14 +1260,17 @@ finish_kernel(ReadsView R, KmerSetView S, const ScreenRec *__restrict__ recs, ui
         __syncthreads();
     }
     const uint32_t total = s_pre[n_lists];
-    constexpr int NSAMP = U * 4 * SPW, SPP = 4 * SPW;
+    static_assert(!QUAD || (SPW == 1 && U == 2), "quad records: stride 16, two rows of sixteen samples (quad_rows)");
+    constexpr int LPR = QUAD ? QUAD_LANES : 1;                        // lanes a record stands for
+    constexpr int SPP = 4 * SPW * LPR, NSAMP = U * SPP;               // samples of a contiguous piece (a record row), of a record
+    constexpr uint32_t ROW_MASK = (1u << SPP) - 1u;
     const int k = S.k;
     const uint32_t smask = S.smask;
     const bool fast = R.len_magic32 != 0;
     const uint64_t chunk_bases = (uint64_t)screen_block * U * 64;
     const uint64_t mask_lo = (KW == 1 && k < 32) ? (1ULL << (2 * k)) - 1 : ~0ULL;
     const uint64_t mask_hi = KW == 2 ? (1ULL << (2 * k - 64)) - 1 : 0;
-    // a run of n_adj samples covers s + (n_adj - 1) * stride >= k bases; its samples lie in one 16-byte piece of the recording lane
+    // a run of n_adj samples covers s + (n_adj - 1) * stride >= k bases; its samples lie in one piece of the record (16 bytes of the recording lane; QUAD: 64 of the quad)
     const uint32_t n_adj = (uint32_t)((S.k - S.s + S.stride - 1) / S.stride) + 1;
     const uint32_t run_span = (uint32_t)S.s + (n_adj - 1) * (uint32_t)S.stride;
     uint32_t run_ok = 0;                              // bits whose sample has n_adj - 1 successors inside its piece
@@ -1255,11 +1295,11 @@ finish_kernel(ReadsView R, KmerSetView S, const ScreenRec *__restrict__ recs, ui
         const uint64_t cb = (uint64_t)rec.chunk * chunk_bases;
         uint64_t rq = 0; uint32_t rrem = 0;
         if (fast) { rq = __umul64hi(cb, R.len_magic); rrem = (uint32_t)(cb - rq * R.uniform_len); }
-        uint32_t m = rec.hitmask;
+        uint32_t m = QUAD ? quad_rows(rec.hitmask) : rec.hitmask;
         uint32_t runs = m & run_ok;                   // bit B (sample i) starts a run iff bits B, B-1, ..., B-(n_adj-1) are set (ragged reads too: whether a run lies
                                                       // inside one read is looked up through the offsets' block index where it is taken up)
         for (uint32_t j = 1; j < n_adj; j++) runs &= m << j;
-        if (PHASE == 0 && SPW == 1 && KW == 2 && fast) {
+        if (PHASE == 0 && SPW == 1 && KW == 2 && fast && !QUAD) {
             // Runs across the lane border (k > 32; for shorter k a run is two samples and the extra arithmetic does not pay): the records of a list are in lane order, so the next record is usually the next lane
             // of the same chunk, whose 16-byte pieces follow this lane's in the stream.  A run may then start in this lane's
             // piece and end in that one's (a run of k > 32 is three or four samples long and rarely fits one piece: 0.252 -> 0.237 ms
@@ -1281,10 +1321,10 @@ finish_kernel(ReadsView R, KmerSetView S, const ScreenRec *__restrict__ recs, ui
         // run start of its own inside the same read.  (Should that one fail -- rare: its two samples are bait s-mers -- the read
         // goes to phase 1, which looks at every positive.)
         uint32_t lf_runs = 0; bool lf = false;
-        if (PHASE == 0 && SPW == 1) {
+        if (PHASE == 0 && SPW == 1 && (!QUAD || MF_QUAD_LEFT)) {
             const uint32_t lc = __shfl_up(rec.chunk, 1), lt = __shfl_up(rec.tid, 1);
             lf_runs = __shfl_up(runs, 1);
-            lf = (threadIdx.x & 63) != 0 && lc == rec.chunk && lt + 1 == rec.tid;
+            lf = (threadIdx.x & 63) != 0 && lc == rec.chunk && lt + LPR == rec.tid;
         }
         if (PHASE == 0) m = runs; else runs = 0;      // phase 0 looks at run starts only, phase 1 at every positive on its own
         uint64_t passed_r = ~0ULL, passed_r2 = ~0ULL; // the last two reads this record has passed
@@ -1300,7 +1340,7 @@ finish_kernel(ReadsView R, KmerSetView S, const ScreenRec *__restrict__ recs, ui
                 const int bit = 31 - __clz(m);
                 m &= ~(1u << bit);
                 const int idx = NSAMP - 1 - bit;
-                const int sj = idx % SPW, sq = (idx / SPW) & 3, su = idx / (4 * SPW);
+                const int sj = idx % SPW, sq = (idx / SPW) % (4 * LPR), su = idx / SPP;          // (QUAD: sq counts through the quad's four lanes)
                 const uint32_t off = ((((uint32_t)su * screen_block + rec.tid) * 4 + sq) << 4) + (uint32_t)sj * 8;
                 g0 = cb + off;
                 const uint32_t span = is_run ? run_span : (uint32_t)S.s;        // bases that have to lie inside one read
@@ -1312,10 +1352,10 @@ finish_kernel(ReadsView R, KmerSetView S, const ScreenRec *__restrict__ recs, ui
                     if (offr + span > R.uniform_len || g0 + span > R.total_bases) continue;
                     r = rq + dq;
                     if (PHASE == 0 && SPW == 1 && lf) {
-                        const uint32_t nib = (lf_runs >> (4 * (U - 1 - su))) & 15u;           // the left lane's run starts in the same piece row
+                        const uint32_t nib = (lf_runs >> (SPP * (U - 1 - su))) & ROW_MASK;    // the left record's run starts in the same piece row
                         if (nib) {
-                            const int qn = 3 - (__ffs(nib) - 1);                               // the one nearest to this lane
-                            if ((uint32_t)(64 + 16 * (sq - qn)) <= offr) continue;             // ... lies inside this read: that lane's job
+                            const int qn = SPP - 1 - (__ffs(nib) - 1);                         // the one nearest to this record
+                            if ((uint32_t)(16 * (SPP + sq - qn)) <= offr) continue;            // ... lies inside this read: that record's job
                         }
                     }
                 } else {
@@ -1328,10 +1368,10 @@ finish_kernel(ReadsView R, KmerSetView S, const ScreenRec *__restrict__ recs, ui
                     r = read_holding(R, g0, span, &r_start);
                     if (r == ~0ULL) continue;
                     if (PHASE == 0 && SPW == 1 && lf) {                                          // (as above, with the sample's offset inside its read looked up)
-                        const uint32_t nib = (lf_runs >> (4 * (U - 1 - su))) & 15u;
+                        const uint32_t nib = (lf_runs >> (SPP * (U - 1 - su))) & ROW_MASK;
                         if (nib) {
-                            const int qn = 3 - (__ffs(nib) - 1);
-                            if ((uint64_t)(64 + 16 * (sq - qn)) <= g0 - r_start) continue;
+                            const int qn = SPP - 1 - (__ffs(nib) - 1);
+                            if ((uint64_t)(16 * (SPP + sq - qn)) <= g0 - r_start) continue;
                         }
                     }
                 }
@@ -1847,7 +1887,7 @@ template <auto Kernel> static void raise_lds_limit_once(size_t max_bytes)
 
 template <int SPW, int CANON>
 static void launch_screen_spw(const ReadsView &R, const KmerSetView &S, void *recs, uint32_t *rec_counts, int n_cu, hipStream_t st,
-                              const KernelTiming *tm, uint32_t *clear, uint64_t clear_vec4)
+                              const KernelTiming *tm, uint32_t *clear, uint64_t clear_vec4, bool quad)
 {
     const int key = screen_grid_key(S.stride, S.front_mode, S.canon);
     const uint64_t grid = screen_grid_for(R, n_cu, key);
@@ -1880,6 +1920,12 @@ static void launch_screen_spw(const ReadsView &R, const KmerSetView &S, void *re
         return;
     }
     const size_t lds1 = (sizeof(uint32_t) << S.bloom_log2w) + 16;
+    if constexpr (SPW == 1) if (quad) {          // one record per four lanes, for the finish kernels' quad variant
+        raise_lds_limit_once<&screen_kernel<SPW, SCREEN_U, CANON, true>>(128 * 1024 + 16);
+        MF_LAUNCH((screen_kernel<SPW, SCREEN_U, CANON, true>), dim3((unsigned)grid), dim3(SCREEN_BLOCK), lds1, st, tm, R, S,
+                  static_cast<ScreenRec *>(recs), cap, rec_counts, reinterpret_cast<uint4 *>(clear), clear ? clear_vec4 : (uint64_t)0);
+        return;
+    }
     raise_lds_limit_once<&screen_kernel<SPW, SCREEN_U, CANON>>(128 * 1024 + 16);
     MF_LAUNCH((screen_kernel<SPW, SCREEN_U, CANON>), dim3((unsigned)grid), dim3(SCREEN_BLOCK), lds1, st, tm, R, S,
               static_cast<ScreenRec *>(recs), cap, rec_counts, reinterpret_cast<uint4 *>(clear), clear ? clear_vec4 : (uint64_t)0);
@@ -1900,20 +1946,22 @@ static void launch_mark_spw(const ReadsView &R, const KmerSetView &S, const void
 }
 
 hipError_t launch_screen(const ReadsView &R, const KmerSetView &S, void *recs, uint32_t *rec_counts, int n_cu, hipStream_t st,
-                         const KernelTiming *tm, uint32_t *clear, uint64_t clear_vec4)
+                         const KernelTiming *tm, uint32_t *clear, uint64_t clear_vec4, bool quad)
 {
+    if (quad && !quad_records_fit(S)) return hipErrorInvalidValue;
     // (canonical keys: KmerSetView::canon is 1 for sixteen-base samples, 2 for shorter ones)
-    if (S.stride == 16 && S.canon == 1) launch_screen_spw<1, 1>(R, S, recs, rec_counts, n_cu, st, tm, clear, clear_vec4);
-    else if (S.stride == 16 && S.canon) launch_screen_spw<1, 2>(R, S, recs, rec_counts, n_cu, st, tm, clear, clear_vec4);
-    else if (S.stride == 16) launch_screen_spw<1, 0>(R, S, recs, rec_counts, n_cu, st, tm, clear, clear_vec4);
-    else if (S.canon) launch_screen_spw<2, 2>(R, S, recs, rec_counts, n_cu, st, tm, clear, clear_vec4);
-    else launch_screen_spw<2, 0>(R, S, recs, rec_counts, n_cu, st, tm, clear, clear_vec4);
+    if (S.stride == 16 && S.canon == 1) launch_screen_spw<1, 1>(R, S, recs, rec_counts, n_cu, st, tm, clear, clear_vec4, quad);
+    else if (S.stride == 16 && S.canon) launch_screen_spw<1, 2>(R, S, recs, rec_counts, n_cu, st, tm, clear, clear_vec4, quad);
+    else if (S.stride == 16) launch_screen_spw<1, 0>(R, S, recs, rec_counts, n_cu, st, tm, clear, clear_vec4, quad);
+    else if (S.canon) launch_screen_spw<2, 2>(R, S, recs, rec_counts, n_cu, st, tm, clear, clear_vec4, quad);
+    else launch_screen_spw<2, 0>(R, S, recs, rec_counts, n_cu, st, tm, clear, clear_vec4, quad);
     return hipGetLastError();
 }
 
 hipError_t launch_finish(const ReadsView &R, const KmerSetView &S, const void *recs, const uint32_t *rec_counts, uint32_t *bits,
-                         unsigned long long *partials, int n_cu, hipStream_t st, const KernelTiming *tm, hipEvent_t done, uint32_t *cand)
+                         unsigned long long *partials, int n_cu, hipStream_t st, const KernelTiming *tm, hipEvent_t done, uint32_t *cand, bool quad)
 {
+    if (quad && !quad_records_fit(S)) return hipErrorInvalidValue;
     const int key = screen_grid_key(S.stride, S.front_mode, S.canon);
     const uint64_t lists = screen_grid_for(R, n_cu, key);
     if (lists == 0) {               // (an empty read set) nothing to settle: the tallies read zero and `done` still completes, as in launch_exact
@@ -1930,13 +1978,14 @@ hipError_t launch_finish(const ReadsView &R, const KmerSetView &S, const void *r
     bool done_attached = false;
     if (done && !tm1) { tm1 = &last; done_attached = true; }
     static const unsigned fgrid = std::min<unsigned>(EXACT_MAX_GRID, std::max<unsigned>(64, getenv("MF_FINISH_GRID") ? (unsigned)atoi(getenv("MF_FINISH_GRID")) : FINISH_GRID));
-#define MF_LAUNCH_FINISH(SPW, KW) do { \
-        MF_LAUNCH((finish_kernel<SPW, SCREEN_U, KW, 0>), dim3(fgrid), dim3(FINISH_BLOCK), 0, st, tm0, R, S, rc, cap, rec_counts, \
+#define MF_LAUNCH_FINISH(SPW, KW, QUAD) do { \
+        MF_LAUNCH((finish_kernel<SPW, SCREEN_U, KW, 0, QUAD>), dim3(fgrid), dim3(FINISH_BLOCK), 0, st, tm0, R, S, rc, cap, rec_counts, \
                   (uint32_t)lists, (uint32_t)SCREEN_BLOCK, bits, partials, cand); \
-        MF_LAUNCH((finish_kernel<SPW, SCREEN_U, KW, 1>), dim3(fgrid), dim3(FINISH_BLOCK), 0, st, tm1, R, S, rc, cap, rec_counts, \
+        MF_LAUNCH((finish_kernel<SPW, SCREEN_U, KW, 1, QUAD>), dim3(fgrid), dim3(FINISH_BLOCK), 0, st, tm1, R, S, rc, cap, rec_counts, \
                   (uint32_t)lists, (uint32_t)SCREEN_BLOCK, bits, partials, cand); } while (0)
-    if (S.stride == 16) { if (S.kw == 1) MF_LAUNCH_FINISH(1, 1); else MF_LAUNCH_FINISH(1, 2); }
-    else                { if (S.kw == 1) MF_LAUNCH_FINISH(2, 1); else MF_LAUNCH_FINISH(2, 2); }
+    if (quad)                { if (S.kw == 1) MF_LAUNCH_FINISH(1, 1, true); else MF_LAUNCH_FINISH(1, 2, true); }
+    else if (S.stride == 16) { if (S.kw == 1) MF_LAUNCH_FINISH(1, 1, false); else MF_LAUNCH_FINISH(1, 2, false); }
+    else                     { if (S.kw == 1) MF_LAUNCH_FINISH(2, 1, false); else MF_LAUNCH_FINISH(2, 2, false); }
 #undef MF_LAUNCH_FINISH
     if (done && !done_attached) (void)hipEventRecord(done, st);
     return hipGetLastError();
