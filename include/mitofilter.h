@@ -374,7 +374,8 @@ int mf_filter_fastq_files_placed(mf_kmerset *ks, const char *fq1, const char *fq
  * coordinate c = start + i for strand 0 and c = start + (L - 1 - i) for strand 1; on strand 1 the letter is complemented, so counts are
  * always in the bait's forward letters.  The base is counted when 0 <= c < len_j and it is a valid letter: an invalid read base (N)
  * counts nowhere, and a base that hangs over either end of the record counts nowhere -- in particular NOT in the neighbouring record,
- * although global positions are contiguous.  Reads that are ambiguous, unplaced or not passing contribute nothing.  Invalid bait
+ * although global positions are contiguous (only the extended calls below pile such bases, in a table of their own).  Reads that are
+ * ambiguous, unplaced or not passing contribute nothing.  Invalid bait
  * positions still receive counts.  There is no handling of indels or clipping: behind an insertion the shifted bases pile up as
  * mismatches.  The result is four uint32_t per position of the set, mf_pileup_t { a, c, g, t }, each clamped at 0xFFFFFFFE.
  * a + c + g + t at a position is at most the position's base depth (mf_place); the two are equal where no covering read has an N there.
@@ -577,6 +578,49 @@ int mf_filter_fastq_files_gapped(mf_kmerset *ks, const char *fq1, const char *fq
               uint32_t band, uint32_t *base_depth, mf_place_record_t *place_records, mf_pileup_t *pileup, uint8_t *consensus,
               mf_pileup_record_t *pileup_records, mf_indel_t *indels, mf_align_record_t *align_records, mf_pileup_t *ins_pile, uint8_t *gapped,
               uint64_t *gapped_starts, mf_gapped_record_t *gapped_records, uint64_t *unplaced, uint64_t *kept, uint64_t *total);
+
+/* ---- extended records: the gapped calls with the bases that hang over a record's ends piled up, and both ends called.
+ * mf_align_extended and mf_filter_fastq_files_extended are mf_align_gapped and mf_filter_fastq_files_gapped with `extend` behind `band`
+ * and four outputs behind gapped_records, each optional.  extend is E, 0 <= E <= MF_EXTEND_MAX; more is MF_E_ARG.  With extend == 0 the
+ * four must be NULL (else MF_E_ARG) and the calls ARE the gapped ones: nothing more is allocated, the same kernels run, the same bits
+ * come back.  Asking for any of the four implies the pile-up counters and the gapped consensus, asked for or not.  Band, cut, keep rule
+ * and placement are exactly the gapped calls'; band 0 is allowed (the path is then the placement's diagonal).  Nucleotide sets only.
+ * ABI 5 still.  Nothing above changes: base depth, pile-up and over_begin / over_end count what they counted.
+ * The rule.
+ *   Extension pile.  An ACCEPTED read's DIAGONAL step that puts oriented read base x[i] on record coordinate c with c < 0 or c >= len_j
+ *   has the offset e = -1 - c at the begin (side 0) and e = c - len_j at the end (side 1); e = 0 is the column next to the record.  When
+ *   e < E and x[i] is a valid letter the step adds 1 at ext_pile[(2 j + side) * E + e][letter], in the bait's forward letters as
+ *   everywhere.  An N adds nowhere and its column is not shifted; insertion and deletion steps outside [0, len) add nowhere; steps with
+ *   e >= E add nowhere; rejected, ambiguous, unplaced and non-passing reads add nothing.  A base beyond record j's end goes to j's end
+ *   table, never to the neighbouring record, although global positions are contiguous.  Output: mf_pileup_t[R * 2 * E], clamped at
+ *   0xFFFFFFFE; the call below goes by the unclamped sums.
+ *   For every record and e, the four counts at end offset e sum to at most the number of the record's accepted reads with
+ *   ref_end - len_j > e (begin: -ref_begin > e), and to exactly that where no overhanging base is an N.
+ *   Call.  Per record and side, for e = 0, 1, ..: n_e is the sum of the four counts at offset e; column e is emitted iff
+ *   n_e >= min_depth and exactly one letter has the largest count, and emission stops at the first e that is not emitted.  A tie emits
+ *   nothing and stops the end: an N at a growing end would only break the next generation's k-mers.  The byte is that letter in upper case.
+ *   Result.  extended holds, for every record in order: the emitted begin columns from the farthest to e = 0, then the record's bytes
+ *   of the gapped consensus of the same call (at band 0 the plain consensus), then the emitted end columns from e = 0 up.
+ *   extended_starts: R + 1 offsets into extended.  mf_extend_record_t per record: begin_bases and end_bases are the emitted columns,
+ *   begin_piled and end_piled the unclamped sum of all counts of that end's table, length == gapped length + begin_bases + end_bases.
+ *   The caller's buffer of positions * (1 + 2 * band) + 2 * R * E bytes is always enough.
+ * File level: the counters add over mates, batches and devices before they are clamped; the call is made once, from the sums.
+ * Device memory: 2 * E * 4 64-bit counters a record behind the insertion pile (256 KB a record at E = 4096); where they cannot be
+ * allocated the call returns MF_E_NOMEM and names the size. */
+#define MF_EXTEND_MAX 4096
+typedef struct { uint64_t length, begin_bases, end_bases, begin_piled, end_piled; } mf_extend_record_t;
+int mf_align_extended(const mf_kmerset *ks, const mf_reads *reads, uint32_t threshold, int mode, uint32_t min_depth, uint32_t max_permille,
+              int keep, uint32_t band, uint32_t extend, uint32_t *out_bits, uint32_t *keep_bits, mf_place_t *place_out, mf_align_t *align_out,
+              uint32_t *base_depth, mf_place_record_t *place_records, mf_pileup_t *pileup, uint8_t *consensus, mf_pileup_record_t *pileup_records,
+              mf_indel_t *indels, mf_align_record_t *align_records, mf_pileup_t *ins_pile, uint8_t *gapped, uint64_t *gapped_starts,
+              mf_gapped_record_t *gapped_records, mf_pileup_t *ext_pile, uint8_t *extended, uint64_t *extended_starts,
+              mf_extend_record_t *extend_records, uint64_t *unplaced, mf_filter_stats_t *stats);
+int mf_filter_fastq_files_extended(mf_kmerset *ks, const char *fq1, const char *fq2, const char *out1, const char *out2,
+              uint32_t threshold, int pair_mode, const int *devices, int n_devices, uint32_t min_depth, uint32_t max_permille, int keep,
+              uint32_t band, uint32_t extend, uint32_t *base_depth, mf_place_record_t *place_records, mf_pileup_t *pileup, uint8_t *consensus,
+              mf_pileup_record_t *pileup_records, mf_indel_t *indels, mf_align_record_t *align_records, mf_pileup_t *ins_pile, uint8_t *gapped,
+              uint64_t *gapped_starts, mf_gapped_record_t *gapped_records, mf_pileup_t *ext_pile, uint8_t *extended, uint64_t *extended_starts,
+              mf_extend_record_t *extend_records, uint64_t *unplaced, uint64_t *kept, uint64_t *total);
 
 /* Options that select which kernels a filter pass runs (process-wide; every variant gives the same bits and is parity-tested):
  *   pass=default|split|serial   adapt=0|1   finish_streams=0|1|2   screen_streams=1|2   split_pipe=0|1   exact_co=0|1

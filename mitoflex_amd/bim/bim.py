@@ -139,7 +139,7 @@ def kmer_bait_map(threads: int, fasta_file: str, basedir: str, prefix: str,
                   fastq1: str, fastq2: Optional[str], quality: int = 30,
                   kmer: int = 31, threshold: int = 1, devices: int = 1, anchors: str = "host",
                   max_permille: Optional[int] = None, keep: Optional[int] = None, band: Optional[int] = None,
-                  gapped: bool = False) -> Tuple[str, str, Optional[str]]:
+                  gapped: bool = False, extend: int = 0) -> Tuple[str, str, Optional[str]]:
     """Drop-in for `bwa_map`: returns (stats, fq1, fq2).  `stats` stands where the BAM path was and is what `cal_insert`
     takes; `threads` and `quality` are accepted for signature compatibility and ignored.  anchors: "host" estimates the insert
     sizes in Python from the first anchor of each mate of a sample of the kept pairs; "device" places every kept mate on the GPU
@@ -152,10 +152,13 @@ def kmer_bait_map(threads: int, fasta_file: str, basedir: str, prefix: str,
     (mitofilter.filter_fastq_files_aligned): a mate with a true indel against the bait costs its indel's bases, not the mismatches
     behind it, and is kept under a tight cut.  None keeps today's calls.
     gapped: with band, the aligning call is the gapped one (mitofilter.filter_fastq_files_aligned(gapped=True)); the files it writes are
+    the same.  Without band it is a ValueError.
+    extend: with band, the aligning call is the extending one (mitofilter.filter_fastq_files_aligned(extend=E)); the files it writes are
     the same.  Without band it is a ValueError."""
     from mitoflex_amd import mitofilter as mf
     if gapped and band is None:
         raise ValueError("gapped needs a band: the gapped consensus comes from the banded alignment")
+    _check_extend(extend, band)
     if anchors not in ("host", "device"):
         raise ValueError('anchors is "host" or "device"')
     if max_permille is not None and not 0 <= int(max_permille) <= 1000:
@@ -174,7 +177,7 @@ def kmer_bait_map(threads: int, fasta_file: str, basedir: str, prefix: str,
                                            max_permille=1000 if max_permille is None else int(max_permille), keep=keep)
         else:
             mf.filter_fastq_files_aligned(ks, fastq1, fastq2, fq1, fq2, int(band), threshold, mf.PAIR_EITHER, n_devices=devices, pileup=False,
-                                          max_permille=1000 if max_permille is None else int(max_permille), keep=keep, gapped=bool(gapped))
+                                          max_permille=1000 if max_permille is None else int(max_permille), keep=keep, extend=int(extend), gapped=bool(gapped))
     finally:
         ks.close()
     stats = path.join(basedir, prefix + ".bait.stats")
@@ -192,8 +195,16 @@ def _check_band(band: Optional[int], kmer: int):
         raise ValueError("band is a number from 0 to 31 and below kmer")
 
 
+def _check_extend(extend: int, band: Optional[int]):
+    if not 0 <= int(extend) <= 4096:
+        raise ValueError("extend is a number from 0 to 4096")
+    if int(extend) and band is None:
+        raise ValueError("extend needs a band: the overhanging bases get their columns from the banded alignment")
+
+
 def consensus_bait(fasta_file: str, fq1: str, fq2: Optional[str], out_fasta: str, kmer: int = 31, min_depth: int = 3,
-                   max_permille: Optional[int] = None, band: Optional[int] = None, gapped: bool = False):
+                   max_permille: Optional[int] = None, band: Optional[int] = None, gapped: bool = False,
+                   extend: int = 0):
     """A polished bait for the next generation: the reads of (fq1, fq2) -- the kept reads of a bait step -- are placed on the bait
     `fasta_file` and piled up on the device (mitofilter.filter_fastq_files_pileup), and the consensus is written to `out_fasta` under the
     bait's record names: the reads' letter where at least `min_depth` bases agree on one, N where the most is tied, the bait's own
@@ -208,10 +219,14 @@ def consensus_bait(fasta_file: str, fq1: str, fq2: Optional[str], out_fasta: str
     today's calls.
     gapped: with band, the GAPPED consensus is written instead (include/mitofilter.h, gapped consensus): a position that more than half
     of its covering reads delete is left out, the bases that more than half of them insert behind a position are written behind it, and
-    the polished bait has the sample's length and coordinates.  Without band it is a ValueError."""
+    the polished bait has the sample's length and coordinates.  Without band it is a ValueError.
+    extend: with band (band 0 too), the EXTENDED records are written instead (include/mitofilter.h, extended records): every record's
+    gapped consensus between the columns that the reads overhanging its ends agree on, up to `extend` (at most 4096) a side, so that the
+    next generation's bait reaches reads the old ends shared no k-mer with.  Without band it is a ValueError."""
     from mitoflex_amd import mitofilter as mf
     if gapped and band is None:
         raise ValueError("gapped needs a band: the gapped consensus comes from the banded alignment")
+    _check_extend(extend, band)
     if min_depth < 1:
         raise ValueError("min_depth is at least 1")
     if max_permille is not None and not 0 <= int(max_permille) <= 1000:
@@ -228,10 +243,12 @@ def consensus_bait(fasta_file: str, fq1: str, fq2: Optional[str], out_fasta: str
             out1, out2 = path.join(tmp, "k.1.fq"), path.join(tmp, "k.2.fq") if fq2 is not None else None
             if band is not None:
                 v = mf.filter_fastq_files_aligned(ks, fq1, fq2, out1, out2, int(band), 1, mf.PAIR_EITHER, min_depth=min_depth,
-                                                  max_permille=1000 if max_permille is None else int(max_permille), gapped=bool(gapped))
+                                                  max_permille=1000 if max_permille is None else int(max_permille), extend=int(extend), gapped=bool(gapped))
                 consensus, records = v.consensus, v.pileup_records
                 if gapped:
                     consensus, starts = v.gapped, v.gapped_starts
+                if int(extend):
+                    consensus, starts = v.extended, v.extended_starts
             elif max_permille is None:
                 _, _, _, consensus, records, _ = mf.filter_fastq_files_pileup(ks, fq1, fq2, out1, out2, 1, mf.PAIR_EITHER, min_depth=min_depth)
             else:

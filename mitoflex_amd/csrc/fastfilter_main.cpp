@@ -44,7 +44,10 @@
 // count on stdout is what was written (include/mitofilter.h, the keep rule; the reports do not depend on it).  With --band W,
 // --gapped-consensus writes the consensus that calls deletions and insertions too, as FASTA under the bait's record names, and --insertions
 // the letters of the inserted bases (name, 1-based position, offset inside the insertion behind it, base depth, A, C, G, T; include/mitofilter.h,
-// gapped consensus); without either no call changes.  It has no CPU fallback: without the library or a GPU it exits non-zero, which shell_call turns into a RuntimeError
+// gapped consensus); without either no call changes.  With --band W --extend E, --extended-consensus writes every record's gapped consensus
+// between the columns that the reads overhanging its ends agree on, up to E a side, as FASTA, and --extension-report the overhanging bases
+// (name, begin or end, 1-based distance from the record, depth, A, C, G, T; include/mitofilter.h, extended records); without the three flags
+// no call changes.  It has no CPU fallback: without the library or a GPU it exits non-zero, which shell_call turns into a RuntimeError
 // (helper.py:82-86).
 #include "../../include/mitofilter.h"
 #include "mf_coldtrace.h"
@@ -458,8 +461,8 @@ static std::string exe_dir()
 // what the command line asks for (checked: one kind of report at most)
 struct BaitArgs {
     std::string bait, fq1, fq2, out1, out2, pair = "either", libpath, report, group_report, group_sep, depth_report, depth_profile, place_report, base_depth_file, pileup_file, consensus_file,
-                variants_file, score_report, indels_file, gapped_file, insertions_file;
-    unsigned min_depth = 1, thr = 1, max_permille = 1000, band = 0;
+                variants_file, score_report, indels_file, gapped_file, insertions_file, extended_file, extension_report;
+    unsigned min_depth = 1, thr = 1, max_permille = 1000, band = 0, extend = 0;          // extend: --extend, the columns an end may grow by
     bool aligned = false;                      // --band: the placed reads are aligned inside the band before they are scored and cut
     int keep = MF_KEEP_PASSING;                // --write: which mates the verifying call writes
     int group_field = -1, k = 0, devices = 1, gcode = 5; bool protein = false;
@@ -484,6 +487,8 @@ struct BaitResult {
     std::vector<mf_indel_t> indels;
     std::vector<mf_pileup_t> ins_pile;          // with --gapped-consensus or --insertions: 2 * band entries a position
     std::vector<uint8_t> gapped; std::vector<uint64_t> gapped_starts;
+    std::vector<mf_pileup_t> ext_pile;          // with --extend: 2 * extend entries a record
+    std::vector<uint8_t> extended; std::vector<uint64_t> extended_starts;
 };
 
 // 0, or the exit code of a command line that cannot be run
@@ -531,6 +536,13 @@ static int parse_bait_args(int argc, char **argv, BaitArgs &A)
         else if (o == "--indels") A.indels_file = need("--indels");
         else if (o == "--gapped-consensus") A.gapped_file = need("--gapped-consensus");
         else if (o == "--insertions") A.insertions_file = need("--insertions");
+        else if (o == "--extend") {
+            const std::string v = need("--extend"); char *end = nullptr; const unsigned long x = strtoul(v.c_str(), &end, 10);
+            if (v.empty() || *end || v[0] < '0' || v[0] > '9' || x < 1 || x > MF_EXTEND_MAX) { fprintf(stderr, "error: --extend wants the columns a record end may grow by, from 1 to %d\n", MF_EXTEND_MAX); return 1; }
+            A.extend = (unsigned)x;
+        }
+        else if (o == "--extended-consensus") A.extended_file = need("--extended-consensus");
+        else if (o == "--extension-report") A.extension_report = need("--extension-report");
         else if (o == "--write") {
             const std::string v = need("--write");
             if (v == "passing") A.keep = MF_KEEP_PASSING; else if (v == "accepted") A.keep = MF_KEEP_ACCEPTED; else if (v == "placed") A.keep = MF_KEEP_PLACED;
@@ -565,7 +577,8 @@ static int parse_bait_args(int argc, char **argv, BaitArgs &A)
               "       [--report FILE | --group-report FILE [--group-field N] [--group-sep C] | --depth-report FILE [--depth-profile FILE]\n"
               "        | --place-report FILE [--base-depth FILE] | [--pileup FILE] [--consensus FILE] [--variants FILE] [--min-depth N]]\n"
               "       [--score-report FILE] [--max-mismatch PERMILLE]   (with or without the placement or the pile-up reports)\n"
-              "       [--band W [--indels FILE] [--gapped-consensus FILE] [--insertions FILE]]   (wherever --max-mismatch may go: the placed reads are aligned inside 2 W + 1 diagonals, indels cost one edit a base)\n"
+              "       [--band W [--indels FILE] [--gapped-consensus FILE] [--insertions FILE]\n"
+              "        [--extend E [--extended-consensus FILE] [--extension-report FILE]]]   (wherever --max-mismatch may go: the placed reads are aligned inside 2 W + 1 diagonals, indels cost one edit a base)\n"
               "       [--write passing|accepted|placed]   (which mates are written: all that pass, not those the cut rejects, only placed and accepted ones)\n"
               "       fastfilter bait --protein --bait PROTEINS.fa [--code 5] [-k 9] ...   (six-frame peptide k-mers)\n", stderr);
         return 1;
@@ -586,13 +599,15 @@ static int parse_bait_args(int argc, char **argv, BaitArgs &A)
     }
     const bool gapped = !A.gapped_file.empty() || !A.insertions_file.empty();
     if (gapped && !have_band) { fprintf(stderr, "error: --gapped-consensus and --insertions need --band\n"); return 1; }
-    if (have_min_depth && !piled && A.gapped_file.empty()) { fprintf(stderr, "error: --min-depth needs --pileup, --consensus or --variants\n"); return 1; }
+    if ((!A.extended_file.empty() || !A.extension_report.empty()) && !A.extend) { fprintf(stderr, "error: --extended-consensus and --extension-report need --extend\n"); return 1; }
+    if (A.extend && !have_band) { fprintf(stderr, "error: --extend needs --band (--band 0 is fine)\n"); return 1; }
+    if (have_min_depth && !piled && A.gapped_file.empty() && A.extended_file.empty()) { fprintf(stderr, "error: --min-depth needs --pileup, --consensus or --variants\n"); return 1; }
     const bool keeping = A.keep != MF_KEEP_PASSING;
-    if (have_max_mismatch && !placed && !piled && A.score_report.empty() && !keeping) {
-        fprintf(stderr, "error: --max-mismatch needs --place-report, --base-depth, --pileup, --consensus, --variants, --score-report or --write accepted|placed\n");
+    if (have_max_mismatch && !placed && !piled && A.score_report.empty() && !keeping && !A.extend) {
+        fprintf(stderr, "error: --max-mismatch needs --place-report, --base-depth, --pileup, --consensus, --variants, --score-report, --extend or --write accepted|placed\n");
         return 1;
     }
-    if (have_band && !placed && !piled && A.score_report.empty() && !keeping && A.indels_file.empty() && !gapped) {
+    if (have_band && !placed && !piled && A.score_report.empty() && !keeping && A.indels_file.empty() && !gapped && !A.extend) {
         fprintf(stderr, "error: --band needs --place-report, --base-depth, --pileup, --consensus, --variants, --score-report, --indels or --write accepted|placed\n");
         return 1;
     }
@@ -698,7 +713,19 @@ static int bait_run(const BaitArgs &A, BaitResult &R, mf_kmerset **ks_out, declt
             if (A.piled) { R.pile.assign(positions, mf_pileup_t{}); R.consensus.assign(positions, 0); R.letters.assign(positions, 0); }
             if (with_depth) { R.profile.assign(positions, 0); R.place_recs.assign(n_rec, mf_place_record_t{}); }
             if (rc == MF_OK && A.piled) rc = p_mf_kmerset_bait_letters(ks, R.letters.data(), R.letters.size(), nullptr);
-            if (rc == MF_OK && A.aligned && (!A.gapped_file.empty() || !A.insertions_file.empty())) {          // ... and with the gapped consensus
+            if (rc == MF_OK && A.aligned && A.extend) {          // ... with the records' ends extended (and the gapped outputs where they are asked for)
+                SYM(mf_filter_fastq_files_extended)
+                const size_t span = 2 * (size_t)A.band, E = A.extend;
+                const bool gap = !A.gapped_file.empty() || !A.insertions_file.empty();
+                R.align_recs.assign(n_rec, mf_align_record_t{}); R.indels.assign(positions, mf_indel_t{});
+                if (gap) { R.ins_pile.assign(std::max<size_t>(positions * span, 1), mf_pileup_t{}); R.gapped.assign(positions * (1 + span), 0); R.gapped_starts.assign(n_rec + 1, 0); }
+                R.ext_pile.assign(n_rec * 2 * E, mf_pileup_t{}); R.extended.assign(positions * (1 + span) + 2 * n_rec * E, 0); R.extended_starts.assign(n_rec + 1, 0);
+                rc = files(p_mf_filter_fastq_files_extended, A.min_depth, A.max_permille, A.keep, A.band, A.extend, with_depth ? R.profile.data() : nullptr,
+                           with_depth ? R.place_recs.data() : nullptr, A.piled ? R.pile.data() : nullptr, A.piled ? R.consensus.data() : nullptr, (mf_pileup_record_t *)nullptr,
+                           R.indels.data(), R.align_recs.data(), gap && span ? R.ins_pile.data() : nullptr, gap ? R.gapped.data() : nullptr,
+                           gap ? R.gapped_starts.data() : nullptr, (mf_gapped_record_t *)nullptr, R.ext_pile.data(), R.extended.data(), R.extended_starts.data(),
+                           (mf_extend_record_t *)nullptr, R.unplaced);
+            } else if (rc == MF_OK && A.aligned && (!A.gapped_file.empty() || !A.insertions_file.empty())) {          // ... and with the gapped consensus
                 SYM(mf_filter_fastq_files_gapped)
                 const size_t span = 2 * (size_t)A.band;
                 R.align_recs.assign(n_rec, mf_align_record_t{}); R.indels.assign(positions, mf_indel_t{});
@@ -773,7 +800,9 @@ static bool write_reports(const BaitArgs &A, const BaitResult &R)
                                                                                       : write_score_report(f, R.names, R.starts, R.score_recs.data()); })
         && write_file(A.indels_file, "indel table", [&](FILE *f) { return write_indels(f, R.names, R.starts, R.profile.data(), R.indels.data()); })
         && write_file(A.gapped_file, "gapped consensus", [&](FILE *f) { return write_gapped_consensus(f, R.names, R.gapped_starts.data(), R.gapped.data()); })
-        && write_file(A.insertions_file, "insertion table", [&](FILE *f) { return write_insertions(f, R.names, R.starts, R.profile.data(), R.ins_pile.data(), 2 * A.band); });
+        && write_file(A.insertions_file, "insertion table", [&](FILE *f) { return write_insertions(f, R.names, R.starts, R.profile.data(), R.ins_pile.data(), 2 * A.band); })
+        && write_file(A.extended_file, "extended consensus", [&](FILE *f) { return write_gapped_consensus(f, R.names, R.extended_starts.data(), R.extended.data()); })
+        && write_file(A.extension_report, "extension report", [&](FILE *f) { return write_extension_report(f, R.names, R.ext_pile.data(), A.extend); });
 }
 
 static int bait_main(int argc, char **argv)

@@ -23,7 +23,9 @@
 //                  (align_adds): the pile-up of the diagonal steps, the deleted positions, the insertion runs.  The GAPPED
 //                  instantiations (the gapped consensus, include/mitofilter.h) also add the letter of every inserted base into the
 //                  insertion pile, at its offset inside its run (align_run_offset, mf_align.h); the plain ones take an empty
-//                  argument more and are otherwise the code they were.
+//                  argument more and are otherwise the code they were.  The EXTEND instantiations (extended records, include/
+//                  mitofilter.h; they are GAPPED ones, with a span of 0 at band 0) add the base of a diagonal step that lies outside
+//                  the record into the extension pile of that end of the record instead of nowhere.
 // Work memory: align_work_words(max_len) words a wave, as many waves as the launch has: bounded whatever the number of reads.
 #include "mf_align_launch.h"
 #include "mf_vote_dev.h"
@@ -119,10 +121,13 @@ __device__ __forceinline__ AlignResult align_read(const ReadsView &R, uint64_t b
 // positions its row deletes into indel[.][0], an inserted base into indel[.][2] and, where it begins a run, indel[.][1].
 // GAPPED: the t-th base of an insertion run also into ins_pile[(position) * span + t][letter], span = 2 W; t < span holds the store
 // inside the position's own entries whatever the walk counted.
-template <bool GAPPED>
+// EXTEND: the base of a diagonal step outside the record, at offset e of an end of record j (extend_offset, mf_call.h), into
+// ext_pile[(2 j + side) * E + e][letter] when e < E -- which holds the store inside that end's own entries; it adds nowhere otherwise.
+template <bool GAPPED, bool EXTEND>
 __device__ __forceinline__ void align_adds(const ReadsView &R, uint64_t b0, bool hasn, uint64_t L, uint32_t strand, uint64_t s0, int64_t len,
                                            const unsigned long long *ent, unsigned long long *__restrict__ pile, unsigned long long *__restrict__ indel,
-                                           unsigned long long *__restrict__ ins_pile, uint32_t span, int lane)
+                                           unsigned long long *__restrict__ ins_pile, uint32_t span, unsigned long long *__restrict__ ext_pile, uint32_t E,
+                                           uint32_t j, int lane)
 {
     for (uint64_t b = (uint64_t)lane; b < L; b += 64) {
         const unsigned long long e = ent[b];
@@ -132,7 +137,17 @@ __device__ __forceinline__ void align_adds(const ReadsView &R, uint64_t b0, bool
             if (p >= 0 && p < len) atomicAdd(&indel[ALIGN_INDEL * (s0 + (uint64_t)p)], 1ull);
         }
         const int64_t p = c - 1;
-        if (p < 0 || p >= len) continue;
+        if (p < 0 || p >= len) {
+            if constexpr (EXTEND) {
+                if (ent_inserted(e)) continue;
+                uint32_t side;
+                const uint64_t off = extend_offset(p, len, side);
+                if (off >= (uint64_t)E) continue;
+                const uint32_t x = oriented_base(R, b0, hasn, L, strand, b);
+                if (x < ALIGN_X_NONE) atomicAdd(&ext_pile[4 * extend_entry(j, side, E, off) + x], 1ull);
+            }
+            continue;
+        }
         if (!ent_inserted(e)) {
             if (!pile) continue;
             const uint32_t x = oriented_base(R, b0, hasn, L, strand, b);
@@ -158,14 +173,16 @@ struct AlignArgs {
 };
 
 // What the gapped launch takes beside the plain one (nothing otherwise: the plain instantiations take no argument they would read).
-template <bool GAPPED> struct GapArgs {};
-template <> struct GapArgs<true> { unsigned long long *__restrict__ ins_pile; };
+// The extending launch is a gapped one that takes the extension pile and its columns an end as well.
+template <bool GAPPED, bool EXTEND = false> struct GapArgs {};
+template <> struct GapArgs<true, false> { unsigned long long *__restrict__ ins_pile; };
+template <> struct GapArgs<true, true> { unsigned long long *__restrict__ ins_pile, *__restrict__ ext_pile; uint32_t extend; };
 
-template <int KW, bool GAPPED>
+template <int KW, bool GAPPED, bool EXTEND>
 __global__ void __launch_bounds__(ASSIGN_BLOCK)
 align_kernel(ReadsView R, KmerSetView S, const Anchor *__restrict__ anchor, const uint64_t *__restrict__ rec_start, const uint32_t *__restrict__ list,
              const unsigned long long *__restrict__ n_list_p, uint32_t n_rec, PlaceOut *__restrict__ place, unsigned long long *__restrict__ diff,
-             unsigned long long *__restrict__ counts, unsigned long long *__restrict__ pile, AlignArgs A, GapArgs<GAPPED> G)
+             unsigned long long *__restrict__ counts, unsigned long long *__restrict__ pile, AlignArgs A, GapArgs<GAPPED, EXTEND> G)
 {
     __shared__ uint32_t s_hist[HIST_MAX];
     // forward, reverse, over_begin, over_end of every record; not placed; behind them rejected and the 32 bins of every record
@@ -212,9 +229,11 @@ align_kernel(ReadsView R, KmerSetView S, const Anchor *__restrict__ anchor, cons
             }
         }
         if (placed && accept) {
-            unsigned long long *ins_pile = nullptr;
+            unsigned long long *ins_pile = nullptr, *ext_pile = nullptr; uint32_t extend = 0;
             if constexpr (GAPPED) ins_pile = G.ins_pile;
-            align_adds<GAPPED>(R, src.b0, src.hasn, L, W.strand(), W.s0, W.len, ent, pile, A.indel, ins_pile, 2u * (uint32_t)A.band, lane);
+            if constexpr (EXTEND) { ext_pile = G.ext_pile; extend = G.extend; }
+            align_adds<GAPPED, EXTEND>(R, src.b0, src.hasn, L, W.strand(), W.s0, W.len, ent, pile, A.indel, ins_pile, 2u * (uint32_t)A.band, ext_pile, extend,
+                                       W.record(), lane);
         }
     }
     if (lane == 0 && sum_any) flush();
@@ -243,12 +262,18 @@ hipError_t launch_align(const ReadsView &R, const KmerSetView &S, const Anchor *
     const uint64_t n = std::max<uint64_t>(P.max_len, 1);
     const AlignArgs A{P.cut.bait, P.cut.max_permille, (int)P.band, P.align, P.cut.sums, P.indel, P.cut.keep_bits, P.cut.keep, P.work, P.max_len, 64 * ((n + 31) / 32),
                       align_work_words(P.max_len)};
-    dispatch_kw_flag(S.kw, P.ins_pile && P.band, [&](auto KW, auto GAPPED) {          // (band 0: the insertion pile has no entry)
-        GapArgs<decltype(GAPPED)::value> G;
+    const auto launch = [&](auto KW, auto GAPPED, auto EXTEND) {
+        GapArgs<decltype(GAPPED)::value, decltype(EXTEND)::value> G;
         if constexpr (decltype(GAPPED)::value) G.ins_pile = P.ins_pile;
-        hipLaunchKernelGGL((align_kernel<decltype(KW)::value, decltype(GAPPED)::value>), dim3(grid), dim3(ASSIGN_BLOCK), 0, st, R, S, anchor, rec_start, list, n_list,
-                           n_rec, place, diff, counts, pile, A, G);
-    });
+        if constexpr (decltype(EXTEND)::value) { G.ext_pile = P.ext_pile; G.extend = P.extend; }
+        hipLaunchKernelGGL((align_kernel<decltype(KW)::value, decltype(GAPPED)::value, decltype(EXTEND)::value>), dim3(grid), dim3(ASSIGN_BLOCK), 0, st, R, S, anchor,
+                           rec_start, list, n_list, n_rec, place, diff, counts, pile, A, G);
+    };
+    // (an extending launch is a gapped one whatever the band: at band 0 the span is 0 and the insertion pile, which has no entry, is not touched)
+    if (P.ext_pile && P.extend) {
+        if (S.kw == 1) launch(std::integral_constant<int, 1>{}, std::true_type{}, std::true_type{});
+        else launch(std::integral_constant<int, 2>{}, std::true_type{}, std::true_type{});
+    } else dispatch_kw_flag(S.kw, P.ins_pile && P.band, [&](auto KW, auto GAPPED) { launch(KW, GAPPED, std::false_type{}); });          // (band 0: the insertion pile has no entry)
     return hipGetLastError();
 }
 

@@ -14,10 +14,13 @@ constexpr uint32_t ALIGN_INDEL = 3;            // counters a position: del, ins,
 // each of align_waves(..) waves -- the direction bits of a read's band and what the traceback leaves per read base; max_len: no listed
 // read is longer.  ins_pile (optional; the gapped launch): 4 * 2 * band counters a position, [position][run offset][A, C, G, T], zeroed --
 // the letters of the inserted bases of the accepted reads; everything else is the plain launch's.
+// ext_pile, extend (optional; the extending launch, a gapped one): 4 * 2 * extend counters a record, [record][begin, end][offset][A, C, G, T],
+// zeroed -- the bases of the accepted reads' diagonal steps outside their record, below `extend` columns from it.
 struct PlaceAlign {
     PlaceCut cut; uint32_t band; AlignOut *align; unsigned long long *indel;
     unsigned long long *work; uint64_t max_len;
     unsigned long long *ins_pile;
+    unsigned long long *ext_pile = nullptr; uint32_t extend = 0;
 };
 // 64-bit words of work memory a wave needs for reads of up to max_len bases: two direction bits a cell (64 lanes x 32 rows a block of
 // 64 words), then one word a read base

@@ -64,4 +64,23 @@ MF_SCORE_HD uint32_t gapped_call_position(unsigned long long D, unsigned long lo
     return m;
 }
 
+// The extension of a record's ends (include/mitofilter.h, "extended records").  A record coordinate c outside [0, len) lies at offset
+// -1 - c of the begin (side 0) or c - len of the end (side 1); offset 0 is the column next to the record.
+MF_SCORE_HD uint64_t extend_offset(int64_t c, int64_t len, uint32_t &side)
+{
+    side = c < 0 ? 0u : 1u;
+    return c < 0 ? (uint64_t)(-1 - c) : (uint64_t)(c - len);
+}
+// the entry of (record j, side, offset e < E) in a table of E columns an end, two ends a record
+MF_SCORE_HD uint64_t extend_entry(uint64_t j, uint32_t side, uint32_t E, uint64_t e) { return (2 * j + side) * (uint64_t)E + e; }
+// The call at one column, from unclamped counts: emitted iff at least min_depth bases lie there and exactly one letter has the most;
+// byte: that letter in upper case.  An end emits its columns up to the first that is not.
+MF_SCORE_HD bool extend_call_column(unsigned long long c0, unsigned long long c1, unsigned long long c2, unsigned long long c3, uint32_t min_depth, uint8_t &byte)
+{
+    uint32_t best; bool tied;
+    strict_most4(c0, c1, c2, c3, best, tied);
+    byte = (uint8_t)((CALL_LETTERS >> (8 * best)) & 255u);
+    return c0 + c1 + c2 + c3 >= (unsigned long long)min_depth && !tied;
+}
+
 } // namespace mf

@@ -72,4 +72,11 @@ hipError_t launch_gapped_call(const unsigned long long *diff, uint64_t total, co
                               const uint8_t *consensus, const uint64_t *rec_start, uint32_t n_rec, uint32_t min_depth, unsigned long long *partial,
                               PileOut *ins_out, uint8_t *count, uint8_t *bytes, unsigned long long *rec_sums, hipStream_t st);
 
+// The ends of the records called (include/mitofilter.h, "extended records") from the extension pile of an extending placement: ext_pile,
+// 4 * extend counters an end, [record][begin, end][offset][A, C, G, T].  Per end (2 * n_rec of them, `extend` columns each): ext_out
+// (optional) = its columns clamped at PLACE_CLAMP; bytes[end * extend ..] = the bytes of the columns it emits, by offset; sums
+// [EXTEND_END_SUMS * end] = how many it emits, then the unclamped sum of all its counts.
+hipError_t launch_extend_call(const unsigned long long *ext_pile, uint32_t extend, uint32_t n_rec, uint32_t min_depth, PileOut *ext_out, uint8_t *bytes,
+                              unsigned long long *sums, hipStream_t st);
+
 } // namespace mf

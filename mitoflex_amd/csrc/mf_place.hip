@@ -406,6 +406,40 @@ gapped_call_kernel(const unsigned long long *__restrict__ diff, uint64_t n, cons
     if (rec_sums) walk.finish();
 }
 
+// The ends of the records called (include/mitofilter.h, "extended records"): one wave per (record, side), n_ends = 2 R of them, each over
+// its E columns of ext_pile, lanes taking the offsets lane, lane + 64, ..  Every column: the clamped counters into ext_out (optional) and
+// extend_call_column (mf_call.h) from the unclamped ones; a ballot finds the first column that is not emitted, the bytes of the columns
+// before it go to bytes[end * E ..] in the order of the offsets.  sums[EXTEND_END_SUMS * end]: the emitted columns, then the unclamped
+// sum of all counts of the end's table.
+__global__ void __launch_bounds__(PS_BLOCK)
+extend_call_kernel(const unsigned long long *__restrict__ ext_pile, uint32_t E, uint32_t n_ends, uint32_t min_depth, PileOut *__restrict__ ext_out,
+                   uint8_t *__restrict__ bytes, unsigned long long *__restrict__ sums)
+{
+    const uint32_t end = (blockIdx.x * PS_BLOCK + threadIdx.x) >> 6, lane = threadIdx.x & 63u;
+    if (end >= n_ends) return;                                      // (wave-uniform)
+    const unsigned long long *const t = ext_pile + 4 * (uint64_t)end * E;
+    unsigned long long piled = 0;
+    uint32_t emitted = E;                                           // the first column that is not emitted
+    bool open = true;
+    for (uint32_t base = 0; base < E; base += 64) {
+        const uint32_t e = base + lane;
+        const bool in = e < E;
+        unsigned long long c0 = 0, c1 = 0, c2 = 0, c3 = 0;
+        if (in) { c0 = t[4 * (uint64_t)e]; c1 = t[4 * (uint64_t)e + 1]; c2 = t[4 * (uint64_t)e + 2]; c3 = t[4 * (uint64_t)e + 3]; }
+        piled += c0 + c1 + c2 + c3;
+        if (in && ext_out) ext_out[(uint64_t)end * E + e] = pile_clamped(c0, c1, c2, c3);
+        if (!open) continue;
+        uint8_t byte;
+        const bool emit = extend_call_column(c0, c1, c2, c3, min_depth, byte) && in;
+        const unsigned long long stop = __ballot(!emit);
+        const uint32_t first = stop ? (uint32_t)__ffsll((long long)stop) - 1u : 64u;
+        if (lane < first) bytes[(uint64_t)end * E + e] = byte;      // (emit holds for these lanes: e < E)
+        if (stop) { emitted = base + first; open = false; }
+    }
+    piled = wave_sum_u64(piled);
+    if (lane == 0) { sums[EXTEND_END_SUMS * end] = emitted; sums[EXTEND_END_SUMS * end + 1] = piled; }
+}
+
 hipError_t launch_build_anchor(const BaitView &B, const uint64_t *rec_start, uint32_t n_rec, const KmerSetView &S, Anchor *anchor, uint32_t *lo,
                                uint32_t *hi, hipStream_t st)
 {
@@ -497,6 +531,15 @@ hipError_t launch_gapped_call(const unsigned long long *diff, uint64_t total, co
     launch_tile_partials(diff, total, partial, nb, st);
     hipLaunchKernelGGL(gapped_call_kernel, dim3((unsigned)nb), dim3(PS_BLOCK), 0, st, diff, total, partial, indel, ins_pile, span, consensus, rec_start, n_rec,
                        min_depth, ins_out, count, bytes, rec_sums);
+    return hipGetLastError();
+}
+
+hipError_t launch_extend_call(const unsigned long long *ext_pile, uint32_t extend, uint32_t n_rec, uint32_t min_depth, PileOut *ext_out, uint8_t *bytes,
+                              unsigned long long *sums, hipStream_t st)
+{
+    if (!extend || !n_rec) return hipSuccess;
+    const uint32_t n_ends = 2 * n_rec;
+    hipLaunchKernelGGL(extend_call_kernel, dim3(grid_of(n_ends, PS_BLOCK / 64)), dim3(PS_BLOCK), 0, st, ext_pile, extend, n_ends, min_depth, ext_out, bytes, sums);
     return hipGetLastError();
 }
 

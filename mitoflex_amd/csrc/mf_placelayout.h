@@ -22,16 +22,21 @@ constexpr uint32_t ALIGN_POSITION_COUNTERS = 3;          // ... and its counters
 // of every record (ALIGN_RECORD_SUMS R) -- and a fifth section behind them: del, ins, ins_bases of every position.
 // A GAPPED aligning placement (mf_align_gapped with the insertion pile or the gapped consensus asked for) keeps a sixth section behind
 // the indel counters: the insertion pile, 4 * span words a position (span = 2 * band), [position][run offset][A, C, G, T].
+// An EXTENDING placement (mf_align_extended with extend > 0 and an extension output asked for; it is a gapped one) keeps a seventh section
+// behind the insertion pile: the extension pile, 4 * 2 * extend words a record, [record][begin, end][offset][A, C, G, T].
 // Every offset into the array is computed here.
 struct PlaceLayout {
-    size_t n_pile, n_diff, n_cnt, n_rec; bool verify; uint32_t max_permille; bool align; uint32_t band; size_t n_indel, n_ins;
-    PlaceLayout(uint64_t positions, size_t n_rec_, bool pileup, bool verify_, uint32_t max_permille_, bool align_ = false, uint32_t band_ = 0, bool gapped = false)
+    size_t n_pile, n_diff, n_cnt, n_rec; bool verify; uint32_t max_permille; bool align; uint32_t band; size_t n_indel, n_ins; uint32_t extend; size_t n_ext;
+    PlaceLayout(uint64_t positions, size_t n_rec_, bool pileup, bool verify_, uint32_t max_permille_, bool align_ = false, uint32_t band_ = 0, bool gapped = false,
+                uint32_t extend_ = 0)
         : n_pile(pileup ? 4 * (size_t)positions : 0), n_diff((size_t)positions + 1), n_cnt(4 * n_rec_ + 1), n_rec(n_rec_), verify(verify_), max_permille(max_permille_),
           align(align_), band(band_), n_indel(align_ ? ALIGN_POSITION_COUNTERS * (size_t)positions : 0),
-          n_ins(align_ && gapped ? 4 * (size_t)(2 * band_) * (size_t)positions : 0) {}
+          n_ins(align_ && gapped ? 4 * (size_t)(2 * band_) * (size_t)positions : 0), extend(align_ && gapped ? extend_ : 0),
+          n_ext(4 * 2 * (size_t)extend * n_rec_) {}
     size_t n_sums() const { return align ? ALIGN_RECORD_SUMS : 2; }
     size_t n_score() const { return verify ? ((size_t)SCORE_GATHERED + n_sums()) * n_rec : 0; }
-    size_t words() const { return n_pile + n_diff + n_cnt + n_score() + n_indel + n_ins; }
+    size_t words() const { return n_pile + n_diff + n_cnt + n_score() + n_indel + n_ins + n_ext; }
+    unsigned long long *ext(unsigned long long *base) const { return n_ext ? cnt(base) + n_cnt + n_score() + n_indel + n_ins : nullptr; }
     uint32_t span() const { return 2 * band; }
     unsigned long long *ins(unsigned long long *base) const { return n_ins ? cnt(base) + n_cnt + n_score() + n_indel : nullptr; }
     unsigned long long *indel(unsigned long long *base) const { return n_indel ? cnt(base) + n_cnt + n_score() : nullptr; }
@@ -71,7 +76,10 @@ struct PlaceLayout {
 // temporaries of its own.  A gapped call (gapped_span >= 0, the span of its insertion pile) has three sections more behind the spare
 // bytes of the positions buffer, the first at a multiple of 16 -- the clamped insertion pile (span entries a position), the number of
 // bytes every position emits, those bytes (1 + span a position) -- and its record sums (GAPPED_SUMS a record) at the end of the sums
-// buffer.  Every offset is computed here.
+// buffer.  An extending call (extend > 0; it is a gapped one) has two sections more behind those, the first at a multiple of 16 -- the
+// clamped extension pile (extend entries an end, two ends a record), the bytes every end emits (extend an end) -- and its sums
+// (EXTEND_END_SUMS an end) at the end of the sums buffer.  Every offset is computed here.
+constexpr uint32_t EXTEND_END_SUMS = 2;                  // counters an end of the extension call: emitted columns, piled bases
 constexpr uint32_t GAPPED_SUMS = 4;                      // counters a record of the gapped call: the fields of mf_gapped_record_t
 struct ReportScratch {
     struct Section {
@@ -82,8 +90,10 @@ struct ReportScratch {
     Section pile_out, depth, consensus, spare;         // of the positions buffer
     Section gap_sums;                                  // of the sums buffer, a gapped call
     Section ins_out, gap_count, gap_bytes;             // of the positions buffer, a gapped call
+    Section ext_sums;                                  // of the sums buffer, an extending call
+    Section ext_out, ext_bytes;                        // of the positions buffer, an extending call
     size_t sums_bytes, pos_bytes;
-    ReportScratch(uint64_t positions, size_t n_rec, uint64_t scan_tiles, bool place, bool pile, int gapped_span = -1)
+    ReportScratch(uint64_t positions, size_t n_rec, uint64_t scan_tiles, bool place, bool pile, int gapped_span = -1, uint32_t extend = 0)
     {
         const size_t P = (size_t)std::max<uint64_t>(positions, 1), R = std::max<size_t>(n_rec, 1);
         size_t at = 0;
@@ -91,6 +101,7 @@ struct ReportScratch {
         put(work, place ? (2 * n_rec + (size_t)scan_tiles + 1) * 8 : 0);
         put(pile_sums, pile ? PILE_SUMS * R * 8 : 0);
         put(gap_sums, gapped_span >= 0 ? GAPPED_SUMS * R * 8 : 0);
+        put(ext_sums, gapped_span >= 0 && extend ? EXTEND_END_SUMS * 2 * R * 8 : 0);
         sums_bytes = at; at = 0;
         put(pile_out, pile ? P * sizeof(mf_pileup_t) : 0);
         put(depth, place ? P * 4 : 0);
@@ -102,6 +113,11 @@ struct ReportScratch {
             put(ins_out, P * span * sizeof(mf_pileup_t));
             put(gap_count, P);
             put(gap_bytes, P * (1 + span));
+            if (extend) {
+                at = (at + 15) / 16 * 16;
+                put(ext_out, 2 * R * (size_t)extend * sizeof(mf_pileup_t));
+                put(ext_bytes, 2 * R * (size_t)extend);
+            }
         }
         pos_bytes = at;
     }

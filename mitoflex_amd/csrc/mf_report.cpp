@@ -388,6 +388,7 @@ static int pileup_tables(mf_kmerset *ks, int device, DevTables *T)
 
 static int pile_nomem(size_t words) { (void)hipGetLastError(); return fail(MF_E_NOMEM, "the pile-up counters need %llu bytes on the device", (unsigned long long)(words * 8)); }
 static int gap_nomem(size_t words) { (void)hipGetLastError(); return fail(MF_E_NOMEM, "the pile-up counters and the insertion pile need %llu bytes on the device", (unsigned long long)(words * 8)); }
+static int ext_nomem(size_t words) { (void)hipGetLastError(); return fail(MF_E_NOMEM, "the pile-up counters, the insertion pile and the extension pile need %llu bytes on the device", (unsigned long long)(words * 8)); }
 
 // Everything a call of the placement family is asked for: mf_place, mf_pileup, mf_verify and their file-level calls are each one of
 // these and one call of a driver below.  family: the name the messages use.  with_pileup: the layout holds pile-up counters.  A family
@@ -407,8 +408,14 @@ struct PlaceRequest {
     // a gapped aligning family: the insertion pile (positions * 2 * band entries), the gapped consensus (room for positions * (1 + 2 * band)
     // bytes), its R + 1 record offsets and its record summaries.  All null: the aligning family as it was.
     mf_pileup_t *ins_pile = nullptr; uint8_t *gapped = nullptr; uint64_t *gapped_starts = nullptr; mf_gapped_record_t *gapped_records = nullptr;
-    bool gap() const { return align && (ins_pile || gapped || gapped_starts || gapped_records); }
-    int (*nomem() const)(size_t) { return gap() ? gap_nomem : with_pileup ? pile_nomem : nullptr; }
+    // an extending family (a gapped one): the columns an end, the extension pile (R * 2 * extend entries), the extended records (room for
+    // positions * (1 + 2 * band) + 2 * R * extend bytes), their R + 1 offsets and their summaries.  extend 0: the gapped family as it was.
+    uint32_t extend = 0;
+    mf_pileup_t *ext_pile = nullptr; uint8_t *extended = nullptr; uint64_t *extended_starts = nullptr; mf_extend_record_t *extend_records = nullptr;
+    bool ext_asked() const { return ext_pile || extended || extended_starts || extend_records; }
+    bool ext() const { return align && extend && ext_asked(); }
+    bool gap() const { return align && (ins_pile || gapped || gapped_starts || gapped_records || ext()); }
+    int (*nomem() const)(size_t) { return ext() ? ext_nomem : gap() ? gap_nomem : with_pileup ? pile_nomem : nullptr; }
     // the one argument check of the family (a resident call checks its read set behind it)
     int check(const mf_kmerset *ks) const
     {
@@ -416,16 +423,18 @@ struct PlaceRequest {
         if (min_depth == 0) return fail(MF_E_ARG, "min_depth is 0: a called position needs at least one base");
         if (keep < MF_KEEP_PASSING || keep > MF_KEEP_PLACED) return fail(MF_E_ARG, "keep is %d: the keep mode is MF_KEEP_PASSING (0), MF_KEEP_ACCEPTED (1) or MF_KEEP_PLACED (2)", keep);
         if (align && band > ALIGN_MAX_BAND) return fail(MF_E_ARG, "band is %u: the band is a number from 0 to %u and below k", band, ALIGN_MAX_BAND);
+        if (extend > MF_EXTEND_MAX) return fail(MF_E_ARG, "extend is %u: a record grows by 0 to %u columns an end", extend, (unsigned)MF_EXTEND_MAX);
+        if (!extend && ext_asked()) return fail(MF_E_ARG, "extend is 0: ext_pile, extended, extended_starts and extend_records must be NULL");
         if (!ks) return fail(MF_E_ARG, "NULL handle");
         if (ks->kind != MF_KIND_NUCLEOTIDE) return fail(MF_E_ARG, "%s needs a nucleotide bait set", family);
         if (align && !align_band_ok(band, ks->k)) return fail(MF_E_ARG, "band is %u: the band stays below k = %d", band, ks->k);
         return MF_OK;
     }
-    PlaceLayout layout(const mf_kmerset *ks) const { return PlaceLayout(ks->positions(), ks->rec_len().size(), with_pileup, verify, max_permille, align, band, gap()); }
+    PlaceLayout layout(const mf_kmerset *ks) const { return PlaceLayout(ks->positions(), ks->rec_len().size(), with_pileup, verify, max_permille, align, band, gap(), ext() ? extend : 0); }
     ReportScratch scratch(const mf_kmerset *ks) const
     {
         return ReportScratch(ks->positions(), ks->rec_len().size(), place_scan_tiles(ks->positions()), base_depth || place_records || gap(), with_pileup,
-                             gap() ? (int)(2 * band) : -1);
+                             gap() ? (int)(2 * band) : -1, ext() ? extend : 0);
     }
 };
 
@@ -477,7 +486,7 @@ static int place_after_filter(mf_kmerset *ks, mf_reads *r, const PlaceLayout &L,
         const hipError_t e = dev_reserve(r->d_awork, r->cap_awork, bytes, false);
         if (e == hipErrorOutOfMemory) { (void)hipGetLastError(); return fail(MF_E_NOMEM, "the alignment of reads of up to %llu bases needs %llu bytes on the device", (unsigned long long)max_len, (unsigned long long)bytes); }
         HIPCHK(e);
-        const PlaceAlign pa{cut, L.band, align, L.indel(t), r->d_awork, max_len, L.ins(t)};
+        const PlaceAlign pa{cut, L.band, align, L.indel(t), r->d_awork, max_len, L.ins(t), L.ext(t), L.extend};
         HIPCHK(launch_align(r->v, T->view, T->anchor, T->place_starts, r->d_alist, r->d_acnt, (uint32_t)ks->rec_len().size(), place, L.diff(t), L.cnt(t), L.pile(t),
                             pa, ctx->n_cu, st));
     } else {
@@ -516,7 +525,7 @@ static int placement_report(mf_kmerset *ks, int device, hipStream_t st, const Pl
     static_assert(sizeof(mf_pileup_t) == 16 && sizeof(PileOut) == 16 && sizeof(mf_pileup_record_t) == 8 * PILE_SUMS, "pile-up records");
     static_assert(sizeof(mf_score_t) == 8 && sizeof(ScoreOut) == 8 && sizeof(mf_score_record_t) == 8 * (4 + MF_SCORE_BINS) && MF_SCORE_BINS == SCORE_BINS, "score records");
     static_assert(sizeof(mf_align_t) == 24 && sizeof(AlignOut) == 24 && sizeof(mf_indel_t) == 12 && sizeof(mf_align_record_t) == 8 * (7 + MF_SCORE_BINS), "align records");
-    static_assert(sizeof(mf_gapped_record_t) == 8 * GAPPED_SUMS, "gapped records");
+    static_assert(sizeof(mf_gapped_record_t) == 8 * GAPPED_SUMS && sizeof(mf_extend_record_t) == 40, "gapped and extend records");
     static_assert(ALIGN_SUMS == ALIGN_RECORD_SUMS && ALIGN_INDEL == ALIGN_POSITION_COUNTERS, "the kernel's counters are the layout's");
     DevTables *T; int rc = placement_tables(ks, device, L, &T); if (rc) return rc;
     const uint64_t total = ks->positions(), n_rec = L.n_rec;
@@ -530,7 +539,8 @@ static int placement_report(mf_kmerset *ks, int device, hipStream_t st, const Pl
         if (q.place_records && n_rec) HIPCHK(hipMemcpyAsync(h_sum.data(), work, 2 * n_rec * 8, hipMemcpyDeviceToHost, st));
     }
     const bool gap = q.gap();          // (the gapped call reads the consensus bytes on the device, asked for or not)
-    std::vector<uint8_t> h_gcount, h_gbytes; std::vector<unsigned long long> h_gsum;
+    const bool ext = q.ext();          // (the extended records hold the gapped bytes, asked for or not)
+    std::vector<uint8_t> h_gcount, h_gbytes, h_ebytes; std::vector<unsigned long long> h_gsum, h_esum;
     if (q.with_pileup && (q.pileup || q.consensus || q.pileup_records || gap)) {
         unsigned long long *psums = S.pile_sums.in<unsigned long long>(sums); PileOut *out = S.pile_out.in<PileOut>(pos); uint8_t *cons = S.consensus.in<uint8_t>(pos);
         if (q.pileup_records && n_rec) HIPCHK(hipMemsetAsync(psums, 0, PILE_SUMS * n_rec * 8, st));
@@ -541,10 +551,10 @@ static int placement_report(mf_kmerset *ks, int device, hipStream_t st, const Pl
         if (q.pileup_records && n_rec) HIPCHK(hipMemcpyAsync(q.pileup_records, psums, PILE_SUMS * n_rec * 8, hipMemcpyDeviceToHost, st));
     }
     const size_t span = L.span();
+    const bool call = gap && (q.gapped || q.gapped_starts || q.extended || q.extended_starts || q.extend_records);          // (the gapped record summaries come from the kernel's sums)
     if (gap) {
         unsigned long long *work = S.work.in<unsigned long long>(sums), *gsums = S.gap_sums.in<unsigned long long>(sums);
         PileOut *ins_out = S.ins_out.in<PileOut>(pos); uint8_t *gcount = S.gap_count.in<uint8_t>(pos), *gbytes = S.gap_bytes.in<uint8_t>(pos);
-        const bool call = q.gapped || q.gapped_starts;          // (the record summaries come from the kernel's sums)
         if (n_rec) HIPCHK(hipMemsetAsync(gsums, 0, GAPPED_SUMS * n_rec * 8, st));
         HIPCHK(launch_gapped_call(L.diff(t), total, L.indel(t), L.ins(t), (uint32_t)span, S.consensus.in<uint8_t>(pos), T->place_starts, (uint32_t)n_rec, q.min_depth,
                                   work + 2 * n_rec, q.ins_pile ? ins_out : nullptr, gcount, gbytes, gsums, st));
@@ -556,23 +566,45 @@ static int placement_report(mf_kmerset *ks, int device, hipStream_t st, const Pl
         }
         if (q.gapped_records && n_rec) { h_gsum.resize(GAPPED_SUMS * n_rec); HIPCHK(hipMemcpyAsync(h_gsum.data(), gsums, h_gsum.size() * 8, hipMemcpyDeviceToHost, st)); }
     }
+    const size_t E = L.extend, n_ends = 2 * n_rec;
+    if (ext && n_rec) {          // both ends of every record called, once, from the sums
+        unsigned long long *esums = S.ext_sums.in<unsigned long long>(sums);
+        PileOut *ext_out = S.ext_out.in<PileOut>(pos); uint8_t *ebytes = S.ext_bytes.in<uint8_t>(pos);
+        HIPCHK(launch_extend_call(L.ext(t), (uint32_t)E, (uint32_t)n_rec, q.min_depth, q.ext_pile ? ext_out : nullptr, ebytes, esums, st));
+        if (q.ext_pile) HIPCHK(hipMemcpyAsync(q.ext_pile, ext_out, n_ends * E * sizeof(PileOut), hipMemcpyDeviceToHost, st));
+        h_ebytes.resize(n_ends * E); h_esum.resize(EXTEND_END_SUMS * n_ends);
+        HIPCHK(hipMemcpyAsync(h_ebytes.data(), ebytes, h_ebytes.size(), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(h_esum.data(), esums, h_esum.size() * 8, hipMemcpyDeviceToHost, st));
+    }
     if (!h_indel.empty()) HIPCHK(hipMemcpyAsync(h_indel.data(), L.indel(t), h_indel.size() * 8, hipMemcpyDeviceToHost, st));
     HIPCHK(hipMemcpyAsync(h_cnt.data(), L.cnt(t), h_cnt.size() * 8, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     for (size_t p = 0; p < h_indel.size() / ALIGN_INDEL; p++)          // (clamped like the depth)
         q.indels[p] = mf_indel_t{clamp_count(h_indel[ALIGN_INDEL * p]), clamp_count(h_indel[ALIGN_INDEL * p + 1]), clamp_count(h_indel[ALIGN_INDEL * p + 2])};
-    if (gap && (q.gapped || q.gapped_starts)) {          // the positions' bytes, concatenated record by record
+    if (call) {          // the positions' bytes, concatenated record by record; an extending call: between the bytes its ends emit
         const std::vector<uint64_t> starts = record_starts(ks);
-        uint64_t at = 0;
+        uint64_t at = 0, xat = 0;
         for (uint64_t j = 0; j < n_rec; j++) {
             if (q.gapped_starts) q.gapped_starts[j] = at;
+            const uint64_t at0 = at;
+            // (the begin columns from the farthest to the one next to the record)
+            const size_t nb = ext ? std::min<size_t>(h_esum[EXTEND_END_SUMS * (2 * j)], E) : 0, ne = ext ? std::min<size_t>(h_esum[EXTEND_END_SUMS * (2 * j + 1)], E) : 0;
+            if (ext && q.extended_starts) q.extended_starts[j] = xat;
+            if (ext && q.extended) for (size_t e = 0; e < nb; e++) q.extended[xat + e] = h_ebytes[(2 * j) * E + (nb - 1 - e)];
+            xat += nb;
             for (uint64_t p = starts[j]; p < starts[j + 1]; p++) {
                 const size_t m = std::min<size_t>(h_gcount[p], 1 + span);
                 if (q.gapped) memcpy(q.gapped + at, h_gbytes.data() + p * (1 + span), m);
-                at += m;
+                if (ext && q.extended) memcpy(q.extended + xat, h_gbytes.data() + p * (1 + span), m);
+                at += m; xat += m;
             }
+            if (ext && q.extended) memcpy(q.extended + xat, h_ebytes.data() + (2 * j + 1) * E, ne);
+            xat += ne;
+            if (ext && q.extend_records)
+                q.extend_records[j] = mf_extend_record_t{at - at0 + nb + ne, nb, ne, h_esum[EXTEND_END_SUMS * (2 * j) + 1], h_esum[EXTEND_END_SUMS * (2 * j + 1) + 1]};
         }
         if (q.gapped_starts) q.gapped_starts[n_rec] = at;
+        if (ext && q.extended_starts) q.extended_starts[n_rec] = xat;
     }
     for (size_t j = 0; j < h_gsum.size() / GAPPED_SUMS; j++)
         q.gapped_records[j] = mf_gapped_record_t{h_gsum[GAPPED_SUMS * j], h_gsum[GAPPED_SUMS * j + 1], h_gsum[GAPPED_SUMS * j + 2], h_gsum[GAPPED_SUMS * j + 3]};
@@ -690,7 +722,20 @@ int mf_align_gapped(const mf_kmerset *ks, const mf_reads *reads, uint32_t thresh
                     mf_pileup_t *pileup, uint8_t *consensus, mf_pileup_record_t *pileup_records, mf_indel_t *indels, mf_align_record_t *align_records,
                     mf_pileup_t *ins_pile, uint8_t *gapped, uint64_t *gapped_starts, mf_gapped_record_t *gapped_records, uint64_t *unplaced, mf_filter_stats_t *stats)
 {
-    PlaceRequest q{"alignment", true, pileup || consensus || pileup_records || ins_pile || gapped || gapped_starts || gapped_records};
+    return mf_align_extended(ks, reads, threshold, mode, min_depth, max_permille, keep, band, 0, out_bits, keep_bits, place_out, align_out, base_depth, place_records,
+                             pileup, consensus, pileup_records, indels, align_records, ins_pile, gapped, gapped_starts, gapped_records, nullptr, nullptr, nullptr, nullptr,
+                             unplaced, stats);
+}
+
+int mf_align_extended(const mf_kmerset *ks, const mf_reads *reads, uint32_t threshold, int mode, uint32_t min_depth, uint32_t max_permille, int keep, uint32_t band,
+                      uint32_t extend, uint32_t *out_bits, uint32_t *keep_bits, mf_place_t *place_out, mf_align_t *align_out, uint32_t *base_depth,
+                      mf_place_record_t *place_records, mf_pileup_t *pileup, uint8_t *consensus, mf_pileup_record_t *pileup_records, mf_indel_t *indels,
+                      mf_align_record_t *align_records, mf_pileup_t *ins_pile, uint8_t *gapped, uint64_t *gapped_starts, mf_gapped_record_t *gapped_records,
+                      mf_pileup_t *ext_pile, uint8_t *extended, uint64_t *extended_starts, mf_extend_record_t *extend_records, uint64_t *unplaced,
+                      mf_filter_stats_t *stats)
+{
+    PlaceRequest q{"alignment", true, pileup || consensus || pileup_records || ins_pile || gapped || gapped_starts || gapped_records || ext_pile || extended || extended_starts || extend_records};
+    q.extend = extend; q.ext_pile = ext_pile; q.extended = extended; q.extended_starts = extended_starts; q.extend_records = extend_records;
     q.min_depth = min_depth; q.max_permille = max_permille; q.keep = keep; q.keep_bits = keep_bits; q.align = true; q.band = band;
     q.place_out = place_out; q.align_out = align_out; q.base_depth = base_depth; q.place_records = place_records;
     q.pileup = pileup; q.consensus = consensus; q.pileup_records = pileup_records; q.indels = indels; q.align_records = align_records;
@@ -955,7 +1000,20 @@ int mf_filter_fastq_files_gapped(mf_kmerset *ks, const char *fq1, const char *fq
                                  mf_pileup_record_t *pileup_records, mf_indel_t *indels, mf_align_record_t *align_records, mf_pileup_t *ins_pile, uint8_t *gapped,
                                  uint64_t *gapped_starts, mf_gapped_record_t *gapped_records, uint64_t *unplaced, uint64_t *kept, uint64_t *total)
 {
-    PlaceRequest q{"alignment", true, pileup || consensus || pileup_records || ins_pile || gapped || gapped_starts || gapped_records};
+    return mf_filter_fastq_files_extended(ks, fq1, fq2, out1, out2, threshold, pair_mode, devices, n_devices, min_depth, max_permille, keep, band, 0, base_depth,
+                                          place_records, pileup, consensus, pileup_records, indels, align_records, ins_pile, gapped, gapped_starts, gapped_records,
+                                          nullptr, nullptr, nullptr, nullptr, unplaced, kept, total);
+}
+
+int mf_filter_fastq_files_extended(mf_kmerset *ks, const char *fq1, const char *fq2, const char *out1, const char *out2,
+                                   uint32_t threshold, int pair_mode, const int *devices, int n_devices, uint32_t min_depth, uint32_t max_permille, int keep,
+                                   uint32_t band, uint32_t extend, uint32_t *base_depth, mf_place_record_t *place_records, mf_pileup_t *pileup, uint8_t *consensus,
+                                   mf_pileup_record_t *pileup_records, mf_indel_t *indels, mf_align_record_t *align_records, mf_pileup_t *ins_pile, uint8_t *gapped,
+                                   uint64_t *gapped_starts, mf_gapped_record_t *gapped_records, mf_pileup_t *ext_pile, uint8_t *extended,
+                                   uint64_t *extended_starts, mf_extend_record_t *extend_records, uint64_t *unplaced, uint64_t *kept, uint64_t *total)
+{
+    PlaceRequest q{"alignment", true, pileup || consensus || pileup_records || ins_pile || gapped || gapped_starts || gapped_records || ext_pile || extended || extended_starts || extend_records};
+    q.extend = extend; q.ext_pile = ext_pile; q.extended = extended; q.extended_starts = extended_starts; q.extend_records = extend_records;
     q.min_depth = min_depth; q.max_permille = max_permille; q.keep = keep; q.align = true; q.band = band; q.base_depth = base_depth; q.place_records = place_records;
     q.pileup = pileup; q.consensus = consensus; q.pileup_records = pileup_records; q.indels = indels; q.align_records = align_records;
     q.ins_pile = ins_pile; q.gapped = gapped; q.gapped_starts = gapped_starts; q.gapped_records = gapped_records; q.unplaced = unplaced;

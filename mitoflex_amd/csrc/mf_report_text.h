@@ -187,4 +187,20 @@ inline bool write_insertions(FILE *f, const Names &names, const Starts &starts, 
     return written(f);
 }
 
+// --extension-report: name, end (begin or end), 1-based distance from the record, depth (the bases of the column), A, C, G, T of every
+// (record, end, offset) of the extension pile (extend entries an end, begin then end of every record) with a count that is not zero
+inline bool write_extension_report(FILE *f, const Names &names, const mf_pileup_t *ext_pile, uint32_t extend)
+{
+    if (!f) return false;
+    fputs("name\tend\toffset\tdepth\tA\tC\tG\tT\n", f);
+    for (size_t i = 0; i < names.size(); i++)
+        for (uint32_t side = 0; side < 2; side++)
+            for (uint32_t e = 0; e < extend; e++) {
+                const mf_pileup_t &c = ext_pile[(2 * i + side) * (size_t)extend + e];
+                if (c.a || c.c || c.g || c.t)
+                    fprintf(f, "%s\t%s\t%u\t%llu\t%u\t%u\t%u\t%u\n", names[i].c_str(), side ? "end" : "begin", e + 1, (ull)c.a + c.c + c.g + c.t, c.a, c.c, c.g, c.t);
+            }
+    return written(f);
+}
+
 } // namespace mf_text

@@ -58,6 +58,10 @@ ALIGN_RECORD = np.dtype([("accepted", np.uint64), ("rejected", np.uint64), ("com
                          ("insertions", np.uint64), ("deletions", np.uint64), ("gapped", np.uint64), ("hist", np.uint64, (SCORE_BINS,))])
 # the per-record summary of the gapped consensus (mf_gapped_record_t)
 GAPPED_RECORD = np.dtype([("length", np.uint64), ("deleted", np.uint64), ("insertions", np.uint64), ("inserted_bases", np.uint64)])
+# the per-record summary of the extended records (mf_extend_record_t); EXTEND_MAX: the most columns an end grows by in one call
+EXTEND_RECORD = np.dtype([("length", np.uint64), ("begin_bases", np.uint64), ("end_bases", np.uint64), ("begin_piled", np.uint64),
+                          ("end_piled", np.uint64)])
+EXTEND_MAX = 4096
 INDEL_VARIANT = np.dtype([("record", np.uint32), ("pos", np.uint64), ("depth", np.uint64), ("del", np.uint64), ("ins", np.uint64),
                           ("ins_bases", np.uint64)])
 # a variant position (pileup_variants): pos is 0-based inside the record, ref / alt are letters
@@ -82,6 +86,7 @@ EXPORTS = (
     "mf_verify_keep", "mf_filter_fastq_files_verified_keep",
     "mf_align", "mf_filter_fastq_files_aligned",
     "mf_align_gapped", "mf_filter_fastq_files_gapped",
+    "mf_align_extended", "mf_filter_fastq_files_extended",
 )
 
 
@@ -215,6 +220,11 @@ def load(path: Optional[str] = None):
     L.mf_filter_fastq_files_gapped.argtypes = [vp, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_uint32, C.c_int,
                                                C.POINTER(C.c_int), C.c_int, C.c_uint32, C.c_uint32, C.c_int, C.c_uint32, vp, vp, vp, vp, vp, vp,
                                                vp, vp, vp, vp, vp, vp, u64p, u64p]
+    L.mf_align_extended.argtypes = [vp, vp, C.c_uint32, C.c_int, C.c_uint32, C.c_uint32, C.c_int, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp, vp, vp, vp,
+                                    vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(FilterStats)]
+    L.mf_filter_fastq_files_extended.argtypes = [vp, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_uint32, C.c_int,
+                                                 C.POINTER(C.c_int), C.c_int, C.c_uint32, C.c_uint32, C.c_int, C.c_uint32, C.c_uint32, vp, vp, vp, vp,
+                                                 vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, u64p, u64p]
     if L.mf_abi_version() != 5:
         raise MitoFilterError("libmitofilter_hip ABI version mismatch")
     _lib = L
@@ -595,8 +605,11 @@ class Aligned(Verified):
     """What an aligning call gives (include/mitofilter.h, banded alignment): Verified's fields with score and score_records None, and
     align ALIGN[n] (align_reads only), indels INDEL[positions], align_records ALIGN_RECORD[R] and keep_bits u32[ceil(n/32)] (align_reads
     only; the pass bits under KEEP_PASSING).  A call with gapped=True (include/mitofilter.h, gapped consensus) also gives ins_pile
-    PILEUP[positions, 2 * band], gapped u8[its length], gapped_starts u64[R + 1] and gapped_records GAPPED_RECORD[R]; None otherwise."""
-    __slots__ = ("keep_bits", "align", "indels", "align_records", "ins_pile", "gapped", "gapped_starts", "gapped_records")
+    PILEUP[positions, 2 * band], gapped u8[its length], gapped_starts u64[R + 1] and gapped_records GAPPED_RECORD[R]; None otherwise.
+    A call with extend=E > 0 (include/mitofilter.h, extended records) also gives ext_pile PILEUP[R, 2, E] ([record, begin / end, offset
+    from the record]), extended u8[its length], extended_starts u64[R + 1] and extend_records EXTEND_RECORD[R]; None otherwise."""
+    __slots__ = ("keep_bits", "align", "indels", "align_records", "ins_pile", "gapped", "gapped_starts", "gapped_records",
+                 "ext_pile", "extended", "extended_starts", "extend_records")
 
 
 def _gapped_outputs(ks: KmerSet, band: int):
@@ -611,26 +624,52 @@ def _gapped_outputs(ks: KmerSet, band: int):
     return ptrs, lambda: {"ins_pile": ins[:P, :span], "gapped": gapped[:int(gstarts[-1])], "gapped_starts": gstarts, "gapped_records": grec[:R]}
 
 
+def _extend_outputs(ks: KmerSet, band: int, extend: int):
+    """the four outputs of an extending call, as _gapped_outputs gives the gapped call's"""
+    starts = ks.record_starts
+    P, R, span, E = int(starts[-1]), len(starts) - 1, 2 * int(band), int(extend)
+    ext = np.zeros((max(R, 1), 2, E), dtype=PILEUP)
+    extended = np.zeros(max(P * (1 + span) + 2 * R * E, 1), dtype=np.uint8)
+    xstarts = np.zeros(R + 1, dtype=np.uint64)
+    xrec = np.zeros(max(R, 1), dtype=EXTEND_RECORD)
+    ptrs = [ext.ctypes.data, extended.ctypes.data, xstarts.ctypes.data, xrec.ctypes.data]
+    return ptrs, lambda: {"ext_pile": ext[:R], "extended": extended[:int(xstarts[-1])], "extended_starts": xstarts, "extend_records": xrec[:R]}
+
+
+def _check_extend(extend: int):
+    if not 0 <= int(extend) <= EXTEND_MAX:
+        raise ValueError("extend is a number from 0 to %d" % EXTEND_MAX)
+
+
 def _check_band(band: int):
     if not 0 <= int(band) <= ALIGN_MAX_BAND:
         raise ValueError("band is a number from 0 to %d (and below k)" % ALIGN_MAX_BAND)
 
 
 def align_reads(ks: KmerSet, reads: Reads, band: int = 8, min_depth: int = 1, max_permille: int = 1000, keep: int = KEEP_PASSING,
-                pileup: bool = True, threshold: int = 1, mode: int = MODE_SCREENED, gapped: bool = False) -> Aligned:
+                pileup: bool = True, threshold: int = 1, mode: int = MODE_SCREENED, extend: int = 0, gapped: bool = False) -> Aligned:
     """One filter pass, then every placed read aligned to its record inside the band of 2 * band + 1 diagonals around its placement and
     cut at max_permille edits per thousand alignment columns; base depth, the records, the keep bits and (pileup=True) the pile-up
     follow the alignment, and indels counts deletions and insertions per bait position (include/mitofilter.h: mf_align).  band = 0 is
     verify_reads.  gapped=True: the letters of the inserted bases and the consensus that calls deletions and insertions too
-    (mf_align_gapped).  -> Aligned with bits, keep_bits, place, align and the shared fields."""
+    (mf_align_gapped).  extend=E > 0: the bases that hang over the records' ends piled up to E columns from them, both ends called and
+    the extended records (mf_align_extended); the gapped fields are filled only with gapped=True.  -> Aligned with bits, keep_bits, place,
+    align and the shared fields."""
     _check_cut(min_depth, max_permille, keep)
     _check_band(band)
+    _check_extend(extend)
     per_read, read_results = _read_outputs(reads, PLACE, ALIGN)
     ptrs, results = _report_outputs(ks, _ALIGN_FIELDS, () if pileup else _PILEUP_FIELDS[:3])
     n = reads.info.n_reads
     keep_bits = np.zeros(max((n + 31) // 32, 1), dtype=np.uint32)
     more = {}
-    if gapped:
+    if int(extend) > 0:
+        gptrs, gresults = _gapped_outputs(ks, band) if gapped else ([None] * 4, dict)
+        xptrs, xresults = _extend_outputs(ks, band, extend)
+        _chk(load().mf_align_extended(ks._h, reads._h, threshold, mode, min_depth, max_permille, int(keep), int(band), int(extend), per_read[0],
+                                      keep_bits.ctypes.data, *per_read[1:], *ptrs[:-1], *gptrs, *xptrs, ptrs[-1], None))
+        more = {**gresults(), **xresults()}
+    elif gapped:
         gptrs, gresults = _gapped_outputs(ks, band)
         _chk(load().mf_align_gapped(ks._h, reads._h, threshold, mode, min_depth, max_permille, int(keep), int(band), per_read[0],
                                     keep_bits.ctypes.data, *per_read[1:], *ptrs[:-1], *gptrs, ptrs[-1], None))
@@ -681,6 +720,38 @@ def gapped_consensus(record_starts, base_depth, indels, ins_pile, consensus, min
         rec[j] = (len(out) - int(gstarts[j]), int(deleted[lo:hi].sum()), int((n_cols[lo:hi] > 0).sum()), int(n_cols[lo:hi].sum()))
     gstarts[R] = len(out)
     return np.frombuffer(bytes(out), np.uint8), gstarts, rec
+
+
+def extended_consensus(gapped, gapped_starts, ext_pile, min_depth: int = 1):
+    """The call rule of the extended records (include/mitofilter.h) over the downloaded outputs of an extending call, valid where no
+    counter is clamped: per record and end the columns from the record outwards that hold at least min_depth bases and one letter with
+    strictly the most, up to the first that does not; the begin columns from the farthest, the record's gapped bytes, the end columns.
+    ext_pile: PILEUP[R, 2, E].  -> (extended u8, extended_starts u64[R + 1], extend_records EXTEND_RECORD[R]).  Needs no device."""
+    if int(min_depth) < 1:
+        raise ValueError("min_depth is at least 1")
+    gstarts = np.asarray(gapped_starts, dtype=np.uint64)
+    R = len(gstarts) - 1
+    ext = np.asarray(ext_pile)
+    if ext.dtype != PILEUP or ext.ndim != 3 or ext.shape[:2] != (R, 2):
+        raise ValueError("ext_pile is PILEUP[R, 2, E]")
+    body = np.asarray(gapped, dtype=np.uint8)
+    if len(body) < int(gstarts[-1]):
+        raise ValueError("gapped is shorter than gapped_starts says")
+    counts = np.stack([ext[f].astype(np.int64) for f in ("a", "c", "g", "t")], axis=3)          # [R, 2, E, 4]
+    most = counts.max(axis=3)
+    emit = (counts.sum(axis=3) >= int(min_depth)) & ((counts == most[..., None]).sum(axis=3) == 1)
+    n_cols = np.minimum.accumulate(emit, axis=2).sum(axis=2)                                    # up to the first that is not
+    letters = np.frombuffer(b"ACGT", np.uint8)[counts.argmax(axis=3)]
+    out, xstarts, rec = bytearray(), np.zeros(R + 1, np.uint64), np.zeros(R, dtype=EXTEND_RECORD)
+    for j in range(R):
+        xstarts[j] = len(out)
+        nb, ne = int(n_cols[j, 0]), int(n_cols[j, 1])
+        out += letters[j, 0, :nb][::-1].tobytes()
+        out += body[int(gstarts[j]):int(gstarts[j + 1])].tobytes()
+        out += letters[j, 1, :ne].tobytes()
+        rec[j] = (len(out) - int(xstarts[j]), nb, ne, int(counts[j, 0].sum()), int(counts[j, 1].sum()))
+    xstarts[R] = len(out)
+    return np.frombuffer(bytes(out), np.uint8), xstarts, rec
 
 
 def indel_variants(record_starts, base_depth, indels, min_depth: int = 1, min_permille: int = 500) -> np.ndarray:
@@ -904,13 +975,21 @@ def filter_fastq_files_verified(ks: KmerSet, fq1: str, fq2: Optional[str], out1:
 def filter_fastq_files_aligned(ks: KmerSet, fq1: str, fq2: Optional[str], out1: str, out2: Optional[str], band: int = 8,
                                threshold: int = 1, pair_mode: int = PAIR_EITHER, devices: Optional[Sequence[int]] = None,
                                n_devices: int = 1, min_depth: int = 1, max_permille: int = 1000, pileup: bool = True,
-                               keep: int = KEEP_PASSING, gapped: bool = False) -> Aligned:
+                               keep: int = KEEP_PASSING, extend: int = 0, gapped: bool = False) -> Aligned:
     """filter_fastq_files_verified behind the banded alignment (mf_filter_fastq_files_aligned): the cut, the keep rule and the reports
     are those of align_reads, added over the mates.  gapped=True: the insertion pile added over the mates and the gapped consensus
-    called from the sums (mf_filter_fastq_files_gapped).  -> Aligned with kept, total and the shared fields."""
+    called from the sums (mf_filter_fastq_files_gapped).  extend=E > 0: the extension pile added over the mates and both ends of every
+    record called from the sums (mf_filter_fastq_files_extended).  -> Aligned with kept, total and the shared fields."""
     _check_cut(min_depth, max_permille, keep)
     _check_band(band)
+    _check_extend(extend)
     ptrs, results = _report_outputs(ks, _ALIGN_FIELDS, () if pileup else _PILEUP_FIELDS[:3])
+    if int(extend) > 0:
+        gptrs, gresults = _gapped_outputs(ks, band) if gapped else ([None] * 4, dict)
+        xptrs, xresults = _extend_outputs(ks, band, extend)
+        kept, total = _files_call("mf_filter_fastq_files_extended", ks, fq1, fq2, out1, out2, threshold, pair_mode, devices, n_devices,
+                                  min_depth, max_permille, int(keep), int(band), int(extend), *ptrs[:-1], *gptrs, *xptrs, ptrs[-1])
+        return Aligned(kept=kept, total=total, **results(), **gresults(), **xresults())
     if not gapped:
         kept, total = _files_call("mf_filter_fastq_files_aligned", ks, fq1, fq2, out1, out2, threshold, pair_mode, devices, n_devices,
                                   min_depth, max_permille, int(keep), int(band), *ptrs)
