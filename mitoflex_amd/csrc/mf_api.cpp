@@ -404,11 +404,16 @@ static int kmerset_new(const char *text, size_t len, int k, int device, mf_kmers
             // 4 Mbp 3.87 -> 2.59 ms a pass, 8.5 Mbp 6.88 -> 4.64, profiles/r06/d_front_variants2.txt)
             while (lg < FRONT2_MAX_LOG2B + 2 && (keys_bound >> lg) > 32) lg++;
             if (g_opt.front2_log2b > 0) lg = (uint32_t)g_opt.front2_log2b;
-            ks->f2_log2b = lg;
+            // A block index is taken from the bits of the hash that end just below bit 2s (stage1_index_lo): an index wider than the 2s bits of a sample
+            // shorter than 16 bases would reach into the bases that follow it in the stream -- the screens look a sample up as it lies there, the
+            // build inserts the masked s-mer -- and bait s-mers would be missed.  No table is wider than that (a forced front3_log2b of 25 .. 27 at
+            // s = 12, 27 at s = 13 was; 2^(2s) blocks hold every s-mer there is, so a wider table would gain nothing either).
+            const uint32_t lg_max = 2 * (uint32_t)ks->geom.s;
+            ks->f2_log2b = std::min(lg, lg_max);
             uint32_t lg3 = 0;
             if ((keys_bound >> lg) > 12) { lg3 = lg + 1; while (lg3 < 27 && (4ull << lg3) < keys_bound) lg3++; }
             if (g_opt.front3_log2b >= 0) lg3 = (uint32_t)g_opt.front3_log2b;
-            ks->f3_log2b = (mode == 2 || mode == 4) ? lg3 : 0;          // (modes 1 and 3 keep their LDS table and never see a bait that overloads front2)
+            ks->f3_log2b = (mode == 2 || mode == 4) ? std::min(lg3, lg_max) : 0;        // (modes 1 and 3 keep their LDS table and never see a bait that overloads front2)
         }
     }
     DevTables *T; int rc = build_on_device(ks, device, &T);
@@ -810,7 +815,7 @@ static int enqueue_pass(mf_reads *r, const KmerSetView &S, uint32_t thr, int mod
         if (P.screen) HIPCHK(launch_mark(r->v, S, r->d_recs[q], r->d_rec_counts[q], cand, n_cu, sf, t1));
         HIPCHK(launch_exact(r->v, S, cand, thr, count_all, r->d_bits[P.q_out], P.kind == PassKind::ONE_STREAM ? r->d_hits : nullptr, tally_of(r, P.q_out), n_cu, sf, t2, P.exact_coresident, done));
     }
-    r->flip = P.flip; r->cur = P.cur; r->sample_pass = P.sample_pass;
+    r->flip = P.flip; r->cur = P.cur; r->sample_pass = P.sample_pass; r->tally_regions = P.tally_regions;
     return MF_OK;
 }
 
@@ -868,7 +873,9 @@ int filter_common(const mf_kmerset *ks_, const mf_reads *reads_, uint32_t thr, i
     // join: finish kernels still running on the second stream belong to this call (unrecorded events are no-ops)
     for (int i = 0; i < NSETS; i++) HIPCHK(hipStreamWaitEvent(st, r->ev_finish[i], 0));
     HIPCHK(hipEventRecord(e_end, st));
-    const int regions = r->sample_pass ? TallyLayout::REGIONS : 1;          // (a screen + finish pass: phase 0, phase 1, the exact kernel behind them)
+    // the regions the call's passes wrote (every pass of a call plans the same kernels): a screen + finish pass phase 0 and phase 1, and the third only with
+    // the exact kernel behind them -- without it that region still holds what a k >= 48 pass on this buffer set left there, whatever set came since
+    const int regions = r->tally_regions;
     const unsigned long long *part = pass_per_step ? all_tallies.p + (size_t)(steps - 1) * TallyLayout::words() : r->d_counters[r->cur];          // pinned host memory, complete once the stream is
     if (out_bits) HIPCHK(hipMemcpyAsync(out_bits, r->d_bits[r->cur], ((r->v.n_reads + 31) / 32) * 4, hipMemcpyDeviceToHost, st));
     if (hits_out && r->v.n_reads) HIPCHK(hipMemcpyAsync(hits_out, r->d_hits, r->v.n_reads * 4, hipMemcpyDeviceToHost, st));

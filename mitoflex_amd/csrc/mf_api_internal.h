@@ -143,6 +143,7 @@ struct mf_reads {
     hipEvent_t ev_screen[NSETS] = {}, ev_finish[NSETS] = {};          // ordering between the two streams
     hipEvent_t ev_call[2] = {};                                       // begin / end of a call's passes
     bool cand_clean[NSETS] = {}, sample_pass = false;     // sample_pass: the latest pass was a screen + finish one
+    int tally_regions = 1;      // the regions of its tally block the latest pass wrote (PassPlan::tally_regions): the others hold what earlier passes left
     mf::PassFeedback fb;        // what the last call's tallies say about the input (mf_passplan.h)
     int cur = 0, flip = 0;      // flip: parity of the pipelined passes enqueued so far (which of two streams a pass's screen / finish kernels take)
     unsigned long long *tally_override = nullptr;       // set per pass by filter_common when every pass's tally is wanted

@@ -5,7 +5,9 @@
 #include "mf_kernels_cfg.h"
 namespace mf {
 // A pass's tally block: three regions -- phase 0 and phase 1 of the finish kernels, the exact kernel behind finish -- of EXACT_MAX_GRID (pass,
-// candidate) pairs, two 64-bit words a pair.  Every other kind of pass tallies into region 0 alone.
+// candidate) pairs, two 64-bit words a pair.  Every other kind of pass tallies into region 0 alone.  Nothing clears a block between passes: a
+// kernel overwrites its workgroups' pairs of the region it tallies into (the exact and protein kernels zero the rest of theirs) and leaves the
+// other regions as an earlier pass -- of another set, perhaps -- left them.  So a pass is summed over the regions it wrote, PassPlan::tally_regions.
 struct TallyLayout {
     static constexpr int REGIONS = 3;
     static constexpr size_t region(int i) { return (size_t)i * EXACT_MAX_GRID * 2; }          // word offset of region i
@@ -32,6 +34,7 @@ struct PassPlan {
     PassStream screen_on = PassStream::MAIN, later_on = PassStream::MAIN;          // two_streams: not the same, ev_screen[q] orders them; screen: one runs (and, but in a FINISH pass, a mark kernel)
     bool two_streams = false, wait_prev_finish = false, screen = false, screen_clears_bits = false, needs_cand = false, exact_behind_finish = false, exact_coresident = false;
     int flip = 0, cur = 0; bool sample_pass = false;          // what the read set holds after the pass
+    int tally_regions = 1;          // the leading regions of the tally block this pass writes: what its totals are summed over (TallyLayout::sum)
 };
 inline PassPlan plan_pass(const PassKnobs &kn, const PassInputs &in)
 {
@@ -82,6 +85,7 @@ inline PassPlan plan_pass(const PassKnobs &kn, const PassInputs &in)
 #define MF_FINISH_EXACT (in.k >= 48)
 #endif
     p.exact_behind_finish = finish && MF_FINISH_EXACT;          // (merges into the finish kernels' bits, tallies into region 2)
+    p.tally_regions = !finish ? 1 : p.exact_behind_finish ? 3 : 2;          // (a finish pass without it leaves region 2 as a pass of another set wrote it)
     p.needs_cand = split || p.exact_behind_finish;
     // the exact kernel takes its co-resident form when a screen follows (a screen workgroup holds 128 KiB of every CU's LDS for the whole pass), its
     // full form behind the last screen of the call (exact_co, tests: the co-resident form behind every screen)

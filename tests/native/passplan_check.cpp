@@ -27,9 +27,9 @@ static bool read_case(FILE *f, PassKnobs &kn, PassInputs &in)
 static void print_plan(const PassPlan &p)
 {
     static const char *const kinds[] = {"PROTEIN", "FINISH", "SPLIT_PIPELINED", "ONE_STREAM"}, *const streams[] = {"MAIN", "FINISH_A", "SCREEN_ALT", "FINISH_B"};
-    printf("%s %d %d %d %s %s %d %d %d %d %d %d %d %d %d\n", kinds[(int)p.kind], (int)p.two_streams, p.q, p.q_out, streams[(int)p.screen_on], streams[(int)p.later_on],
+    printf("%s %d %d %d %s %s %d %d %d %d %d %d %d %d %d %d\n", kinds[(int)p.kind], (int)p.two_streams, p.q, p.q_out, streams[(int)p.screen_on], streams[(int)p.later_on],
            (int)p.screen, (int)p.wait_prev_finish, (int)p.screen_clears_bits, (int)p.needs_cand, (int)p.exact_behind_finish, (int)p.exact_coresident, p.flip, p.cur,
-           (int)p.sample_pass);
+           (int)p.sample_pass, p.tally_regions);
 }
 
 int main(int argc, char **argv)

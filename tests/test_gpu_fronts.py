@@ -73,6 +73,35 @@ def test_forced_forms_match_oracle(mf, ol, bait_text, front, k, form):
     ks.close()
 
 
+@pytest.mark.parametrize("k", [19, 20, 28])
+@pytest.mark.parametrize("mode", [2, 4])
+def test_front3_is_no_wider_than_a_sample(mf, ol, bait_text, front, k, mode):
+    """samples shorter than 16 bases (s = 12 at k = 19, 13 at k = 20 and 28), both strands in the tables, the largest front3 that can be
+    asked for: a block index wider than the 2 s bits of a sample would be taken from the bases BEHIND the sample in the screens and from
+    the masked s-mer in the build -- bait s-mers missed, bits lost.  The set keeps the table to 2^(2 s) blocks, and bits and hit counts
+    equal the oracle's."""
+    s = {19: 12, 20: 13, 28: 13}[k]
+    front(mode, 6, 27, 0)          # (front2 at its smallest: nearly every sample goes on to front3)
+    ks = mf.KmerSet.from_text(bait_text, k)
+    info = ks.info
+    assert info.front_mode == mode and info.canonical_screen == 0 and info.screen_s == s
+    assert 0 < info.front3_log2_blocks <= 2 * s and info.front2_log2_blocks <= 2 * s
+    t = ol.OracleTable(bait_text, k)
+    seqs = make_reads(bait_text, 5000, seed=300 + k)
+    R = ol.OracleReads.from_seqs(seqs)
+    reads = mf.Reads.from_packed(R.words, R.offsets, R.npos)
+    for thr in (1, 2):
+        obits, ohits = ol.filter_reads(t, R, thr, threads=4)
+        bits, hits, _ = mf.filter_reads(ks, reads, thr, mf.MODE_SCREENED, want_hits=True)
+        assert np.array_equal(hits, ohits), (k, mode, thr)
+        assert np.array_equal(bits, obits), (k, mode, thr)
+        bits2, _, st = mf.filter_reads(ks, reads, thr, mf.MODE_SCREENED)
+        assert np.array_equal(bits2, obits), (k, mode, thr)
+        assert st.n_pass == int(bits_to_bool(obits, len(seqs)).sum()) > 0
+    reads.close()
+    ks.close()
+
+
 @pytest.mark.parametrize("k", [17, 19, 21, 25, 27])
 @pytest.mark.parametrize("form", [(0, 0, -1), (1, 6, -1), (3, 0, -1), (4, 6, 8), (2, 6, 12), (0, 0, -1, 1), (1, 6, -1, 1), (4, 6, 8, 1), (2, 6, 12, 1)])
 def test_stride8_sets_through_the_finish_kernels(mf, ol, bait_text, front, k, form):

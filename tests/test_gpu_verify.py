@@ -89,7 +89,11 @@ def identities(v, n_reads):
 
 def check(mf, ks, reads, V, seqs, want, thr, mode, min_depth, max_permille):
     """one mf_verify call against what the oracle gave for (thr, max_permille)"""
-    v = mf.verify_reads(ks, reads, thr, mode, min_depth, max_permille)
+    return check_result(mf.verify_reads(ks, reads, thr, mode, min_depth, max_permille), V, seqs, want, min_depth)
+
+
+def check_result(v, V, seqs, want, min_depth):
+    """what a verifying call gave (with a keep mode or without) against what the oracle gave for its threshold and cut"""
     n = len(seqs)
     assert np.array_equal(bits_to_bool(v.bits, n), want["passes"])
     got = rows_of(v.place)

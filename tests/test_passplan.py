@@ -26,9 +26,9 @@ KINDS = {"default": {}, "split": {"pass": 1}, "serial": {"pass": 2}, "split-co":
 
 def expected_plan(c):
     """The decision table.  Returns the driver's line: kind two_streams q q_out screen_on later_on screen wait_prev_finish screen_clears_bits
-    needs_cand exact_behind_finish exact_coresident flip cur sample_pass."""
-    def line(kind, two=0, q=0, q_out=0, screen_on="MAIN", later_on="MAIN", screen=0, wait=0, clears=0, cand=0, behind=0, co=0, flip=c["flip"], cur=c["cur"], sample=0):
-        return " ".join(str(int(x) if not isinstance(x, str) else x) for x in (kind, two, q, q_out, screen_on, later_on, screen, wait, clears, cand, behind, co, flip, cur, sample))
+    needs_cand exact_behind_finish exact_coresident flip cur sample_pass tally_regions."""
+    def line(kind, two=0, q=0, q_out=0, screen_on="MAIN", later_on="MAIN", screen=0, wait=0, clears=0, cand=0, behind=0, co=0, flip=c["flip"], cur=c["cur"], sample=0, regions=1):
+        return " ".join(str(int(x) if not isinstance(x, str) else x) for x in (kind, two, q, q_out, screen_on, later_on, screen, wait, clears, cand, behind, co, flip, cur, sample, regions))
     if c["prot"]:          # one kernel on the main stream, bits and tally of the current set
         return line("PROTEIN", q_out=c["cur"])
     screened = c["mode"] == SCREENED and c["s"] > 0
@@ -41,7 +41,8 @@ def expected_plan(c):
         later = ("FINISH_B" if fin2 and odd else "FINISH_A") if two else "MAIN"
         screen_on = "SCREEN_ALT" if two and c["screen_streams"] == 2 and odd else "MAIN"
         behind = c["k"] >= 48
-        return line("FINISH", two, q, q, screen_on, later, 1, two, 1, behind, behind, behind and c["more"], odd, q, 1)
+        # the tally regions the pass writes: the two phases of the finish kernels, and the third only with the exact kernel behind them
+        return line("FINISH", two, q, q, screen_on, later, 1, two, 1, behind, behind, behind and c["more"], odd, q, 1, 3 if behind else 2)
     if screened and not c["count_all"] and c["overlap"] and c["split_pipe"] and c["pass"] != 2 and not c["split_serial"]:
         q = (c["cur"] + 1) % (c["nsets"] if c["kw"] == 2 else 2)
         odd = c["flip"] ^ 1
@@ -88,7 +89,8 @@ def test_the_cases_reach_every_kind_and_every_rule():
     assert {p[0] for p in plans} == {"PROTEIN", "FINISH", "SPLIT_PIPELINED", "ONE_STREAM"}
     for kind, column, values in (("FINISH", 1, "01"), ("FINISH", 2, "0123"), ("FINISH", 4, ("MAIN", "SCREEN_ALT")), ("FINISH", 5, ("MAIN", "FINISH_A", "FINISH_B")),
                                  ("FINISH", 10, "01"), ("FINISH", 11, "01"), ("SPLIT_PIPELINED", 2, "0123"), ("SPLIT_PIPELINED", 4, ("MAIN", "SCREEN_ALT")),
-                                 ("SPLIT_PIPELINED", 11, "01"), ("ONE_STREAM", 3, "012"), ("ONE_STREAM", 6, "01")):
+                                 ("SPLIT_PIPELINED", 11, "01"), ("ONE_STREAM", 3, "012"), ("ONE_STREAM", 6, "01"),
+                                 ("FINISH", 15, "23"), ("SPLIT_PIPELINED", 15, "1"), ("ONE_STREAM", 15, "1"), ("PROTEIN", 15, "1")):
         assert {p[column] for p in plans if p[0] == kind} == set(values), (kind, column)
     # the seven configurations are the seven they are named for
     kinds = {name: expected_plan(dict(DEFAULT, **ch)).split() for name, ch in KINDS.items()}
@@ -123,6 +125,39 @@ def test_seven_passes_rotate_sets_and_streams(run):
         for p in passes:
             assert " ".join(p) == expected_plan(c)
             c.update(flip=int(p[12]), cur=int(p[13]))
+
+
+def test_a_call_is_summed_over_the_regions_its_pass_wrote(run):
+    """One read set, calls of different sets one after the other: nothing clears a tally block between passes, so what a pass does not write is
+    what an earlier pass left.  Modelled here: every pass stamps its call's number into the regions its kernels write -- region 0 for every
+    kind, region 1 too for screen + finish, region 2 only with the exact kernel behind them (k >= 48) -- of the block of its q_out; a call's
+    answer reads the leading tally_regions of the last pass's block and must meet its own stamp alone.  (Summing all three regions after
+    every screen + finish pass met the k = 63 stamp in a later k = 31 call: after three pipelined k = 63 passes in the very next call, with
+    single passes in the third call.)"""
+    k63, k31 = dict(DEFAULT, kw=2, k=63), dict(DEFAULT)
+    single = {"overlap": 0, "more": 0}
+    calls = [(k63, 3), (k31, 1), (k31, 1), (k31, 1),                                                 # sequence a
+             (dict(k63, **single), 1), (dict(k31, **single), 1), (dict(k31, **single), 1),           # sequence b
+             (dict(k31, thr=2, **single), 1), (dict(k63, **single), 1), (dict(k31, prot=1), 1), (dict(k31, **single), 1), (dict(k31, **single), 1),
+             (dict(k31, k=47, kw=2), 5), (dict(k63, k=48), 5), (dict(k31, k=47, kw=2), 5), (k31, 2)]
+    seen_regions, stale_met = set(), []
+    for number, (c, steps) in enumerate(calls, 1):
+        if number in (1, 5):          # a freshly uploaded read set: zeroed blocks
+            blocks, flip, cur = [[0, 0, 0] for _ in range(3)], 0, 0
+        for step in range(steps):
+            row = dict(c, flip=flip, cur=cur, more=int(c["overlap"] and step + 1 < steps))
+            p = run(["plan " + _row(row)])[0].split()
+            assert " ".join(p) == expected_plan(row)
+            writes = {"FINISH": 3 if int(p[10]) else 2}.get(p[0], 1)          # (by kind and exact_behind_finish: not read from tally_regions)
+            blocks[int(p[3])][:writes] = [number] * writes
+            flip, cur = int(p[12]), int(p[13])
+        regions = int(p[15])
+        seen_regions.add(regions)
+        assert int(p[3]) == cur and blocks[cur][:regions] == [number] * regions, (number, c, blocks, regions)
+        if p[0] == "FINISH" and set(blocks[cur]) - {0, number}:          # what the sum over all three regions would have met
+            stale_met.append(number)
+    assert seen_regions == {1, 2, 3}
+    assert stale_met[:4] == [2, 3, 4, 7] and len(stale_met) >= 6, stale_met          # (sequence a: the next call on; sequence b: the third)
 
 
 def test_tally_layout(run):
