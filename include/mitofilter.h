@@ -65,7 +65,8 @@ typedef struct {
     uint64_t n_windows;    /* sum over records of max(0, len-k+1) */
     int32_t  screen_s;     /* s-mer length used by the screen, 0 = screen disabled */
     int32_t  screen_stride;/* sample stride in bases */
-    uint32_t bloom_words;  /* LDS bit-table size in u32 words */
+    uint32_t bloom_words;  /* nucleotide sets: the screen's LDS bit table in u32 words; protein sets: the key bit table in u32
+                              words, staged in LDS when <= 16384 and read through L2 when larger */
     uint32_t smer_slots;   /* exact s-mer table slots */
     uint64_t n_smers;      /* distinct s-mers (both strands) */
     int32_t  kind;         /* MF_KIND_*; for MF_KIND_PROTEIN k is the peptide k-mer length (ABI 2) */

@@ -519,7 +519,7 @@ int mf_kmerset_info(const mf_kmerset *ks, mf_kmerset_info_t *info)
     memset(info, 0, sizeof *info);
     info->k = ks->k; info->key_words = ks->kw; info->slots = ks->slots; info->n_windows = ks->n_windows;
     info->screen_s = ks->geom.s; info->screen_stride = ks->geom.stride;
-    info->bloom_words = ks->geom.s ? (uint32_t)ks->screen_words() : 0; info->smer_slots = ks->stab_slots;
+    info->bloom_words = ks->kind == MF_KIND_PROTEIN ? 1u << ks->kb_log2w : ks->geom.s ? (uint32_t)ks->screen_words() : 0; info->smer_slots = ks->stab_slots;
     if (!ks->dev.empty()) { info->n_keys = ks->dev.begin()->second.n_keys; info->n_smers = ks->dev.begin()->second.n_smers; }
     info->kind = ks->kind; info->genetic_code = ks->genetic_code;
     info->front_mode = ks->front_mode; info->front2_log2_blocks = ks->front_mode ? ks->f2_log2b : 0; info->front3_log2_blocks = ks->f3_log2b; info->canonical_screen = ks->canon ? 1u : 0u;

@@ -104,6 +104,18 @@ def _fuzz_nucleotide(mf, ol, seed, opts=None):
 
 @pytest.mark.parametrize("seed", range(int(os.environ.get("MF_FUZZ_SEEDS", "40")) // 2))
 def test_fuzz_protein(mf, ol, seed):
+    _fuzz_protein(mf, ol, seed)
+
+
+@pytest.mark.parametrize("seed", range(int(os.environ.get("MF_FUZZ_SEEDS", "40")) // 2))
+def test_fuzz_protein_forced_bit_tables(mf, ol, monkeypatch, seed):
+    """the same configurations with the key bit table forced to a size of its own: saturated or roomy, staged in LDS (<= 2^14 words) or
+    read through L2 with the run counters in front of it"""
+    lg = random.Random(13000 + seed).choice([8, 10, 14, 15, 20])
+    _fuzz_protein(mf, ol, seed, lg, monkeypatch)
+
+
+def _fuzz_protein(mf, ol, seed, lg=None, monkeypatch=None):
     from oracle import prot_bait_ref as pr
     rng = random.Random(9000 + seed)
     kp = rng.randint(4, 12)
@@ -117,8 +129,14 @@ def test_fuzz_protein(mf, ol, seed):
     R = ol.OracleReads.from_seqs(seqs)
     t = ol.OracleTable(db, kp, protein=True)
     obits, ohits = ol.pfilter_reads(t, R, code, thr, threads=4)
-    ks = mf.KmerSet.protein_from_text(db, kp, code)
-    cfg = dict(seed=seed, kp=kp, code=code, n_reads=len(seqs), thr=thr, prots=[len(p) for p in prots])
+    cfg = dict(seed=seed, kp=kp, code=code, n_reads=len(seqs), thr=thr, prots=[len(p) for p in prots], kbloom_log2w=lg)
+    if lg is None:
+        ks = mf.KmerSet.protein_from_text(db, kp, code)
+    else:
+        with monkeypatch.context() as m:                     # for the construction of the protein set alone
+            m.setenv("MF_KBLOOM_LOG2W", str(lg))
+            ks = mf.KmerSet.protein_from_text(db, kp, code)
+        assert ks.info.bloom_words == 1 << lg, cfg
     assert np.array_equal(ks.export_table(), t.keys), cfg
     reads = mf.Reads.from_packed(R.words, R.offsets, R.npos)
     bits, hits, _ = mf.filter_reads(ks, reads, thr, want_hits=True)

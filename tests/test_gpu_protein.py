@@ -40,6 +40,7 @@ def test_peptide_table_byte_identical(mf, ol, db, kp):
     info = ks.info
     assert (info.k, info.key_words, info.slots, info.n_keys, info.kind, info.genetic_code) == (kp, 1, t.slots, t.n_keys, mf.KIND_PROTEIN, 5)
     assert info.screen_s == 0
+    assert info.bloom_words <= 16384                                     # a small database: its key bit table is staged in LDS
     assert np.array_equal(ks.export_table(), t.keys)
 
 
@@ -119,6 +120,7 @@ def test_large_database_uses_global_bit_table(mf, ol):
     ks = mf.KmerSet.protein_from_text(prot_fa, 8, 5)
     t = ol.OracleTable(prot_fa, 8, protein=True)
     assert ks.info.n_windows > (1 << 17) and ks.info.n_keys == t.n_keys
+    assert ks.info.bloom_words > 16384                                   # more words than the LDS form stages
     assert np.array_equal(ks.export_table(), t.keys)
     seqs = make_reads(gene_fa, 40000, seed=17, uniform=True, mito_frac=0.2)
     R = ol.OracleReads.from_seqs(seqs)
