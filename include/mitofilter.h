@@ -196,6 +196,19 @@ int mf_filter_resident(const mf_kmerset *ks, const mf_reads *reads, uint32_t thr
 int mf_filter_resident_passes(const mf_kmerset *ks, const mf_reads *reads, uint32_t threshold, int mode,
                               int steps, uint64_t *n_pass_per_step, mf_filter_stats_t *stats);
 
+/* Same as mf_filter_resident_passes, and the result bitmap of EVERY one of the `steps` passes in bits_per_step: steps rows of
+ * ceil(n_reads/32) u32, pass s at s * ceil(n_reads/32), bit r of a row set = read r passed in that pass.  n_pass_per_step is
+ * optional here.  A row is what the pass left in the result bitmap of its own buffer set: behind the pass's last kernel, on the
+ * stream that carries it, the bitmap is copied into a device log (n_reads/8 bytes a pass), and where an event orders that
+ * kernel against the screen that next clears the bitmap, the event is recorded again behind the copy.  The plans, kernels,
+ * arguments, streams and events of the passes are those of mf_filter_resident_passes, and the host does not synchronise
+ * between passes.  The copy is one short node more per pass, so the overlap of consecutive passes is not timed exactly as in
+ * mf_filter_resident.  What it catches: a pass that wrote to the wrong buffer set, a bitmap cleared wrongly or not at all, a
+ * stale buffer, a wait that the plan left out -- faults of the plan and the kernels.  It is no race detector.  No reference
+ * counterpart (test support for the pipelined pass).  MF_E_ARG: bits_per_step NULL, steps < 1. */
+int mf_filter_resident_bits(const mf_kmerset *ks, const mf_reads *reads, uint32_t threshold, int mode, int steps,
+                            uint32_t *bits_per_step, uint64_t *n_pass_per_step, mf_filter_stats_t *stats);
+
 /* One-shot over host buffers (SURVEY.md 8b name): H2D, filter, D2H. */
 int mf_filter_packed(const mf_kmerset *ks, int device,
                      const uint32_t *words, const uint64_t *offsets, uint64_t n_reads,

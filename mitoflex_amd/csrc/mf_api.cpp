@@ -777,7 +777,9 @@ static int clean_cand(mf_reads *r, int q, hipStream_t st)
     if (!r->cand_clean[q]) { HIPCHK(hipMemsetAsync(r->d_cand[q], 0, r->bitmap_bytes, st)); r->cand_clean[q] = true; }
     return MF_OK;
 }
-static int enqueue_pass(mf_reads *r, const KmerSetView &S, uint32_t thr, int mode, bool count_all, DevCtx *ctx, hipEvent_t *ev, bool overlap, bool more = false)
+// bits_log (mf_filter_resident_bits): where on the device this pass's result bitmap is copied to, behind the pass's last kernel
+static int enqueue_pass(mf_reads *r, const KmerSetView &S, uint32_t thr, int mode, bool count_all, DevCtx *ctx, hipEvent_t *ev, bool overlap, bool more = false,
+                        uint32_t *bits_log = nullptr)
 {
     options_from_env_once();          // (the options are read on every pass, once: bench.py times the serial form next to the default one in one process)
     const PassKnobs knobs{g_opt.pass, g_opt.finish_streams, g_opt.screen_streams, g_opt.split_pipe, g_opt.exact_co, g_opt.s8_finish};
@@ -815,12 +817,20 @@ static int enqueue_pass(mf_reads *r, const KmerSetView &S, uint32_t thr, int mod
         if (P.screen) HIPCHK(launch_mark(r->v, S, r->d_recs[q], r->d_rec_counts[q], cand, n_cu, sf, t1));
         HIPCHK(launch_exact(r->v, S, cand, thr, count_all, r->d_bits[P.q_out], P.kind == PassKind::ONE_STREAM ? r->d_hits : nullptr, tally_of(r, P.q_out), n_cu, sf, t2, P.exact_coresident, done));
     }
+    // The result bitmap of the pass's own buffer set as its last kernel left it, on that kernel's stream.  With two streams the screen that next clears this
+    // set's bitmap -- and the join that ends the call -- wait on ev_finish[q] alone: recorded again behind the copy, it completes only when the copy has.
+    // (One stream: the stream's order does the same.)
+    if (bits_log && r->v.n_reads) {
+        HIPCHK(hipMemcpyAsync(bits_log, r->d_bits[P.q_out], ((r->v.n_reads + 31) / 32) * 4, hipMemcpyDeviceToDevice, sf));
+        if (done) HIPCHK(hipEventRecord(done, sf));
+    }
     r->flip = P.flip; r->cur = P.cur; r->sample_pass = P.sample_pass; r->tally_regions = P.tally_regions;
     return MF_OK;
 }
 
-int filter_common(const mf_kmerset *ks_, const mf_reads *reads_, uint32_t thr, int mode, uint32_t *out_bits,
-                  uint32_t *hits_out, int steps, mf_filter_stats_t *stats, uint64_t *pass_per_step)
+// filter_common (mf_api_internal.h), and for mf_filter_resident_bits the result bitmap of every pass: bits_per_step, `steps` rows of ceil(n_reads / 32) words
+static int filter_passes(const mf_kmerset *ks_, const mf_reads *reads_, uint32_t thr, int mode, uint32_t *out_bits,
+                         uint32_t *hits_out, int steps, mf_filter_stats_t *stats, uint64_t *pass_per_step, uint32_t *bits_per_step)
 {
     mf_kmerset *ks = const_cast<mf_kmerset *>(ks_);
     mf_reads *r = const_cast<mf_reads *>(reads_);
@@ -864,9 +874,15 @@ int filter_common(const mf_kmerset *ks_, const mf_reads *reads_, uint32_t thr, i
         memset(all_tallies.p, 0, (size_t)steps * TallyLayout::bytes());
     }
     struct OverrideReset { mf_reads *r; ~OverrideReset() { r->tally_override = nullptr; } } override_reset{r};
+    // every pass's result bitmap when the caller wants them all (mf_filter_resident_bits): a device log, a row a pass, which each pass copies its buffer
+    // set's own bitmap into behind its last kernel (enqueue_pass) -- a set's bitmap is cleared again nsets passes on
+    const size_t bit_words = (r->v.n_reads + 31) / 32;
+    DevScratch log_mem; uint32_t *d_log = nullptr;
+    if (bits_per_step && bit_words) HIPCHK(log_mem.alloc(d_log, (size_t)steps * bit_words * 4));
     for (int i = 0; i < steps; i++) {
         if (pass_per_step) r->tally_override = all_tallies.p + (size_t)i * TallyLayout::words();
-        rc = enqueue_pass(r, T->view, thr, mode, count_all, ctx, n_sampled && i % stride == 0 ? &ev[(size_t)(i / stride) * 6] : nullptr, pipelined, i + 1 < steps);
+        rc = enqueue_pass(r, T->view, thr, mode, count_all, ctx, n_sampled && i % stride == 0 ? &ev[(size_t)(i / stride) * 6] : nullptr, pipelined, i + 1 < steps,
+                          d_log ? d_log + (size_t)i * bit_words : nullptr);
         if (rc) return rc;
     }
     lap("enqueued");
@@ -879,6 +895,7 @@ int filter_common(const mf_kmerset *ks_, const mf_reads *reads_, uint32_t thr, i
     const unsigned long long *part = pass_per_step ? all_tallies.p + (size_t)(steps - 1) * TallyLayout::words() : r->d_counters[r->cur];          // pinned host memory, complete once the stream is
     if (out_bits) HIPCHK(hipMemcpyAsync(out_bits, r->d_bits[r->cur], ((r->v.n_reads + 31) / 32) * 4, hipMemcpyDeviceToHost, st));
     if (hits_out && r->v.n_reads) HIPCHK(hipMemcpyAsync(hits_out, r->d_hits, r->v.n_reads * 4, hipMemcpyDeviceToHost, st));
+    if (d_log) HIPCHK(hipMemcpyAsync(bits_per_step, d_log, (size_t)steps * bit_words * 4, hipMemcpyDeviceToHost, st));          // (behind the join: every pass's copy is in)
     lap("copies");
     HIPCHK(hipStreamSynchronize(st));
     lap("synced");
@@ -907,6 +924,12 @@ int filter_common(const mf_kmerset *ks_, const mf_reads *reads_, uint32_t thr, i
     return MF_OK;
 }
 
+int filter_common(const mf_kmerset *ks, const mf_reads *reads, uint32_t thr, int mode, uint32_t *out_bits,
+                  uint32_t *hits_out, int steps, mf_filter_stats_t *stats, uint64_t *pass_per_step)
+{
+    return filter_passes(ks, reads, thr, mode, out_bits, hits_out, steps, stats, pass_per_step, nullptr);
+}
+
 extern "C" {
 
 int mf_filter(const mf_kmerset *ks, const mf_reads *reads, uint32_t threshold, int mode,
@@ -927,6 +950,14 @@ int mf_filter_resident_passes(const mf_kmerset *ks, const mf_reads *reads, uint3
 {
     if (!n_pass_per_step) return fail(MF_E_ARG, "n_pass_per_step is NULL");
     return filter_common(ks, reads, threshold, mode, nullptr, nullptr, steps, stats, n_pass_per_step);
+}
+
+int mf_filter_resident_bits(const mf_kmerset *ks, const mf_reads *reads, uint32_t threshold, int mode, int steps,
+                            uint32_t *bits_per_step, uint64_t *n_pass_per_step, mf_filter_stats_t *stats)
+{
+    if (!bits_per_step) return fail(MF_E_ARG, "bits_per_step is NULL");
+    if (steps < 1) return fail(MF_E_ARG, "steps must be >= 1");
+    return filter_passes(ks, reads, threshold, mode, nullptr, nullptr, steps, stats, n_pass_per_step, bits_per_step);
 }
 
 int mf_filter_packed(const mf_kmerset *ks, int device, const uint32_t *words, const uint64_t *offsets, uint64_t n_reads,

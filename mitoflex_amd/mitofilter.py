@@ -75,7 +75,7 @@ EXPORTS = (
     "mf_kmerset_build_from_fasta", "mf_kmerset_build_from_text", "mf_kmerset_build_protein_from_fasta",
     "mf_kmerset_build_protein_from_text", "mf_kmerset_info", "mf_kmerset_export",
     "mf_kmerset_free", "mf_reads_from_packed", "mf_reads_from_fastq", "mf_reads_synth", "mf_reads_synth_ex", "mf_free_host",
-    "mf_reads_info", "mf_reads_free", "mf_filter", "mf_filter_resident", "mf_filter_resident_passes", "mf_filter_packed",
+    "mf_reads_info", "mf_reads_free", "mf_filter", "mf_filter_resident", "mf_filter_resident_passes", "mf_filter_resident_bits", "mf_filter_packed",
     "mf_filter_fastq_files", "mf_filter_fastq_files_on", "mf_last_ingest_stats", "mf_h2d_bandwidth", "mf_set_option", "mf_qualfilter_files", "mf_release_cached",
     "mf_kmerset_record_count", "mf_kmerset_record_name", "mf_assign", "mf_filter_fastq_files_by_record",
     "mf_kmerset_group_records", "mf_kmerset_group_count", "mf_kmerset_group_name", "mf_assign_groups", "mf_filter_fastq_files_by_group",
@@ -168,6 +168,7 @@ def load(path: Optional[str] = None):
     L.mf_filter.argtypes = [vp, vp, C.c_uint32, C.c_int, vp, vp, C.POINTER(FilterStats)]
     L.mf_filter_resident.argtypes = [vp, vp, C.c_uint32, C.c_int, C.c_int, C.POINTER(FilterStats)]
     L.mf_filter_resident_passes.argtypes = [vp, vp, C.c_uint32, C.c_int, C.c_int, vp, C.POINTER(FilterStats)]
+    L.mf_filter_resident_bits.argtypes = [vp, vp, C.c_uint32, C.c_int, C.c_int, vp, vp, C.POINTER(FilterStats)]
     L.mf_filter_packed.argtypes = [vp, C.c_int, vp, vp, C.c_uint64, vp, C.c_uint64, C.c_uint32, vp]
     L.mf_filter_fastq_files.argtypes = [vp, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_uint32, C.c_int,
                                         C.c_int, u64p, u64p]
@@ -853,6 +854,16 @@ def filter_resident_passes(ks: KmerSet, reads: Reads, threshold: int = 1, mode: 
     per = np.zeros(steps, dtype=np.uint64)
     _chk(load().mf_filter_resident_passes(ks._h, reads._h, threshold, mode, steps, per.ctypes.data, C.byref(st)))
     return per, st
+
+
+def filter_resident_bits(ks: KmerSet, reads: Reads, threshold: int = 1, mode: int = MODE_SCREENED, steps: int = 1):
+    """`steps` passes back to back; -> (bits[steps, words]: the result bitmap every pass left in its own buffer set, passing reads of every
+    pass, stats).  Test support for the pipelined pass."""
+    st = FilterStats()
+    bits = np.zeros((max(steps, 1), (reads.info.n_reads + 31) // 32), dtype=np.uint32)          # (steps < 1: the library's error)
+    per = np.zeros(max(steps, 1), dtype=np.uint64)
+    _chk(load().mf_filter_resident_bits(ks._h, reads._h, threshold, mode, steps, bits.ctypes.data, per.ctypes.data, C.byref(st)))
+    return bits, per, st
 
 
 def filter_packed(ks: KmerSet, words, offsets, npos, threshold: int = 1, device: int = 0) -> np.ndarray:

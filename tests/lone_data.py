@@ -235,6 +235,21 @@ def _cached_length(k: int, L: int, bait_text: str) -> SimpleNamespace:          
     return _with_oracle(k, ("uniform", L), uniform_lens(L), LENGTH_SEEDS.get((k, L), SEED), bait_text, share)
 
 
+@functools.lru_cache(maxsize=4)
+def paired_set(k: int, layout: str, bait_text: str) -> SimpleNamespace:
+    """The stream of cached_set(k, layout) with every two neighbouring reads taken as ONE read (every second offset; words and npos are the
+    set's own), and the oracle's bits at threshold 2.  A lone set's own threshold-2 bitmap is all but empty -- empty for k >= 48, where no
+    bait k-mer occurs twice -- so a threshold-2 pass on it can only show a bit that should not be there.  Here a read passes when both its
+    halves hold a window: two hits, one from each, and a pass that loses either clears the bit.  -> n_reads, offsets, obits2."""
+    from oracle import oracle_lib as ol
+    s = cached_set(k, layout, bait_text)
+    offsets = np.ascontiguousarray(np.concatenate((s.offsets[:-1:2], s.offsets[-1:])))
+    obits2, _ = ol.filter_reads(ol.OracleTable(bait_text, k), ol.OracleReads.from_arrays(s.words, offsets, s.npos), 2, threads=4)
+    for a in (offsets, obits2):
+        a.flags.writeable = False
+    return SimpleNamespace(k=k, layout=layout, n_reads=offsets.size - 1, offsets=offsets, obits2=obits2)
+
+
 def cached_set(k: int, layout, bait_text: str) -> SimpleNamespace:
     """the set of (k, layout) with the oracle's answers: obits / ohits at threshold 1, obits2 at threshold 2 (one generation and two
     oracle runs a set, shared by every test of a module that asks for it; nothing writes to it).  layout: "uniform", "ragged", or

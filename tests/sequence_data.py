@@ -10,11 +10,13 @@ An op is (set, thr, call, mode, opts):
          hits      filter_reads(want_hits=True)
          res2/3/5  filter_resident with that many steps
          passes4   filter_resident_passes with 4 steps
+         rbits3    filter_resident_bits with 3 steps: the bits every pass left in its own buffer set, fetched for real
   mode   "S" screened, "E" exhaustive
   opts   "name=value" options in force for that call only
 
-The conditions the sequences rest on -- every expected value passes some reads and not all, and any two different expected values differ,
-so that a buffer left over from the call before would show -- are asserted on the CPU by test_sequence_data.py."""
+The conditions the sequences rest on -- every expected value passes some reads and not all, any two different expected values differ,
+so that a buffer left over from the call before would show, and every expected bitmap has a read r with bit r set and bit r ^ 1 clear, so
+that a pass bit moved to the neighbouring read (every count stays right) would show -- are asserted on the CPU by test_sequence_data.py."""
 import functools
 import os
 import random
@@ -37,8 +39,9 @@ SETS = {"k21": (21, {}), "k29": (29, {}), "k31": (31, {}), "k33": (33, {}), "k41
         "k31f2": (31, {"front": 2}), "k31f3c": (31, {"front": 3, "canon": 1}), "k31f4": (31, {"front": 4}), "k21f1": (21, {"front": 1}),
         "prot": (PROT_KP, {})}
 BUILD_DEFAULTS = {"front": -1, "canon": -1, "front2_log2b": 0, "front3_log2b": -1}
-CALLS = ("bits", "hits", "res2", "res3", "res5", "passes4")
-STEPS = {"bits": 1, "hits": 1, "res2": 2, "res3": 3, "res5": 5, "passes4": 4}
+CALLS = ("bits", "hits", "res2", "res3", "res5", "passes4", "rbits3")
+STEPS = {"bits": 1, "hits": 1, "res2": 2, "res3": 3, "res5": 5, "passes4": 4, "rbits3": 3}
+RETURNS_BITS = ("bits", "hits", "rbits3")          # the calls that hand their own bits back: the others are followed by a recompute
 MODES = ("S", "E")
 OPTIONS = ((), ("pass=split",), ("pass=serial",), ("s8_finish=1",), ("finish_streams=2",), ("exact_co=1",))
 CALL_DEFAULTS = {"pass": "default", "s8_finish": -1, "finish_streams": 0, "exact_co": 0}
@@ -50,19 +53,29 @@ def op(set_, thr=1, call="bits", mode="S", *opts):
     return Op(set_, thr, call, mode, tuple(opts))
 
 
-def fetch_of(o):
-    """the filter_reads that fetches the bits a resident call left: same set, threshold and mode, no option"""
+def recompute_of(o):
+    """the filter_reads behind a resident call that returns no bits: same set, threshold and mode, no option.  It fetches nothing of what
+    the resident call left -- it is one more pass, whose own bits it returns -- and holds the handle's state after the call to the oracle.
+    What the passes of a pipelined call themselves wrote is read by rbits3."""
     return Op(o.set, o.thr, "bits", o.mode, ())
 
 
-def with_fetches(ops):
-    """the sequence as it is run: every resident call followed by the call that fetches its bits (an op like any other)"""
+def with_recomputes(ops):
+    """the sequence as it is run: every resident call that returns no bits followed by its recompute (an op like any other)"""
     out = []
     for o in ops:
         out.append(o)
-        if o.call not in ("bits", "hits"):
-            out.append(fetch_of(o))
+        if o.call not in RETURNS_BITS:
+            out.append(recompute_of(o))
     return out
+
+
+def moved_bit_shows(bits, n):
+    """whether some read r has bit r set and bit r ^ 1 clear: only then does a pass bit that went to the neighbouring read change the bitmap"""
+    b = bits_to_bool(bits, n)
+    if n % 2:
+        b = np.concatenate((b, [False]))
+    return bool((b[0::2] != b[1::2]).any())
 
 
 def show(ops):
@@ -139,28 +152,33 @@ def rich_expected(R, key):
 
 # ---------------------------------------------------------------------------------------------------------------- directed sequences
 def directed():
-    """name -> ops (without the fetches).  What each is written for:
+    """name -> ops (without the recomputes).  What each is written for:
     a  a pipelined k = 63 call leaves an exact-kernel tally in the third region of all three buffer sets; k = 31 never writes that region
     b  the same with single passes: the sets alternate, so the third call meets the region the first one wrote
     c  three-set rotation (two-word keys), then two-set rotation, both sides of k = 48 (exact kernel behind finish or not), per-pass tallies
     d  protein and nucleotide passes in turn; hit counts between them
     e  one set through every kind of pass: one-stream with hits, finish, exhaustive, candidate bitmap, and back
     f  record-list geometry: lane records and quad records, canonical and plain keys, the forms of the large-bait screen, thr 1 then thr 2
-    g  the pass kind changed by option under one set, single and pipelined calls under each"""
+    g  the pass kind changed by option under one set, single and pipelined calls under each
+    In a, c and g a filter_resident_bits call (rbits3) follows a call of ANOTHER set: its first passes write into bitmaps that still hold that
+    set's result, and every pass's own bits are compared.  A single pass of a third set follows it: what the log copies left behind."""
     seq = {}
-    seq["a"] = [op("k63", 1, "res3")] + [op("k31")] * 3
+    seq["a"] = [op("k63", 1, "res3")] + [op("k31")] * 3 + [op("k63", 1, "rbits3"), op("k21")]
     seq["b"] = [op("k63"), op("k31"), op("k31")]
-    seq["c"] = [op("k48", 1, "res5"), op("k47", 1, "res5"), op("k41", 1, "passes4"), op("k33")]
+    seq["c"] = [op("k48", 1, "res5"), op("k47", 1, "res5"), op("k41", 1, "passes4"), op("k33"), op("k48", 1, "rbits3"), op("k31"), op("k41", 1, "rbits3"), op("k63")]
     seq["d"] = [op("prot"), op("k31"), op("prot", 1, "hits"), op("k21"), op("k31", 2)]
     seq["e"] = [op("k31", 1, "hits"), op("k31"), op("k31", 1, "bits", "E"), op("k31", 2), op("k31"), op("k31", 7, "hits"), op("k31")]
     seq["f"] = [op(s, thr) for s in ("k31f2", "k21", "k31", "k31f3c", "k31f4", "k31f2") for thr in (1, 2)]
-    for name, set_, base in (("g31", "k31", ()), ("g21", "k21", ("s8_finish=1",))):
+    for name, set_, base, other in (("g31", "k31", (), "k41"), ("g21", "k21", ("s8_finish=1",), "k29")):
         seq[name] = [op(set_, 1, call, "S", *(base + extra)) for extra in ((), ("pass=split",), ("pass=serial",), ()) for call in ("bits", "res3")]
+        for extra in ((), ("pass=split",), ("pass=serial",)):
+            seq[name] += [op(other), op(set_, 1, "rbits3", "S", *(base + extra)), op("k63")]
     return seq
 
 
 # the bait-rich handle, adaptation on: the feedback turns to the candidate-bitmap pass and back while the set changes under it
-RICH_SEQUENCE = [op("k31"), op("k31"), op("k63"), op("k63"), op("k31"), op("k21", 1, "bits", "S", "s8_finish=1"), op("k31"), op("k41", 1, "res3"), op("k31")]
+RICH_SEQUENCE = [op("k31"), op("k31"), op("k63"), op("k63"), op("k31"), op("k21", 1, "bits", "S", "s8_finish=1"), op("k31"), op("k41", 1, "res3"), op("k31"),
+                 op("k63", 1, "rbits3"), op("k41"), op("k31", 1, "rbits3"), op("k21", 1, "bits", "S", "s8_finish=1")]
 
 
 # ------------------------------------------------------------------------------------------------------------------ random sequences

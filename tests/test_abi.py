@@ -20,6 +20,23 @@ def test_exports_match_header(built_lib):
     assert built_lib.mf_abi_version() == 5
 
 
+def test_per_pass_entry_points_refuse_bad_arguments(built_lib):
+    """mf_filter_resident_passes / mf_filter_resident_bits: a NULL output, steps < 1 and NULL handles are MF_E_ARG, named in the message,
+    before any device is touched; the outputs stay as they were"""
+    import ctypes as C
+    MF_E_ARG = -1
+    lib = built_lib
+    per = (C.c_uint64 * 4)(*[7] * 4)
+    bits = (C.c_uint32 * 8)(*[9] * 8)
+    assert lib.mf_filter_resident_passes(None, None, 1, 0, 4, None, None) == MF_E_ARG and b"n_pass_per_step" in lib.mf_last_error()
+    assert lib.mf_filter_resident_passes(None, None, 1, 0, 4, per, None) == MF_E_ARG and b"NULL handle" in lib.mf_last_error()
+    assert lib.mf_filter_resident_bits(None, None, 1, 0, 4, None, per, None) == MF_E_ARG and b"bits_per_step" in lib.mf_last_error()
+    for steps in (0, -1):
+        assert lib.mf_filter_resident_bits(None, None, 1, 0, steps, bits, per, None) == MF_E_ARG and b"steps" in lib.mf_last_error()
+    assert lib.mf_filter_resident_bits(None, None, 1, 0, 2, bits, None, None) == MF_E_ARG and b"NULL handle" in lib.mf_last_error()
+    assert list(per) == [7] * 4 and list(bits) == [9] * 8
+
+
 def test_no_cpu_fallback(built_lib):
     from mitoflex_amd import mitofilter as mf
     if mf.device_count() > 0:

@@ -5,9 +5,10 @@ and which of it a pass touches depends on the k-mer set, the threshold, the call
 handle for the one set it tests; here the read set stays and everything else changes under it (tests/sequence_data.py: the inputs, the
 sequences and what each directed one is written for; tests/test_sequence_data.py: their conditions, without a device).
 
-After EVERY op: bits equal the oracle's (after a resident call they are fetched by a filter_reads of the same set and threshold, an op
-like any other), hit counts equal the oracle's when asked for, stats.n_pass is the oracle's count, every entry of filter_resident_passes
-is, and stats.n_candidates is what the same op gives as the first call of a freshly uploaded handle (the 6 000-read sets: below 100 000
+After EVERY op: bits equal the oracle's (a resident call that returns none is followed by a filter_reads of the same set and threshold,
+an op like any other, which recomputes them; filter_resident_bits returns what every one of its passes left in its own buffer set, and
+every row equals the oracle's), hit counts equal the oracle's when asked for, stats.n_pass is the oracle's count, every entry of
+filter_resident_passes and of filter_resident_bits is, and stats.n_candidates is what the same op gives as the first call of a freshly uploaded handle (the 6 000-read sets: below 100 000
 reads nothing adapts, so the pass kind is a function of the op).  test_fresh_handles_agree_on_every_op establishes first that two fresh
 handles agree on that figure: they do for every op but those that run screen + finish passes (sequence_data.finish_pass says why),
 which are compared on n_pass alone.  All comparisons are exact."""
@@ -87,20 +88,24 @@ def handles(mf, ol):
 
 
 def run_op(mf, sets, reads, o):
-    """-> (bits or None, hits or None, stats, passing reads of every pass or None)"""
+    """-> (bits or None, hits or None, stats, passing reads of every pass or None, bits of every pass or None)"""
     ks, mode = sets[o.set], mf.MODE_SCREENED if o.mode == "S" else mf.MODE_EXHAUSTIVE
     with forced(mf, call_options(o), sd.CALL_DEFAULTS):
         if o.call in ("bits", "hits"):
             bits, hits, st = mf.filter_reads(ks, reads, o.thr, mode, want_hits=o.call == "hits")
-            return bits, hits, st, None
+            return bits, hits, st, None, None
         if o.call == "passes4":
             per, st = mf.filter_resident_passes(ks, reads, o.thr, mode, sd.STEPS[o.call])
-            return None, None, st, per
-        return None, None, mf.filter_resident(ks, reads, o.thr, mode, sd.STEPS[o.call]), None
+            return None, None, st, per, None
+        if o.call == "rbits3":
+            rows, per, st = mf.filter_resident_bits(ks, reads, o.thr, mode, sd.STEPS[o.call])
+            assert rows.shape[0] == len(per) == sd.STEPS[o.call]
+            return None, None, st, per, rows
+        return None, None, mf.filter_resident(ks, reads, o.thr, mode, sd.STEPS[o.call]), None, None
 
 
 def check_op(got, want, what):
-    bits, hits, st, per = got
+    bits, hits, st, per, rows = got
     assert st.n_reads == want.hits.size, what
     if bits is not None:
         assert np.array_equal(bits, want.bits), what
@@ -109,6 +114,9 @@ def check_op(got, want, what):
     assert st.n_pass == want.n_pass, (st.n_pass, want.n_pass, what)
     if per is not None:
         assert [int(x) for x in per] == [want.n_pass] * len(per), what
+    if rows is not None:
+        wrong = [i for i, row in enumerate(rows) if not np.array_equal(row, want.bits)]
+        assert not wrong, ("passes whose own bits differ from the oracle's", wrong, what)
 
 
 # what an op gives as the first call of a fresh handle: (n_pass, n_candidates), computed once an op and layout
@@ -128,9 +136,9 @@ def fresh(mf, sets, layout, o):
 
 
 def run_sequence(mf, sets, reads, layout, ops, label):
-    """the ops and the fetches behind the resident ones, every one checked; the message of a failure names the ops up to it"""
+    """the ops and the recomputes behind the resident ones that return no bits, every one checked; the message of a failure names the ops up to it"""
     done = []
-    for o in sd.with_fetches(ops):
+    for o in sd.with_recomputes(ops):
         done.append(o)
         what = "%s on the %s handle, failing at op %d of: %s" % (label, layout, len(done), sd.show(done))
         got = run_op(mf, sets, reads, o)
@@ -198,8 +206,9 @@ def test_bait_rich_handle_adapts_while_the_set_changes(mf, ol, sets):
         want = {key: sd.rich_expected(R, key) for key in dict.fromkeys(sd.key_of(o.set) for o in sd.RICH_SEQUENCE)}
         counts = {key: w.n_pass for key, w in want.items()}
         assert len(set(counts.values())) == len(counts) and all(0 < n < sd.RICH_N for n in counts.values()), counts
+        assert all(sd.moved_bit_shows(w.bits, sd.RICH_N) for w in want.values()), counts          # (the set is made on the device: its conditions are held here)
         done, candidates = [], []
-        for o in sd.with_fetches(sd.RICH_SEQUENCE):
+        for o in sd.with_recomputes(sd.RICH_SEQUENCE):
             done.append(o)
             got = run_op(mf, sets, reads, o)
             candidates.append(int(got[2].n_candidates))

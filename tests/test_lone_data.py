@@ -101,6 +101,31 @@ def test_windows_cover_every_alignment_and_border(lone, k, layout):
     assert s.g0[-1] + k == s.total and s.kind[-1] == ld.PLAIN and s.read[-1] == s.n_reads - 1
 
 
+RESIDENT_BITS_KS = [21, 31, 41, 48, 63]          # the sets whose every pipelined pass tests/test_gpu_resident_bits.py reads
+
+
+@pytest.mark.parametrize("layout", ld.LAYOUTS)
+@pytest.mark.parametrize("k", RESIDENT_BITS_KS)
+def test_expected_bitmaps_show_a_moved_or_stale_bit(lone, bait_text, k, layout):
+    """What the per-pass bit comparisons rest on: some reads pass and not all; some read r has bit r set and bit r ^ 1 clear, so that a pass
+    bit moved to the neighbouring read (every count stays right) changes the bitmap; and the two thresholds, which run on one handle, differ
+    in their bits.  The threshold-1 bitmap holds all of it at every k.  The set's own threshold-2 bitmap does NOT for k >= 48: no bait
+    k-mer occurs twice, no read has two hits, the bitmap is empty (measured when this test was written: 0 reads at k = 48 and 63, both
+    layouts) -- a threshold-2 pass on the set itself shows only the bits of the threshold-1 passes before it that were not cleared.  So the
+    threshold-2 passes are also run on the stream with two neighbouring reads taken as one (lone_data.paired_set), whose bitmap holds
+    every condition at every k."""
+    from tests.sequence_data import moved_bit_shows
+    from tests.util_data import bits_to_bool
+    s, p = lone(k, layout), ld.paired_set(k, layout, bait_text)
+    n1, n2, np2 = (int(bits_to_bool(b, n).sum()) for b, n in ((s.obits, s.n_reads), (s.obits2, s.n_reads), (p.obits2, p.n_reads)))
+    print(k, layout, "pass at threshold 1:", n1, "at threshold 2:", n2, "at threshold 2, reads paired:", np2, "of", p.n_reads)
+    assert 0 < n1 < s.n_reads and moved_bit_shows(s.obits, s.n_reads), (k, layout, n1)
+    assert not np.array_equal(s.obits, s.obits2)
+    assert (n2 == 0) == (k >= 48) and (n2 == 0 or moved_bit_shows(s.obits2, s.n_reads)), (k, layout, n2)
+    assert p.n_reads == (s.n_reads + 1) // 2 and p.offsets[0] == 0 and p.offsets[-1] == s.total and np.array_equal(p.offsets[:-1], s.offsets[:-1:2])
+    assert 0.002 * p.n_reads < np2 < 0.1 * p.n_reads and moved_bit_shows(p.obits2, p.n_reads), (k, layout, np2)
+
+
 # --------------------------------------------------------------------------- the length axis: ("uniform", L), LENGTH_CHUNKS chunks
 MAX_STRAY_READS_SHORT = 3       # (the stream is 13 times shorter than the one MAX_STRAY_READS was set for)
 KL = [(k, L) for k in ld.LENGTH_KS for L in ld.lengths_for(k)]

@@ -1,7 +1,8 @@
 """Conditions on the INPUTS of tests/test_gpu_handle_sequences.py (tests/sequence_data.py), held against the C oracle alone: no GPU.
 A sequence of calls on one read-set handle shows a buffer left over from the call before only if that call's result differs from this
-one's -- so every expected value passes some reads and not all, and any two different expected values differ; and the random sequences
-change the set often enough and reach every kind of op."""
+one's -- so every expected value passes some reads and not all, and any two different expected values differ; a pass bit that moved to the
+neighbouring read shows only where one of the two is set -- so every expected bitmap has such a pair; and the random sequences change the set
+often enough and reach every kind of op."""
 import itertools
 
 import numpy as np
@@ -42,6 +43,20 @@ def test_every_expected_value_passes_some_reads_and_not_all(ol, layout):
 
 
 @pytest.mark.parametrize("layout", sd.LAYOUTS)
+def test_a_moved_pass_bit_shows_in_every_expected_value(ol, layout):
+    """every expected bitmap -- each is compared with the rows of an rbits3 op somewhere -- has a read r with bit r set and bit r ^ 1 clear:
+    a pass bit written to the neighbouring read leaves every count right and changes the bitmap only there"""
+    lacking = [(key, thr) for key in sd.KEYS for thr in sd.THRESHOLDS if not sd.moved_bit_shows(sd.expected(layout, key, thr).bits, sd.N_READS)]
+    assert not lacking, lacking
+
+
+def test_moved_bit_shows():
+    bits = lambda *reads: np.array([sum(1 << r for r in reads)], dtype=np.uint32)
+    assert not sd.moved_bit_shows(bits(), 6) and not sd.moved_bit_shows(bits(0, 1, 4, 5), 6) and not sd.moved_bit_shows(bits(0, 1, 2, 3, 4, 5), 6)
+    assert sd.moved_bit_shows(bits(3), 6) and sd.moved_bit_shows(bits(0, 1, 2), 6) and sd.moved_bit_shows(bits(4), 5) and not sd.moved_bit_shows(bits(2, 3), 5)
+
+
+@pytest.mark.parametrize("layout", sd.LAYOUTS)
 def test_any_two_expected_values_differ(ol, layout):
     """Any op may follow any other in a random sequence.  Two entries of different keys differ in their bits AND in their hit counts; two
     thresholds of one key differ in their bits (a read's hit count is what it is at every threshold: asserted, too) and in how many pass."""
@@ -65,7 +80,7 @@ def test_sets_and_keys():
     assert all(set(forced) <= set(sd.BUILD_DEFAULTS) for _, forced in sd.SETS.values())
     assert sd.KEYS == ("k21", "k29", "k31", "k33", "k41", "k47", "k48", "k63", "prot")
     assert [sd.key_of(s) for s in ("k31f2", "k31f3c", "k31f4", "k21f1", "prot")] == ["k31", "k31", "k31", "k21", "prot"]
-    assert sum(len(set(sd.grid("k31", thr))) for thr in sd.THRESHOLDS) == 3 * 6 * 2 * 6
+    assert sum(len(set(sd.grid("k31", thr))) for thr in sd.THRESHOLDS) == 3 * 7 * 2 * 6 and sd.STEPS["rbits3"] == 3 and set(sd.STEPS) == set(sd.CALLS)
     for opts in sd.OPTIONS:
         assert all(o.split("=")[0] in sd.CALL_DEFAULTS for o in opts)
 
@@ -73,12 +88,12 @@ def test_sets_and_keys():
 def test_which_ops_run_screen_and_finish_passes():
     """the ops that are compared on n_pass alone: the rule, case by case"""
     f = sd.finish_pass
-    assert f(sd.op("k31")) and f(sd.op("k63", 1, "res3")) and f(sd.op("k29", 1, "passes4", "S", "exact_co=1")) and f(sd.op("k31f2", 1, "res5", "S", "finish_streams=2"))
+    assert f(sd.op("k31")) and f(sd.op("k63", 1, "res3")) and f(sd.op("k41", 1, "rbits3")) and not f(sd.op("k41", 2, "rbits3")) and f(sd.op("k29", 1, "passes4", "S", "exact_co=1")) and f(sd.op("k31f2", 1, "res5", "S", "finish_streams=2"))
     assert not f(sd.op("k31", 2)) and not f(sd.op("k31", 1, "hits")) and not f(sd.op("k31", 1, "bits", "E")) and not f(sd.op("k31", 1, "res3", "S", "pass=split"))
     assert not f(sd.op("prot")) and not f(sd.op("k21")) and not f(sd.op("k21f1", 1, "res5", "S", "exact_co=1"))
     assert f(sd.op("k21", 1, "bits", "S", "s8_finish=1")) and f(sd.op("k21", 1, "res3", "S", "pass=serial")) and not f(sd.op("k21", 1, "res3", "S", "s8_finish=1", "pass=split"))
     share = [f(o) for s in sd.SETS for thr in sd.THRESHOLDS for o in sd.grid(s, thr)]
-    assert 0.08 < sum(share) / len(share) < 0.12          # a tenth of the grid's 2808 ops: the rest is compared on n_candidates too
+    assert 0.08 < sum(share) / len(share) < 0.12          # a tenth of the grid's 3276 ops: the rest is compared on n_candidates too
 
 
 def test_directed_sequences():
@@ -87,17 +102,29 @@ def test_directed_sequences():
     for ops in list(seq.values()) + [sd.RICH_SEQUENCE]:
         assert all(o.set in sd.SETS and o.thr in sd.THRESHOLDS and o.call in sd.CALLS and o.mode in sd.MODES for o in ops)
         assert all(o.split("=")[0] in sd.CALL_DEFAULTS for x in ops for o in x.opts)
-        run = sd.with_fetches(ops)
-        assert len(run) == len(ops) + sum(o.call not in ("bits", "hits") for o in ops)
-        for x, y in zip(run, run[1:]):          # a resident call is followed by the fetch of its bits
-            if x.call not in ("bits", "hits"):
+        run = sd.with_recomputes(ops)
+        assert len(run) == len(ops) + sum(o.call not in ("bits", "hits", "rbits3") for o in ops)
+        for x, y in zip(run, run[1:]):          # a resident call that returns no bits is followed by the recompute of them
+            if x.call not in ("bits", "hits", "rbits3"):
                 assert y == sd.Op(x.set, x.thr, "bits", x.mode, ())
-    assert [(o.set, o.call) for o in seq["a"]] == [("k63", "res3"), ("k31", "bits"), ("k31", "bits"), ("k31", "bits")]
+    assert [(o.set, o.call) for o in seq["a"]] == [("k63", "res3"), ("k31", "bits"), ("k31", "bits"), ("k31", "bits"), ("k63", "rbits3"), ("k21", "bits")]
     assert [o.set for o in seq["b"]] == ["k63", "k31", "k31"] and {o.call for o in seq["b"]} == {"bits"}
-    assert [(o.set, o.call) for o in seq["c"]] == [("k48", "res5"), ("k47", "res5"), ("k41", "passes4"), ("k33", "bits")]
+    assert [(o.set, o.call) for o in seq["c"]][:4] == [("k48", "res5"), ("k47", "res5"), ("k41", "passes4"), ("k33", "bits")]
+    assert [(o.set, o.call) for o in seq["c"]][4:] == [("k48", "rbits3"), ("k31", "bits"), ("k41", "rbits3"), ("k63", "bits")]
     assert [(o.set, o.thr) for o in seq["f"]][:4] == [("k31f2", 1), ("k31f2", 2), ("k21", 1), ("k21", 2)] and seq["f"][-1].set == "k31f2"
     assert [o.opts for o in seq["g21"]][2:6] == [("s8_finish=1", "pass=split")] * 2 + [("s8_finish=1", "pass=serial")] * 2
-    assert [o.set for o in sd.RICH_SEQUENCE] == ["k31", "k31", "k63", "k63", "k31", "k21", "k31", "k41", "k31"]
+    assert [o.set for o in sd.RICH_SEQUENCE] == ["k31", "k31", "k63", "k63", "k31", "k21", "k31", "k41", "k31", "k63", "k41", "k31", "k21"]
+    assert len(seq["g31"]) == len(seq["g21"]) == 8 + 9 and [o.call for o in seq["g31"]][:8] == ["bits", "res3"] * 4
+    assert [o.opts for o in seq["g21"] if o.call == "rbits3"] == [("s8_finish=1",), ("s8_finish=1", "pass=split"), ("s8_finish=1", "pass=serial")]
+    # an rbits3 op of a directed sequence follows a call of another set -- its passes write into bitmaps that hold that set's result, which differs
+    # (test_any_two_expected_values_differ) -- and a single pass of a third set follows it
+    for name, ops in list(seq.items()) + [("rich", sd.RICH_SEQUENCE)]:
+        run = sd.with_recomputes(ops)
+        at = [i for i, o in enumerate(run) if o.call == "rbits3"]
+        assert bool(at) == (name in ("a", "c", "g31", "g21", "rich")), name
+        for i in at:
+            keys = [sd.key_of(run[j].set) for j in (i - 1, i, i + 1)]
+            assert len(set(keys)) == 3 and run[i + 1].call == "bits" and run[i].thr == run[i + 1].thr == 1, (name, i, keys)
     # in every directed sequence, neighbours that differ in (key, threshold) exist: it changes what a call expects
     for name, ops in seq.items():
         assert len({(sd.key_of(o.set), o.thr, o.call == "hits", o.mode) for o in ops}) > 1 or name.startswith("g"), name
