@@ -636,6 +636,63 @@ int mf_filter_fastq_files_extended(mf_kmerset *ks, const char *fq1, const char *
               uint64_t *gapped_starts, mf_gapped_record_t *gapped_records, mf_pileup_t *ext_pile, uint8_t *extended, uint64_t *extended_starts,
               mf_extend_record_t *extend_records, uint64_t *unplaced, uint64_t *kept, uint64_t *total);
 
+/* ---- pairs: the two mates of a pair seen together -- the insert they span, and the RESCUE of a mate the vote cannot place from the
+ * window its placed mate implies.  Every call above treats a mate as a lone read: a read in a diverged stretch of the bait (no k-mer
+ * in common with it) draws no vote, a read inside a repeat or inside a stretch two records share has no anchor window, and neither adds
+ * to base depth, the pile-up or the consensus -- although its mate a few hundred bases away is placed without trouble.  Aligners call
+ * this mate rescue (`bwa mem` does it; the reference gets its pile-up from `bwa mem`, see the placement section).  Nucleotide sets only.
+ * ABI 5 still.  Nothing above changes.
+ * A paired call takes two read sets of equal n_reads on one device: read i of the first set and read i of the second are mates.  It
+ * takes min_insert >= 1, max_insert >= min_insert with max_insert - min_insert + 1 <= MF_RESCUE_MAX and max_insert < 2^31, rescue (0 or
+ * 1), rescue_permille (0 .. 1000) and the verifying call's threshold, mode, min_depth, max_permille.
+ * The rule.
+ *   1. Each set is verified as today: filtered, placed by vote, scored and cut at max_permille exactly as mf_verify does it.  Both sets
+ *      add into ONE set of counters, as the file-level calls already sum mates.  A mate is SETTLED when it is placed by vote and accepted.
+ *   2. Insert.  The insert of two settled mates on one record and on opposite strands is `end` of the strand-1 mate minus `start` of the
+ *      strand-0 mate; it is reported when it is above 0, else as -1.  The pair is PROPER when min_insert <= insert <= max_insert.
+ *   3. Rescue target.  With rescue = 1, a pair with exactly one settled mate A (record j, strand s, start a, end e) is looked at when the
+ *      other mate B, of L bases, has record >= MF_PLACE_AMBIGUOUS: B did not pass, or passed but is ambiguous.  A mate that was placed and
+ *      rejected is never rescued.
+ *   4. Candidates.  B's candidates lie on record j and on strand 1 - s.  For s = 0 the candidate starts are a + d - L for every d in
+ *      [min_insert, max_insert]; for s = 1 they are e - d.  Either way the pair's insert would be d.  Each candidate is scored by the
+ *      verification rule, unchanged: only bases inside record j are compared -- bases in a neighbouring record never, although global
+ *      positions are contiguous --, and only valid read bases on valid bait letters.  A candidate is ADMISSIBLE when compared >= k and
+ *      mismatches * 1000 <= rescue_permille * compared.
+ *   5. Winner.  B is rescued when exactly one admissible candidate has the fewest mismatches.  Two candidates that share the fewest
+ *      mismatches, whatever their compared, leave B as it was: a shifted copy in a homopolymer or a tandem repeat does not rescue.
+ *   6. What a rescued mate changes.  Its mf_place_t becomes { j, 1 - s, start, start + L, votes = 0, windows as the vote left them }:
+ *      votes == 0 on a placed row is what marks a rescue.  Its mf_score_t is the winning candidate's.  From there on it counts
+ *      everywhere an accepted placed read counts -- base depth, forward / reverse / over_begin / over_end, the score sums and its
+ *      histogram bin, the pile-up -- whatever max_permille says: rescue_permille is its cut.  It leaves unplaced[0] if it passed, else
+ *      unplaced[1].  The identities of the verification section keep holding with n_reads being both sets' reads.  The pass bits are not
+ *      touched, and the paired call has no keep mode.
+ *   7. Per pair: mf_pair_t { kind, insert }.  MF_PAIR_NONE: no mate is settled.  MF_PAIR_PROPER.  MF_PAIR_DISCORDANT: both are settled
+ *      and the pair is not proper.  MF_PAIR_RESCUED_1 / _2: mate 1 / mate 2 was rescued.  MF_PAIR_SINGLE_1 / _2: mate 1 / mate 2 is
+ *      settled and the other is neither settled nor rescued.  insert is -1 for NONE and SINGLE_*, and for a discordant pair without one;
+ *      a rescued pair's insert is the winning d.
+ *   8. Per record: mf_pair_record_t.  cross counts the pairs whose settled mates lie on different records, at mate 1's record;
+ *      discordant counts the other discordant pairs, on their common record; proper likewise.  rescued and single are counted at the
+ *      settled mate's record.  insert_sum runs over the proper and the rescued pairs.  pairs_none: one uint64_t, the pairs of kind NONE.
+ *      Sum(proper + discordant + cross + rescued + single) + pairs_none == n_reads of one set.
+ *   9. With rescue = 0 every output except the pair outputs equals what two mf_verify calls give, added up.
+ * Outputs: bits1 / bits2, place1 / place2, score1 / score2 (per read of either set), pairs (n_reads entries), base_depth, place_records,
+ * pileup, consensus, pileup_records, score_records as mf_verify gives them, pair_records (R entries), pairs_none, unplaced (2 u64, over
+ * both sets), stats (both passes: counts and times added).  Every output is optional; the pile-up counters are allocated only when
+ * pileup, consensus or pileup_records is asked for.
+ * MF_E_ARG before any device work: a NULL handle; a protein set; unequal n_reads; sets on different devices; the insert and permille
+ * ranges above; rescue other than 0 or 1; min_depth == 0.  Placement's limits apply. */
+#define MF_RESCUE_MAX 4096
+enum { MF_PAIR_NONE = 0, MF_PAIR_PROPER = 1, MF_PAIR_DISCORDANT = 2, MF_PAIR_RESCUED_1 = 3, MF_PAIR_RESCUED_2 = 4, MF_PAIR_SINGLE_1 = 5,
+       MF_PAIR_SINGLE_2 = 6 };
+typedef struct { uint32_t kind; int32_t insert; } mf_pair_t;
+typedef struct { uint64_t proper, discordant, cross, rescued, single, insert_sum; } mf_pair_record_t;
+int mf_place_pairs(const mf_kmerset *ks, const mf_reads *reads1, const mf_reads *reads2, uint32_t threshold, int mode, uint32_t min_depth,
+              uint32_t max_permille, uint32_t min_insert, uint32_t max_insert, int rescue, uint32_t rescue_permille, uint32_t *bits1,
+              uint32_t *bits2, mf_place_t *place1, mf_place_t *place2, mf_score_t *score1, mf_score_t *score2, mf_pair_t *pairs,
+              uint32_t *base_depth, mf_place_record_t *place_records, mf_pileup_t *pileup, uint8_t *consensus,
+              mf_pileup_record_t *pileup_records, mf_score_record_t *score_records, mf_pair_record_t *pair_records, uint64_t *pairs_none,
+              uint64_t *unplaced, mf_filter_stats_t *stats);
+
 /* Options that select which kernels a filter pass runs (process-wide; every variant gives the same bits and is parity-tested):
  *   pass=default|split|serial   adapt=0|1   finish_streams=0|1|2   screen_streams=1|2   split_pipe=0|1   exact_co=0|1
  * and, read when a k-mer set is BUILT (ABI 5; every form gives the same bits -- tests force them on small baits):

@@ -202,9 +202,31 @@ def _check_extend(extend: int, band: Optional[int]):
         raise ValueError("extend needs a band: the overhanging bases get their columns from the banded alignment")
 
 
+def rescue_window(sizes, lo: float = 0.01, hi: float = 0.99) -> Tuple[int, int]:
+    """The insert window (min_insert, max_insert) for mitofilter.place_pairs from the inserts of the pairs the vote placed (`sizes`: what
+    place_pairs(rescue=False).pairs["insert"] or mitofilter.pair_inserts gives; values <= 0 are no insert): their `lo` and `hi`
+    quantiles, and where that is wider than mitofilter.RESCUE_MAX inserts, the RESCUE_MAX inserts around the median.  ValueError when
+    no pair has an insert."""
+    import numpy as np
+    from mitoflex_amd import mitofilter as mf
+    if not 0.0 <= lo <= hi <= 1.0:
+        raise ValueError("the quantiles are 0 <= lo <= hi <= 1")
+    v = np.asarray(sizes, dtype=np.int64)
+    v = np.sort(v[v > 0])
+    if v.size == 0:
+        raise ValueError("no pair has an insert: the window cannot be estimated")
+    a, b = int(v[int(lo * (v.size - 1))]), int(v[int(hi * (v.size - 1))])
+    if b - a + 1 > mf.RESCUE_MAX:
+        median = int(v[(v.size - 1) // 2])
+        a = max(1, median - mf.RESCUE_MAX // 2)
+        b = a + mf.RESCUE_MAX - 1
+    return a, b
+
+
 def consensus_bait(fasta_file: str, fq1: str, fq2: Optional[str], out_fasta: str, kmer: int = 31, min_depth: int = 3,
                    max_permille: Optional[int] = None, band: Optional[int] = None, gapped: bool = False,
-                   extend: int = 0):
+                   extend: int = 0, pairs: bool = False, min_insert: Optional[int] = None, max_insert: Optional[int] = None,
+                   rescue_permille: int = 100):
     """A polished bait for the next generation: the reads of (fq1, fq2) -- the kept reads of a bait step -- are placed on the bait
     `fasta_file` and piled up on the device (mitofilter.filter_fastq_files_pileup), and the consensus is written to `out_fasta` under the
     bait's record names: the reads' letter where at least `min_depth` bases agree on one, N where the most is tied, the bait's own
@@ -222,11 +244,24 @@ def consensus_bait(fasta_file: str, fq1: str, fq2: Optional[str], out_fasta: str
     the polished bait has the sample's length and coordinates.  Without band it is a ValueError.
     extend: with band (band 0 too), the EXTENDED records are written instead (include/mitofilter.h, extended records): every record's
     gapped consensus between the columns that the reads overhanging its ends agree on, up to `extend` (at most 4096) a side, so that the
-    next generation's bait reaches reads the old ends shared no k-mer with.  Without band it is a ValueError."""
+    next generation's bait reaches reads the old ends shared no k-mer with.  Without band it is a ValueError.
+    pairs: the two files are loaded into memory (mitofilter.Reads.from_fastq) and placed as PAIRS (mitofilter.place_pairs; include/
+    mitofilter.h, pairs): a mate the vote cannot place -- in a diverged stretch, a repeat, a stretch two records share -- is looked for
+    in the window [min_insert, max_insert] its placed mate implies and piled where it fits at no more than `rescue_permille`
+    mismatches per thousand compared bases (100, one base in ten: a policy choice, not a measured value).  The window comes from a
+    first pass without rescue (rescue_window) when it is not given.  With band, gapped, extend or without fq2 it is a ValueError."""
     from mitoflex_amd import mitofilter as mf
     if gapped and band is None:
         raise ValueError("gapped needs a band: the gapped consensus comes from the banded alignment")
     _check_extend(extend, band)
+    if pairs and (band is not None or gapped or int(extend) or fq2 is None):
+        raise ValueError("pairs takes two files and neither band, gapped nor extend: a rescued mate lies on its diagonal")
+    if not pairs and (min_insert is not None or max_insert is not None):
+        raise ValueError("min_insert and max_insert belong to pairs=True")
+    if (min_insert is None) != (max_insert is None):
+        raise ValueError("min_insert and max_insert are given together")
+    if not 0 <= int(rescue_permille) <= 1000:
+        raise ValueError("rescue_permille is a number from 0 to 1000")
     if min_depth < 1:
         raise ValueError("min_depth is at least 1")
     if max_permille is not None and not 0 <= int(max_permille) <= 1000:
@@ -241,7 +276,10 @@ def consensus_bait(fasta_file: str, fq1: str, fq2: Optional[str], out_fasta: str
         names, starts = ks.record_names, ks.record_starts
         with tempfile.TemporaryDirectory(prefix="consensus_bait_") as tmp:          # (the call writes its kept reads; they are not wanted)
             out1, out2 = path.join(tmp, "k.1.fq"), path.join(tmp, "k.2.fq") if fq2 is not None else None
-            if band is not None:
+            if pairs:
+                consensus, records = _consensus_of_pairs(mf, ks, fq1, fq2, min_depth, 1000 if max_permille is None else int(max_permille), min_insert,
+                                                         max_insert, int(rescue_permille))
+            elif band is not None:
                 v = mf.filter_fastq_files_aligned(ks, fq1, fq2, out1, out2, int(band), 1, mf.PAIR_EITHER, min_depth=min_depth,
                                                   max_permille=1000 if max_permille is None else int(max_permille), extend=int(extend), gapped=bool(gapped))
                 consensus, records = v.consensus, v.pileup_records
@@ -259,6 +297,24 @@ def consensus_bait(fasta_file: str, fq1: str, fq2: Optional[str], out_fasta: str
     with open(out_fasta, "w") as f:
         f.write(mf.consensus_fasta(names, starts, consensus))
     return records
+
+
+def _consensus_of_pairs(mf, ks, fq1, fq2, min_depth, max_permille, min_insert, max_insert, rescue_permille):
+    """consensus and pile-up records of the two files placed as pairs; the window estimated from the vote-placed pairs when not given"""
+    r1 = mf.Reads.from_fastq(fq1, 0)
+    try:
+        r2 = mf.Reads.from_fastq(fq2, 0)
+        try:
+            if min_insert is None:
+                first = mf.place_pairs(ks, r1, r2, 1, mf.RESCUE_MAX, rescue=False, min_depth=min_depth, max_permille=max_permille, pileup=False)
+                min_insert, max_insert = rescue_window(first.pairs["insert"])
+            p = mf.place_pairs(ks, r1, r2, int(min_insert), int(max_insert), rescue=True, rescue_permille=rescue_permille, min_depth=min_depth,
+                               max_permille=max_permille)
+            return p.consensus, p.pileup_records
+        finally:
+            r2.close()
+    finally:
+        r1.close()
 
 
 def cal_insert(bam: str, basedir: str, prefix: str) -> float:

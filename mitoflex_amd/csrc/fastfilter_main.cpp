@@ -825,8 +825,89 @@ static int bait_main(int argc, char **argv)
     return 0;
 }
 
+// `fastfilter pairs`: the two kept files of a bait step placed as PAIRS (mf_place_pairs; include/mitofilter.h, pairs) -- both files are
+// read into memory --, and the reports of the verifying family over both mates plus the pair report.  Prints the rescued mates.
+static int pairs_main(int argc, char **argv)
+{
+    std::string bait, fq1, fq2, libpath, pair_report, place_report, base_depth_file, consensus_file, score_report;
+    unsigned long k = 31, min_insert = 0, max_insert = 0, rescue_permille = 100, max_permille = 1000, min_depth = 1;
+    bool rescue = true;
+    static const char *usage = "usage: fastfilter pairs --bait BAIT.fa [-k 31] --fq1 A.fq --fq2 B.fq --min-insert N --max-insert M [--no-rescue] [--rescue-permille 100]\n"
+                               "       [--max-mismatch PERMILLE] [--min-depth D] [--pair-report FILE] [--place-report FILE] [--base-depth FILE] [--consensus FILE] [--score-report FILE]\n"
+                               "       (the files are read into memory: the kept files of a bait step; 1 <= N <= M, at most 4096 inserts wide)\n";
+    for (int a = 2; a < argc; a++) {
+        const std::string o = argv[a];
+        auto need = [&](const char *name) -> std::string {
+            if (a + 1 >= argc) { fprintf(stderr, "error: %s requires a value\n", name); exit(1); }
+            return argv[++a];
+        };
+        auto number = [&](const char *name, unsigned long lo, unsigned long hi, unsigned long &out) {
+            const std::string v = need(name); char *end = nullptr; const unsigned long x = strtoul(v.c_str(), &end, 10);
+            if (v.empty() || *end || v[0] < '0' || v[0] > '9' || x < lo || x > hi) { fprintf(stderr, "error: %s wants a number from %lu to %lu\n", name, lo, hi); exit(1); }
+            out = x;
+        };
+        if (o == "--bait") bait = need("--bait");
+        else if (o == "--fq1") fq1 = need("--fq1");
+        else if (o == "--fq2") fq2 = need("--fq2");
+        else if (o == "--lib") libpath = need("--lib");
+        else if (o == "-k" || o == "--kmer") number("-k", 1, 64, k);
+        else if (o == "--min-insert") number("--min-insert", 1, 0x7FFFFFFFul, min_insert);
+        else if (o == "--max-insert") number("--max-insert", 1, 0x7FFFFFFFul, max_insert);
+        else if (o == "--no-rescue") rescue = false;
+        else if (o == "--rescue-permille") number("--rescue-permille", 0, 1000, rescue_permille);
+        else if (o == "--max-mismatch") number("--max-mismatch", 0, 1000, max_permille);
+        else if (o == "--min-depth") number("--min-depth", 1, 0xFFFFFFFFul, min_depth);
+        else if (o == "--pair-report") pair_report = need("--pair-report");
+        else if (o == "--place-report") place_report = need("--place-report");
+        else if (o == "--base-depth") base_depth_file = need("--base-depth");
+        else if (o == "--consensus") consensus_file = need("--consensus");
+        else if (o == "--score-report") score_report = need("--score-report");
+        else { fprintf(stderr, "error: unknown option '%s' for fastfilter pairs\n", o.c_str()); return 1; }
+    }
+    if (bait.empty() || fq1.empty() || fq2.empty() || !min_insert || !max_insert) { fputs(usage, stderr); return 1; }
+    if (max_insert < min_insert || max_insert - min_insert + 1 > MF_RESCUE_MAX) {
+        fprintf(stderr, "error: --min-insert .. --max-insert is a window of 1 to %d inserts\n", MF_RESCUE_MAX);
+        return 1;
+    }
+    if (libpath.empty()) { const char *e = getenv("MITOFILTER_LIB"); if (e && *e) libpath = e; }
+    if (libpath.empty()) libpath = exe_dir() + "/../libmitofilter_hip.so";
+    void *h = dlopen(libpath.c_str(), RTLD_NOW | RTLD_LOCAL);
+    if (!h) { fprintf(stderr, "error: cannot load %s: %s (pair-aware placement has no CPU fallback)\n", libpath.c_str(), dlerror()); return 2; }
+#define SYM(name) auto p_##name = (decltype(&name))dlsym(h, #name); if (!p_##name) { fprintf(stderr, "error: %s lacks symbol %s\n", libpath.c_str(), #name); return 2; }
+    SYM(mf_abi_version) SYM(mf_last_error) SYM(mf_kmerset_build_from_fasta) SYM(mf_kmerset_free) SYM(mf_reads_from_fastq) SYM(mf_reads_free) SYM(mf_reads_info)
+    SYM(mf_kmerset_record_count) SYM(mf_kmerset_record_name) SYM(mf_kmerset_record_starts) SYM(mf_place_pairs)
+#undef SYM
+    if (p_mf_abi_version() != MF_ABI_VERSION) { fprintf(stderr, "error: ABI version mismatch\n"); return 2; }
+    mf_kmerset *ks = nullptr; mf_reads *r1 = nullptr, *r2 = nullptr;
+    auto fail = [&]() { fprintf(stderr, "error: %s\n", p_mf_last_error()); if (r2) p_mf_reads_free(r2); if (r1) p_mf_reads_free(r1); if (ks) p_mf_kmerset_free(ks); return 3; };
+    if (p_mf_kmerset_build_from_fasta(bait.c_str(), (int)k, 0, &ks) != MF_OK) return fail();
+    if (p_mf_reads_from_fastq(fq1.c_str(), 0, &r1) != MF_OK || p_mf_reads_from_fastq(fq2.c_str(), 0, &r2) != MF_OK) return fail();
+    std::vector<std::string> names; std::vector<uint64_t> starts;
+    if (fetch_names(ks, p_mf_kmerset_record_count, p_mf_kmerset_record_name, names) != MF_OK || fetch_starts(ks, p_mf_kmerset_record_starts, names.size(), starts) != MF_OK) return fail();
+    const size_t positions = (size_t)std::max<uint64_t>(starts.back(), 1), n_rec = std::max<size_t>(names.size(), 1);
+    std::vector<uint32_t> depth(positions, 0); std::vector<uint8_t> consensus(positions, 0);
+    std::vector<mf_place_record_t> place_recs(n_rec); std::vector<mf_score_record_t> score_recs(n_rec); std::vector<mf_pair_record_t> pair_recs(n_rec);
+    uint64_t none = 0, unplaced[2] = {0, 0};
+    if (p_mf_place_pairs(ks, r1, r2, 1, MF_MODE_SCREENED, (uint32_t)min_depth, (uint32_t)max_permille, (uint32_t)min_insert, (uint32_t)max_insert, rescue ? 1 : 0,
+                         (uint32_t)rescue_permille, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, depth.data(), place_recs.data(), nullptr,
+                         consensus_file.empty() ? nullptr : consensus.data(), nullptr, score_recs.data(), pair_recs.data(), &none, unplaced, nullptr) != MF_OK) return fail();
+    using namespace mf_text;
+    const bool ok = write_file(pair_report, "pair report", [&](FILE *f) { return write_pair_report(f, names, starts, pair_recs.data(), none); })
+        && write_file(place_report, "placement report", [&](FILE *f) { return write_place_report(f, names, starts, place_recs.data(), depth.data(), unplaced[0]); })
+        && write_file(base_depth_file, "base depth", [&](FILE *f) { return write_base_depth(f, names, starts, depth.data()); })
+        && write_file(consensus_file, "consensus", [&](FILE *f) { return write_consensus(f, names, starts, consensus.data()); })
+        && write_file(score_report, "score report", [&](FILE *f) { return write_score_report(f, names, starts, score_recs.data()); });
+    unsigned long long rescued = 0;
+    for (size_t j = 0; j < names.size(); j++) rescued += pair_recs[j].rescued;
+    p_mf_reads_free(r2); p_mf_reads_free(r1); p_mf_kmerset_free(ks);
+    if (!ok) return 3;
+    printf("%llu\n", rescued);
+    return 0;
+}
+
 int main(int argc, char **argv)
 {
     if (argc >= 2 && strcmp(argv[1], "bait") == 0) return bait_main(argc, argv);
+    if (argc >= 2 && strcmp(argv[1], "pairs") == 0) return pairs_main(argc, argv);
     return contig_filter_main(argc, argv);
 }

@@ -81,20 +81,6 @@ __global__ void __launch_bounds__(256) max_read_len_kernel(const uint64_t *__res
     if ((threadIdx.x & 63) == 0 && len) atomicMax(max_len, len);
 }
 
-// The bases of a read of L bases at b0, placed as W says, into pile: [position][letter].  The whole wave calls it; lane l takes bases
-// l, l + 64, ..  Consecutive lanes add to consecutive positions: no two lanes of an instruction share a counter.
-__device__ __forceinline__ void pile_bases(const ReadsView &R, uint64_t b0, bool hasn, uint64_t L, const Winner &W, unsigned long long *__restrict__ pile, int lane)
-{
-    for (uint64_t i = (uint64_t)lane; i < L; i += 64) {
-        uint32_t letter = read_letter(R, b0 + i, hasn);
-        if (letter == READ_LETTER_NONE) continue;                                                                       // an N counts nowhere
-        int64_t c = W.start + (int64_t)i;
-        if (W.strand()) { c = W.start + (int64_t)(L - 1 - i); letter ^= 3u; }
-        if (c < 0 || c >= W.len) continue;                                                                              // an overhang counts nowhere
-        atomicAdd(&pile[4 * (W.s0 + (uint64_t)c) + letter], 1ull);
-    }
-}
-
 // What a verifying launch is given beside a placing one (nothing otherwise: the plain instantiations take no argument more than before).
 // KEEP: a verifying launch that is also given a keep bitmap; the verifying launches without one keep their code and their registers.
 template <bool VERIFY, bool KEEP> struct VerifyArgs { static constexpr bool verify = false, keep_rule = false; };

@@ -6,6 +6,7 @@
 #include "mf_api_internal.h"
 #include "mf_pipeline.h"
 #include "mf_align.h"
+#include "mf_pairs.h"
 
 #include <atomic>
 #include <string.h>
@@ -750,6 +751,106 @@ int mf_verify(const mf_kmerset *ks, const mf_reads *reads, uint32_t threshold, i
 {
     return mf_verify_keep(ks, reads, threshold, mode, min_depth, max_permille, MF_KEEP_PASSING, out_bits, nullptr, place_out, score_out, base_depth,
                           place_records, pileup, consensus, pileup_records, score_records, unplaced, stats);
+}
+
+// The paired call (include/mitofilter.h, "pairs"): each set filtered, placed, scored and cut as mf_verify does it, both into ONE set of
+// counters (the first set's cached buffers); then the pair kernels over both sets' pass bits and placements -- which are therefore always
+// made on the device, asked for or not; the scores only where the cut can reject or the caller asks -- and the report once.
+int mf_place_pairs(const mf_kmerset *ks_, const mf_reads *reads1, const mf_reads *reads2, uint32_t threshold, int mode, uint32_t min_depth, uint32_t max_permille,
+                   uint32_t min_insert, uint32_t max_insert, int rescue, uint32_t rescue_permille, uint32_t *bits1, uint32_t *bits2, mf_place_t *place1,
+                   mf_place_t *place2, mf_score_t *score1, mf_score_t *score2, mf_pair_t *pairs, uint32_t *base_depth, mf_place_record_t *place_records,
+                   mf_pileup_t *pileup, uint8_t *consensus, mf_pileup_record_t *pileup_records, mf_score_record_t *score_records,
+                   mf_pair_record_t *pair_records, uint64_t *pairs_none, uint64_t *unplaced, mf_filter_stats_t *stats)
+{
+    static_assert(sizeof(mf_pair_t) == 8 && sizeof(PairOut) == 8 && sizeof(mf_pair_record_t) == 8 * PAIR_RECORD_COUNTERS, "pair records");
+    static_assert(MF_RESCUE_MAX == RESCUE_MAX && MF_PAIR_SINGLE_2 == PAIR_SINGLE_2 && MF_PAIR_RESCUED_1 == PAIR_RESCUED_1, "the kernels' constants are the header's");
+    mf_kmerset *ks = const_cast<mf_kmerset *>(ks_);
+    mf_reads *r1 = const_cast<mf_reads *>(reads1), *r2 = const_cast<mf_reads *>(reads2);
+    PlaceRequest q{"pair-aware placement", true, pileup || consensus || pileup_records};
+    q.min_depth = min_depth; q.max_permille = max_permille; q.base_depth = base_depth; q.place_records = place_records;
+    q.pileup = pileup; q.consensus = consensus; q.pileup_records = pileup_records; q.score_records = score_records; q.unplaced = unplaced;
+    // the numbers first, as the family's own check takes them; then the handles
+    if (min_insert < 1 || max_insert < min_insert || max_insert > 0x7FFFFFFFu || max_insert - min_insert + 1 > MF_RESCUE_MAX)
+        return fail(MF_E_ARG, "the insert window is %u .. %u: 1 <= min_insert <= max_insert < 2^31, at most %u inserts wide", min_insert, max_insert, (unsigned)MF_RESCUE_MAX);
+    if (rescue != 0 && rescue != 1) return fail(MF_E_ARG, "rescue is %d: 0 or 1", rescue);
+    if (rescue_permille > 1000) return fail(MF_E_ARG, "rescue_permille is %u: the cut is a number from 0 to 1000", rescue_permille);
+    int rc = q.check(ks); if (rc) return rc;
+    if (!r1 || !r2) return fail(MF_E_ARG, "NULL handle");
+    if (r1 == r2) return fail(MF_E_ARG, "reads1 and reads2 are one read set: a paired call takes the two mate sets");
+    if (r1->v.n_reads != r2->v.n_reads)
+        return fail(MF_E_ARG, "the mate sets hold %llu and %llu reads: read i of one is the mate of read i of the other", (unsigned long long)r1->v.n_reads, (unsigned long long)r2->v.n_reads);
+    if (r1->device != r2->device) return fail(MF_E_ARG, "the mate sets lie on devices %d and %d: a paired call takes both on one", r1->device, r2->device);
+    mf_filter_stats_t s1{}, s2{};
+    rc = filter_common(ks, r1, threshold, mode, bits1, nullptr, 1, stats ? &s1 : nullptr); if (rc) return rc;
+    rc = filter_common(ks, r2, threshold, mode, bits2, nullptr, 1, stats ? &s2 : nullptr); if (rc) return rc;
+    if (stats) {
+        *stats = s1;
+        stats->n_reads += s2.n_reads; stats->n_pass += s2.n_pass; stats->n_candidates += s2.n_candidates; stats->algorithmic_bytes += s2.algorithmic_bytes;
+        stats->ms_total += s2.ms_total; stats->ms_screen += s2.ms_screen; stats->ms_mark += s2.ms_mark; stats->ms_exact += s2.ms_exact;
+    }
+    DevCtx *ctx, *ctx2;
+    rc = get_ctx(r1->device, &ctx, r1->lane); if (rc) return rc;
+    rc = get_ctx(r2->device, &ctx2, r2->lane); if (rc) return rc;
+    hipStream_t st = ctx->stream;
+    const uint64_t n = r1->v.n_reads;
+    const uint32_t n_rec = (uint32_t)ks->rec_len().size();
+    const PlaceLayout L = q.layout(ks);
+    const ReportScratch S = q.scratch(ks);
+    const hipError_t e = dev_reserve(r1->d_rtot, r1->cap_rtot, L.words() * 8, false);
+    if (e == hipErrorOutOfMemory && q.nomem()) return q.nomem()(L.words());
+    HIPCHK(e);
+    HIPCHK(dev_reserve(r1->d_rsum, r1->cap_rsum, S.sums_bytes, false));
+    HIPCHK(dev_reserve(r1->d_rpos, r1->cap_rpos, S.pos_bytes, false));
+    HIPCHK(hipMemsetAsync(r1->d_rtot, 0, L.words() * 8, st));
+    // each set on its own stream; place_after_filter ends synchronised, so the second set adds into counters the first has left
+    uint64_t listed[2] = {0, 0};
+    mf_reads *const sets[2] = {r1, r2};
+    DevCtx *const ctxs[2] = {ctx, ctx2};
+    ScoreOut *d_scores[2] = {nullptr, nullptr};
+    for (int m = 0; m < 2 && n; m++) {
+        mf_reads *r = sets[m];
+        // the kernels read a placement only where the pass bit is set, and place_kernel writes every listed read's: the arrays are
+        // initialised only where the caller gets them; the scores exist only where something reads them
+        HIPCHK(dev_reserve(r->d_place, r->cap_place, n * sizeof(PlaceOut), true));
+        if (m ? place2 != nullptr : place1 != nullptr) HIPCHK(launch_place_init(r->d_place, n, ctxs[m]->stream));
+        d_scores[m] = nullptr;
+        if ((m ? score2 != nullptr : score1 != nullptr) || max_permille < 1000) {
+            HIPCHK(dev_reserve(r->d_score, r->cap_score, n * sizeof(ScoreOut), true));
+            HIPCHK(hipMemsetAsync(d_scores[m] = r->d_score, 0, n * sizeof(ScoreOut), ctxs[m]->stream));
+        }
+        rc = place_after_filter(ks, r, L, r1->d_rtot, r->d_place, d_scores[m], &listed[m]); if (rc) return rc;
+    }
+    const PairLayout P(n_rec);
+    std::vector<unsigned long long> h_pc(P.words(), 0);
+    if (n) {
+        HIPCHK(dev_reserve(r1->d_pair, r1->cap_pair, P.words() * 8 + n * sizeof(PairOut) + n * 4, true));
+        unsigned long long *d_pc = r1->d_pair;
+        PairOut *d_pairs = reinterpret_cast<PairOut *>(d_pc + P.words());
+        uint32_t *d_list = reinterpret_cast<uint32_t *>(d_pairs + n);
+        const PairWindow win{min_insert, max_insert, rescue_permille};
+        HIPCHK(hipMemsetAsync(d_pc, 0, P.words() * 8, st));
+        HIPCHK(launch_pair_list(r1->d_bits[r1->cur], r2->d_bits[r2->cur], r1->d_place, r2->d_place, d_scores[0], d_scores[1], n, max_permille, win, n_rec, d_pairs, rescue ? d_list : nullptr, d_pc, ctx->n_cu, st));
+        if (rescue) {
+            DevTables *T; rc = placement_tables(ks, r1->device, L, &T); if (rc) return rc;
+            const ScoreBait bait{T->pile_words, T->pile_words_n - 1, T->pile_valid, T->pile_valid_n - 1};
+            HIPCHK(launch_rescue(r1->v, r2->v, r1->d_bits[r1->cur], r2->d_bits[r2->cur], r1->d_place, r2->d_place, d_scores[0], d_scores[1], d_list, n, win, ks->k, bait, T->place_starts, n_rec, d_pairs, d_pc,
+                                 L.diff(r1->d_rtot), L.cnt(r1->d_rtot), L.score_sums(r1->d_rtot), L.pile(r1->d_rtot), ctx->n_cu, st));
+        }
+        if (place1) HIPCHK(hipMemcpyAsync(place1, r1->d_place, n * sizeof(PlaceOut), hipMemcpyDeviceToHost, st));
+        if (place2) HIPCHK(hipMemcpyAsync(place2, r2->d_place, n * sizeof(PlaceOut), hipMemcpyDeviceToHost, st));
+        if (score1) HIPCHK(hipMemcpyAsync(score1, d_scores[0], n * sizeof(ScoreOut), hipMemcpyDeviceToHost, st));
+        if (score2) HIPCHK(hipMemcpyAsync(score2, d_scores[1], n * sizeof(ScoreOut), hipMemcpyDeviceToHost, st));
+        if (pairs) HIPCHK(hipMemcpyAsync(pairs, d_pairs, n * sizeof(PairOut), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(h_pc.data(), d_pc, P.words() * 8, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));          // (the report is told how many reads do not pass: a rescued one that did not is taken off)
+    }
+    if (pair_records)
+        for (size_t j = 0; j < n_rec; j++) {
+            const unsigned long long *c = h_pc.data() + PAIR_RECORD_COUNTERS * j;
+            pair_records[j] = mf_pair_record_t{c[0], c[1], c[2], c[3], c[4], c[5]};
+        }
+    if (pairs_none) *pairs_none = h_pc[P.none()];
+    return placement_report(ks, r1->device, st, L, r1->d_rtot, q, S, r1->d_rsum, r1->d_rpos, (n - listed[0]) + (n - listed[1]) - h_pc[P.rescued_not_passing()]);
 }
 
 } // extern "C"

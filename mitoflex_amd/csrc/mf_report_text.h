@@ -203,4 +203,20 @@ inline bool write_extension_report(FILE *f, const Names &names, const mf_pileup_
     return written(f);
 }
 
+// --pair-report (`fastfilter pairs`): per record the pairs by kind (include/mitofilter.h, pairs) and the mean insert of the proper and
+// the rescued ones (0.000 when there are none), then a last line for the pairs without a settled mate
+inline bool write_pair_report(FILE *f, const Names &names, const Starts &starts, const mf_pair_record_t *recs, uint64_t pairs_none)
+{
+    if (!f) return false;
+    fputs("record\tname\tlength\tproper\tdiscordant\tcross\trescued\tsingle\tmean_insert\n", f);
+    for (size_t i = 0; i < names.size(); i++) {
+        const mf_pair_record_t &d = recs[i];
+        const uint64_t with_insert = d.proper + d.rescued;
+        fprintf(f, "%zu\t%s\t%llu\t%llu\t%llu\t%llu\t%llu\t%llu\t%.3f\n", i, names[i].c_str(), (ull)(starts[i + 1] - starts[i]), (ull)d.proper, (ull)d.discordant,
+                (ull)d.cross, (ull)d.rescued, (ull)d.single, with_insert ? (double)d.insert_sum / (double)with_insert : 0.0);
+    }
+    fprintf(f, "-\t*none*\t%llu\n", (ull)pairs_none);
+    return written(f);
+}
+
 } // namespace mf_text

@@ -1,5 +1,6 @@
 // What place_kernel (mf_place.hip) and align_kernel (mf_align.hip) share, each stated once: the anchor vote that places a listed read
-// (place_vote), its winner decoded (Winner), a read's letter (read_letter), what lane 0 commits for the read (commit_read), and the
+// (place_vote), its winner decoded (Winner), a read's letter (read_letter), the bases it piles (pile_bases, which rescue_kernel of mf_pairs.hip calls too), what lane 0 commits for the read
+// (commit_read), and the
 // launchers' choice of an instantiation (dispatch_kw_flag).
 #pragma once
 #include "mf_place.h"
@@ -44,6 +45,20 @@ __device__ __forceinline__ Winner winner_at(uint32_t rs, int32_t start, const ui
 __device__ __forceinline__ Winner winner_of(uint64_t best_key, const uint64_t *__restrict__ rec_start)
 {
     return winner_at(__builtin_amdgcn_readfirstlane((uint32_t)(best_key >> 32)), (int32_t)__builtin_amdgcn_readfirstlane((uint32_t)best_key), rec_start);
+}
+
+// The bases of a read of L bases at b0, placed as W says, into pile: [position][letter].  The whole wave calls it; lane l takes bases
+// l, l + 64, ..  Consecutive lanes add to consecutive positions: no two lanes of an instruction share a counter.
+__device__ __forceinline__ void pile_bases(const ReadsView &R, uint64_t b0, bool hasn, uint64_t L, const Winner &W, unsigned long long *__restrict__ pile, int lane)
+{
+    for (uint64_t i = (uint64_t)lane; i < L; i += 64) {
+        uint32_t letter = read_letter(R, b0 + i, hasn);
+        if (letter == READ_LETTER_NONE) continue;                                                                       // an N counts nowhere
+        int64_t c = W.start + (int64_t)i;
+        if (W.strand()) { c = W.start + (int64_t)(L - 1 - i); letter ^= 3u; }
+        if (c < 0 || c >= W.len) continue;                                                                              // an overhang counts nowhere
+        atomicAdd(&pile[4 * (W.s0 + (uint64_t)c) + letter], 1ull);
+    }
 }
 
 // What lane 0 commits for listed read r of L bases once the vote (and, in a cutting launch, the cut) is known.  placed: the vote has a

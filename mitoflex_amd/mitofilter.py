@@ -68,6 +68,12 @@ INDEL_VARIANT = np.dtype([("record", np.uint32), ("pos", np.uint64), ("depth", n
 VARIANT = np.dtype([("record", np.uint32), ("pos", np.uint64), ("ref", "S1"), ("alt", "S1"), ("depth", np.uint64), ("alt_count", np.uint64)])
 # the largest insert size pair_inserts keeps (bim.estimate_insert_sizes' rule)
 MAX_INSERT = 100000
+# pair-aware placement (include/mitofilter.h, pairs): the most inserts a rescue window holds, the kinds of a pair, a pair, a record's pairs
+RESCUE_MAX = 4096
+PAIR_NONE, PAIR_PROPER, PAIR_DISCORDANT, PAIR_RESCUED_1, PAIR_RESCUED_2, PAIR_SINGLE_1, PAIR_SINGLE_2 = range(7)
+PAIR = np.dtype([("kind", np.uint32), ("insert", np.int32)])
+PAIR_RECORD = np.dtype([("proper", np.uint64), ("discordant", np.uint64), ("cross", np.uint64), ("rescued", np.uint64), ("single", np.uint64),
+                        ("insert_sum", np.uint64)])
 
 # every symbol include/mitofilter.h declares (checked by tests/test_abi.py)
 EXPORTS = (
@@ -87,6 +93,7 @@ EXPORTS = (
     "mf_align", "mf_filter_fastq_files_aligned",
     "mf_align_gapped", "mf_filter_fastq_files_gapped",
     "mf_align_extended", "mf_filter_fastq_files_extended",
+    "mf_place_pairs",
 )
 
 
@@ -226,6 +233,8 @@ def load(path: Optional[str] = None):
     L.mf_filter_fastq_files_extended.argtypes = [vp, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_uint32, C.c_int,
                                                  C.POINTER(C.c_int), C.c_int, C.c_uint32, C.c_uint32, C.c_int, C.c_uint32, C.c_uint32, vp, vp, vp, vp,
                                                  vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, u64p, u64p]
+    L.mf_place_pairs.argtypes = [vp, vp, vp, C.c_uint32, C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_uint32, vp, vp, vp, vp, vp, vp,
+                                 vp, vp, vp, vp, vp, vp, vp, vp, u64p, vp, C.POINTER(FilterStats)]
     if L.mf_abi_version() != 5:
         raise MitoFilterError("libmitofilter_hip ABI version mismatch")
     _lib = L
@@ -840,6 +849,46 @@ def pair_inserts(place1: np.ndarray, place2: np.ndarray) -> np.ndarray:
     size = end - start
     ok &= (size > 0) & (size <= MAX_INSERT)
     return np.where(ok, size, -1).astype(np.int64)
+
+
+class Paired(Verified):
+    """What place_pairs gives (include/mitofilter.h, pairs): Verified's report fields over BOTH mate sets, and per set bits1 / bits2
+    u32[ceil(n/32)], place1 / place2 PLACE[n], score1 / score2 SCORE[n]; pairs PAIR[n] (kind, insert), pair_records PAIR_RECORD[R] and
+    pairs_none, the pairs without a settled mate.  A rescued mate's place row holds votes == 0.  bits, place, score, kept and total are
+    None."""
+    __slots__ = ("bits1", "bits2", "place1", "place2", "score1", "score2", "pairs", "pair_records", "pairs_none")
+
+
+def place_pairs(ks: KmerSet, reads1: Reads, reads2: Reads, min_insert: int, max_insert: int, rescue: bool = True, rescue_permille: int = 100,
+                min_depth: int = 1, max_permille: int = 1000, pileup: bool = True, threshold: int = 1, mode: int = MODE_SCREENED) -> Paired:
+    """Both mate sets verified as verify_reads does it, into one set of counters; then pair by pair the insert and the kind of the pair
+    and, with rescue=True, the rescue of a mate the vote cannot place: every insert d in [min_insert, max_insert] (at most RESCUE_MAX
+    of them) gives one candidate on the settled mate's record and on the opposite strand, scored by the verification rule; the mate is
+    placed on the one admissible candidate (compared >= k, mismatches * 1000 <= rescue_permille * compared) with strictly the fewest
+    mismatches, and from there on counts as an accepted placed read (include/mitofilter.h: mf_place_pairs).  The default
+    rescue_permille of 100, one base in ten, is a policy choice and not a measured value.  -> Paired."""
+    _check_cut(min_depth, max_permille)
+    if not 1 <= int(min_insert) <= int(max_insert) < 2 ** 31 or int(max_insert) - int(min_insert) + 1 > RESCUE_MAX:
+        raise ValueError("the insert window is 1 <= min_insert <= max_insert, at most RESCUE_MAX inserts wide")
+    if not 0 <= int(rescue_permille) <= 1000:
+        raise ValueError("rescue_permille is a number from 0 to 1000")
+    n = reads1.info.n_reads
+    if reads2.info.n_reads != n:
+        raise ValueError("the mate sets differ in length")
+    per1, results1 = _read_outputs(reads1, PLACE, SCORE)
+    per2, results2 = _read_outputs(reads2, PLACE, SCORE)
+    pairs = np.zeros(max(n, 1), dtype=PAIR)
+    R = len(ks.record_starts) - 1
+    pair_records = np.zeros(max(R, 1), dtype=PAIR_RECORD)
+    none = C.c_uint64()
+    ptrs, results = _report_outputs(ks, _VERIFY_FIELDS, () if pileup else _PILEUP_FIELDS[:3])
+    _chk(load().mf_place_pairs(ks._h, reads1._h, reads2._h, threshold, mode, min_depth, max_permille, int(min_insert), int(max_insert), int(bool(rescue)),
+                               int(rescue_permille), per1[0], per2[0], per1[1], per2[1], per1[2], per2[2], pairs.ctypes.data, *ptrs[:-1],
+                               pair_records.ctypes.data, C.byref(none), ptrs[-1], None))
+    bits1, place1, score1 = results1()
+    bits2, place2, score2 = results2()
+    return Paired(bits1=bits1, bits2=bits2, place1=place1, place2=place2, score1=score1, score2=score2, pairs=pairs[:n], pair_records=pair_records[:R],
+                  pairs_none=none.value, **results())
 
 
 def filter_resident(ks: KmerSet, reads: Reads, threshold: int = 1, mode: int = MODE_SCREENED, steps: int = 1) -> FilterStats:
