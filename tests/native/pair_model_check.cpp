@@ -7,10 +7,14 @@
 // The model: candidate c of the window goes to lane c mod 64, which folds it (rescue_fold_add); the 64 folds are combined in the
 // butterfly's order (rescue_fold_merge); rescue_wins and the fold's d decide.  The reference: every candidate scored base by base over
 // strings, the admissible ones with the fewest mismatches counted.
-// The sweep: window widths 1, 63, 64, 65 and 4096 with the true insert first, last and inside; L = k, 47, 48, 49, 150, 151; every
-// b0 mod 16; both strands; the mate over both ends of the FIRST and of the LAST record of the set (exactly k bases inside, and k - 1),
+// The long read's path: a read beyond the 994 bases a wave stages is scored from the stream itself with its full b0 -- sixteen bases at a
+// time without an N, and with one base by base over every offset that holds none, as the kernel's loop over read_letter and score_base
+// does; both are held to the staged copy's score (and so to the per-base loop), at every candidate for the lengths around the limit.
+// The sweep: window widths 1, 63, 64, 65 and 4096 (the reads beyond 151 bases: 1 and 65, no ties) with the true insert first, last and inside; L = k, 47, 48, 49,
+// 150, 151, 993, 994, 995, 1200 (994 with b0 mod 16 = 15 fills the slice's 64 words); every b0 mod 16; both strands; the mate over both ends of the FIRST and of the LAST record of the set (exactly k bases inside, and k - 1),
 // at either end and inside; a bait N and a read N in the footprint; ties planted through a stretch of period 7.
-// Prints "pair model ok: <cases> cases <rescued> rescued <ties> ties <short> short" and exits 0, or the first difference and exits 1.
+// Prints "pair model ok: <cases> cases <rescued> rescued <ties> ties <short> short <candidates of reads with an N scored from the stream>
+// streamed_n" and exits 0, or the first difference and exits 1.
 #include "../../mitoflex_amd/csrc/mf_rescue.h"
 
 #include <cstdio>
@@ -52,9 +56,9 @@ static Case per_base(const std::string &rec, const std::string &read, uint32_t s
 int main()
 {
     const uint32_t k = 21, permille = 100;
-    const int lengths[] = {(int)k, 47, 48, 49, 150, 151};
+    const int lengths[] = {(int)k, 47, 48, 49, 150, 151, 993, 994, 995, 1200};
     const uint32_t widths[] = {1, 63, 64, 65, 4096};
-    unsigned long long cases = 0, rescued = 0, ties = 0, shorts = 0;
+    unsigned long long cases = 0, rescued = 0, ties = 0, shorts = 0, streamed_n = 0;
     for (int L : lengths)
         for (int which_rec = 0; which_rec < 2; which_rec++)                     // the record under test: the set's first, its last
             for (int with_n = 0; with_n < 2; with_n++)
@@ -81,6 +85,7 @@ int main()
                                 for (uint32_t strand_a = 0; strand_a < 2; strand_a++)
                                     for (uint32_t bmod = 0; bmod < 16; bmod++) {
                                         if (width == 4096 && (bmod % 8 != 3 || where == 2)) continue;
+                                        if (L > 151 && (tie || (width != 1 && width != 65) || where == 2)) continue;          // (the long reads: fewer windows)
                                         if (width == 1 && where) continue;
                                         const int read_n = (int)(rnd() & 1u);
                                         const uint32_t strand = strand_a ^ 1u;                 // the looked-for mate's
@@ -106,6 +111,7 @@ int main()
                                         for (uint64_t g = 0; g < nb; g++) rw.w[g >> 4] |= (g < b0 ? rnd() & 3u : code(read[g - b0] == 'N' ? 'T' : read[g - b0])) << (2 * (g & 15));
                                         // what a wave stages
                                         const uint32_t nw = (uint32_t)(((b0 & 15u) + (uint64_t)L + 15) >> 4);
+                                        if (L <= 994 && nw > 64) { printf("DIFFERS: %u words of a staged read of %d bases\n", nw, L); return 1; }
                                         Words staged(nw), nmask(2 * (((size_t)L + 63) / 64));
                                         for (uint32_t t = 0; t < nw; t++) { const uint64_t g = (b0 >> 4) + t; staged.w[t] = rw.w[g < rw.n - 1 ? g : rw.n - 1]; }
                                         for (int64_t i = 0; i < L; i++) if (read[(size_t)i] == 'N') nmask.w[i >> 5] |= 1u << (i & 31);
@@ -126,9 +132,19 @@ int main()
                                                        (long long)start, strand, bmod, (uint32_t)sc, (uint32_t)(sc >> 32), want.compared, want.mismatches);
                                                 return 1;
                                             }
-                                            if (!read_n && (c == 0 || c == off)) {          // the long read's path: the stream itself
-                                                const uint64_t sg = mf::rescue_score_chunks(rw.w, rw.n - 1, b0, (uint64_t)L, strand, start, SB, s0, len);
-                                                if (sg != sc) { printf("DIFFERS: the stream and its staged copy\n"); return 1; }
+                                            if (c == 0 || c == off || L > 151) {          // the long read's path: the stream itself, the read's first base at b0
+                                                uint64_t sg = 0;
+                                                if (!read_n) sg = mf::rescue_score_chunks(rw.w, rw.n - 1, b0, (uint64_t)L, strand, start, SB, s0, len);
+                                                else {
+                                                    for (uint64_t o = 0; o < (uint64_t)L; o++)
+                                                        if (read[(size_t)o] != 'N') sg += mf::score_base(rw.w, b0, (uint64_t)L, strand, start, SB, s0, len, o);
+                                                    streamed_n++;
+                                                }
+                                                if (sg != sc) {
+                                                    printf("DIFFERS: the stream and its staged copy: L %d N %d start %lld strand %u b0 %u: %u/%u against %u/%u\n", L, read_n,
+                                                           (long long)start, strand, bmod, (uint32_t)sg, (uint32_t)(sg >> 32), (uint32_t)sc, (uint32_t)(sc >> 32));
+                                                    return 1;
+                                                }
                                             }
                                             if (want.compared < k) continue;
                                             reached = true;
@@ -155,6 +171,6 @@ int main()
                                     }
                     }
                 }
-    printf("pair model ok: %llu cases %llu rescued %llu ties %llu short\n", cases, rescued, ties, shorts);
+    printf("pair model ok: %llu cases %llu rescued %llu ties %llu short %llu streamed_n\n", cases, rescued, ties, shorts, streamed_n);
     return 0;
 }
