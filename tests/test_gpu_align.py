@@ -71,9 +71,10 @@ def identities(a, want=None):
         assert np.array_equal(a.pileup_records["mismatches"], r["mismatches"])
 
 
-def check(mf, ks, reads, o, seqs, want, band, max_permille, keep, min_depth=2):
-    """one mf_align call against what the oracle gave for (band, max_permille)"""
-    return check_result(mf, mf.align_reads(ks, reads, band, min_depth, max_permille, keep), o, seqs, want, keep, min_depth)
+def check(mf, ks, reads, o, seqs, want, band, max_permille, keep, min_depth=2, threshold=1, mode=0):
+    """one mf_align call against what the oracle gave for (threshold, band, max_permille); mode 0 is MODE_SCREENED"""
+    a = mf.align_reads(ks, reads, band, min_depth, max_permille, keep, threshold=threshold, mode=mode)
+    return check_result(mf, a, o, seqs, want, keep, min_depth)
 
 
 def check_result(mf, a, o, seqs, want, keep, min_depth):

@@ -101,14 +101,18 @@ def owners(text, k):
     return _owner_cache[key]
 
 
-def check_assign(mf, ol, ks, text, seqs, k, thr, mode):
-    R = ol.OracleReads.from_seqs(seqs)
-    reads = mf.Reads.from_packed(R.words, R.offsets, R.npos)
+def check_assign(mf, ol, ks, text, seqs, k, thr, mode, reads=None):
+    """reads: the uploaded set of seqs, left open; without one the set is uploaded here and closed"""
+    own_upload = reads is None
+    if own_upload:
+        R = ol.OracleReads.from_seqs(seqs)
+        reads = mf.Reads.from_packed(R.words, R.offsets, R.npos)
     n_rec = len(read_fasta_records(text))
     passes, oassign, ocounts = oracle_assign(seqs, k, owners(text, k), thr, n_rec)
     fbits, _, _ = mf.filter_reads(ks, reads, thr, mode)
     bits, assign, counts = mf.assign_reads(ks, reads, thr, mode)
-    reads.close()
+    if own_upload:
+        reads.close()
     assert np.array_equal(bits, fbits)
     assert np.array_equal(bits_to_bool(bits, len(seqs)), passes)
     bad = np.nonzero(assign != oassign)[0]
