@@ -693,6 +693,52 @@ int mf_place_pairs(const mf_kmerset *ks, const mf_reads *reads1, const mf_reads 
               mf_pileup_record_t *pileup_records, mf_score_record_t *score_records, mf_pair_record_t *pair_records, uint64_t *pairs_none,
               uint64_t *unplaced, mf_filter_stats_t *stats);
 
+/* ---- pairs with a band: mf_align_pairs is mf_place_pairs with `band` and `extend` behind max_permille, and with the aligning family's
+ * outputs in place of the scores: both mate sets aligned, and a rescued mate aligned around its seed.  So one consensus has both the
+ * rescued mates -- the only reads over a diverged stretch -- and the indels and the growing ends the banded alignment calls there.
+ * Nucleotide sets only.  ABI 5 still.  Nothing above changes; there is no keep mode, as in mf_place_pairs.
+ * The rule.
+ *   1. Each set is aligned exactly as mf_align_extended does it: filtered, placed by vote, aligned inside the band, cut at max_permille
+ *      on edits per thousand columns.  Both sets add into ONE set of counters: base depth, the place counters, the pile-up, the indel
+ *      table, the insertion pile, the extension pile, the align sums and the histogram.  A mate is SETTLED when it is placed by vote and
+ *      the aligned cut accepts it.
+ *   2. Insert, PROPER, rescue target, candidates and winner are rules 2 - 5 of the pairs section, word for word.  All of them go by the
+ *      mf_place_t rows (start, end: the vote's diagonal), not by ref_begin / ref_end.  The candidates are scored UNGAPPED by the
+ *      verification rule; rescue_permille and compared >= k apply to the ungapped candidate; a tie rescues nothing.  The seed is
+ *      ungapped: a mate with an indel well inside it is found only through the matches of its longer side, the other side lying shifted
+ *      on the seed's diagonal, so it needs a looser rescue_permille than a mate without one.  The value is a policy choice, not measured.
+ *   3. A rescued mate is then aligned as any placed read is: inside the 2 * band + 1 diagonals around the winning candidate's start, on
+ *      record j and strand 1 - s, by the banded-alignment rule unchanged.  It is ACCEPTED whatever the alignment's permille:
+ *      rescue_permille on the seed is its cut.  Its mf_place_t is { j, 1 - s, start, start + L, votes = 0, windows as the vote left
+ *      them }; its mf_align_t is the alignment's.  From there on it adds everywhere an accepted aligned read adds: base depth over the
+ *      clipped [ref_begin, ref_end); forward / reverse; over_begin / over_end by ref_begin / ref_end; the five align sums, `gapped` and
+ *      the bin min(edits, 31); the pile-up of its diagonal steps; del / ins / ins_bases; the insertion pile in a gapped call; the
+ *      extension pile in an extending call.  It leaves unplaced[0] if it passed, else unplaced[1].  The pair's insert is the winning d.
+ *      Its clipped footprint is not empty: the seed compares at least k > band columns inside the record on diagonal 0 of the band, the
+ *      path is monotone and ends within band columns of the seed's diagonal, so [ref_begin, ref_end) holds a column of the record; and
+ *      whatever an alignment did, the two depth adds are clamped into [0, len] of the record.
+ *   4. Identities.  At band == 0 (extend == 0, the gapped outputs NULL) every output mf_place_pairs also has equals that call's bit for
+ *      bit; mf_align_t's compared / mismatches are mf_score_t's, its ref_begin / ref_end are start / end.  At rescue == 0 every output
+ *      except the pair outputs equals two mf_align_extended calls added up.  The aligning section's identities hold with n_reads being
+ *      both sets' reads (accepted == forward + reverse; sum(hist) == accepted + rejected; base_sum == the sum of the clipped footprints;
+ *      the pile-up record's mismatches == the align record's), and the pair section's sum identity holds.
+ * Outputs: mf_place_pairs's with align1 / align2 for score1 / score2, then indels, align_records, the four gapped and the four extended
+ * outputs as mf_align_extended gives them, each over both sets; every output optional.  Which counters are allocated follows the
+ * single-set calls: the pile-up counters with any pile-up, gapped or extended output, the insertion pile with a gapped or extended one,
+ * the extension pile with extend > 0 and an extended one.
+ * MF_E_ARG before any device work: everything mf_place_pairs refuses; band above 31 or not below k; extend above MF_EXTEND_MAX;
+ * extension outputs with extend == 0.  MF_E_NOMEM names the size, as the gapped and extended calls give it.
+ * Device memory: beside the single-set calls', one work slice per resident wave of the rescue (24 bytes a base of the longer set's
+ * longest read: a rescue target need not pass), bounded whatever the number of pairs. */
+int mf_align_pairs(const mf_kmerset *ks, const mf_reads *reads1, const mf_reads *reads2, uint32_t threshold, int mode, uint32_t min_depth,
+              uint32_t max_permille, uint32_t band, uint32_t extend, uint32_t min_insert, uint32_t max_insert, int rescue,
+              uint32_t rescue_permille, uint32_t *bits1, uint32_t *bits2, mf_place_t *place1, mf_place_t *place2, mf_align_t *align1,
+              mf_align_t *align2, mf_pair_t *pairs, uint32_t *base_depth, mf_place_record_t *place_records, mf_pileup_t *pileup,
+              uint8_t *consensus, mf_pileup_record_t *pileup_records, mf_indel_t *indels, mf_align_record_t *align_records,
+              mf_pileup_t *ins_pile, uint8_t *gapped, uint64_t *gapped_starts, mf_gapped_record_t *gapped_records, mf_pileup_t *ext_pile,
+              uint8_t *extended, uint64_t *extended_starts, mf_extend_record_t *extend_records, mf_pair_record_t *pair_records,
+              uint64_t *pairs_none, uint64_t *unplaced, mf_filter_stats_t *stats);
+
 /* Options that select which kernels a filter pass runs (process-wide; every variant gives the same bits and is parity-tested):
  *   pass=default|split|serial   adapt=0|1   finish_streams=0|1|2   screen_streams=1|2   split_pipe=0|1   exact_co=0|1
  * and, read when a k-mer set is BUILT (ABI 5; every form gives the same bits -- tests force them on small baits):

@@ -255,7 +255,7 @@ def consensus_bait(fasta_file: str, fq1: str, fq2: Optional[str], out_fasta: str
         raise ValueError("gapped needs a band: the gapped consensus comes from the banded alignment")
     _check_extend(extend, band)
     if pairs and (band is not None or gapped or int(extend) or fq2 is None):
-        raise ValueError("pairs takes two files and neither band, gapped nor extend: a rescued mate lies on its diagonal")
+        raise ValueError("pairs takes two files and neither band, gapped nor extend: a rescued mate lies on its diagonal (consensus_bait_pairs aligns it)")
     if not pairs and (min_insert is not None or max_insert is not None):
         raise ValueError("min_insert and max_insert belong to pairs=True")
     if (min_insert is None) != (max_insert is None):
@@ -294,6 +294,68 @@ def consensus_bait(fasta_file: str, fq1: str, fq2: Optional[str], out_fasta: str
                 consensus, records = v.consensus, v.pileup_records
     finally:
         ks.close()
+    with open(out_fasta, "w") as f:
+        f.write(mf.consensus_fasta(names, starts, consensus))
+    return records
+
+
+def consensus_bait_pairs(fasta_file: str, fq1: str, fq2: str, out_fasta: str, kmer: int = 31, min_depth: int = 1,
+                         max_permille: Optional[int] = None, band: int = 8, gapped: bool = True, extend: int = 0,
+                         min_insert: Optional[int] = None, max_insert: Optional[int] = None, rescue_permille: int = 100):
+    """consensus_bait(pairs=True) with a band: the two files are loaded into memory and aligned as PAIRS (mitofilter.align_pairs; include/
+    mitofilter.h, pairs with a band).  Both mate sets are aligned inside `band`; a mate the vote cannot place is looked for in the window
+    [min_insert, max_insert] its settled mate implies -- the candidates are scored ungapped, at no more than `rescue_permille` mismatches
+    per thousand compared bases -- and is then aligned around the candidate that won, so the polished bait has the rescued mates over a
+    diverged stretch AND the indels and the ends the banded alignment calls there.  The seed is ungapped: a mate with an indel well inside
+    it is found only with a looser rescue_permille (100 is a policy choice, not a measured value).  The window comes from a first call
+    without rescue (rescue_window) when it is not given.
+    Written to out_fasta under the bait's record names: the extended records when `extend` is given, otherwise the gapped consensus when
+    `gapped` is set, otherwise the consensus.  Returns the pile-up's record summaries."""
+    from mitoflex_amd import mitofilter as mf
+    if fq2 is None:
+        raise ValueError("consensus_bait_pairs takes two files")
+    if (min_insert is None) != (max_insert is None):
+        raise ValueError("min_insert and max_insert are given together")
+    if min_insert is not None and (not 1 <= int(min_insert) <= int(max_insert) < 2 ** 31 or int(max_insert) - int(min_insert) + 1 > mf.RESCUE_MAX):
+        raise ValueError("the insert window is 1 <= min_insert <= max_insert, at most %d inserts wide" % mf.RESCUE_MAX)
+    if not 0 <= int(rescue_permille) <= 1000:
+        raise ValueError("rescue_permille is a number from 0 to 1000")
+    if min_depth < 1:
+        raise ValueError("min_depth is at least 1")
+    if max_permille is not None and not 0 <= int(max_permille) <= 1000:
+        raise ValueError("max_permille is a number from 0 to 1000")
+    if kmer < 1:
+        raise ValueError("kmer is at least 1")
+    if band is None:
+        raise ValueError("band is a number from 0 to 31 and below kmer")
+    _check_band(band, kmer)
+    _check_extend(extend, band)
+    if path.abspath(out_fasta) == path.abspath(fasta_file):
+        raise ValueError("out_fasta would overwrite the bait")
+    cut = 1000 if max_permille is None else int(max_permille)
+    ks = mf.KmerSet.from_fasta(fasta_file, kmer, 0)
+    try:
+        names, starts = ks.record_names, ks.record_starts
+        r1 = mf.Reads.from_fastq(fq1, 0)
+        try:
+            r2 = mf.Reads.from_fastq(fq2, 0)
+            try:
+                if min_insert is None:
+                    first = mf.align_pairs(ks, r1, r2, 1, mf.RESCUE_MAX, int(band), rescue=False, min_depth=min_depth, max_permille=cut, pileup=False)
+                    min_insert, max_insert = rescue_window(first.pairs["insert"])
+                p = mf.align_pairs(ks, r1, r2, int(min_insert), int(max_insert), int(band), rescue=True, rescue_permille=int(rescue_permille),
+                                   min_depth=min_depth, max_permille=cut, gapped=bool(gapped), extend=int(extend))
+            finally:
+                r2.close()
+        finally:
+            r1.close()
+    finally:
+        ks.close()
+    consensus, records = p.consensus, p.pileup_records
+    if gapped:
+        consensus, starts = p.gapped, p.gapped_starts
+    if int(extend):
+        consensus, starts = p.extended, p.extended_starts
     with open(out_fasta, "w") as f:
         f.write(mf.consensus_fasta(names, starts, consensus))
     return records

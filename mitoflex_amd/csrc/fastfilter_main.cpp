@@ -827,13 +827,19 @@ static int bait_main(int argc, char **argv)
 
 // `fastfilter pairs`: the two kept files of a bait step placed as PAIRS (mf_place_pairs; include/mitofilter.h, pairs) -- both files are
 // read into memory --, and the reports of the verifying family over both mates plus the pair report.  Prints the rescued mates.
+// With --band W the call is mf_align_pairs (include/mitofilter.h, pairs with a band): both files aligned, a rescued mate aligned around
+// its seed; --score-report then has the aligned columns, and --indels, --gapped-consensus, --insertions and, with --extend E,
+// --extended-consensus and --extension-report are the bait subcommand's files, by its writers and under its dependency rules.  Without
+// --band every file and the printed line are what they were.
 static int pairs_main(int argc, char **argv)
 {
     std::string bait, fq1, fq2, libpath, pair_report, place_report, base_depth_file, consensus_file, score_report;
-    unsigned long k = 31, min_insert = 0, max_insert = 0, rescue_permille = 100, max_permille = 1000, min_depth = 1;
-    bool rescue = true;
+    std::string indels_file, gapped_file, insertions_file, extended_file, extension_report;
+    unsigned long k = 31, min_insert = 0, max_insert = 0, rescue_permille = 100, max_permille = 1000, min_depth = 1, band = 0, extend = 0;
+    bool rescue = true, have_band = false;
     static const char *usage = "usage: fastfilter pairs --bait BAIT.fa [-k 31] --fq1 A.fq --fq2 B.fq --min-insert N --max-insert M [--no-rescue] [--rescue-permille 100]\n"
                                "       [--max-mismatch PERMILLE] [--min-depth D] [--pair-report FILE] [--place-report FILE] [--base-depth FILE] [--consensus FILE] [--score-report FILE]\n"
+                               "       [--band W [--indels FILE] [--gapped-consensus FILE] [--insertions FILE] [--extend E [--extended-consensus FILE] [--extension-report FILE]]]\n"
                                "       (the files are read into memory: the kept files of a bait step; 1 <= N <= M, at most 4096 inserts wide)\n";
     for (int a = 2; a < argc; a++) {
         const std::string o = argv[a];
@@ -862,6 +868,13 @@ static int pairs_main(int argc, char **argv)
         else if (o == "--base-depth") base_depth_file = need("--base-depth");
         else if (o == "--consensus") consensus_file = need("--consensus");
         else if (o == "--score-report") score_report = need("--score-report");
+        else if (o == "--band") { number("--band", 0, 31, band); have_band = true; }
+        else if (o == "--indels") indels_file = need("--indels");
+        else if (o == "--gapped-consensus") gapped_file = need("--gapped-consensus");
+        else if (o == "--insertions") insertions_file = need("--insertions");
+        else if (o == "--extend") number("--extend", 1, MF_EXTEND_MAX, extend);
+        else if (o == "--extended-consensus") extended_file = need("--extended-consensus");
+        else if (o == "--extension-report") extension_report = need("--extension-report");
         else { fprintf(stderr, "error: unknown option '%s' for fastfilter pairs\n", o.c_str()); return 1; }
     }
     if (bait.empty() || fq1.empty() || fq2.empty() || !min_insert || !max_insert) { fputs(usage, stderr); return 1; }
@@ -869,6 +882,13 @@ static int pairs_main(int argc, char **argv)
         fprintf(stderr, "error: --min-insert .. --max-insert is a window of 1 to %d inserts\n", MF_RESCUE_MAX);
         return 1;
     }
+    // the bait subcommand's dependency rules
+    const bool gap = !gapped_file.empty() || !insertions_file.empty();
+    if (gap && !have_band) { fprintf(stderr, "error: --gapped-consensus and --insertions need --band\n"); return 1; }
+    if ((!extended_file.empty() || !extension_report.empty()) && !extend) { fprintf(stderr, "error: --extended-consensus and --extension-report need --extend\n"); return 1; }
+    if (extend && !have_band) { fprintf(stderr, "error: --extend needs --band (--band 0 is fine)\n"); return 1; }
+    if (!indels_file.empty() && !have_band) { fprintf(stderr, "error: --indels needs --band\n"); return 1; }
+    if (have_band && band >= k) { fprintf(stderr, "error: --band stays below k (%lu)\n", k); return 1; }
     if (libpath.empty()) { const char *e = getenv("MITOFILTER_LIB"); if (e && *e) libpath = e; }
     if (libpath.empty()) libpath = exe_dir() + "/../libmitofilter_hip.so";
     void *h = dlopen(libpath.c_str(), RTLD_NOW | RTLD_LOCAL);
@@ -888,6 +908,23 @@ static int pairs_main(int argc, char **argv)
     std::vector<uint32_t> depth(positions, 0); std::vector<uint8_t> consensus(positions, 0);
     std::vector<mf_place_record_t> place_recs(n_rec); std::vector<mf_score_record_t> score_recs(n_rec); std::vector<mf_pair_record_t> pair_recs(n_rec);
     uint64_t none = 0, unplaced[2] = {0, 0};
+    std::vector<mf_align_record_t> align_recs; std::vector<mf_indel_t> indels; std::vector<mf_pileup_t> ins_pile, ext_pile;
+    std::vector<uint8_t> gapped, extended; std::vector<uint64_t> gapped_starts, extended_starts;
+    if (have_band) {
+#define SYM(name) auto p_##name = (decltype(&name))dlsym(h, #name); if (!p_##name) { fprintf(stderr, "error: %s lacks symbol %s\n", libpath.c_str(), #name); return 2; }
+        SYM(mf_align_pairs)
+#undef SYM
+        const size_t span = 2 * (size_t)band, E = extend;
+        align_recs.assign(n_rec, mf_align_record_t{}); indels.assign(positions, mf_indel_t{});
+        if (gap) { ins_pile.assign(std::max<size_t>(positions * span, 1), mf_pileup_t{}); gapped.assign(positions * (1 + span), 0); gapped_starts.assign(n_rec + 1, 0); }
+        if (E) { ext_pile.assign(n_rec * 2 * E, mf_pileup_t{}); extended.assign(positions * (1 + span) + 2 * n_rec * E, 0); extended_starts.assign(n_rec + 1, 0); }
+        if (p_mf_align_pairs(ks, r1, r2, 1, MF_MODE_SCREENED, (uint32_t)min_depth, (uint32_t)max_permille, (uint32_t)band, (uint32_t)extend, (uint32_t)min_insert,
+                             (uint32_t)max_insert, rescue ? 1 : 0, (uint32_t)rescue_permille, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, depth.data(),
+                             place_recs.data(), nullptr, consensus_file.empty() ? nullptr : consensus.data(), nullptr, indels.data(), align_recs.data(),
+                             gap && span ? ins_pile.data() : nullptr, gap ? gapped.data() : nullptr, gap ? gapped_starts.data() : nullptr, nullptr,
+                             E ? ext_pile.data() : nullptr, E ? extended.data() : nullptr, E ? extended_starts.data() : nullptr, nullptr, pair_recs.data(), &none, unplaced,
+                             nullptr) != MF_OK) return fail();
+    } else
     if (p_mf_place_pairs(ks, r1, r2, 1, MF_MODE_SCREENED, (uint32_t)min_depth, (uint32_t)max_permille, (uint32_t)min_insert, (uint32_t)max_insert, rescue ? 1 : 0,
                          (uint32_t)rescue_permille, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, depth.data(), place_recs.data(), nullptr,
                          consensus_file.empty() ? nullptr : consensus.data(), nullptr, score_recs.data(), pair_recs.data(), &none, unplaced, nullptr) != MF_OK) return fail();
@@ -896,7 +933,13 @@ static int pairs_main(int argc, char **argv)
         && write_file(place_report, "placement report", [&](FILE *f) { return write_place_report(f, names, starts, place_recs.data(), depth.data(), unplaced[0]); })
         && write_file(base_depth_file, "base depth", [&](FILE *f) { return write_base_depth(f, names, starts, depth.data()); })
         && write_file(consensus_file, "consensus", [&](FILE *f) { return write_consensus(f, names, starts, consensus.data()); })
-        && write_file(score_report, "score report", [&](FILE *f) { return write_score_report(f, names, starts, score_recs.data()); });
+        && write_file(score_report, "score report", [&](FILE *f) { return have_band ? write_align_report(f, names, starts, align_recs.data())
+                                                                                    : write_score_report(f, names, starts, score_recs.data()); })
+        && write_file(indels_file, "indel table", [&](FILE *f) { return write_indels(f, names, starts, depth.data(), indels.data()); })
+        && write_file(gapped_file, "gapped consensus", [&](FILE *f) { return write_gapped_consensus(f, names, gapped_starts.data(), gapped.data()); })
+        && write_file(insertions_file, "insertion table", [&](FILE *f) { return write_insertions(f, names, starts, depth.data(), ins_pile.data(), 2 * (unsigned)band); })
+        && write_file(extended_file, "extended consensus", [&](FILE *f) { return write_gapped_consensus(f, names, extended_starts.data(), extended.data()); })
+        && write_file(extension_report, "extension report", [&](FILE *f) { return write_extension_report(f, names, ext_pile.data(), (unsigned)extend); });
     unsigned long long rescued = 0;
     for (size_t j = 0; j < names.size(); j++) rescued += pair_recs[j].rescued;
     p_mf_reads_free(r2); p_mf_reads_free(r1); p_mf_kmerset_free(ks);

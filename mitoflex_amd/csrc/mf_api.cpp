@@ -564,7 +564,7 @@ void reads_release(mf_reads *r)
         hipFree(r->d_hits); hipFree(r->d_npos_blk); hipFree(r->d_off_blk);
         hipFree(r->d_alist); hipFree(r->d_assign); hipFree(r->d_apairs); hipFree(r->d_acnt);
         hipFree(r->d_rpos); hipFree(r->d_rtot); hipFree(r->d_rsum); hipFree(r->d_place); hipFree(r->d_score); hipFree(r->d_keep);
-        hipFree(r->d_align); hipFree(r->d_awork); hipFree(r->d_pair);
+        hipFree(r->d_align); hipFree(r->d_awork); hipFree(r->d_pair); hipFree(r->d_pwork);
     }
     delete r;
 }

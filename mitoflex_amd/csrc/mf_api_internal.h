@@ -163,6 +163,7 @@ struct mf_reads {
     mf::AlignOut *d_align = nullptr; size_t cap_align = 0;          // mf_align's per-read alignments
     unsigned long long *d_awork = nullptr; size_t cap_awork = 0;    // ... and its kernel's work memory, a slice a wave (mf_align_launch.h)
     unsigned long long *d_pair = nullptr; size_t cap_pair = 0;      // mf_place_pairs (on the first set): the pair counters, the per-pair results, the rescue list
+    unsigned long long *d_pwork = nullptr; size_t cap_pwork = 0;    // mf_align_pairs (on the first set): the aligning rescue's work memory, a slice a wave over the longer set's longest read
     // capacities (bytes), so that a handle can be refilled batch after batch without touching the allocator
     size_t cap_words = 0, cap_offsets = 0, cap_npos = 0, cap_bitmap = 0, cap_recs = 0, cap_rec_counts = 0, cap_hits = 0, cap_npos_blk = 0, cap_off_blk = 0;
 };

@@ -3,6 +3,7 @@
 #pragma once
 #include "mf_place.h"
 #include "mf_rescue.h"
+#include "mf_align_launch.h"
 
 namespace mf {
 
@@ -39,5 +40,27 @@ hipError_t launch_rescue(const ReadsView &R1, const ReadsView &R2, const uint32_
                          ScoreOut *score1, ScoreOut *score2, const uint32_t *list, uint64_t n_pairs, PairWindow win, int k, const ScoreBait &bait, const uint64_t *rec_start, uint32_t n_rec, PairOut *pairs,
                          unsigned long long *counters, unsigned long long *diff, unsigned long long *counts, unsigned long long *sums,
                          unsigned long long *pile, int n_cu, hipStream_t st);
+
+// The aligning forms (include/mitofilter.h, "pairs with a band").  launch_pair_list_aligned is launch_pair_list over the sets' alignments:
+// a placed mate is settled when align_accepts accepts its alignment (read only where max_permille < 1000).
+hipError_t launch_pair_list_aligned(const uint32_t *bits1, const uint32_t *bits2, const PlaceOut *place1, const PlaceOut *place2, const AlignOut *align1,
+                                    const AlignOut *align2, uint64_t n, uint32_t max_permille, PairWindow win, uint32_t n_rec, PairOut *pairs, uint32_t *list, unsigned long long *counters, int n_cu, hipStream_t st);
+
+// What the aligning rescue takes beside launch_rescue's arguments: the counters of an aligning layout (sums: ALIGN_SUMS a record; indel;
+// ins_pile and ext_pile / extend as PlaceAlign holds them), the sets' alignments (optional), the band, and the work memory: work holds
+// align_work_words(max_len) words for each of rescue_align_waves(n_pairs, max_len, n_cu) waves; max_len: no read of EITHER set is longer
+// (a rescue target need not pass, so it is on no list).
+struct RescueAlign {
+    uint32_t band; AlignOut *align1, *align2; unsigned long long *sums, *indel, *ins_pile, *ext_pile; uint32_t extend;
+    unsigned long long *work; uint64_t max_len;
+};
+// the waves of the aligning rescue: align_waves' rule, so never more than the bound on the work memory allows
+uint64_t rescue_align_waves(uint64_t n_pairs, uint64_t max_len, int n_cu);
+// launch_rescue with the seed scored ungapped as there, and the winner then aligned inside the band around the seed's start: committed
+// with the alignment's footprint, edits and sums, and added wherever an accepted aligned read adds.
+hipError_t launch_rescue_aligned(const ReadsView &R1, const ReadsView &R2, const uint32_t *bits1, const uint32_t *bits2, PlaceOut *place1, PlaceOut *place2,
+                                 const uint32_t *list, uint64_t n_pairs, PairWindow win, int k, const ScoreBait &bait, const uint64_t *rec_start,
+                                 uint32_t n_rec, PairOut *pairs, unsigned long long *counters, unsigned long long *diff, unsigned long long *counts,
+                                 unsigned long long *pile, const RescueAlign &A, int n_cu, hipStream_t st);
 
 } // namespace mf

@@ -13,9 +13,17 @@
 //                      folds.  A strict winner is committed by lane 0 as an accepted placed read of votes 0 (commit_read, the score sums,
 //                      the bin), the wave piles its bases (pile_bases), and lane 0 writes the pair's kind and insert.  A read too long for
 //                      the slice is scored from global memory.  Rescued reads are few: plain global atomics.
+// The aligning forms (include/mitofilter.h, "pairs with a band") are instantiations of the same two kernels:
+//   pair_list_kernel<true>   reads the sets' alignments where the plain one reads their scores: settled is align_accepts.
+//   rescue_kernel<true, ..>  staging, scan, fold and butterfly are the plain kernel's -- the seed is ungapped.  The winner is then aligned
+//                      by the whole wave inside the band around the candidate's start (align_read, mf_align_dev.h) in the wave's own
+//                      slice of work memory; lane 0 writes the alignment, commits the read with the alignment's footprint and its edits
+//                      as the bin, and adds the five align sums; the wave adds what an accepted aligned read adds (align_adds<GAPPED,
+//                      EXTEND>, the instantiations launch_align picks).
 #include "mf_pairs.h"
-#include "mf_vote_dev.h"
+#include "mf_align_dev.h"
 #include <algorithm>
+#include <type_traits>
 
 namespace mf {
 
@@ -24,9 +32,15 @@ constexpr uint32_t PAIR_LDS = 1024;                      // pair counters up to 
 
 __device__ __forceinline__ bool pass_bit(const uint32_t *__restrict__ bits, uint64_t i) { return (bits[i >> 5] >> ((uint32_t)i & 31u)) & 1u; }
 
+// what a set's cut went by: its scores, or (ALIGN) its alignments
+template <bool ALIGN> using CutOut = std::conditional_t<ALIGN, AlignOut, ScoreOut>;
+__device__ __forceinline__ bool cut_accepts(const ScoreOut &s, uint32_t max_permille) { return score_accepts(s.compared, s.mismatches, max_permille); }
+__device__ __forceinline__ bool cut_accepts(const AlignOut &a, uint32_t max_permille) { return align_accepts(a.compared, a.mismatches, a.insertions, a.deletions, max_permille); }
+
+template <bool ALIGN>
 __global__ void __launch_bounds__(PAIR_BLOCK)
 pair_list_kernel(const uint32_t *__restrict__ bits1, const uint32_t *__restrict__ bits2, const PlaceOut *__restrict__ place1, const PlaceOut *__restrict__ place2,
-                 const ScoreOut *__restrict__ score1, const ScoreOut *__restrict__ score2, uint64_t n, uint32_t max_permille, PairWindow win, uint32_t n_rec,
+                 const CutOut<ALIGN> *__restrict__ score1, const CutOut<ALIGN> *__restrict__ score2, uint64_t n, uint32_t max_permille, PairWindow win, uint32_t n_rec,
                  PairOut *__restrict__ pairs, uint32_t *__restrict__ list, unsigned long long *__restrict__ counters)
 {
     __shared__ unsigned long long s_cnt[PAIR_LDS];
@@ -48,8 +62,8 @@ pair_list_kernel(const uint32_t *__restrict__ bits1, const uint32_t *__restrict_
             const PlaceOut a = pass_bit(bits1, i) ? place1[i] : none, b = pass_bit(bits2, i) ? place2[i] : none;
             bool set1 = a.record < PLACE_AMBIGUOUS, set2 = b.record < PLACE_AMBIGUOUS;
             if (max_permille < 1000) {                       // (at 1000 every placed read is accepted: the scores are not read)
-                if (set1) { const ScoreOut s = score1[i]; set1 = score_accepts(s.compared, s.mismatches, max_permille); }
-                if (set2) { const ScoreOut s = score2[i]; set2 = score_accepts(s.compared, s.mismatches, max_permille); }
+                if (set1) { const CutOut<ALIGN> s = score1[i]; set1 = cut_accepts(s, max_permille); }
+                if (set2) { const CutOut<ALIGN> s = score2[i]; set2 = cut_accepts(s, max_permille); }
             }
             PairOut out{PAIR_NONE, -1};
             if (set1 && set2) {
@@ -110,12 +124,23 @@ __device__ __forceinline__ RescueFold wave_fold(RescueFold f)
     return f;
 }
 
+// What the aligning rescue takes beside the plain one (nothing otherwise, as GapArgs of mf_align.hip): the sets' alignments (optional),
+// the band, the indel table, the insertion pile (GAPPED) and the extension pile with its columns an end (EXTEND), and the work memory:
+// work_words words a wave, the direction bits in the first dir_words of them.
+template <bool ALIGN> struct RescueAlignArgs {};
+template <> struct RescueAlignArgs<true> {
+    AlignOut *__restrict__ align1, *__restrict__ align2; int band;
+    unsigned long long *__restrict__ indel, *__restrict__ ins_pile, *__restrict__ ext_pile; uint32_t extend;
+    unsigned long long *work; uint64_t dir_words, work_words;
+};
+
+template <bool ALIGN, bool GAPPED, bool EXTEND>
 __global__ void __launch_bounds__(RESCUE_BLOCK)
 rescue_kernel(ReadsView R1, ReadsView R2, const uint32_t *__restrict__ bits1, const uint32_t *__restrict__ bits2, PlaceOut *__restrict__ place1,
               PlaceOut *__restrict__ place2, ScoreOut *__restrict__ score1, ScoreOut *__restrict__ score2,
               const uint32_t *__restrict__ list, PairWindow win, uint32_t k, ScoreBait bait, const uint64_t *__restrict__ rec_start, uint32_t n_rec,
               PairOut *__restrict__ pairs, unsigned long long *__restrict__ counters, unsigned long long *__restrict__ diff, unsigned long long *__restrict__ counts,
-              unsigned long long *__restrict__ sums, unsigned long long *__restrict__ pile)
+              unsigned long long *__restrict__ sums, unsigned long long *__restrict__ pile, RescueAlignArgs<ALIGN> G)
 {
     __shared__ uint32_t s_words[RESCUE_BLOCK / 64][RESCUE_WORDS];
     __shared__ uint32_t s_nmask[RESCUE_BLOCK / 64][RESCUE_NMASK];
@@ -182,14 +207,32 @@ rescue_kernel(ReadsView R1, ReadsView R2, const uint32_t *__restrict__ bits1, co
         if (won) {
             const int64_t start = rescue_start(A.strand, A.start, A.end, L, d);
             const Winner W = winner_at((j << 1) | strand, (int32_t)start, rec_start);
+            // ALIGN: the seed's diagonal is the band's middle; the wave's slice holds a read of either set (max_len is over both)
+            AlignResult a{0, 0, 0, 0, 0, 0};
+            unsigned long long *ent = nullptr;
+            if constexpr (ALIGN) {
+                unsigned long long *const dirs = G.work + (((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6) * G.work_words;
+                ent = dirs + G.dir_words;
+                a = align_read(R, b0, hasn, L, strand, start, s0, len, bait, G.band, dirs, ent, lane);
+            }
             if (lane == 0) {
-                const uint64_t sc = score_at(start);
-                const uint32_t compared = (uint32_t)sc, mismatches = (uint32_t)(sc >> 32);
-                PlaceOut *const place = b_is_2 ? place2 : place1; ScoreOut *const score = b_is_2 ? score2 : score1;
-                commit_read(true, true, W, L, start, start + (int64_t)L, true, mismatches, 0u, B.windows, r, n_rec, place, diff, cnt, nullptr, 0);
-                atomicAdd(&sums[2 * (size_t)j], (unsigned long long)compared);
-                atomicAdd(&sums[2 * (size_t)j + 1], (unsigned long long)mismatches);
-                if (score) score[r] = ScoreOut{compared, mismatches};
+                PlaceOut *const place = b_is_2 ? place2 : place1;
+                if constexpr (ALIGN) {
+                    AlignOut *const align = b_is_2 ? G.align2 : G.align1;
+                    if (align) align[r] = AlignOut{a.compared, a.mismatches, a.insertions, a.deletions, (int32_t)a.ref_begin, (int32_t)a.ref_end};
+                    commit_read(true, true, W, L, a.ref_begin, a.ref_end, true, a.mismatches + a.insertions + a.deletions, 0u, B.windows, r, n_rec, place, diff, cnt, nullptr, 0);
+                    const unsigned long long v[ALIGN_SUMS] = {a.compared, a.mismatches, a.insertions, a.deletions, (a.insertions | a.deletions) != 0};
+#pragma unroll
+                    for (uint32_t q = 0; q < ALIGN_SUMS; q++) if (v[q]) atomicAdd(&sums[ALIGN_SUMS * (size_t)j + q], v[q]);
+                } else {
+                    const uint64_t sc = score_at(start);
+                    const uint32_t compared = (uint32_t)sc, mismatches = (uint32_t)(sc >> 32);
+                    ScoreOut *const score = b_is_2 ? score2 : score1;
+                    commit_read(true, true, W, L, start, start + (int64_t)L, true, mismatches, 0u, B.windows, r, n_rec, place, diff, cnt, nullptr, 0);
+                    atomicAdd(&sums[2 * (size_t)j], (unsigned long long)compared);
+                    atomicAdd(&sums[2 * (size_t)j + 1], (unsigned long long)mismatches);
+                    if (score) score[r] = ScoreOut{compared, mismatches};
+                }
                 // it is no longer among the passing reads that are not placed -- or among the reads that do not pass
                 if (B.record == PLACE_AMBIGUOUS) atomicAdd(&counts[4 * (size_t)n_rec], ~0ull);
                 else atomicAdd(&counters[P.rescued_not_passing()], 1ull);
@@ -197,26 +240,43 @@ rescue_kernel(ReadsView R1, ReadsView R2, const uint32_t *__restrict__ bits1, co
                 atomicAdd(&counters[PAIR_RECORD_COUNTERS * (size_t)j + 3], 1ull);
                 atomicAdd(&counters[PAIR_RECORD_COUNTERS * (size_t)j + 5], (unsigned long long)d);
             }
-            if (pile) pile_bases(R, b0, hasn, L, W, pile, lane);
+            if constexpr (ALIGN)
+                align_adds<GAPPED, EXTEND>(R, b0, hasn, L, strand, s0, len, ent, pile, G.indel, G.ins_pile, 2u * (uint32_t)G.band, G.ext_pile, G.extend, j, lane);
+            else if (pile) pile_bases(R, b0, hasn, L, W, pile, lane);
         } else if (lane == 0) {
             pairs[r] = PairOut{b_is_2 ? PAIR_SINGLE_1 : PAIR_SINGLE_2, -1};
             atomicAdd(&counters[PAIR_RECORD_COUNTERS * (size_t)j + 4], 1ull);
         }
-        if (staged) wave_lds_sync();                     // (the next pair's words overwrite these)
+        if (ALIGN || staged) wave_lds_sync();            // (the next pair's words overwrite these, and an aligning wave's next read its work slice)
     }
     cnt.hist_end(lane);
+}
+
+template <bool ALIGN>
+static hipError_t pair_list_launch(const uint32_t *bits1, const uint32_t *bits2, const PlaceOut *place1, const PlaceOut *place2, const CutOut<ALIGN> *score1,
+                                   const CutOut<ALIGN> *score2, uint64_t n, uint32_t max_permille,
+                                   PairWindow win, uint32_t n_rec, PairOut *pairs, uint32_t *list, unsigned long long *counters, int n_cu, hipStream_t st)
+{
+    if (!n) return hipSuccess;
+    // eight workgroups a CU at most, each over its share of the pairs
+    const unsigned grid = std::min<unsigned>(grid_of(n, PAIR_BLOCK), (unsigned)(n_cu > 0 ? n_cu : 1) * 8u);
+    hipLaunchKernelGGL(pair_list_kernel<ALIGN>, dim3(grid), dim3(PAIR_BLOCK), 0, st, bits1, bits2, place1, place2, score1, score2, n, max_permille, win, n_rec,
+                       pairs, list, counters);
+    return hipGetLastError();
 }
 
 hipError_t launch_pair_list(const uint32_t *bits1, const uint32_t *bits2, const PlaceOut *place1, const PlaceOut *place2, const ScoreOut *score1,
                             const ScoreOut *score2, uint64_t n, uint32_t max_permille,
                             PairWindow win, uint32_t n_rec, PairOut *pairs, uint32_t *list, unsigned long long *counters, int n_cu, hipStream_t st)
 {
-    if (!n) return hipSuccess;
-    // eight workgroups a CU at most, each over its share of the pairs
-    const unsigned grid = std::min<unsigned>(grid_of(n, PAIR_BLOCK), (unsigned)(n_cu > 0 ? n_cu : 1) * 8u);
-    hipLaunchKernelGGL(pair_list_kernel, dim3(grid), dim3(PAIR_BLOCK), 0, st, bits1, bits2, place1, place2, score1, score2, n, max_permille, win, n_rec,
-                       pairs, list, counters);
-    return hipGetLastError();
+    return pair_list_launch<false>(bits1, bits2, place1, place2, score1, score2, n, max_permille, win, n_rec, pairs, list, counters, n_cu, st);
+}
+
+hipError_t launch_pair_list_aligned(const uint32_t *bits1, const uint32_t *bits2, const PlaceOut *place1, const PlaceOut *place2, const AlignOut *align1,
+                                    const AlignOut *align2, uint64_t n, uint32_t max_permille,
+                                    PairWindow win, uint32_t n_rec, PairOut *pairs, uint32_t *list, unsigned long long *counters, int n_cu, hipStream_t st)
+{
+    return pair_list_launch<true>(bits1, bits2, place1, place2, align1, align2, n, max_permille, win, n_rec, pairs, list, counters, n_cu, st);
 }
 
 hipError_t launch_rescue(const ReadsView &R1, const ReadsView &R2, const uint32_t *bits1, const uint32_t *bits2, PlaceOut *place1, PlaceOut *place2,
@@ -228,8 +288,33 @@ hipError_t launch_rescue(const ReadsView &R1, const ReadsView &R2, const uint32_
     if (!n_pairs) return hipSuccess;
     // the launch shape of launch_place: 32 waves a CU at most, never more waves than pairs
     const uint64_t waves = std::min<uint64_t>((uint64_t)(n_cu > 0 ? n_cu : 1) * 32, n_pairs);
-    hipLaunchKernelGGL(rescue_kernel, dim3(grid_of(waves, RESCUE_BLOCK / 64)), dim3(RESCUE_BLOCK), 0, st, R1, R2, bits1, bits2, place1, place2, score1, score2, list, win,
-                       (uint32_t)k, bait, rec_start, n_rec, pairs, counters, diff, counts, sums, pile);
+    hipLaunchKernelGGL((rescue_kernel<false, false, false>), dim3(grid_of(waves, RESCUE_BLOCK / 64)), dim3(RESCUE_BLOCK), 0, st, R1, R2, bits1, bits2, place1, place2, score1, score2, list, win,
+                       (uint32_t)k, bait, rec_start, n_rec, pairs, counters, diff, counts, sums, pile, RescueAlignArgs<false>{});
+    return hipGetLastError();
+}
+
+static_assert(ASSIGN_BLOCK % RESCUE_BLOCK == 0, "align_waves counts whole workgroups of align_kernel: whole workgroups of this kernel too");
+
+uint64_t rescue_align_waves(uint64_t n_pairs, uint64_t max_len, int n_cu) { return align_waves(n_pairs, max_len, n_cu); }
+
+hipError_t launch_rescue_aligned(const ReadsView &R1, const ReadsView &R2, const uint32_t *bits1, const uint32_t *bits2, PlaceOut *place1, PlaceOut *place2,
+                                 const uint32_t *list, uint64_t n_pairs, PairWindow win, int k, const ScoreBait &bait, const uint64_t *rec_start,
+                                 uint32_t n_rec, PairOut *pairs, unsigned long long *counters, unsigned long long *diff, unsigned long long *counts,
+                                 unsigned long long *pile, const RescueAlign &A, int n_cu, hipStream_t st)
+{
+    if (!n_pairs) return hipSuccess;
+    // launch_align's shape and its bound on the work memory: whole workgroups, each wave with a slice of its own
+    const unsigned grid = (unsigned)(rescue_align_waves(n_pairs, A.max_len, n_cu) / (RESCUE_BLOCK / 64));
+    const uint64_t n = std::max<uint64_t>(A.max_len, 1);
+    const RescueAlignArgs<true> G{A.align1, A.align2, (int)A.band, A.indel, A.ins_pile, A.ext_pile, A.extend, A.work, 64 * ((n + 31) / 32), align_work_words(A.max_len)};
+    const auto launch = [&](auto GAPPED, auto EXTEND) {
+        hipLaunchKernelGGL((rescue_kernel<true, decltype(GAPPED)::value, decltype(EXTEND)::value>), dim3(grid), dim3(RESCUE_BLOCK), 0, st, R1, R2, bits1, bits2, place1,
+                           place2, (ScoreOut *)nullptr, (ScoreOut *)nullptr, list, win, (uint32_t)k, bait, rec_start, n_rec, pairs, counters, diff, counts, A.sums, pile, G);
+    };
+    // (the instantiations launch_align picks: an extending launch is a gapped one whatever the band; at band 0 the insertion pile has no entry)
+    if (A.ext_pile && A.extend) launch(std::true_type{}, std::true_type{});
+    else if (A.ins_pile && A.band) launch(std::true_type{}, std::false_type{});
+    else launch(std::false_type{}, std::false_type{});
     return hipGetLastError();
 }
 

@@ -453,9 +453,10 @@ static int placement_tables(mf_kmerset *ks, int device, const PlaceLayout &L, De
 // the device) takes the scores.  keep_dev (optional, a verifying layout only): the read set's keep bitmap, a copy of the pass bitmap,
 // in which the kernel clears the bits of the reads the keep mode `keep` does not write (keep_clears, mf_score.h).  An aligning layout:
 // the placed reads are aligned inside L.band instead (launch_align, in the read set's work memory d_awork); align (optional, zeroed,
-// n_reads entries on the device) takes the alignments and score stays null.  Ends synchronised.
+// n_reads entries on the device) takes the alignments and score stays null; *longest (optional): the set's longest read, which sized the
+// work memory.  Ends synchronised.
 static int place_after_filter(mf_kmerset *ks, mf_reads *r, const PlaceLayout &L, unsigned long long *t, PlaceOut *place, ScoreOut *score, uint64_t *listed,
-                              uint32_t *keep_dev = nullptr, int keep = MF_KEEP_PASSING, AlignOut *align = nullptr)
+                              uint32_t *keep_dev = nullptr, int keep = MF_KEEP_PASSING, AlignOut *align = nullptr, uint64_t *longest = nullptr)
 {
     DevTables *T; int rc = placement_tables(ks, r->device, L, &T); if (rc) return rc;
     DevCtx *ctx; rc = get_ctx(r->device, &ctx, r->lane); if (rc) return rc;
@@ -483,6 +484,7 @@ static int place_after_filter(mf_kmerset *ks, mf_reads *r, const PlaceLayout &L,
     if (L.verify || L.align) cut = PlaceCut{ScoreBait{T->pile_words, T->pile_words_n - 1, T->pile_valid, T->pile_valid_n - 1}, L.max_permille, L.score_sums(t), keep_dev, keep};
     if (L.align) {
         const uint64_t max_len = r->v.uniform_len ? r->v.uniform_len : v;
+        if (longest) *longest = max_len;
         const size_t bytes = (size_t)(align_waves(n, max_len, ctx->n_cu) * align_work_words(max_len)) * 8;
         const hipError_t e = dev_reserve(r->d_awork, r->cap_awork, bytes, false);
         if (e == hipErrorOutOfMemory) { (void)hipGetLastError(); return fail(MF_E_NOMEM, "the alignment of reads of up to %llu bases needs %llu bytes on the device", (unsigned long long)max_len, (unsigned long long)bytes); }
@@ -753,27 +755,33 @@ int mf_verify(const mf_kmerset *ks, const mf_reads *reads, uint32_t threshold, i
                           place_records, pileup, consensus, pileup_records, score_records, unplaced, stats);
 }
 
-// The paired call (include/mitofilter.h, "pairs"): each set filtered, placed, scored and cut as mf_verify does it, both into ONE set of
-// counters (the first set's cached buffers); then the pair kernels over both sets' pass bits and placements -- which are therefore always
-// made on the device, asked for or not; the scores only where the cut can reject or the caller asks -- and the report once.
-int mf_place_pairs(const mf_kmerset *ks_, const mf_reads *reads1, const mf_reads *reads2, uint32_t threshold, int mode, uint32_t min_depth, uint32_t max_permille,
-                   uint32_t min_insert, uint32_t max_insert, int rescue, uint32_t rescue_permille, uint32_t *bits1, uint32_t *bits2, mf_place_t *place1,
-                   mf_place_t *place2, mf_score_t *score1, mf_score_t *score2, mf_pair_t *pairs, uint32_t *base_depth, mf_place_record_t *place_records,
-                   mf_pileup_t *pileup, uint8_t *consensus, mf_pileup_record_t *pileup_records, mf_score_record_t *score_records,
-                   mf_pair_record_t *pair_records, uint64_t *pairs_none, uint64_t *unplaced, mf_filter_stats_t *stats)
+} // extern "C"
+
+// What a paired call is asked for beside its PlaceRequest: the window, the rescue, the per-set and the per-pair outputs.  score1 / score2
+// are the plain call's, align1 / align2 the aligning call's (q.align); every output is optional.
+struct PairRequest {
+    uint32_t min_insert, max_insert; int rescue; uint32_t rescue_permille;
+    uint32_t *bits1, *bits2; mf_place_t *place1, *place2; mf_score_t *score1, *score2; mf_align_t *align1, *align2;
+    mf_pair_t *pairs; mf_pair_record_t *pair_records; uint64_t *pairs_none;
+};
+
+// The paired calls (include/mitofilter.h, "pairs" and "pairs with a band"): each set filtered, placed, scored -- or, for an aligning
+// request, aligned -- and cut as the single-set call does it, both into ONE set of counters (the first set's cached buffers); then the
+// pair kernels over both sets' pass bits and placements -- which are therefore always made on the device, asked for or not; the scores
+// or alignments only where the cut can reject or the caller asks -- and the report once.
+static int pairs_resident(const mf_kmerset *ks_, const mf_reads *reads1, const mf_reads *reads2, uint32_t threshold, int mode, mf_filter_stats_t *stats,
+                          const PlaceRequest &q, const PairRequest &p)
 {
     static_assert(sizeof(mf_pair_t) == 8 && sizeof(PairOut) == 8 && sizeof(mf_pair_record_t) == 8 * PAIR_RECORD_COUNTERS, "pair records");
     static_assert(MF_RESCUE_MAX == RESCUE_MAX && MF_PAIR_SINGLE_2 == PAIR_SINGLE_2 && MF_PAIR_RESCUED_1 == PAIR_RESCUED_1, "the kernels' constants are the header's");
     mf_kmerset *ks = const_cast<mf_kmerset *>(ks_);
     mf_reads *r1 = const_cast<mf_reads *>(reads1), *r2 = const_cast<mf_reads *>(reads2);
-    PlaceRequest q{"pair-aware placement", true, pileup || consensus || pileup_records};
-    q.min_depth = min_depth; q.max_permille = max_permille; q.base_depth = base_depth; q.place_records = place_records;
-    q.pileup = pileup; q.consensus = consensus; q.pileup_records = pileup_records; q.score_records = score_records; q.unplaced = unplaced;
+    const uint32_t max_permille = q.max_permille;
     // the numbers first, as the family's own check takes them; then the handles
-    if (min_insert < 1 || max_insert < min_insert || max_insert > 0x7FFFFFFFu || max_insert - min_insert + 1 > MF_RESCUE_MAX)
-        return fail(MF_E_ARG, "the insert window is %u .. %u: 1 <= min_insert <= max_insert < 2^31, at most %u inserts wide", min_insert, max_insert, (unsigned)MF_RESCUE_MAX);
-    if (rescue != 0 && rescue != 1) return fail(MF_E_ARG, "rescue is %d: 0 or 1", rescue);
-    if (rescue_permille > 1000) return fail(MF_E_ARG, "rescue_permille is %u: the cut is a number from 0 to 1000", rescue_permille);
+    if (p.min_insert < 1 || p.max_insert < p.min_insert || p.max_insert > 0x7FFFFFFFu || p.max_insert - p.min_insert + 1 > MF_RESCUE_MAX)
+        return fail(MF_E_ARG, "the insert window is %u .. %u: 1 <= min_insert <= max_insert < 2^31, at most %u inserts wide", p.min_insert, p.max_insert, (unsigned)MF_RESCUE_MAX);
+    if (p.rescue != 0 && p.rescue != 1) return fail(MF_E_ARG, "rescue is %d: 0 or 1", p.rescue);
+    if (p.rescue_permille > 1000) return fail(MF_E_ARG, "rescue_permille is %u: the cut is a number from 0 to 1000", p.rescue_permille);
     int rc = q.check(ks); if (rc) return rc;
     if (!r1 || !r2) return fail(MF_E_ARG, "NULL handle");
     if (r1 == r2) return fail(MF_E_ARG, "reads1 and reads2 are one read set: a paired call takes the two mate sets");
@@ -781,8 +789,8 @@ int mf_place_pairs(const mf_kmerset *ks_, const mf_reads *reads1, const mf_reads
         return fail(MF_E_ARG, "the mate sets hold %llu and %llu reads: read i of one is the mate of read i of the other", (unsigned long long)r1->v.n_reads, (unsigned long long)r2->v.n_reads);
     if (r1->device != r2->device) return fail(MF_E_ARG, "the mate sets lie on devices %d and %d: a paired call takes both on one", r1->device, r2->device);
     mf_filter_stats_t s1{}, s2{};
-    rc = filter_common(ks, r1, threshold, mode, bits1, nullptr, 1, stats ? &s1 : nullptr); if (rc) return rc;
-    rc = filter_common(ks, r2, threshold, mode, bits2, nullptr, 1, stats ? &s2 : nullptr); if (rc) return rc;
+    rc = filter_common(ks, r1, threshold, mode, p.bits1, nullptr, 1, stats ? &s1 : nullptr); if (rc) return rc;
+    rc = filter_common(ks, r2, threshold, mode, p.bits2, nullptr, 1, stats ? &s2 : nullptr); if (rc) return rc;
     if (stats) {
         *stats = s1;
         stats->n_reads += s2.n_reads; stats->n_pass += s2.n_pass; stats->n_candidates += s2.n_candidates; stats->algorithmic_bytes += s2.algorithmic_bytes;
@@ -800,25 +808,32 @@ int mf_place_pairs(const mf_kmerset *ks_, const mf_reads *reads1, const mf_reads
     if (e == hipErrorOutOfMemory && q.nomem()) return q.nomem()(L.words());
     HIPCHK(e);
     HIPCHK(dev_reserve(r1->d_rsum, r1->cap_rsum, S.sums_bytes, false));
-    HIPCHK(dev_reserve(r1->d_rpos, r1->cap_rpos, S.pos_bytes, false));
+    const hipError_t e2 = dev_reserve(r1->d_rpos, r1->cap_rpos, S.pos_bytes, false);
+    if (e2 == hipErrorOutOfMemory && q.gap()) { (void)hipGetLastError(); return fail(MF_E_NOMEM, "the gapped consensus needs %llu bytes on the device", (unsigned long long)S.pos_bytes); }
+    HIPCHK(e2);
     HIPCHK(hipMemsetAsync(r1->d_rtot, 0, L.words() * 8, st));
     // each set on its own stream; place_after_filter ends synchronised, so the second set adds into counters the first has left
-    uint64_t listed[2] = {0, 0};
+    uint64_t listed[2] = {0, 0}, longest[2] = {0, 0};
     mf_reads *const sets[2] = {r1, r2};
     DevCtx *const ctxs[2] = {ctx, ctx2};
     ScoreOut *d_scores[2] = {nullptr, nullptr};
+    AlignOut *d_aligns[2] = {nullptr, nullptr};
     for (int m = 0; m < 2 && n; m++) {
         mf_reads *r = sets[m];
         // the kernels read a placement only where the pass bit is set, and place_kernel writes every listed read's: the arrays are
-        // initialised only where the caller gets them; the scores exist only where something reads them
+        // initialised only where the caller gets them; the scores (an aligning call: the alignments) exist only where something reads them
         HIPCHK(dev_reserve(r->d_place, r->cap_place, n * sizeof(PlaceOut), true));
-        if (m ? place2 != nullptr : place1 != nullptr) HIPCHK(launch_place_init(r->d_place, n, ctxs[m]->stream));
+        if (m ? p.place2 != nullptr : p.place1 != nullptr) HIPCHK(launch_place_init(r->d_place, n, ctxs[m]->stream));
         d_scores[m] = nullptr;
-        if ((m ? score2 != nullptr : score1 != nullptr) || max_permille < 1000) {
+        if (!q.align && ((m ? p.score2 != nullptr : p.score1 != nullptr) || max_permille < 1000)) {
             HIPCHK(dev_reserve(r->d_score, r->cap_score, n * sizeof(ScoreOut), true));
             HIPCHK(hipMemsetAsync(d_scores[m] = r->d_score, 0, n * sizeof(ScoreOut), ctxs[m]->stream));
         }
-        rc = place_after_filter(ks, r, L, r1->d_rtot, r->d_place, d_scores[m], &listed[m]); if (rc) return rc;
+        if (q.align && ((m ? p.align2 != nullptr : p.align1 != nullptr) || max_permille < 1000)) {
+            HIPCHK(dev_reserve(r->d_align, r->cap_align, n * sizeof(AlignOut), true));
+            HIPCHK(hipMemsetAsync(d_aligns[m] = r->d_align, 0, n * sizeof(AlignOut), ctxs[m]->stream));
+        }
+        rc = place_after_filter(ks, r, L, r1->d_rtot, r->d_place, d_scores[m], &listed[m], nullptr, MF_KEEP_PASSING, d_aligns[m], &longest[m]); if (rc) return rc;
     }
     const PairLayout P(n_rec);
     std::vector<unsigned long long> h_pc(P.words(), 0);
@@ -827,30 +842,77 @@ int mf_place_pairs(const mf_kmerset *ks_, const mf_reads *reads1, const mf_reads
         unsigned long long *d_pc = r1->d_pair;
         PairOut *d_pairs = reinterpret_cast<PairOut *>(d_pc + P.words());
         uint32_t *d_list = reinterpret_cast<uint32_t *>(d_pairs + n);
-        const PairWindow win{min_insert, max_insert, rescue_permille};
+        const PairWindow win{p.min_insert, p.max_insert, p.rescue_permille};
         HIPCHK(hipMemsetAsync(d_pc, 0, P.words() * 8, st));
-        HIPCHK(launch_pair_list(r1->d_bits[r1->cur], r2->d_bits[r2->cur], r1->d_place, r2->d_place, d_scores[0], d_scores[1], n, max_permille, win, n_rec, d_pairs, rescue ? d_list : nullptr, d_pc, ctx->n_cu, st));
-        if (rescue) {
+        if (q.align) HIPCHK(launch_pair_list_aligned(r1->d_bits[r1->cur], r2->d_bits[r2->cur], r1->d_place, r2->d_place, d_aligns[0], d_aligns[1], n, max_permille, win, n_rec, d_pairs, p.rescue ? d_list : nullptr, d_pc, ctx->n_cu, st));
+        else HIPCHK(launch_pair_list(r1->d_bits[r1->cur], r2->d_bits[r2->cur], r1->d_place, r2->d_place, d_scores[0], d_scores[1], n, max_permille, win, n_rec, d_pairs, p.rescue ? d_list : nullptr, d_pc, ctx->n_cu, st));
+        if (p.rescue) {
             DevTables *T; rc = placement_tables(ks, r1->device, L, &T); if (rc) return rc;
             const ScoreBait bait{T->pile_words, T->pile_words_n - 1, T->pile_valid, T->pile_valid_n - 1};
-            HIPCHK(launch_rescue(r1->v, r2->v, r1->d_bits[r1->cur], r2->d_bits[r2->cur], r1->d_place, r2->d_place, d_scores[0], d_scores[1], d_list, n, win, ks->k, bait, T->place_starts, n_rec, d_pairs, d_pc,
-                                 L.diff(r1->d_rtot), L.cnt(r1->d_rtot), L.score_sums(r1->d_rtot), L.pile(r1->d_rtot), ctx->n_cu, st));
+            if (q.align) {
+                // a target need not pass and so is on no list: the slice holds the longest read of either set
+                const uint64_t max_len = std::max(longest[0], longest[1]);
+                const size_t bytes = (size_t)(rescue_align_waves(n, max_len, ctx->n_cu) * align_work_words(max_len)) * 8;
+                const hipError_t ew = dev_reserve(r1->d_pwork, r1->cap_pwork, bytes, false);
+                if (ew == hipErrorOutOfMemory) { (void)hipGetLastError(); return fail(MF_E_NOMEM, "the alignment of rescued mates of up to %llu bases needs %llu bytes on the device", (unsigned long long)max_len, (unsigned long long)bytes); }
+                HIPCHK(ew);
+                const RescueAlign ra{L.band, d_aligns[0], d_aligns[1], L.score_sums(r1->d_rtot), L.indel(r1->d_rtot), L.ins(r1->d_rtot), L.ext(r1->d_rtot), L.extend, r1->d_pwork, max_len};
+                HIPCHK(launch_rescue_aligned(r1->v, r2->v, r1->d_bits[r1->cur], r2->d_bits[r2->cur], r1->d_place, r2->d_place, d_list, n, win, ks->k, bait, T->place_starts, n_rec, d_pairs, d_pc,
+                                             L.diff(r1->d_rtot), L.cnt(r1->d_rtot), L.pile(r1->d_rtot), ra, ctx->n_cu, st));
+            } else
+                HIPCHK(launch_rescue(r1->v, r2->v, r1->d_bits[r1->cur], r2->d_bits[r2->cur], r1->d_place, r2->d_place, d_scores[0], d_scores[1], d_list, n, win, ks->k, bait, T->place_starts, n_rec, d_pairs, d_pc,
+                                     L.diff(r1->d_rtot), L.cnt(r1->d_rtot), L.score_sums(r1->d_rtot), L.pile(r1->d_rtot), ctx->n_cu, st));
         }
-        if (place1) HIPCHK(hipMemcpyAsync(place1, r1->d_place, n * sizeof(PlaceOut), hipMemcpyDeviceToHost, st));
-        if (place2) HIPCHK(hipMemcpyAsync(place2, r2->d_place, n * sizeof(PlaceOut), hipMemcpyDeviceToHost, st));
-        if (score1) HIPCHK(hipMemcpyAsync(score1, d_scores[0], n * sizeof(ScoreOut), hipMemcpyDeviceToHost, st));
-        if (score2) HIPCHK(hipMemcpyAsync(score2, d_scores[1], n * sizeof(ScoreOut), hipMemcpyDeviceToHost, st));
-        if (pairs) HIPCHK(hipMemcpyAsync(pairs, d_pairs, n * sizeof(PairOut), hipMemcpyDeviceToHost, st));
+        if (p.place1) HIPCHK(hipMemcpyAsync(p.place1, r1->d_place, n * sizeof(PlaceOut), hipMemcpyDeviceToHost, st));
+        if (p.place2) HIPCHK(hipMemcpyAsync(p.place2, r2->d_place, n * sizeof(PlaceOut), hipMemcpyDeviceToHost, st));
+        if (p.score1 && d_scores[0]) HIPCHK(hipMemcpyAsync(p.score1, d_scores[0], n * sizeof(ScoreOut), hipMemcpyDeviceToHost, st));
+        if (p.score2 && d_scores[1]) HIPCHK(hipMemcpyAsync(p.score2, d_scores[1], n * sizeof(ScoreOut), hipMemcpyDeviceToHost, st));
+        if (p.align1 && d_aligns[0]) HIPCHK(hipMemcpyAsync(p.align1, d_aligns[0], n * sizeof(AlignOut), hipMemcpyDeviceToHost, st));
+        if (p.align2 && d_aligns[1]) HIPCHK(hipMemcpyAsync(p.align2, d_aligns[1], n * sizeof(AlignOut), hipMemcpyDeviceToHost, st));
+        if (p.pairs) HIPCHK(hipMemcpyAsync(p.pairs, d_pairs, n * sizeof(PairOut), hipMemcpyDeviceToHost, st));
         HIPCHK(hipMemcpyAsync(h_pc.data(), d_pc, P.words() * 8, hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));          // (the report is told how many reads do not pass: a rescued one that did not is taken off)
     }
-    if (pair_records)
+    if (p.pair_records)
         for (size_t j = 0; j < n_rec; j++) {
             const unsigned long long *c = h_pc.data() + PAIR_RECORD_COUNTERS * j;
-            pair_records[j] = mf_pair_record_t{c[0], c[1], c[2], c[3], c[4], c[5]};
+            p.pair_records[j] = mf_pair_record_t{c[0], c[1], c[2], c[3], c[4], c[5]};
         }
-    if (pairs_none) *pairs_none = h_pc[P.none()];
+    if (p.pairs_none) *p.pairs_none = h_pc[P.none()];
     return placement_report(ks, r1->device, st, L, r1->d_rtot, q, S, r1->d_rsum, r1->d_rpos, (n - listed[0]) + (n - listed[1]) - h_pc[P.rescued_not_passing()]);
+}
+
+extern "C" {
+
+int mf_place_pairs(const mf_kmerset *ks, const mf_reads *reads1, const mf_reads *reads2, uint32_t threshold, int mode, uint32_t min_depth, uint32_t max_permille,
+                   uint32_t min_insert, uint32_t max_insert, int rescue, uint32_t rescue_permille, uint32_t *bits1, uint32_t *bits2, mf_place_t *place1,
+                   mf_place_t *place2, mf_score_t *score1, mf_score_t *score2, mf_pair_t *pairs, uint32_t *base_depth, mf_place_record_t *place_records,
+                   mf_pileup_t *pileup, uint8_t *consensus, mf_pileup_record_t *pileup_records, mf_score_record_t *score_records,
+                   mf_pair_record_t *pair_records, uint64_t *pairs_none, uint64_t *unplaced, mf_filter_stats_t *stats)
+{
+    PlaceRequest q{"pair-aware placement", true, pileup || consensus || pileup_records};
+    q.min_depth = min_depth; q.max_permille = max_permille; q.base_depth = base_depth; q.place_records = place_records;
+    q.pileup = pileup; q.consensus = consensus; q.pileup_records = pileup_records; q.score_records = score_records; q.unplaced = unplaced;
+    const PairRequest p{min_insert, max_insert, rescue, rescue_permille, bits1, bits2, place1, place2, score1, score2, nullptr, nullptr, pairs, pair_records, pairs_none};
+    return pairs_resident(ks, reads1, reads2, threshold, mode, stats, q, p);
+}
+
+int mf_align_pairs(const mf_kmerset *ks, const mf_reads *reads1, const mf_reads *reads2, uint32_t threshold, int mode, uint32_t min_depth,
+                   uint32_t max_permille, uint32_t band, uint32_t extend, uint32_t min_insert, uint32_t max_insert, int rescue, uint32_t rescue_permille,
+                   uint32_t *bits1, uint32_t *bits2, mf_place_t *place1, mf_place_t *place2, mf_align_t *align1, mf_align_t *align2, mf_pair_t *pairs,
+                   uint32_t *base_depth, mf_place_record_t *place_records, mf_pileup_t *pileup, uint8_t *consensus, mf_pileup_record_t *pileup_records,
+                   mf_indel_t *indels, mf_align_record_t *align_records, mf_pileup_t *ins_pile, uint8_t *gapped, uint64_t *gapped_starts,
+                   mf_gapped_record_t *gapped_records, mf_pileup_t *ext_pile, uint8_t *extended, uint64_t *extended_starts, mf_extend_record_t *extend_records,
+                   mf_pair_record_t *pair_records, uint64_t *pairs_none, uint64_t *unplaced, mf_filter_stats_t *stats)
+{
+    PlaceRequest q{"pair-aware alignment", true, pileup || consensus || pileup_records || ins_pile || gapped || gapped_starts || gapped_records || ext_pile || extended || extended_starts || extend_records};
+    q.extend = extend; q.ext_pile = ext_pile; q.extended = extended; q.extended_starts = extended_starts; q.extend_records = extend_records;
+    q.min_depth = min_depth; q.max_permille = max_permille; q.align = true; q.band = band;
+    q.base_depth = base_depth; q.place_records = place_records;
+    q.pileup = pileup; q.consensus = consensus; q.pileup_records = pileup_records; q.indels = indels; q.align_records = align_records;
+    q.ins_pile = ins_pile; q.gapped = gapped; q.gapped_starts = gapped_starts; q.gapped_records = gapped_records; q.unplaced = unplaced;
+    const PairRequest p{min_insert, max_insert, rescue, rescue_permille, bits1, bits2, place1, place2, nullptr, nullptr, align1, align2, pairs, pair_records, pairs_none};
+    return pairs_resident(ks, reads1, reads2, threshold, mode, stats, q, p);
 }
 
 } // extern "C"

@@ -94,6 +94,7 @@ EXPORTS = (
     "mf_align_gapped", "mf_filter_fastq_files_gapped",
     "mf_align_extended", "mf_filter_fastq_files_extended",
     "mf_place_pairs",
+    "mf_align_pairs",
 )
 
 
@@ -235,6 +236,8 @@ def load(path: Optional[str] = None):
                                                  vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, u64p, u64p]
     L.mf_place_pairs.argtypes = [vp, vp, vp, C.c_uint32, C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_uint32, vp, vp, vp, vp, vp, vp,
                                  vp, vp, vp, vp, vp, vp, vp, vp, u64p, vp, C.POINTER(FilterStats)]
+    L.mf_align_pairs.argtypes = [vp, vp, vp, C.c_uint32, C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_uint32,
+                                 *([vp] * 23), u64p, vp, C.POINTER(FilterStats)]
     if L.mf_abi_version() != 5:
         raise MitoFilterError("libmitofilter_hip ABI version mismatch")
     _lib = L
@@ -851,6 +854,13 @@ def pair_inserts(place1: np.ndarray, place2: np.ndarray) -> np.ndarray:
     return np.where(ok, size, -1).astype(np.int64)
 
 
+def _check_pairs(min_insert: int, max_insert: int, rescue_permille: int):
+    if not 1 <= int(min_insert) <= int(max_insert) < 2 ** 31 or int(max_insert) - int(min_insert) + 1 > RESCUE_MAX:
+        raise ValueError("the insert window is 1 <= min_insert <= max_insert, at most RESCUE_MAX inserts wide")
+    if not 0 <= int(rescue_permille) <= 1000:
+        raise ValueError("rescue_permille is a number from 0 to 1000")
+
+
 class Paired(Verified):
     """What place_pairs gives (include/mitofilter.h, pairs): Verified's report fields over BOTH mate sets, and per set bits1 / bits2
     u32[ceil(n/32)], place1 / place2 PLACE[n], score1 / score2 SCORE[n]; pairs PAIR[n] (kind, insert), pair_records PAIR_RECORD[R] and
@@ -868,10 +878,7 @@ def place_pairs(ks: KmerSet, reads1: Reads, reads2: Reads, min_insert: int, max_
     mismatches, and from there on counts as an accepted placed read (include/mitofilter.h: mf_place_pairs).  The default
     rescue_permille of 100, one base in ten, is a policy choice and not a measured value.  -> Paired."""
     _check_cut(min_depth, max_permille)
-    if not 1 <= int(min_insert) <= int(max_insert) < 2 ** 31 or int(max_insert) - int(min_insert) + 1 > RESCUE_MAX:
-        raise ValueError("the insert window is 1 <= min_insert <= max_insert, at most RESCUE_MAX inserts wide")
-    if not 0 <= int(rescue_permille) <= 1000:
-        raise ValueError("rescue_permille is a number from 0 to 1000")
+    _check_pairs(min_insert, max_insert, rescue_permille)
     n = reads1.info.n_reads
     if reads2.info.n_reads != n:
         raise ValueError("the mate sets differ in length")
@@ -889,6 +896,49 @@ def place_pairs(ks: KmerSet, reads1: Reads, reads2: Reads, min_insert: int, max_
     bits2, place2, score2 = results2()
     return Paired(bits1=bits1, bits2=bits2, place1=place1, place2=place2, score1=score1, score2=score2, pairs=pairs[:n], pair_records=pair_records[:R],
                   pairs_none=none.value, **results())
+
+
+class AlignedPairs(Aligned):
+    """What align_pairs gives (include/mitofilter.h, pairs with a band): Aligned's report fields over BOTH mate sets -- indels,
+    align_records and, when asked, the gapped and the extended fields among them -- and per set bits1 / bits2 u32[ceil(n/32)], place1 /
+    place2 PLACE[n], align1 / align2 ALIGN[n]; pairs PAIR[n], pair_records PAIR_RECORD[R] and pairs_none as Paired holds them.  A
+    rescued mate's place row holds votes == 0 and its align row the alignment around the seed.  bits, place, align and keep_bits are
+    None: the paired call has no keep mode."""
+    __slots__ = ("bits1", "bits2", "place1", "place2", "align1", "align2", "pairs", "pair_records", "pairs_none")
+
+
+def align_pairs(ks: KmerSet, reads1: Reads, reads2: Reads, min_insert: int, max_insert: int, band: int = 8, rescue: bool = True,
+                rescue_permille: int = 100, min_depth: int = 1, max_permille: int = 1000, pileup: bool = True, gapped: bool = False, extend: int = 0,
+                threshold: int = 1, mode: int = MODE_SCREENED) -> AlignedPairs:
+    """place_pairs with a band: both mate sets aligned as align_reads does it, into one set of counters; a mate is settled when the
+    aligned cut accepts it; the rescue's candidates are scored ungapped exactly as place_pairs scores them, and the rescued mate is then
+    aligned inside the band around the winning candidate and counts as an accepted aligned read (include/mitofilter.h: mf_align_pairs).
+    The seed is ungapped: a mate with an indel well inside it is found only with a looser rescue_permille, since only its longer side
+    matches on the seed's diagonal; the default of 100 is a policy choice and not a measured value.  gapped and extend as in align_reads.
+    band = 0 is place_pairs.  -> AlignedPairs."""
+    _check_cut(min_depth, max_permille)
+    _check_band(band)
+    _check_extend(extend)
+    _check_pairs(min_insert, max_insert, rescue_permille)
+    n = reads1.info.n_reads
+    if reads2.info.n_reads != n:
+        raise ValueError("the mate sets differ in length")
+    per1, results1 = _read_outputs(reads1, PLACE, ALIGN)
+    per2, results2 = _read_outputs(reads2, PLACE, ALIGN)
+    pairs = np.zeros(max(n, 1), dtype=PAIR)
+    R = len(ks.record_starts) - 1
+    pair_records = np.zeros(max(R, 1), dtype=PAIR_RECORD)
+    none = C.c_uint64()
+    ptrs, results = _report_outputs(ks, _ALIGN_FIELDS, () if pileup else _PILEUP_FIELDS[:3])
+    gptrs, gresults = _gapped_outputs(ks, band) if gapped else ([None] * 4, dict)
+    xptrs, xresults = _extend_outputs(ks, band, extend) if int(extend) > 0 else ([None] * 4, dict)
+    _chk(load().mf_align_pairs(ks._h, reads1._h, reads2._h, threshold, mode, min_depth, max_permille, int(band), int(extend), int(min_insert),
+                               int(max_insert), int(bool(rescue)), int(rescue_permille), per1[0], per2[0], per1[1], per2[1], per1[2], per2[2],
+                               pairs.ctypes.data, *ptrs[:-1], *gptrs, *xptrs, pair_records.ctypes.data, C.byref(none), ptrs[-1], None))
+    bits1, place1, align1 = results1()
+    bits2, place2, align2 = results2()
+    return AlignedPairs(bits1=bits1, bits2=bits2, place1=place1, place2=place2, align1=align1, align2=align2, pairs=pairs[:n],
+                        pair_records=pair_records[:R], pairs_none=none.value, **results(), **gresults(), **xresults())
 
 
 def filter_resident(ks: KmerSet, reads: Reads, threshold: int = 1, mode: int = MODE_SCREENED, steps: int = 1) -> FilterStats:
